@@ -8,7 +8,13 @@ in the containers).  N GPUs = N ranks (one process per GPU), each with its own b
 descriptors all-gathered over RCCL inside the timed region (the exchange step of the retrieval; the reference's
 multi-process entry is utils/engine/base_tester.py:88).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+
+A plain run sets up, warms up, times ONE block of exactly K steps and prints the JSON line (`value`, `ms_per_step`, ...).  `--full`
+adds everything else it measures: the median of `--repeats` blocks (default 5) with per-launch kernel clocks inside them, the roofline
+passes, the A/B blocks (`with_h2d`, the other GEMM form, 7 searches), configs[2]-[4] (`pairs`, `retrieval`, `sequence`) and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step handed its caller: DIR/descriptors.npy (float32 [8, 256], rank 0's
+batch) and, with N > 1 ranks, DIR/gathered.npy (float32 [8 N, 256], the all-gathered descriptors).  The inputs depend only on the arguments.
 
 Launch forms: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the ranks come from the
 environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).  A bare `python bench.py --gpus N` with N > 1 starts the N rank
@@ -50,8 +56,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed K-step block runs this many times back to back (each bracketed by "
-                    "barrier + synchronize); the line reports the MEDIAN block, ms_per_step_min / _max the spread")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements: repeated blocks with kernel clocks, roofline, "
+                    "A/B blocks, configs[2]-[4] blocks, CPU baseline (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the descriptors of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed K-step block runs this many times back to back (each bracketed by "
+                    "barrier + synchronize); the line reports the MEDIAN block, ms_per_step_min / _max the spread (default 1, 5 with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-split-ab", action="store_true", help="skip the secondary A/B block with the split-bf16 K-deep GEMMs")
     ap.add_argument("--no-lazy-ab", action="store_true", help="skip the secondary block without the 3 decoder-only upsampling searches")
@@ -70,8 +79,12 @@ def parse():
 
 
 def make_batch(rank):
+    """The rank's BATCH scans, one seed each (deterministic).  Synthesis is numpy on 120 k rays per scan (~2 s each): the scans are
+    generated on a few host threads, since numpy releases the GIL inside its array operations."""
+    import concurrent.futures as cf
     import lcrnet_amd.synthetic as synthetic
-    return [synthetic.synthetic_scan(rank * BATCH + i) for i in range(BATCH)]
+    with cf.ThreadPoolExecutor(max_workers=max(1, min(BATCH, len(os.sched_getaffinity(0))))) as ex:
+        return list(ex.map(synthetic.synthetic_scan, [rank * BATCH + i for i in range(BATCH)]))
 
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -178,9 +191,9 @@ def main():
     run_steps(8)                 # priming, untimed and not counted: allocator growth for the batches in flight, lazy code-object loads
     run_steps(args.warmup)
     # per distinct batch: stage sizes and the valid (non-padding) entries of the index lists the KPConv layers gather (the
-    # aggregation's flops are 2 * 15 * nnz * C)
+    # aggregation's flops are 2 * 15 * nnz * C); --full only (the roofline's inputs)
     stage_points_all, nnz = [], {}
-    for pts_k, lens_k in inputs:
+    for pts_k, lens_k in (inputs if args.full else []):
         dd0 = pipe.preprocess(pts_k, lens_k)
         sp = [sum(l) for l in dd0["lengths_host"]]
         stage_points_all.append(sp)
@@ -189,10 +202,10 @@ def main():
             if i + 1 < NUM_STAGES:
                 nnz[(sp[i + 1], sp[i])] = int((dd0["subsampling"][i] < sp[i]).sum())
         del dd0
-    stage_points = stage_points_all[0]
+    stage_points = stage_points_all[0] if stage_points_all else None
     # ---- timed region: exactly K steps between barrier + synchronize — R such blocks back to back, the line reports the MEDIAN one
     blocks = []
-    R = max(1, args.repeats)
+    R = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     # per-launch clocks on every SAMPLE-th launch of a kind only: a timed launch is a profiled dispatch (4 event records, timestamped
     # completion signal, system-scope release at kernel end); with every launch timed the pipeline ran 7 % slower (2 409 vs 2 577
     # scans/s).  9 is coprime with the 35 GEMMs / 10 aggregations of a step, so every shape is sampled equally often.
@@ -202,7 +215,7 @@ def main():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
-        if not os.environ.get("LCR_BENCH_NO_KTIMER"):                  # A/B: what the per-launch events cost the timed region
+        if args.full and not os.environ.get("LCR_BENCH_NO_KTIMER"):    # A/B: what the per-launch events cost the timed region
             F.set_timer(timer, SAMPLE)
         t0 = time.perf_counter()
         desc = run_steps(args.steps)
@@ -221,14 +234,19 @@ def main():
     dt_min, dt_max = blocks[order_r[0]][0], blocks[order_r[-1]][0]
     if os.environ.get("LCR_PIPE_STATS") and rank == 0:
         print("pipeline host threads:", {k: (round(v, 4) if isinstance(v, float) else v) for k, v in pipe.stats.items()}, file=sys.stderr)
+    if args.dump_outputs and rank == 0:               # the last timed step's results, before any later block reuses the buffers
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "descriptors.npy"), desc.float().cpu().numpy())
+        if gathered is not None and world > 1:
+            np.save(os.path.join(args.dump_outputs, "gathered.npy"), gathered.float().cpu().numpy())
 
-    summ = timer.records() if rank == 0 else None     # read the timed region's log before anything else is logged
+    summ = timer.records() if rank == 0 and args.full else None     # read the timed region's log before anything else is logged
     # ---- the same steps fed from HOST memory (not the headline): every batch arrives as a pinned host tensor f32 [sum N, 4] (KITTI
     # velodyne rows x, y, z, intensity, as a loader thread reading .bin files would leave them) + i64 lengths, is uploaded on the copy
     # stream `depth` batches ahead (lcrnet_amd.pipeline.HostIngest) and consumed unsliced by the voxel-key kernels.  The reference:
     # `_load_point_cloud(...)[:, :3]` + to_cuda (dataset_overlap_online.py:245-253, utils/engine/single_tester.py:59).
     with_h2d = None
-    secondary = world == 1            # the A/B blocks belong to the single-GPU line; an N-rank run measures the headline only
+    secondary = world == 1 and args.full   # the A/B blocks belong to the single-GPU --full line; an N-rank run measures the headline only
     if secondary and not args.no_h2d and not (args.no_overlap or args.no_thread):
         host_inputs = []
         g = torch.Generator().manual_seed(5)
@@ -362,7 +380,7 @@ def main():
         torch.cuda.empty_cache()
     final_line = None
     iso = None
-    if rank == 0 and not os.environ.get("LCR_BENCH_NO_KTIMER"):
+    if rank == 0 and args.full and not os.environ.get("LCR_BENCH_NO_KTIMER"):
         # Every distinct batch once more with NOTHING else on the GPU (one stream, one batch in flight, outside the timed region) and
         # EVERY launch clocked: the kernels' own durations as a kernel trace of the encoder alone reports them
         # (profiles/rNN_encoder_alone_kernel_summary.md), and the exact flops / launches of a step (no sampling).
@@ -399,12 +417,13 @@ def main():
                                                                                2.0 * m_[0] * m_[1] * m_[2] / (FP32_PEAK_TFLOPS * 1e12))
             iso["flops"].append(sum(2.0 * m[0] * m[1] * m[2] for _, _, m in r["gemm"]))
             iso["flops_agg"].append(sum(2.0 * 15 * nnz.get((M, Ns), M * H) * C for _, _, (M, Ns, H, C, isz) in r["kpconv_aggregate"]))
-    if rank == 0 and os.environ.get("LCR_BENCH_NO_KTIMER"):            # A/B run without per-launch events: the headline only
+    if rank == 0 and args.full and os.environ.get("LCR_BENCH_NO_KTIMER"):   # A/B run without per-launch events: the headline only
         print(json.dumps({"value": round(world * BATCH * args.steps / dt, 3), "ms_per_step": round(dt / args.steps * 1e3, 3),
                           "ms_per_step_min": round(dt_min / args.steps * 1e3, 3), "ms_per_step_max": round(dt_max / args.steps * 1e3, 3), "ktimer": False}), flush=True)
         rank = -1
-    if rank == 0:
-        assert torch.isfinite(desc).all() and abs(float(desc.norm(dim=1).mean()) - 1.0) < 1e-3
+    n_search = 7 if args.no_upsampling else 10
+    roof = None
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel family (by time: the fp32 GEMMs, lcr::k_gemm_f32_deep + k_gemm_f32, profiles/).
         # Compute-bound on the fp32 matrix cores: achieved = algorithmic flops (2*M*N*K per launch) / the kernels' own
         # begin-to-end durations (hipExtLaunchKernel start / stop events on the launch stream = what a kernel trace reports) vs the
@@ -434,7 +453,6 @@ def main():
         bytes_kp = sum(M * H * isz + (M + Ns) * 12 + Ns * C * 4 for _, (M, Ns, H, C, isz) in agg) + \
             sum(M * N * 4 + K * N * 4 for _, (M, N, K) in contr)
         t_kp = tk_agg + sum(t for t, _ in contr)
-        n_search = 7 if args.no_upsampling else 10
         rs_launch = tk_rs / max(len(rsq), 1)                                         # one launch per step (all searches of a batch)
         sp0 = stage_points
         n_queries = 2 * sp0[0] + 3 * sp0[1] + 3 * sp0[2] + 2 * sp0[3] if not args.no_upsampling else sp0[0] + 2 * sp0[1] + 2 * sp0[2] + 2 * sp0[3]
@@ -536,23 +554,26 @@ def main():
                               "frac": round(bytes_kp / t_kp / 1e9 / HBM_PEAK_GBS, 4),
                               "algorithmic_mb_per_step": round(bytes_kp * SAMPLE / args.steps / 1e6, 1),
                               "ms_per_step": round(t_kp * SAMPLE / args.steps * 1e3, 3), "clock": "in the pipeline (sampled)"}}
+    if rank == 0:
+        assert torch.isfinite(desc).all() and abs(float(desc.norm(dim=1).mean()) - 1.0) < 1e-3
         line = {
             "metric": "scans/s (120k-pt KITTI-shape scan -> 256-D descriptor)",
             "value": round(world * BATCH * args.steps / dt, 3), "unit": "scans/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "repeats": R, "ms_per_step_min": round(dt_min / args.steps * 1e3, 3), "ms_per_step_max": round(dt_max / args.steps * 1e3, 3),
-            "timing": "median of %d back-to-back blocks of %d steps, each bracketed by barrier + synchronize (max over ranks)" % (R, args.steps),
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic", **({"forced_one_rank_process_group": backend} if force_dist else {}),
+            "timing": ("median of %d back-to-back blocks of %d steps, each bracketed by barrier + synchronize (max over ranks)" % (R, args.steps)
+                       if R > 1 else "one block of %d steps, bracketed by barrier + synchronize (max over ranks)" % args.steps),
+            "full": args.full, "vs_baseline": None, "dtype": "f32", "data": "synthetic", **({"forced_one_rank_process_group": backend} if force_dist else {}),
             "config": {"workload": "configs[1]: batch of 8 synthetic 64-beam scans (~120k pts, 0.3 m voxel -> ~16k pts), "
                                    "voxelise + 3 subsamples + %d radius searches + KPConv encoder + NetVLAD, seeded random weights"
                                    % n_search,
                        "scans_per_step_per_gpu": BATCH, "raw_points_per_scan": int(raw_pts.shape[0] // BATCH),
-                       "stage_points_per_batch": stage_points, "distinct_input_batches": nb_in, "neighbor_limits": LIMITS,
+                       **({"stage_points_per_batch": stage_points} if stage_points else {}), "distinct_input_batches": nb_in, "neighbor_limits": LIMITS,
                        "streams": "1" if args.no_overlap else ("pre-processing stream (own host thread, 2 batches ahead) + %d encoder stream(s)"
                                                                % (1 if (args.single_encoder or args.no_thread) else 2)),
                        "parallelism": "scan-parallel x%d, all-gather of descriptors%s" % (world, (" (%s)" % backend) if backend else ""),
                        "host": "rank 0 on %d cores (%s)" % bound},
-            "roofline": roof,
+            **({"roofline": roof} if roof is not None else {}),
         }
         if with_h2d is not None:
             line["with_h2d"] = with_h2d
@@ -566,7 +587,7 @@ def main():
         if F.gemm_split_enabled():
             line["dtype"] = ("f32 (K-deep GEMMs, K >= 288 and N >= 64: fp32 operands as bf16 x 3 split, 6 of 9 products on the bf16 matrix cores, fp32 "
                              "accumulate — error vs fp64 <= the fp32-MFMA kernel's; every other GEMM, KPConv and attention: fp32 MFMA)")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(scans)
         final_line = json.dumps(line)
     pipe.close()

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,8 +34,8 @@ def test_one_rank_rccl_group_runs_the_n_rank_path():
     env = dict(os.environ, LCR_BENCH_FORCE_DIST="1", MASTER_PORT="29631")
     env.pop("LCR_BENCH_SINGLE_DEVICE", None)
     env.pop("LCR_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "2", "--full",
+                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["forced_one_rank_process_group"] == "nccl" and line["n_gpus"] == 1 and line["value"] > 0
@@ -46,3 +47,31 @@ def test_one_rank_rccl_group_runs_the_n_rank_path():
     for k in blocks:
         assert line[k]["value"] > 0
     assert line["with_h2d"]["descriptors_max_abs_diff_vs_resident"] == 0.0
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_descriptors(tmp_path):
+    """A plain run (no --full) times one block of exactly --steps steps, carries the headline keys only, and --dump-outputs writes
+    the last timed step's descriptors: float32 [8, 256], unit rows, the same values (1e-5) on a second run with the same arguments."""
+    env = dict(os.environ)
+    for k in ("LCR_BENCH_SINGLE_DEVICE", "LCR_BENCH_BACKEND", "LCR_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["repeats"] == 1 and line["full"] is False
+        assert line["value"] > 0 and abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+        for k in ("roofline", "cpu_baseline", "with_h2d", "pairs", "retrieval", "sequence", "descriptor_only_7_searches"):
+            assert k not in line, k
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["descriptors.npy"], files
+        d = np.load(out / "descriptors.npy")
+        assert d.dtype == np.float32 and d.shape == (8, 256)
+        assert np.isfinite(d).all() and np.allclose(np.linalg.norm(d, axis=1), 1.0, atol=1e-3)
+        dumps.append(d)
+    assert np.allclose(dumps[0], dumps[1], rtol=0, atol=1e-5)      # identical inputs from run to run

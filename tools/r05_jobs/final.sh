@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$ROOT/gpurun_out/r05
 mkdir -p "$OUT"
 cd "$ROOT"
-timeout 900 python bench.py > "$OUT/bench_final.log" 2> "$OUT/bench_final.err"
+timeout 900 python bench.py --full > "$OUT/bench_final.log" 2> "$OUT/bench_final.err"
 tail -1 "$OUT/bench_final.log" | cut -c1-400
 timeout 1500 bash tools/profile_round.sh > "$OUT/profile_round_final.log" 2>&1
 tail -3 "$OUT/profile_round_final.log" | cut -c1-200

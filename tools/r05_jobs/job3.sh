@@ -9,5 +9,5 @@ LCR_GEMM_BATCH_SHORT=0 timeout 600 python tools/pair_bench.py --pairs-per-call 8
 tail -1 "$OUT/pair_bench_batchdeep.log" | cut -c1-1500
 timeout 600 python tools/pair_bench.py --pairs-per-call 1 8 16 32 --pairs 192 --repeats 5 > "$OUT/pair_bench_default.log" 2>&1
 tail -1 "$OUT/pair_bench_default.log" | cut -c1-2500
-timeout 900 python bench.py > "$OUT/bench_default.log" 2> "$OUT/bench_default.err"
+timeout 900 python bench.py --full > "$OUT/bench_default.log" 2> "$OUT/bench_default.err"
 tail -1 "$OUT/bench_default.log" | cut -c1-3000
