@@ -520,6 +520,37 @@ int lcr_local_global_registration_ex(const float* src, const float* ref, const f
 int lcr_inlier_weights(const float* T_all, const int32_t* sel, const float* src, const float* ref, const float* score, int n,
                        float radius, float* w_out, void* stream);
 
+/* Correspondence RANSAC (utils/utils/open3d.py:145-173: Open3D's registration_ransac_based_on_correspondence, point-to-point without
+ * scaling, RANSACConvergenceCriteria(N, N) so that every iteration runs), for S pairs in one call.  Open3D's sampling is random; this
+ * one is deterministic and defined as follows.
+ *   - Pairs: correspondences stacked pair-major, pair s = rows [start[s], start[s+1]) of src / ref f32[n,3] (n_s rows; start int32 [S+1]).
+ *     The result maps src onto ref (experiments/registration/eval.py passes src = anchor, ref = positive).
+ *   - Sampler: hypothesis h (0 <= h < iterations) draws ransac_n rows with replacement (as Open3D's RandUint32() % size does).  Draw j
+ *     is z = SplitMix64(seed + 0x9E3779B97F4A7C15 * (1 + 8h + j)) (the finaliser: z ^= z >> 30, *= 0xBF58476D1CE4E5B9, ^= z >> 27,
+ *     *= 0x94D049BB133111EB, ^= z >> 31; all mod 2^64), row = (hi32(z) * n_s) >> 32.  The key leaves the pair's position in the batch
+ *     out: a pair gives bit-identical results alone or inside any batch.  lcr_ransac_sample_host computes the same indices on the host.
+ *   - Hypothesis: Kabsch with unit weights on the sampled rows; centroids and H = sum (s - c_src)(r - c_ref)^T in fp64, R from the fp64
+ *     Jacobi SVD of the weighted Procrustes (reflection fixed on the smallest singular direction), t = c_ref - R c_src, stored as fp32.
+ *     INVALID (never selected) when the sample is coincident or collinear: sigma_2(H) <= 1e-9 sigma_1(H) or sigma_1(H) <= 1e-30.
+ *   - Score, fp32: with m = the hypothesis' 12 floats (R|t row-major), dx = fma(m2, sz, fma(m1, sy, fma(m0, sx, m3))) - rx (dy, dz
+ *     likewise), d2 = fma(dz, dz, fma(dy, dy, dx * dx)); row i is an inlier iff d2 < thr * thr (fp32 product).  Per hypothesis: inlier
+ *     count and inlier SSE (sum of the inliers' d2 in row order, fp32).
+ *   - Selection: most inliers, ties to the smaller SSE, then to the smaller h — a total order, so the result does not depend on launch
+ *     order.  The winner's transform is returned as it is (no refit on its inliers), with its inlier count and RMSE = sqrt(SSE / count).
+ *     A pair with n_s < ransac_n, without a valid hypothesis, or whose best hypothesis has no inlier returns the identity, 0 inliers,
+ *     RMSE 0 and best_h -1 (Open3D returns an empty result there).
+ * Outputs: T f32[S,4,4], inliers i32[S], rmse f32[S]; nullable: best_h i32[S], and the per-hypothesis detail T_all f32[S*iterations,4,4]
+ * (the identity for invalid hypotheses), counts_all i32[S*iterations] (-1 = invalid), sse_all f32[S*iterations] (index s*iterations+h).
+ * Three launches, no host synchronisation; ws: lcr_ransac_ws_bytes (~64 B per hypothesis).
+ * Domain: 1 <= S <= 65535, 3 <= ransac_n <= 8, 1 <= iterations <= 1e6, any n_s >= 0, 0 < thr with thr * thr finite; LCR_EARG outside. */
+int lcr_ransac_ws_bytes(int S, int iterations, size_t* bytes);
+int lcr_ransac_correspondences(const float* src, const float* ref, const int32_t* start, int S, float thr, int ransac_n, int iterations,
+                               uint64_t seed, float* T, int32_t* inliers, float* rmse, int32_t* best_h, float* T_all, int32_t* counts_all,
+                               float* sse_all, void* ws, size_t ws_bytes, void* stream);
+/* The sampler on the host: idx_host[k * ransac_n + j] = draw j of hypothesis h0 + k for a pair of n rows (1 <= n <= 2^31 - 1,
+ * 1 <= ransac_n <= 8, 0 <= h0, h0 + count <= 1e6). */
+int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, int ransac_n, int64_t n, int32_t* idx_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "rigid3.h"
 
 namespace lcr {
 
@@ -1419,88 +1420,7 @@ __global__ __launch_bounds__(256) void k_build_padded_scores_rows(const float* _
   }
 }
 
-// ---- weighted Procrustes (batched) --------------------------------------------------------------------------------------------
-// 3x3 SVD by one-sided Jacobi (Hestenes) in fp64: A V = U S.  Returns R = V diag(1,1,sign det(V U^T)) U^T.
-__device__ void rotation_from_H(const double H[3][3], double R[3][3]) {
-  double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) A[i][j] = H[i][j];
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-        for (int k = 0; k < 3; ++k) {
-          alpha += A[k][p] * A[k][p];
-          beta += A[k][q] * A[k][q];
-          gamma += A[k][p] * A[k][q];
-        }
-        off = fmax(off, fabs(gamma) / (sqrt(alpha * beta) + 1e-300));
-        if (fabs(gamma) < 1e-300) continue;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int k = 0; k < 3; ++k) {
-          const double ap = A[k][p], aq = A[k][q];
-          A[k][p] = c * ap - s * aq;
-          A[k][q] = s * ap + c * aq;
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq;
-          V[k][q] = s * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  // singular values = column norms of A; U = A / sigma.  Order columns by decreasing sigma (like LAPACK) so that the
-  // reflection fix hits the smallest singular direction.
-  double sig[3];
-  int ord[3] = {0, 1, 2};
-  for (int j = 0; j < 3; ++j) sig[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-  for (int a = 0; a < 2; ++a)
-    for (int b2 = a + 1; b2 < 3; ++b2)
-      if (sig[ord[b2]] > sig[ord[a]]) {
-        const int tmp = ord[a];
-        ord[a] = ord[b2];
-        ord[b2] = tmp;
-      }
-  double U[3][3], Vs[3][3];
-  for (int j = 0; j < 3; ++j) {
-    const int c = ord[j];
-    for (int k = 0; k < 3; ++k) {
-      Vs[k][j] = V[k][c];
-      U[k][j] = sig[c] > 1e-300 ? A[k][c] / sig[c] : 0.0;
-    }
-  }
-  // complete U if rank deficient: third column = u0 x u1 (and second from any orthogonal vector if needed)
-  if (sig[ord[1]] <= 1e-12 * sig[ord[0]] || sig[ord[1]] <= 1e-300) {
-    // pick an axis least aligned with u0
-    int ax = 0;
-    if (fabs(U[1][0]) < fabs(U[ax][0])) ax = 1;
-    if (fabs(U[2][0]) < fabs(U[ax][0])) ax = 2;
-    double e[3] = {0, 0, 0};
-    e[ax] = 1.0;
-    const double d = e[0] * U[0][0] + e[1] * U[1][0] + e[2] * U[2][0];
-    double nrm = 0;
-    for (int k = 0; k < 3; ++k) {
-      U[k][1] = e[k] - d * U[k][0];
-      nrm += U[k][1] * U[k][1];
-    }
-    nrm = sqrt(nrm);
-    for (int k = 0; k < 3; ++k) U[k][1] /= nrm;
-  }
-  if (sig[ord[2]] <= 1e-12 * sig[ord[0]] || sig[ord[2]] <= 1e-300) {
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  }
-  auto det3 = [](const double X[3][3]) {
-    return X[0][0] * (X[1][1] * X[2][2] - X[1][2] * X[2][1]) - X[0][1] * (X[1][0] * X[2][2] - X[1][2] * X[2][0]) +
-           X[0][2] * (X[1][0] * X[2][1] - X[1][1] * X[2][0]);
-  };
-  const double sgn = det3(Vs) * det3(U) >= 0 ? 1.0 : -1.0;   // det(V U^T) = det V * det U
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = Vs[i][0] * U[j][0] + Vs[i][1] * U[j][1] + sgn * Vs[i][2] * U[j][2];
-}
+// ---- weighted Procrustes (batched): rotation_from_H in rigid3.h ------------------------------------------------------------
 
 // problem p uses correspondences [start[p], start[p+1]) of src/ref/w; one wavefront per problem; T out [P,4,4] row-major
 __global__ __launch_bounds__(64) void k_procrustes(const float* __restrict__ src, const float* __restrict__ ref, const float* __restrict__ w,

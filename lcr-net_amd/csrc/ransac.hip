@@ -1,0 +1,286 @@
+// ransac.hip — correspondence RANSAC (utils/utils/open3d.py:145-173: Open3D's registration_ransac_based_on_correspondence with
+// point-to-point estimation without scaling and RANSACConvergenceCriteria(N, N), i.e. every iteration runs), batched over pairs and
+// made deterministic.  The semantics (sampler, hypothesis, score, selection) are stated in include/lcr_hip.h next to the entry points.
+//
+// Three stream-ordered launches per call, no host synchronisation, no allocation:
+//   k_ransac_hyp     one thread per (pair, hypothesis): counter-based sample, fp64 Kabsch (rigid3.h), 12 floats + a valid flag;
+//   k_ransac_score   the hot path.  One wavefront owns 64 hypotheses of one pair, one per lane, its transform in registers, and streams the
+//                    pair's correspondences through LDS; every lane reads the same LDS address (a broadcast, no bank conflict).  Per
+//                    (hypothesis, correspondence): 9 FMA for R s + t, 3 subtracts, 1 mul + 2 FMA for d², a compare and two accumulates —
+//                    VALU-issue bound, nothing else close (DESIGN.md "Correspondence RANSAC").  Each wavefront writes its best candidate;
+//   k_ransac_select  one workgroup per pair reduces the candidates in the total order (count desc, SSE asc, h asc).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "common.h"
+#include "rigid3.h"
+
+namespace lcr {
+
+constexpr int RS_TILE = 64;       // hypotheses per scoring workgroup (one wavefront, one hypothesis per lane)
+constexpr int RS_CHUNK = 128;     // correspondences per LDS chunk (4 KB: two float4 per correspondence; 16 KB would cap a CU at 10 waves)
+constexpr int RS_MAX_N = 8;       // largest ransac_n
+constexpr int RS_HYP = 16;        // floats per stored hypothesis: R|t row-major [12], valid flag [12], pad
+
+// Draw j of hypothesis h: SplitMix64 of seed + golden * (1 + 8h + j), mapped to [0, n) by multiply-shift on the high 32 bits.
+__host__ __device__ inline uint32_t ransac_draw(uint64_t seed, int64_t h, int j, uint32_t n) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * static_cast<uint64_t>(1 + 8 * h + j);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return static_cast<uint32_t>(((z >> 32) * static_cast<uint64_t>(n)) >> 32);
+}
+
+// total order of candidates: more inliers, then smaller SSE, then smaller hypothesis index
+__device__ __forceinline__ bool rs_better(int c1, float s1, int h1, int c2, float s2, int h2) {
+  return c1 > c2 || (c1 == c2 && (s1 < s2 || (s1 == s2 && h1 < h2)));
+}
+
+__device__ __forceinline__ void rs_wave_best(int& c, float& s, int& h) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const int oc = __shfl_xor(c, d), oh = __shfl_xor(h, d);
+    const float os = __shfl_xor(s, d);
+    if (rs_better(oc, os, oh, c, s, h)) {
+      c = oc;
+      s = os;
+      h = oh;
+    }
+  }
+}
+
+// one thread per (pair blockIdx.y, hypothesis h): hyp[(s * iters + h) * 16 + 0..11] = R|t, [12] = 1 valid / 0 invalid (R = I, t = 0)
+__global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ src, const float* __restrict__ ref, const int32_t* __restrict__ start,
+                                                    int iters, int rn, uint64_t seed, float* __restrict__ hyp, float* __restrict__ T_all) {
+  const int s = blockIdx.y;
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= iters) return;
+  const int a = start[s], n = start[s + 1] - a;
+  const int64_t g = static_cast<int64_t>(s) * iters + h;
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
+  bool ok = false;
+  if (n >= rn) {
+    double ps[RS_MAX_N][3], pr[RS_MAX_N][3], cs[3] = {0, 0, 0}, cr[3] = {0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < RS_MAX_N; ++j) {
+      if (j < rn) {
+        const int64_t i = a + static_cast<int64_t>(ransac_draw(seed, h, j, static_cast<uint32_t>(n)));
+        for (int d = 0; d < 3; ++d) {
+          ps[j][d] = src[3 * i + d];
+          pr[j][d] = ref[3 * i + d];
+          cs[d] += ps[j][d];
+          cr[d] += pr[j][d];
+        }
+      }
+    }
+    for (int d = 0; d < 3; ++d) {
+      cs[d] /= rn;
+      cr[d] /= rn;
+    }
+    double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+    for (int j = 0; j < RS_MAX_N; ++j)
+      if (j < rn)
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) H[r][c] += (ps[j][r] - cs[r]) * (pr[j][c] - cr[c]);
+    double Rf[3][3], sv[3];
+    rotation_from_H_sv(H, Rf, sv);
+    ok = !(sv[0] <= 1e-30 || sv[1] <= 1e-9 * sv[0]);       // coincident or collinear sample: never selected
+    if (ok) {
+      for (int r = 0; r < 3; ++r) {
+        t[r] = cr[r];
+        for (int c = 0; c < 3; ++c) {
+          R[r][c] = Rf[r][c];
+          t[r] -= Rf[r][c] * cs[c];
+        }
+      }
+    }
+  }
+  float* o = hyp + RS_HYP * g;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) o[4 * r + c] = static_cast<float>(R[r][c]);
+    o[4 * r + 3] = static_cast<float>(t[r]);
+  }
+  o[12] = ok ? 1.f : 0.f;
+  if (T_all) {
+    float* q = T_all + 16 * g;
+    for (int k = 0; k < 12; ++k) q[k] = o[k];
+    q[12] = q[13] = q[14] = 0.f;
+    q[15] = 1.f;
+  }
+}
+
+// one wavefront per (tile blockIdx.x of 64 hypotheses, pair blockIdx.y); writes the tile's best (count, sse, h) candidate
+__global__ __launch_bounds__(RS_TILE) void k_ransac_score(const float* __restrict__ src, const float* __restrict__ ref, const int32_t* __restrict__ start,
+                                                          int iters, float thr2, const float* __restrict__ hyp, int32_t* __restrict__ cand_count,
+                                                          float* __restrict__ cand_sse, int32_t* __restrict__ cand_h, int32_t* __restrict__ counts_all,
+                                                          float* __restrict__ sse_all) {
+  __shared__ float4 sh[2 * RS_CHUNK];
+  const int s = blockIdx.y, lane = threadIdx.x;
+  const int h = blockIdx.x * RS_TILE + lane;
+  const bool live = h < iters;
+  const int a = start[s], n = start[s + 1] - a;
+  const int64_t g = static_cast<int64_t>(s) * iters + (live ? h : 0);
+  float m[12];
+  const float4* hv = reinterpret_cast<const float4*>(hyp + RS_HYP * g);
+  const float4 m0 = hv[0], m1 = hv[1], m2 = hv[2], m3 = hv[3];
+  m[0] = m0.x, m[1] = m0.y, m[2] = m0.z, m[3] = m0.w;
+  m[4] = m1.x, m[5] = m1.y, m[6] = m1.z, m[7] = m1.w;
+  m[8] = m2.x, m[9] = m2.y, m[10] = m2.z, m[11] = m2.w;
+  const bool valid = live && m3.x != 0.f;
+  int cnt = 0;
+  float sse = 0.f;
+  if (wave_ballot(valid) != 0) {                         // wave-uniform: pairs without a valid hypothesis skip the stream
+    for (int c0 = 0; c0 < n; c0 += RS_CHUNK) {
+      const int cn = min(RS_CHUNK, n - c0);
+      __syncthreads();
+      for (int k = lane; k < cn; k += RS_TILE) {
+        const int64_t i = a + static_cast<int64_t>(c0 + k);
+        sh[2 * k] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], ref[3 * i]);
+        sh[2 * k + 1] = make_float4(ref[3 * i + 1], ref[3 * i + 2], 0.f, 0.f);
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int k = 0; k < cn; ++k) {
+        const float4 p = sh[2 * k], q = sh[2 * k + 1];
+        const float dx = fmaf(m[2], p.z, fmaf(m[1], p.y, fmaf(m[0], p.x, m[3]))) - p.w;
+        const float dy = fmaf(m[6], p.z, fmaf(m[5], p.y, fmaf(m[4], p.x, m[7]))) - q.x;
+        const float dz = fmaf(m[10], p.z, fmaf(m[9], p.y, fmaf(m[8], p.x, m[11]))) - q.y;
+        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+        const bool in = d2 < thr2;
+        cnt += in ? 1 : 0;
+        sse += in ? d2 : 0.f;
+      }
+    }
+  }
+  if (!valid) {
+    cnt = -1;
+    sse = 0.f;
+  }
+  if (live && counts_all) counts_all[g] = cnt;
+  if (live && sse_all) sse_all[g] = sse;
+  int bc = live ? cnt : INT_MIN, bh = live ? h : INT_MAX;
+  float bs = sse;
+  rs_wave_best(bc, bs, bh);
+  if (lane == 0) {
+    const int64_t o = static_cast<int64_t>(s) * gridDim.x + blockIdx.x;
+    cand_count[o] = bc;
+    cand_sse[o] = bs;
+    cand_h[o] = bh;
+  }
+}
+
+// one workgroup per pair: best of the pair's `tiles` candidates; a winner needs at least one inlier (else identity, 0 inliers, best_h -1)
+__global__ __launch_bounds__(256) void k_ransac_select(const float* __restrict__ hyp, int iters, int tiles, const int32_t* __restrict__ cand_count,
+                                                       const float* __restrict__ cand_sse, const int32_t* __restrict__ cand_h, float* __restrict__ T,
+                                                       int32_t* __restrict__ inliers, float* __restrict__ rmse, int32_t* __restrict__ best_h) {
+  __shared__ int s_c[4], s_h[4];
+  __shared__ float s_s[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int bc = INT_MIN, bh = INT_MAX;
+  float bs = 0.f;
+  for (int k = tid; k < tiles; k += blockDim.x) {
+    const int64_t o = static_cast<int64_t>(s) * tiles + k;
+    const int c = cand_count[o], h = cand_h[o];
+    const float e = cand_sse[o];
+    if (rs_better(c, e, h, bc, bs, bh)) {
+      bc = c;
+      bs = e;
+      bh = h;
+    }
+  }
+  rs_wave_best(bc, bs, bh);
+  if ((tid & 63) == 0) {
+    s_c[tid >> 6] = bc;
+    s_s[tid >> 6] = bs;
+    s_h[tid >> 6] = bh;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < static_cast<int>(blockDim.x >> 6); ++w)
+    if (rs_better(s_c[w], s_s[w], s_h[w], bc, bs, bh)) {
+      bc = s_c[w];
+      bs = s_s[w];
+      bh = s_h[w];
+    }
+  float* o = T + 16 * s;
+  if (bc >= 1) {
+    const float* m = hyp + RS_HYP * (static_cast<int64_t>(s) * iters + bh);
+    for (int k = 0; k < 12; ++k) o[k] = m[k];
+    inliers[s] = bc;
+    rmse[s] = sqrtf(bs / static_cast<float>(bc));
+    if (best_h) best_h[s] = bh;
+  } else {
+    for (int k = 0; k < 12; ++k) o[k] = (k % 5 == 0) ? 1.f : 0.f;
+    inliers[s] = 0;
+    rmse[s] = 0.f;
+    if (best_h) best_h[s] = -1;
+  }
+  o[12] = o[13] = o[14] = 0.f;
+  o[15] = 1.f;
+}
+
+}  // namespace lcr
+
+using namespace lcr;
+
+static int ransac_domain(int S, int ransac_n, int iterations, const char* what) {
+  if (S < 1 || S > 65535 || ransac_n < 3 || ransac_n > RS_MAX_N || iterations < 1 || iterations > 1000000) {
+    set_error("%s: outside the domain (1 <= S <= 65535, 3 <= ransac_n <= 8, 1 <= iterations <= 1e6): S=%d ransac_n=%d iterations=%d", what, S,
+              ransac_n, iterations);
+    return LCR_EARG;
+  }
+  return LCR_OK;
+}
+
+extern "C" int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, int ransac_n, int64_t n, int32_t* idx_host) {
+  if (!idx_host || h0 < 0 || count < 0 || h0 + count > 1000000 || ransac_n < 1 || ransac_n > RS_MAX_N || n < 1 || n > INT32_MAX) {
+    set_error("lcr_ransac_sample_host: bad argument (h0=%lld count=%lld ransac_n=%d n=%lld)", static_cast<long long>(h0),
+              static_cast<long long>(count), ransac_n, static_cast<long long>(n));
+    return LCR_EARG;
+  }
+  for (int64_t k = 0; k < count; ++k)
+    for (int j = 0; j < ransac_n; ++j) idx_host[k * ransac_n + j] = static_cast<int32_t>(ransac_draw(seed, h0 + k, j, static_cast<uint32_t>(n)));
+  return LCR_OK;
+}
+
+extern "C" int lcr_ransac_ws_bytes(int S, int iterations, size_t* bytes) {
+  if (!bytes) return LCR_EARG;
+  if (ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ws_bytes") != LCR_OK) return LCR_EARG;
+  const size_t tiles = static_cast<size_t>(div_up(iterations, RS_TILE));
+  Carver c(nullptr, ~size_t(0));
+  c.take<float>(static_cast<size_t>(S) * iterations * RS_HYP);   // hypotheses + valid flags
+  c.take<int32_t>(S * tiles);                                     // per-tile best count
+  c.take<float>(S * tiles);                                       // its SSE
+  c.take<int32_t>(S * tiles);                                     // its hypothesis index
+  *bytes = c.off;
+  return LCR_OK;
+}
+
+extern "C" int lcr_ransac_correspondences(const float* src, const float* ref, const int32_t* start, int S, float thr, int ransac_n, int iterations,
+                                          uint64_t seed, float* T, int32_t* inliers, float* rmse, int32_t* best_h, float* T_all, int32_t* counts_all,
+                                          float* sse_all, void* ws, size_t ws_bytes, void* stream) {
+  if (ransac_domain(S, ransac_n, iterations, "lcr_ransac_correspondences") != LCR_OK) return LCR_EARG;
+  if (!src || !ref || !start || !T || !inliers || !rmse || !ws || !(thr > 0.f) || !std::isfinite(thr) || !std::isfinite(thr * thr)) {
+    set_error("lcr_ransac_correspondences: null pointer or distance threshold not finite and > 0 (thr=%g)", static_cast<double>(thr));
+    return LCR_EARG;
+  }
+  size_t need = 0;
+  lcr_ransac_ws_bytes(S, iterations, &need);
+  if (need > ws_bytes) {
+    set_error("lcr_ransac_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    return LCR_ESPACE;
+  }
+  const int tiles = div_up(iterations, RS_TILE);
+  Carver c(ws, ws_bytes);
+  float* hyp = c.take<float>(static_cast<size_t>(S) * iterations * RS_HYP);
+  int32_t* cc = c.take<int32_t>(static_cast<size_t>(S) * tiles);
+  float* cs = c.take<float>(static_cast<size_t>(S) * tiles);
+  int32_t* ch = c.take<int32_t>(static_cast<size_t>(S) * tiles);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iterations, 256), S), dim3(256), 0, st, src, ref, start, iterations, ransac_n, seed, hyp, T_all);
+  hipLaunchKernelGGL(k_ransac_score, dim3(tiles, S), dim3(RS_TILE), 0, st, src, ref, start, iterations, thr * thr, hyp, cc, cs, ch, counts_all, sse_all);
+  hipLaunchKernelGGL(k_ransac_select, dim3(S), dim3(256), 0, st, hyp, iterations, tiles, cc, cs, ch, T, inliers, rmse, best_h);
+  return check_launch("lcr_ransac_correspondences");
+}

@@ -171,3 +171,21 @@ def registration_summary(gt_transforms, est_transforms, rre_threshold=5.0, rte_t
     m = np.mean(np.asarray(kept, dtype=np.float64), axis=0) if kept else np.full(5, np.nan)
     return {"RR": float(np.mean(acc)) if acc else 0.0, "RRE": float(m[0]), "RTE": float(m[1]), "Rx": float(m[2]), "Ry": float(m[3]),
             "Rz": float(m[4]), "pairs": len(acc), "accepted": len(kept)}
+
+
+# ---- fine-matching metrics of experiments/registration/eval.py:136-156 (utils/utils/registration.py:188-193, 303-317) -------------------
+def inlier_ratio(ref_corr_points, src_corr_points, transform, positive_radius=0.1):
+    """Share of correspondences with |ref - T src| < radius, T (4,4) applied as points @ R^T + t (registration.py:188-193)."""
+    T = np.asarray(transform, dtype=np.float64)
+    src = np.asarray(src_corr_points) @ T[:3, :3].T + T[:3, 3]
+    residuals = np.sqrt(((np.asarray(ref_corr_points) - src) ** 2).sum(1))
+    return float(np.mean(residuals < positive_radius))
+
+
+def fine_matching_metrics(ref_corr_points, src_corr_points, transform, acceptance_radius=0.6, inlier_ratio_threshold=0.05):
+    """One pair's fine-matching block (eval.py:136-156 with config_reg.py:64-65): IR at the acceptance radius, at 0.3 m and 0.1 m, FMR
+    (IR >= inlier_ratio_threshold) and the number of correspondences."""
+    ir = inlier_ratio(ref_corr_points, src_corr_points, transform, acceptance_radius)
+    return {"IR": ir, "IR@0.3": inlier_ratio(ref_corr_points, src_corr_points, transform, 0.3),
+            "IR@0.1": inlier_ratio(ref_corr_points, src_corr_points, transform, 0.1), "FMR": float(ir >= inlier_ratio_threshold),
+            "num_corr": int(np.asarray(ref_corr_points).shape[0])}

@@ -746,3 +746,37 @@ def inlier_weights(T_all, sel, src, ref, score, radius):
     _lib.check(_L().lcr_inlier_weights(_lib.ptr(T_all), _lib.ptr(sel), _lib.ptr(src), _lib.ptr(ref), _lib.ptr(score), src.shape[0], float(radius),
                                        _lib.ptr(w), _sp(T_all)), "lcr_inlier_weights")
     return w
+
+
+def ransac_correspondences(src, ref, start, distance_threshold, ransac_n, num_iterations, seed=0, want_details=False):
+    """Deterministic correspondence RANSAC (include/lcr_hip.h, lcr_ransac_correspondences) for S pairs in one native call:
+    src / ref f32 [n,3] stacked pair-major, start int32 [S+1] -> T [S,4,4] (src onto ref), inliers int32 [S], rmse f32 [S], best_h int32 [S]
+    (and with want_details every hypothesis [S*iters,4,4], its inlier count [S*iters] (-1 = invalid) and inlier SSE [S*iters])."""
+    _lib.require_cuda(src, ref, start)
+    dev = src.device
+    S, iters = start.numel() - 1, int(num_iterations)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_ransac_ws_bytes(S, iters, ctypes.byref(nbytes)), "lcr_ransac_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty((S,), dtype=torch.int32, device=dev)
+    rmse = torch.empty((S,), dtype=torch.float32, device=dev)
+    best = torch.empty((S,), dtype=torch.int32, device=dev)
+    T_all = torch.empty((S * iters, 4, 4), dtype=torch.float32, device=dev) if want_details else None
+    counts = torch.empty((S * iters,), dtype=torch.int32, device=dev) if want_details else None
+    sse = torch.empty((S * iters,), dtype=torch.float32, device=dev) if want_details else None
+    _lib.check(_L().lcr_ransac_correspondences(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S,
+                                               float(distance_threshold), int(ransac_n), iters, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(T),
+                                               _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best), _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse),
+                                               _lib.ptr(ws), ws.numel(), _sp(src)), "lcr_ransac_correspondences")
+    if want_details:
+        return T, inliers, rmse, best, T_all, counts, sse
+    return T, inliers, rmse, best
+
+
+def ransac_sample_host(seed, h0, count, ransac_n, n):
+    """The RANSAC sampler on the host (no GPU): int32 [count, ransac_n] row indices of hypotheses h0 .. h0+count-1 for a pair of n rows."""
+    out = np.empty((int(count), int(ransac_n)), dtype=np.int32)
+    _lib.check(_L().lcr_ransac_sample_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(h0), int(count), int(ransac_n), int(n), out.ctypes.data),
+               "lcr_ransac_sample_host")
+    return out

@@ -1,0 +1,140 @@
+#!/usr/bin/env python
+"""Registration evaluation over saved pair files: the counterpart of experiments/registration/eval.py.
+
+    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd] [--num_corr K] [--seed S] [--pairs-per-call P]
+                                      [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000] [--write-back]
+
+Reads every `{seq}_{anc}_{pos}.npz` of FEATURES_DIR (what io_formats.save_registration / demo.py write; both the pos_/anc_ and the
+ref_/src_ key families of eval.py:96-110 are accepted), keeps the top --num_corr correspondences by corr_scores (:114-118), and
+registers the anchor onto the positive:
+  lgr     the stored `estimated_transform` (falls back to `estimated_transform_lgr`, :171-175);
+  ransac  the deterministic GPU RANSAC of lcrnet_amd.registration with src = anchor, ref = positive and the reference's settings
+          (config_reg.py:69-73: 0.3 m, 4 points, 50 000 iterations); --pairs-per-call pairs go into one native call;
+          --write-back stores `estimated_transform_ransac` in the file as :184-185 do;
+  svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group.
+Prints the reference's Fine Matching line (FMR / IR at acceptance_radius 0.6 with inlier_ratio_threshold 0.05, IR@0.3, IR@0.1,
+num_Corr; config_reg.py:64-65) and Registration line (RR, RRE, RTE, Rx, Ry, Rz: evaluation.registration_summary), then one JSON line.
+Coarse-matching metrics are not computed: the shipped model writes empty gt_node_corr_indices (io_formats.save_registration).
+Like eval.py:92-94 the pair seq 8, anchor 15, positive 58 is skipped."""
+import argparse
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from lcrnet_amd import evaluation as ev  # noqa: E402
+from lcrnet_amd import io_formats as io  # noqa: E402
+
+
+def parse_name(path):
+    seq, anc, pos = os.path.splitext(os.path.basename(path))[0].split("_")
+    try:
+        seq = int(seq)
+    except ValueError:
+        pass
+    return seq, int(anc), int(pos)
+
+
+def load_pair(path, num_corr):
+    d = io.load_registration(path)
+    if "pos_corr_points" in d:
+        pos, anc = d["pos_corr_points"], d["anc_corr_points"]
+    else:
+        pos, anc = d["ref_corr_points"], d["src_corr_points"]
+    scores = d["corr_scores"]
+    if num_corr is not None and scores.shape[0] > num_corr:
+        sel = np.argsort(-scores)[:num_corr]
+        pos, anc, scores = pos[sel], anc[sel], scores[sel]
+    return d, np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(anc, np.float32), np.ascontiguousarray(scores, np.float32)
+
+
+def stacked(items, device):
+    """[(src, ref, w)] -> device tensors stacked pair-major and the int32 [S+1] row offsets."""
+    import torch
+    lens = [len(s) for s, _, _ in items]
+    start = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    cat = lambda k: torch.from_numpy(np.concatenate([it[k] for it in items]) if items else np.zeros((0, 3), np.float32)).to(device)
+    return cat(0).reshape(-1, 3), cat(1).reshape(-1, 3), cat(2).reshape(-1), torch.from_numpy(start).to(device)
+
+
+def estimate_group(method, items, args, device):
+    """Transforms (S,4,4) float64 for a group of pairs in one native call."""
+    import torch
+    src, ref, w, start = stacked(items, device)
+    if method == "ransac":
+        from lcrnet_amd.registration import ransac_batched
+        T, _, _ = ransac_batched(src, ref, start, args.distance_threshold, args.ransac_n, args.num_iterations, args.seed)
+    else:
+        from lcrnet_amd import functional as F
+        T = F.procrustes(src, ref, w, start)
+    torch.cuda.synchronize(device)
+    return T.cpu().numpy().astype(np.float64)
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("features_dir")
+    p.add_argument("--method", choices=["lgr", "ransac", "svd"], default="lgr")
+    p.add_argument("--num_corr", type=int, default=None)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--pairs-per-call", type=int, default=16)
+    p.add_argument("--distance-threshold", type=float, default=0.3)
+    p.add_argument("--ransac-n", type=int, default=4)
+    p.add_argument("--num-iterations", type=int, default=50000)
+    p.add_argument("--write-back", action="store_true", help="store estimated_transform_ransac in each file (eval.py:184-185)")
+    args = p.parse_args(argv)
+    if args.pairs_per_call < 1:
+        p.error("--pairs-per-call must be >= 1")
+
+    files = sorted(glob.glob(os.path.join(args.features_dir, "*.npz")))
+    pairs = []
+    for f in files:
+        seq, anc, pos = parse_name(f)
+        if seq == 8 and anc == 15 and pos == 58:          # eval.py:92-94 ("delete bad data")
+            continue
+        d, pos_pts, anc_pts, scores = load_pair(f, args.num_corr)
+        pairs.append((f, d, pos_pts, anc_pts, scores))
+
+    t0 = time.perf_counter()
+    if args.method == "lgr":
+        est = [d["estimated_transform"] for _, d, _, _, _ in pairs]         # as stored (f32), like eval.py:171-175
+    else:
+        import torch
+        device = torch.device("cuda", torch.cuda.current_device())
+        est = []
+        for g in range(0, len(pairs), args.pairs_per_call):
+            group = pairs[g:g + args.pairs_per_call]
+            est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
+    seconds = time.perf_counter() - t0
+
+    if args.method == "ransac" and args.write_back:
+        for (f, d, _, _, _), T in zip(pairs, est):
+            modified = dict(d)
+            modified["estimated_transform_ransac"] = T
+            np.savez(f, **modified)
+
+    fine = [ev.fine_matching_metrics(b, a, d["transform"]) for _, d, b, a, _ in pairs]
+    fm = {k: float(np.mean([x[k] for x in fine])) if fine else float("nan") for k in ("FMR", "IR", "IR@0.3", "IR@0.1", "num_corr")}
+    reg = ev.registration_summary([d["transform"] for _, d, _, _, _ in pairs], est)
+    print("Pairs: %d" % len(files))
+    print("  Fine Matching, FMR: {:.4f}, IR: {:.3f}, IR@0.3: {:.3f}, IR@0.1: {:.3f}, num_Corr: {:.3f}".format(
+        fm["FMR"], fm["IR"], fm["IR@0.3"], fm["IR@0.1"], fm["num_corr"]))
+    print("  Registration, RR: {:.4f}, RRE: {:.3f}, RTE: {:.3f}, Rx: {:.3f}, Ry: {:.3f}, Rz: {:.3f}".format(
+        reg["RR"], reg["RRE"], reg["RTE"], reg["Rx"], reg["Ry"], reg["Rz"]))
+    out = {"method": args.method, "pairs": reg["pairs"], "accepted": reg["accepted"], "fine_matching": fm,
+           "registration": {k: reg[k] for k in ("RR", "RRE", "RTE", "Rx", "Ry", "Rz")}, "seconds": seconds,
+           "num_corr": args.num_corr, "seed": args.seed, "pairs_per_call": args.pairs_per_call}
+    if args.method == "ransac":
+        out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()
