@@ -551,6 +551,37 @@ int lcr_ransac_correspondences(const float* src, const float* ref, const int32_t
  * 1 <= ransac_n <= 8, 0 <= h0, h0 + count <= 1e6). */
 int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, int ransac_n, int64_t n, int32_t* idx_host);
 
+/* Point-to-point ICP (Open3D's RegistrationICP with TransformationEstimationPointToPoint(with_scaling=False), as the reference's pair
+ * generators run it: data/Kitti/generate_kitti_pairs.py:145-147) for S pairs in one call, made exact and batch-invariant.
+ *   - Pairs: source rows stacked pair-major in src f32[ns,3], target rows in tgt f32[nt,3]; src_len / tgt_len are HOST int64[S].
+ *     init f64[S,4,4] maps source onto target.  Coordinates must be finite (the domain; not checked on the device).
+ *   - Correspondence step at pose T (fp64): source row i (x, y, z) becomes q = fp32(((T00*x + T01*y) + T02*z) + T03) (likewise y, z; no
+ *     contraction).  Its partner is the target row of the same pair with the smallest (d2, row) among those with d2 < r*r (fp32 product),
+ *     d2 = ((dx*dx)+dy*dy)+dz*dz in fp32 without FMA: the row lcr_radius_query_ordered(..., limit = 1) returns for q.
+ *     count = partnered rows, fitness = count / n_src, inlier_rmse = sqrt(sum d2 / count) with the sum in fp64 (0 when count = 0).
+ *   - Update: unit-weight Kabsch on the ORIGINAL source rows p_i and their partners r_j: fp64 centroids and H (moments accumulated
+ *     about the first source / target row of the pair), R from the fp64 Jacobi SVD (reflection fixed on the smallest singular
+ *     direction), T <- [R | c_r - R c_p] (equal to Open3D's update * T in exact arithmetic).  T is left unchanged when count < 3 or
+ *     H is degenerate (sigma_2 <= 1e-9 sigma_1 or sigma_1 <= 1e-30).
+ *   - Loop (Registration.cpp): result_0 at init; for k = 0 .. max_iteration-1: update, result_{k+1}; stop when
+ *     |fitness_{k+1} - fitness_k| < relative_fitness AND |rmse_{k+1} - rmse_k| < relative_rmse.  iterations = updates performed.
+ *   - Outputs at the final T: T f64[S,4,4], fitness f64[S], inlier_rmse f64[S], iterations i32[S].  Nullable: corr i32[ns] (pair-local
+ *     target row of every source row at the final T, or -1), T_hist f64[S, max_iteration+1, 4, 4], fitness_hist / rmse_hist
+ *     f64[S, max_iteration+1] (row k = T_k and result_k for k <= iterations; later rows are not written).
+ *   - A pair with an empty source or target returns init, fitness 0, rmse 0, iterations 0; max_iteration = 0 returns init with result_0.
+ *   - Determinism: every reduction is a fixed tree over the pair's own rows (no float atomics): a pair gives bit-identical outputs alone
+ *     or at any position in any batch, and for any check_every.
+ *   - Host loop: per iteration two launches; every check_every iterations one 4-byte read-back and a stream synchronisation, stopping
+ *     once no pair runs; check_every = 0 never synchronises (all max_iteration trips; finished pairs are no-ops).  No allocation;
+ *     ws: lcr_icp_ws_bytes(S, ns, nt).
+ * Domain: 1 <= S <= 64, 0 <= max_iteration <= 100000, 0 < r with r*r finite, relative criteria >= 0, check_every >= 0, ns, nt <= 2^31-1;
+ * LCR_EARG outside. */
+int lcr_icp_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes);
+int lcr_icp_point_to_point(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, int S, const double* init,
+                           float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse, double* T,
+                           double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist,
+                           double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

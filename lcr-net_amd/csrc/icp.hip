@@ -1,0 +1,374 @@
+// icp.hip — point-to-point ICP (Open3D's RegistrationICP with TransformationEstimationPointToPoint, as the reference's pair generators
+// run it: data/Kitti/generate_kitti_pairs.py:145-147) for S pairs of dense clouds in one call, exact and batch-invariant.  The semantics
+// (correspondence step, update, loop, outputs) are stated in include/lcr_hip.h next to the entry points.
+//
+// Per call: k_icp_init (state from `init`, target lengths to the device), the support grid of radius_search.hip over the targets
+// (cell >= r, built once), then per iteration two stream-ordered launches:
+//   k_icp_match   the hot path.  One thread per source row (a block = ICP_BLOCK consecutive rows of one pair): fp64 transform to fp32 q,
+//                 arg-min of the (d², target row) key over the nine x-runs of q's 3x3x3 cell neighbourhood (the rule of
+//                 lcr_radius_query_ordered's limit == 1 rows), and the row's moments about the pair's anchors reduced over the block in a
+//                 fixed tree into a slab of 17 doubles per block.  A block of a finished pair exits at once.
+//   k_icp_update  one workgroup per pair: the pair's slab rows summed in a fixed order, fitness / rmse, the convergence test, the fp64
+//                 Kabsch (rigid3.h), the history rows, the `done` flag and the count of pairs still running.
+// Why one thread per query and not one wavefront (k_radius_query's form): a nearest-only query needs no row, no sort and no LDS.  Here a
+// lane spends 18.25 VALU instructions per candidate (ISA, 4 candidates per trip), and a wavefront serves 64 queries at once; the
+// cooperative form adds per query a 9-run setup, a prefix scan, an LDS compaction of every in-radius candidate and a 12-shuffle arg-min.
+// Source rows are processed in scan order, so neighbouring lanes query neighbouring cells and their trip counts stay close.  Measured on
+// raw scans at r = 0.5 m (~1 180 candidates per query): one iteration (both kernels) for 1.36 M queries costs 1.9 ms, while
+// lcr_radius_query_ordered(limit = 1) on the same queries takes 8.1 s, because balls of more than 512 rows take its exact
+// re-enumeration path (DESIGN.md "Point-to-point ICP").
+// Reductions never use float atomics: every sum is a fixed tree over the pair's own row indices, so a pair gives the same bits alone or
+// at any position in any batch.
+#include <climits>
+#include <cmath>
+
+#include "common.h"
+#include "grid.h"
+#include "rigid3.h"
+
+namespace lcr {
+
+constexpr int ICP_BLOCK = 256;   // source rows (= threads) per k_icp_match workgroup; also the k_icp_update workgroup size
+constexpr int ICP_UNROLL = 4;    // candidate loads in flight per lane
+constexpr int ICP_MOM = 17;      // count, sum d², sum dp[3], sum dr[3], sum dp dr^T [9]  (dp = p - anchor_src, dr = r - anchor_tgt)
+
+// pair table, by value in the kernel arguments (S <= GRID_MAX_B): stacked row offsets and the first k_icp_match block of every pair
+struct IcpPairs {
+  int     S;
+  int     blk_off[GRID_MAX_B + 1];
+  int64_t src_off[GRID_MAX_B + 1];
+  int64_t tgt_off[GRID_MAX_B + 1];
+};
+
+__device__ __forceinline__ double dadd(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double dmul(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// fp32(((T[4r] * x + T[4r+1] * y) + T[4r+2] * z) + T[4r+3]), no contraction
+__device__ __forceinline__ float icp_row(const double* T, int r, double x, double y, double z) {
+  return static_cast<float>(dadd(dadd(dadd(dmul(T[4 * r], x), dmul(T[4 * r + 1], y)), dmul(T[4 * r + 2], z)), T[4 * r + 3]));
+}
+
+// fixed-order sum of ICP_MOM doubles over a workgroup of ICP_BLOCK threads; the totals land in thread 0's m[]
+__device__ __forceinline__ void icp_block_sum(double (&m)[ICP_MOM], double (*s_red)[ICP_MOM]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < ICP_MOM; ++j)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m[j] = dadd(m[j], __shfl_xor(m[j], d));
+  if (lane == 0)
+#pragma unroll
+    for (int j = 0; j < ICP_MOM; ++j) s_red[w][j] = m[j];
+  __syncthreads();
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int j = 0; j < ICP_MOM; ++j) {
+      double a = s_red[0][j];
+      for (int v = 1; v < ICP_BLOCK / 64; ++v) a = dadd(a, s_red[v][j]);
+      m[j] = a;
+    }
+}
+
+__device__ __forceinline__ int icp_pair_of_block(const IcpPairs& P, int blk) {
+  int s = 0;
+  while (s + 1 < P.S && blk >= P.blk_off[s + 1]) ++s;
+  return s;
+}
+
+__global__ void k_icp_init(IcpPairs P, const double* __restrict__ init, int hist_rows, double* __restrict__ T, double* __restrict__ fitness,
+                           double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ done, int32_t* __restrict__ running,
+                           int64_t* __restrict__ tgt_len, double* __restrict__ T_hist, double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
+  if (threadIdx.x < 2) running[threadIdx.x] = 0;
+  for (int s = threadIdx.x; s < P.S; s += blockDim.x) {
+    const int64_t ns = P.src_off[s + 1] - P.src_off[s], nt = P.tgt_off[s + 1] - P.tgt_off[s];
+    for (int k = 0; k < 16; ++k) T[16 * s + k] = init[16 * s + k];
+    fitness[s] = 0.0;
+    rmse[s] = 0.0;
+    iters[s] = 0;
+    done[s] = (ns == 0 || nt == 0) ? 1 : 0;          // empty source or target: init, fitness 0, rmse 0, 0 iterations
+    tgt_len[s] = nt;
+    const int64_t h0 = static_cast<int64_t>(s) * hist_rows;
+    if (T_hist)
+      for (int k = 0; k < 16; ++k) T_hist[16 * h0 + k] = init[16 * s + k];
+    if (done[s]) {
+      if (fit_hist) fit_hist[h0] = 0.0;
+      if (rmse_hist) rmse_hist[h0] = 0.0;
+    }
+  }
+}
+
+// one thread per source row: correspondence at the pair's current T, moments reduced per block into slab[blockIdx.x][ICP_MOM]
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float* __restrict__ src, const float* __restrict__ tgt,
+                                                         const GridHeader* __restrict__ h, const int32_t* __restrict__ cell_start,
+                                                         const float4* __restrict__ sorted, float r2, const double* __restrict__ T,
+                                                         const int32_t* __restrict__ done, double* __restrict__ slab, int32_t* __restrict__ corr) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_MOM];
+  const int blk = blockIdx.x;
+  const int s = icp_pair_of_block(P, blk);
+  if (done[s]) return;                                         // workgroup-uniform
+  const int64_t a = P.src_off[s], n = P.src_off[s + 1] - a, tb = P.tgt_off[s];
+  const int64_t row = static_cast<int64_t>(blk - P.blk_off[s]) * ICP_BLOCK + threadIdx.x;     // pair-local
+  double m[ICP_MOM];
+#pragma unroll
+  for (int j = 0; j < ICP_MOM; ++j) m[j] = 0.0;
+  if (row < n) {
+    const int64_t i = a + row;
+    double Tm[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
+    const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+    const float qx = icp_row(Tm, 0, x, y, z), qy = icp_row(Tm, 1, x, y, z), qz = icp_row(Tm, 2, x, y, z);
+    const GridCloud& c = h->cloud[s];
+    uint64_t best = ~0ull;
+    if (c.dim[0] > 0) {
+      // the cells of cell_coord() (clamped to [-2, dim+1]) and their 3x3x3 neighbourhood inside the box, as k_radius_query enumerates them
+      const int cx = cell_coord(qx, c.org[0], c.inv_cell, c.dim[0]);
+      const int cy = cell_coord(qy, c.org[1], c.inv_cell, c.dim[1]);
+      const int cz = cell_coord(qz, c.org[2], c.inv_cell, c.dim[2]);
+      const int x0 = max(cx - 1, 0), x1 = min(cx + 1, c.dim[0] - 1);
+      if (x0 <= x1) {
+        for (int zz = max(cz - 1, 0); zz <= min(cz + 1, c.dim[2] - 1); ++zz)
+          for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.dim[1] - 1); ++yy) {
+            const int crow = c.cell_base + (zz * c.dim[1] + yy) * c.dim[0];
+            const int e = cell_start[crow + x1 + 1];
+            // ICP_UNROLL loads in flight per trip; the tail re-reads the run's last candidate, which cannot change an arg-min
+            for (int k = cell_start[crow + x0]; k < e; k += ICP_UNROLL) {
+              float4 p[ICP_UNROLL];
+#pragma unroll
+              for (int u = 0; u < ICP_UNROLL; ++u) p[u] = sorted[min(k + u, e - 1)];
+#pragma unroll
+              for (int u = 0; u < ICP_UNROLL; ++u) {
+                const float dx = fsub(qx, p[u].x), dy = fsub(qy, p[u].y), dz = fsub(qz, p[u].z);
+                const float d2 = fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
+                const uint64_t key = (static_cast<uint64_t>(__float_as_uint(d2)) << 32) | __float_as_uint(p[u].w);
+                best = (d2 < r2 && key < best) ? key : best;
+              }
+            }
+          }
+      }
+    }
+    int32_t j_loc = -1;
+    if (best != ~0ull) {
+      const int64_t j = static_cast<int64_t>(static_cast<uint32_t>(best));
+      j_loc = static_cast<int32_t>(j - tb);
+      const double d2 = static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32)));
+      const double dp[3] = {x - static_cast<double>(src[3 * a]), y - static_cast<double>(src[3 * a + 1]), z - static_cast<double>(src[3 * a + 2])};
+      const double dr[3] = {static_cast<double>(tgt[3 * j]) - static_cast<double>(tgt[3 * tb]),
+                            static_cast<double>(tgt[3 * j + 1]) - static_cast<double>(tgt[3 * tb + 1]),
+                            static_cast<double>(tgt[3 * j + 2]) - static_cast<double>(tgt[3 * tb + 2])};
+      m[0] = 1.0;
+      m[1] = d2;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        m[2 + r] = dp[r];
+        m[5 + r] = dr[r];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) m[8 + 3 * r + q] = dmul(dp[r], dr[q]);
+      }
+    }
+    if (corr) corr[i] = j_loc;
+  }
+  icp_block_sum(m, s_red);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int j = 0; j < ICP_MOM; ++j) slab[static_cast<int64_t>(blk) * ICP_MOM + j] = m[j];
+}
+
+// one workgroup per pair: result_k from the slab, convergence test against result_{k-1}, then update k (T_{k+1}) unless the pair stops
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_update(IcpPairs P, const float* __restrict__ src, const float* __restrict__ tgt,
+                                                          const double* __restrict__ slab, int k, int max_iter, double rel_fit, double rel_rmse,
+                                                          double* __restrict__ T, double* __restrict__ fitness, double* __restrict__ rmse,
+                                                          int32_t* __restrict__ iters, int32_t* __restrict__ done, int32_t* __restrict__ running,
+                                                          double* __restrict__ T_hist, double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_MOM];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (s == 0 && tid == 0) running[(k + 1) & 1] = 0;          // the other slot: read by the host after the previous launch, if at all
+  if (done[s]) return;
+  const int b0 = P.blk_off[s], nb = P.blk_off[s + 1] - b0;
+  double m[ICP_MOM];
+#pragma unroll
+  for (int j = 0; j < ICP_MOM; ++j) m[j] = 0.0;
+  for (int b = tid; b < nb; b += ICP_BLOCK)
+#pragma unroll
+    for (int j = 0; j < ICP_MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * ICP_MOM + j]);
+  icp_block_sum(m, s_red);
+  if (tid != 0) return;
+
+  const int64_t a = P.src_off[s], ns = P.src_off[s + 1] - a, tb = P.tgt_off[s];
+  const int hist_rows = max_iter + 1;
+  const int64_t hrow = static_cast<int64_t>(s) * hist_rows;
+  const double cnt = m[0];
+  const double fit = cnt / static_cast<double>(ns);
+  const double rm = cnt > 0.0 ? sqrt(m[1] / cnt) : 0.0;
+  const bool conv = k > 0 && fabs(fitness[s] - fit) < rel_fit && fabs(rmse[s] - rm) < rel_rmse;
+  fitness[s] = fit;
+  rmse[s] = rm;
+  if (fit_hist) fit_hist[hrow + k] = fit;
+  if (rmse_hist) rmse_hist[hrow + k] = rm;
+  if (conv || k >= max_iter) {
+    done[s] = 1;
+    return;
+  }
+  // update k: unit-weight Kabsch on (p_i, r_j) about the anchors; T unchanged when count < 3 or H is degenerate
+  double Tn[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) Tn[q] = T[16 * s + q];
+  if (cnt >= 3.0) {
+    const double ap[3] = {src[3 * a], src[3 * a + 1], src[3 * a + 2]}, ar[3] = {tgt[3 * tb], tgt[3 * tb + 1], tgt[3 * tb + 2]};
+    double H[3][3], cp[3], cr[3];
+    for (int r = 0; r < 3; ++r) {
+      cp[r] = m[2 + r] / cnt;                                  // centroids relative to the anchors
+      cr[r] = m[5 + r] / cnt;
+    }
+    for (int r = 0; r < 3; ++r)
+      for (int q = 0; q < 3; ++q) H[r][q] = m[8 + 3 * r + q] - cnt * cp[r] * cr[q];
+    double R[3][3], sv[3];
+    rotation_from_H_sv(H, R, sv);
+    if (!(sv[0] <= 1e-30 || sv[1] <= 1e-9 * sv[0])) {
+      for (int r = 0; r < 3; ++r) {
+        const double cpa[3] = {ap[0] + cp[0], ap[1] + cp[1], ap[2] + cp[2]};
+        double t = ar[r] + cr[r];
+        for (int q = 0; q < 3; ++q) {
+          Tn[4 * r + q] = R[r][q];
+          t -= R[r][q] * cpa[q];
+        }
+        Tn[4 * r + 3] = t;
+      }
+    }
+  }
+  for (int q = 0; q < 12; ++q) T[16 * s + q] = Tn[q];
+  T[16 * s + 12] = T[16 * s + 13] = T[16 * s + 14] = 0.0;
+  T[16 * s + 15] = 1.0;
+  iters[s] = k + 1;
+  if (T_hist) {
+    double* o = T_hist + 16 * (hrow + k + 1);
+    for (int q = 0; q < 12; ++q) o[q] = Tn[q];
+    o[12] = o[13] = o[14] = 0.0;
+    o[15] = 1.0;
+  }
+  atomicAdd(&running[k & 1], 1);
+}
+
+}  // namespace lcr
+
+using namespace lcr;
+
+namespace {
+constexpr int ICP_MAX_ITER = 100000;
+
+int icp_blocks_bound(int S, int64_t ns) { return div_up(ns, ICP_BLOCK) + S; }
+
+size_t icp_layout(void* ws, int S, int64_t ns, int64_t nt, size_t grid_bytes, double** slab, int32_t** done, int32_t** running, int64_t** tgt_len) {
+  Carver c(ws, ~size_t(0));
+  c.take<char>(grid_bytes);                                      // the support grid, at the workspace base
+  double* sl = c.take<double>(static_cast<size_t>(icp_blocks_bound(S, ns)) * ICP_MOM);
+  int32_t* dn = c.take<int32_t>(S);
+  int32_t* rn = c.take<int32_t>(2);
+  int64_t* tl = c.take<int64_t>(S);
+  if (slab) {
+    *slab = sl;
+    *done = dn;
+    *running = rn;
+    *tgt_len = tl;
+  }
+  (void)nt;
+  return c.off;
+}
+}  // namespace
+
+extern "C" int lcr_icp_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes) {
+  if (!bytes || S < 1 || S > GRID_MAX_B || ns < 0 || nt < 0 || ns > INT32_MAX || nt > INT32_MAX) {
+    set_error("lcr_icp_ws_bytes: outside the domain (1 <= S <= %d, 0 <= ns, nt <= 2^31-1): S=%d ns=%lld nt=%lld", GRID_MAX_B, S,
+              static_cast<long long>(ns), static_cast<long long>(nt));
+    return LCR_EARG;
+  }
+  size_t g = 0;
+  if (lcr_support_grid_ws_bytes(nt, S, &g) != LCR_OK) return LCR_EARG;
+  *bytes = icp_layout(nullptr, S, ns, nt, g, nullptr, nullptr, nullptr, nullptr);
+  return LCR_OK;
+}
+
+extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, int S, const double* init,
+                                      float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
+                                      double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist,
+                                      double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
+  const float r = max_correspondence_distance;
+  if (S < 1 || S > GRID_MAX_B || max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
+      !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0)) {
+    set_error("lcr_icp_point_to_point: outside the domain (1 <= S <= %d, 0 <= max_iteration <= %d, r > 0 with r*r finite, relative "
+              "criteria >= 0, check_every >= 0): S=%d max_iteration=%d r=%g check_every=%d", GRID_MAX_B, ICP_MAX_ITER, S, max_iteration,
+              static_cast<double>(r), check_every);
+    return LCR_EARG;
+  }
+  if (!src_len || !tgt_len || !init || !T || !fitness || !inlier_rmse || !iterations || !ws) {
+    set_error("lcr_icp_point_to_point: null pointer");
+    return LCR_EARG;
+  }
+  IcpPairs P;
+  P.S = S;
+  P.blk_off[0] = 0;
+  P.src_off[0] = P.tgt_off[0] = 0;
+  for (int s = 0; s < S; ++s) {
+    if (src_len[s] < 0 || tgt_len[s] < 0 || src_len[s] > INT32_MAX || tgt_len[s] > INT32_MAX) {
+      set_error("lcr_icp_point_to_point: pair %d has a negative or too large length (%lld, %lld)", s, static_cast<long long>(src_len[s]),
+                static_cast<long long>(tgt_len[s]));
+      return LCR_EARG;
+    }
+    P.src_off[s + 1] = P.src_off[s] + src_len[s];
+    P.tgt_off[s + 1] = P.tgt_off[s] + tgt_len[s];
+    P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
+  }
+  const int64_t ns = P.src_off[S], nt = P.tgt_off[S];
+  if (ns > INT32_MAX || nt > INT32_MAX || (ns > 0 && !src) || (nt > 0 && !tgt)) {
+    set_error("lcr_icp_point_to_point: more than 2^31-1 rows, or a null point array (ns=%lld nt=%lld)", static_cast<long long>(ns),
+              static_cast<long long>(nt));
+    return LCR_EARG;
+  }
+  size_t need = 0, grid_bytes = 0;
+  lcr_icp_ws_bytes(S, ns, nt, &need);
+  lcr_support_grid_ws_bytes(nt, S, &grid_bytes);
+  if (need > ws_bytes) {
+    set_error("lcr_icp_point_to_point: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    return LCR_ESPACE;
+  }
+  double* slab;
+  int32_t *done, *running;
+  int64_t* tgt_len_dev;
+  icp_layout(ws, S, ns, nt, grid_bytes, &slab, &done, &running, &tgt_len_dev);
+  const GridLayout L = grid_layout(ws, nt, S);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, P, init, max_iteration + 1, T, fitness, inlier_rmse, iterations, done, running, tgt_len_dev,
+                     T_hist, fitness_hist, rmse_hist);
+  if (corr && ns > 0 && hipMemsetAsync(corr, 0xff, static_cast<size_t>(ns) * sizeof(int32_t), st) != hipSuccess) {   // -1 for pairs that never run
+    set_error("lcr_icp_point_to_point: clearing corr failed");
+    return LCR_EHIP;
+  }
+  int rc = check_launch("lcr_icp_point_to_point (init)");
+  if (rc) return rc;
+  rc = lcr_support_grid_build(tgt, tgt_len_dev, S, nt, r, nullptr, ws, grid_bytes, stream);
+  if (rc) return rc;
+  const int nblk = P.blk_off[S];
+  const float r2 = r * r;                                        // fp32 product, as lcr_radius_query
+  for (int k = 0; k <= max_iteration; ++k) {
+    if (nblk > 0)
+      hipLaunchKernelGGL(k_icp_match, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, tgt, L.hdr, L.cell_start, L.sorted, r2, T, done, slab, corr);
+    hipLaunchKernelGGL(k_icp_update, dim3(S), dim3(ICP_BLOCK), 0, st, P, src, tgt, slab, k, max_iteration, relative_fitness, relative_rmse, T,
+                       fitness, inlier_rmse, iterations, done, running, T_hist, fitness_hist, rmse_hist);
+    if ((rc = check_launch("lcr_icp_point_to_point"))) return rc;
+    if (check_every > 0 && k < max_iteration && (k + 1) % check_every == 0) {
+      int32_t still = 0;
+      if (hipMemcpyAsync(&still, running + (k & 1), sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess) {
+        set_error("lcr_icp_point_to_point: read-back of the running count failed");
+        return LCR_EHIP;
+      }
+      if (still == 0) break;
+    }
+  }
+  return LCR_OK;
+}

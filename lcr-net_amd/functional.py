@@ -780,3 +780,40 @@ def ransac_sample_host(seed, h0, count, ransac_n, n):
     _lib.check(_L().lcr_ransac_sample_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(h0), int(count), int(ransac_n), int(n), out.ctypes.data),
                "lcr_ransac_sample_host")
     return out
+
+
+def icp_point_to_point(src, src_len, tgt, tgt_len, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                       check_every=16, want_corr=False, want_history=False):
+    """Point-to-point ICP (include/lcr_hip.h, lcr_icp_point_to_point) for S <= 64 pairs in one native call: src f32 [ns,3] / tgt f32 [nt,3]
+    stacked pair-major with host lengths src_len / tgt_len (S ints), init f64 [S,4,4] (source onto target) on the device ->
+    dict(T f64 [S,4,4], fitness f64 [S], inlier_rmse f64 [S], iterations int32 [S]; with want_corr corr int32 [ns] (pair-local target row or -1);
+    with want_history T_hist f64 [S, max_iteration+1, 4, 4], fitness_hist / rmse_hist f64 [S, max_iteration+1], NaN after `iterations`)."""
+    _lib.require_cuda(src, tgt, init)
+    dev = src.device
+    S, iters = len(src_len), int(max_iteration)
+    sl = np.ascontiguousarray(np.asarray(src_len, dtype=np.int64).reshape(-1))
+    tl = np.ascontiguousarray(np.asarray(tgt_len, dtype=np.int64).reshape(-1))
+    if len(tl) != S or init.shape != (S, 4, 4) or init.dtype != torch.float64:
+        raise ValueError("icp_point_to_point: src_len, tgt_len and init [S,4,4] float64 must describe the same S pairs")
+    if src.shape[0] != int(sl.sum()) or tgt.shape[0] != int(tl.sum()):
+        raise ValueError("icp_point_to_point: the point arrays do not hold sum(src_len) / sum(tgt_len) rows")
+    src, tgt, init = src.contiguous(), tgt.contiguous(), init.contiguous()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_icp_ws_bytes(S, src.shape[0], tgt.shape[0], ctypes.byref(nbytes)), "lcr_icp_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"T": torch.empty((S, 4, 4), **f64), "fitness": torch.empty((S,), **f64), "inlier_rmse": torch.empty((S,), **f64),
+           "iterations": torch.empty((S,), dtype=torch.int32, device=dev)}
+    corr = torch.empty((src.shape[0],), dtype=torch.int32, device=dev) if want_corr else None
+    hist = [torch.full((S, iters + 1, 4, 4), float("nan"), **f64), torch.full((S, iters + 1), float("nan"), **f64),
+            torch.full((S, iters + 1), float("nan"), **f64)] if want_history else [None, None, None]
+    _lib.check(_L().lcr_icp_point_to_point(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, S, _lib.ptr(init),
+                                           float(max_correspondence_distance), iters, float(relative_fitness), float(relative_rmse),
+                                           _lib.ptr(out["T"]), _lib.ptr(out["fitness"]), _lib.ptr(out["inlier_rmse"]), _lib.ptr(out["iterations"]),
+                                           _lib.ptr(corr), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]), int(check_every),
+                                           _lib.ptr(ws), ws.numel(), _sp(src)), "lcr_icp_point_to_point")
+    if want_corr:
+        out["corr"] = corr
+    if want_history:
+        out["T_hist"], out["fitness_hist"], out["rmse_hist"] = hist
+    return out

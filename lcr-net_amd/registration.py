@@ -5,7 +5,11 @@ experiments/registration/eval.py:175-185 runs as the robust baseline (`--method 
 Open3D samples at random; this RANSAC is deterministic: hypothesis h draws its rows from a counter-based hash of (seed, h, draw), is
 scored in fp32 against every correspondence of its pair, and the winner is the hypothesis with the most inliers (ties: smaller inlier
 SSE, then smaller h).  The exact definition is in include/lcr_hip.h (lcr_ransac_correspondences).  All of it runs in HIP kernels
-(csrc/ransac.hip); a pair gives the same bits alone or inside a batch."""
+(csrc/ransac.hip); a pair gives the same bits alone or inside a batch.
+
+Point-to-point ICP on the dense clouds (Open3D's registration_icp with TransformationEstimationPointToPoint, which the reference's pair
+generators run for their ground truth, data/Kitti/generate_kitti_pairs.py:145-147): `registration_icp` (Open3D's call shape) and
+`icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states."""
 import numpy as np
 import torch
 
@@ -48,3 +52,64 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
     start = torch.tensor([0, src.shape[0]], dtype=torch.int32, device=dev)
     T, _, _ = ransac_batched(src, ref, start, distance_threshold, ransac_n, num_iterations, seed)
     return T[0].cpu().numpy().astype(np.float64)
+
+
+# ---- point-to-point ICP (Open3D's registration_icp with TransformationEstimationPointToPoint; data/Kitti/generate_kitti_pairs.py:145-147) ----
+ICP_MAX_PAIRS_PER_CALL = 64          # S per native call (the support grid's cloud limit); icp_batched splits larger batches
+
+
+def icp_batched(src, src_len, tgt, tgt_len, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                check_every=16, want_history=False, want_corr=False):
+    """ICP for S pairs on the GPU.  src f32 [ns,3] / tgt f32 [nt,3]: device tensors stacked pair-major, src_len / tgt_len: host sequences
+    of S ints, init: [S,4,4] source onto target (any float dtype, any device).  -> dict of device tensors (T f64 [S,4,4], fitness f64 [S],
+    inlier_rmse f64 [S], iterations int32 [S], and with want_corr / want_history the corr rows and the per-step history; see
+    functional.icp_point_to_point).  Batches of more than 64 pairs are split into chunks; every pair's result is the same in any chunk."""
+    src_len = [int(x) for x in np.asarray(src_len).reshape(-1)]
+    tgt_len = [int(x) for x in np.asarray(tgt_len).reshape(-1)]
+    S = len(src_len)
+    dev = src.device
+    init = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init))).to(device=dev, dtype=torch.float64).reshape(S, 4, 4)
+    so = np.concatenate([[0], np.cumsum(src_len)]).astype(np.int64)
+    to = np.concatenate([[0], np.cumsum(tgt_len)]).astype(np.int64)
+    parts = []
+    for c0 in range(0, S, ICP_MAX_PAIRS_PER_CALL):
+        c1 = min(S, c0 + ICP_MAX_PAIRS_PER_CALL)
+        parts.append(F.icp_point_to_point(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1], init[c0:c1],
+                                          max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, check_every,
+                                          want_corr=want_corr, want_history=want_history))
+    if len(parts) == 1:
+        return parts[0]
+    return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+class ICPResult:
+    """What Open3D's RegistrationResult carries: transformation (float64 (4,4) ndarray, source onto target), fitness, inlier_rmse,
+    correspondence_set (int64 [K,2]: source row, target row), plus iterations (the updates performed)."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, correspondence_set, iterations):
+        self.transformation, self.fitness, self.inlier_rmse = transformation, fitness, inlier_rmse
+        self.correspondence_set, self.iterations = correspondence_set, iterations
+
+    def __repr__(self):
+        return "ICPResult(fitness=%.6e, inlier_rmse=%.6e, correspondences=%d, iterations=%d)" % (
+            self.fitness, self.inlier_rmse, len(self.correspondence_set), self.iterations)
+
+
+def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """Open3D's call shape, registration_icp(source, target, max_correspondence_distance, init, TransformationEstimationPointToPoint(),
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)), on the GPU.  source / target: numpy arrays or torch tensors
+    [N,3] / [M,3].  Returns an ICPResult."""
+    if torch.is_tensor(target) and target.is_cuda:
+        dev = target.device
+    elif torch.is_tensor(source) and source.is_cuda:
+        dev = source.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    src, tgt = _device_points(source, dev), _device_points(target, dev)
+    T0 = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init, dtype=np.float64))).to(device=dev, dtype=torch.float64).reshape(1, 4, 4)
+    r = icp_batched(src, [src.shape[0]], tgt, [tgt.shape[0]], T0, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+                    want_corr=True)
+    corr = r["corr"].cpu().numpy().astype(np.int64)
+    rows = np.nonzero(corr >= 0)[0]
+    return ICPResult(r["T"][0].cpu().numpy(), float(r["fitness"][0].item()), float(r["inlier_rmse"][0].item()),
+                     np.stack([rows, corr[rows]], axis=1).astype(np.int64), int(r["iterations"][0].item()))

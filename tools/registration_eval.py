@@ -3,6 +3,7 @@
 
     python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd] [--num_corr K] [--seed S] [--pairs-per-call P]
                                       [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000] [--write-back]
+                                      [--refine icp [--icp-distance 0.5] [--icp-iterations 30]]
 
 Reads every `{seq}_{anc}_{pos}.npz` of FEATURES_DIR (what io_formats.save_registration / demo.py write; both the pos_/anc_ and the
 ref_/src_ key families of eval.py:96-110 are accepted), keeps the top --num_corr correspondences by corr_scores (:114-118), and
@@ -12,6 +13,8 @@ registers the anchor onto the positive:
           (config_reg.py:69-73: 0.3 m, 4 points, 50 000 iterations); --pairs-per-call pairs go into one native call;
           --write-back stores `estimated_transform_ransac` in the file as :184-185 do;
   svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group.
+--refine icp (opt-in) then refines every estimate by point-to-point ICP of the dense anchor cloud (`anc_points_f`) onto the positive's
+(`pos_points_f`), Open3D's criteria with --icp-distance / --icp-iterations, batched on the GPU (lcrnet_amd.registration.icp_batched).
 Prints the reference's Fine Matching line (FMR / IR at acceptance_radius 0.6 with inlier_ratio_threshold 0.05, IR@0.3, IR@0.1,
 num_Corr; config_reg.py:64-65) and Registration line (RR, RRE, RTE, Rx, Ry, Rz: evaluation.registration_summary), then one JSON line.
 Coarse-matching metrics are not computed: the shipped model writes empty gt_node_corr_indices (io_formats.save_registration).
@@ -77,6 +80,22 @@ def estimate_group(method, items, args, device):
     return T.cpu().numpy().astype(np.float64)
 
 
+def refine_icp(pairs, est, args, device):
+    """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each."""
+    import torch
+    from lcrnet_amd.registration import icp_batched
+    out = []
+    for g in range(0, len(pairs), args.pairs_per_call):
+        group = pairs[g:g + args.pairs_per_call]
+        srcs = [np.ascontiguousarray(d["anc_points_f"], np.float32).reshape(-1, 3) for _, d, _, _, _ in group]
+        tgts = [np.ascontiguousarray(d["pos_points_f"], np.float32).reshape(-1, 3) for _, d, _, _, _ in group]
+        cat = lambda xs: torch.from_numpy(np.concatenate(xs)).to(device)
+        init = torch.from_numpy(np.stack([np.asarray(T, np.float64) for T in est[g:g + args.pairs_per_call]])).to(device)
+        r = icp_batched(cat(srcs), [len(x) for x in srcs], cat(tgts), [len(x) for x in tgts], init, args.icp_distance, args.icp_iterations)
+        out += list(r["T"].cpu().numpy())
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("features_dir")
@@ -88,6 +107,9 @@ def main(argv=None):
     p.add_argument("--ransac-n", type=int, default=4)
     p.add_argument("--num-iterations", type=int, default=50000)
     p.add_argument("--write-back", action="store_true", help="store estimated_transform_ransac in each file (eval.py:184-185)")
+    p.add_argument("--refine", choices=["icp"], default=None, help="refine each estimate by point-to-point ICP of the dense clouds")
+    p.add_argument("--icp-distance", type=float, default=0.5)
+    p.add_argument("--icp-iterations", type=int, default=30)
     args = p.parse_args(argv)
     if args.pairs_per_call < 1:
         p.error("--pairs-per-call must be >= 1")
@@ -111,6 +133,10 @@ def main(argv=None):
         for g in range(0, len(pairs), args.pairs_per_call):
             group = pairs[g:g + args.pairs_per_call]
             est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
+    scored = est                                          # --write-back stores the method's own estimate, refined or not
+    if args.refine == "icp":
+        import torch
+        scored = refine_icp(pairs, est, args, torch.device("cuda", torch.cuda.current_device()))
     seconds = time.perf_counter() - t0
 
     if args.method == "ransac" and args.write_back:
@@ -121,7 +147,7 @@ def main(argv=None):
 
     fine = [ev.fine_matching_metrics(b, a, d["transform"]) for _, d, b, a, _ in pairs]
     fm = {k: float(np.mean([x[k] for x in fine])) if fine else float("nan") for k in ("FMR", "IR", "IR@0.3", "IR@0.1", "num_corr")}
-    reg = ev.registration_summary([d["transform"] for _, d, _, _, _ in pairs], est)
+    reg = ev.registration_summary([d["transform"] for _, d, _, _, _ in pairs], scored)
     print("Pairs: %d" % len(files))
     print("  Fine Matching, FMR: {:.4f}, IR: {:.3f}, IR@0.3: {:.3f}, IR@0.1: {:.3f}, num_Corr: {:.3f}".format(
         fm["FMR"], fm["IR"], fm["IR@0.3"], fm["IR@0.1"], fm["num_corr"]))
@@ -132,6 +158,8 @@ def main(argv=None):
            "num_corr": args.num_corr, "seed": args.seed, "pairs_per_call": args.pairs_per_call}
     if args.method == "ransac":
         out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
+    if args.refine == "icp":
+        out["refine"] = {"method": "icp", "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
     print(json.dumps(out))
     return out
 
