@@ -218,6 +218,19 @@ int lcr_split_bf16x3(const float* w, int64_t n, uint16_t* planes, void* stream);
 int lcr_split_bf16x3_tiles(const float* w, int N, int K, uint16_t* tiles, void* stream);
 int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs_tiles, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
                         const int64_t* seg_len, int S, int groups, double* stats, void* stream);
+/* The KPConv contraction over a row-masked A (lcr_kpconv_aggregate_mask): the columns [k*block_k, (k+1)*block_k) of row m are read as
+ * zeros when bit k of row_mask[m] is clear, without touching memory there.  block_k = 32 << s (32 ... 256), K <= 16 * block_k.
+ * Results are bit-identical to the unmasked call on an A whose masked blocks hold zeros.
+ * lcr_gemm_f32_masked: C = A[M,K] . B[N,K]^T on the K-deep fp32 form (needs K % 32 == 0 and M*K, N*K < 2^30);
+ * lcr_gemm_f32_bsplit_masked: lcr_gemm_f32_bsplit's split-bf16 form (needs M*K < 2^29).  Epilogues as lcr_gemm_f32. */
+int lcr_gemm_f32_masked(const float* A, const float* B, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
+                        const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask, int block_k, void* stream);
+int lcr_gemm_f32_bsplit_masked(const float* A, const uint16_t* Bs_tiles, float* C, int64_t M, int N, int K, const float* bias,
+                               const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask,
+                               int block_k, void* stream);
+/* 1 when the contraction of a KPConv aggregate [M, K = 15 C] with N outputs may run on the masked entry above (split = 1: the split-bf16
+ * form, 0: the fp32 form) and give what the unmasked call gives; 0 otherwise, and always with environment LCR_KP_MASK=0. */
+int lcr_kpconv_mask_ok(int64_t M, int N, int K, int split);
 /* C = LeakyReLU(GroupNorm(A)) · B^T (+ bias, + statistics of C as above), A being the RAW [M,K] output of the layer whose sums are
  * a_stats[LCR_GN_REPLICAS,S,a_groups,2]: the normalisation happens while A's tiles are staged, the normalised tensor never
  * exists in memory.  Replaces norm_conv + leaky_relu + unary2.mlp of ResidualBlock.forward (modules/kpconv/modules.py:215-217).
@@ -246,6 +259,13 @@ int lcr_kpconv_aggregate_ex(const float* s_feats, const uint8_t* s_pos, const fl
                             const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int C,
                             const float* kernel_points_host, float sigma, float* A, float* nn,
                             const int32_t* order, int flags, void* stream);
+/* Same, and mask[M] (uint16): bit k of mask[m] is set when the kernel-point block A[m, k*C : (k+1)*C] holds a value other than +0 / -0
+ * (NaN and Inf included).  Only those blocks are STORED; the others are left as they were, to be read through
+ * lcr_gemm_f32_masked / lcr_gemm_f32_bsplit_masked, which zero-fill them.  mask = NULL: lcr_kpconv_aggregate_ex. */
+int lcr_kpconv_aggregate_mask(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts,
+                              const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int C,
+                              const float* kernel_points_host, float sigma, float* A, float* nn, uint16_t* mask,
+                              const int32_t* order, int flags, void* stream);
 /* Whole KPConv (kpconv.py:79-122) for C_in = C_out = 32 — the two widest query sets of the encoder — in one launch: the
  * aggregate above lives only as 16-query tiles in LDS and is contracted there with W [15*32, 32] (split-K over the wavefronts,
  * weights in registers); out[M,32] = contraction / neighbour count + bias, plus the GroupNorm sums of `out` ADDED to

@@ -51,6 +51,8 @@ _SIGS = {
     "lcr_roformer_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_size_t, c_vp]),
     "lcr_encoder_forward_ex": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint, c_vp, c_size_t, c_vp]),
     "lcr_kpconv_aggregate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_float, c_vp, c_vp, c_vp, c_vp]),
+    "lcr_kpconv_aggregate_mask": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_float, c_vp, c_vp, c_vp, c_vp,
+                                          c_int, c_vp]),
     "lcr_kpconv_fused": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_int, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_int,
                                  c_int, c_vp, c_vp, c_vp]),
     "lcr_kpconv_cin1": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_float, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
@@ -83,6 +85,9 @@ _SIGS = {
     "lcr_split_bf16x3": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "lcr_split_bf16x3_tiles": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     "lcr_gemm_f32_bsplit": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    "lcr_gemm_f32_bsplit_masked": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
+    "lcr_gemm_f32_masked": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
+    "lcr_kpconv_mask_ok": (c_int, [c_i64, c_int, c_int, c_int]),
     "lcr_log_sinkhorn_ex": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_float, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_top1_matching_ws_bytes": (c_int, [c_i64, c_int, c_int, c_size_p]),
     "lcr_top1_matching": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),

@@ -99,8 +99,9 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
   float* A = ws.take<float>(static_cast<size_t>(M) * 15 * mid);
   float* nn = ws.take<float>(static_cast<size_t>(M));
   float* kpo = ws.take<float>(static_cast<size_t>(M) * mid);
+  uint16_t* kmask = ws.take<uint16_t>(static_cast<size_t>(M));
   double* stc = sp.take();
-  if (!A || !nn || !kpo || !stc) return LCR_ESPACE;
+  if (!A || !nn || !kpo || !kmask || !stc) return LCR_ESPACE;
   // lists that come from a radius search (the reference's radius_neighbors and ours alike) hold their valid entries first, padding (= Ns)
   // behind them: the CALLER says so with LCR_ENC_LISTS_VALID_FIRST and the aggregation may then stop at the first chunk with a hole.
   // Without the flag every chunk is scanned (rows with interior padding are legal input).  LCR_KP_VALID_FIRST=0 ignores the flag.
@@ -112,10 +113,20 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
                                     stc, q.order, s))))
       return rc;
   } else {
-    if ((rc = TURN(lcr_kpconv_aggregate_ex(x, pos, q.pts, sup.pts, idx, 0, M, Ns, H, mid, b.kernel_points_host, b.sigma, A, nn, q.order, vf_flag, s)))) return rc;
     // weights pre-transposed by the caller ([mid, 15 mid]): both operands k-contiguous -> the K-deep GEMM form
-    if (b.kp_wt_split && mid >= 64) {      // N = 32 contractions stream A at the HBM rate on the fp32 form already
-      if ((rc = TURN(lcr_gemm_f32_bsplit(A, b.kp_wt_split, kpo, M, mid, 15 * mid, b.kp_b, nn, q.seg, sp.S, g, stc, s)))) return rc;
+    const bool split = b.kp_wt_split && mid >= 64;     // N = 32 contractions stream A at the HBM rate on the fp32 form already
+    // row masks: the aggregation stores only the kernel-point blocks that are not all zero (a third of them are: kernel points that stick out
+    // of the lidar surface), the contraction zero-fills the others instead of reading them — same results (KPConv.forward_raw does the same)
+    if (!((split || b.kp_wt) && lcr_kpconv_mask_ok(M, mid, 15 * mid, split))) kmask = nullptr;
+    if ((rc = TURN(lcr_kpconv_aggregate_mask(x, pos, q.pts, sup.pts, idx, 0, M, Ns, H, mid, b.kernel_points_host, b.sigma, A, nn, kmask, q.order, vf_flag,
+                                             s))))
+      return rc;
+    if (split) {
+      if ((rc = TURN(kmask ? lcr_gemm_f32_bsplit_masked(A, b.kp_wt_split, kpo, M, mid, 15 * mid, b.kp_b, nn, q.seg, sp.S, g, stc, kmask, mid, s)
+                           : lcr_gemm_f32_bsplit(A, b.kp_wt_split, kpo, M, mid, 15 * mid, b.kp_b, nn, q.seg, sp.S, g, stc, s))))
+        return rc;
+    } else if (kmask) {
+      if ((rc = TURN(lcr_gemm_f32_masked(A, b.kp_wt, kpo, M, mid, 15 * mid, b.kp_b, nn, q.seg, sp.S, g, stc, kmask, mid, s)))) return rc;
     } else if ((rc = TURN(b.kp_wt ? lcr_gemm_f32(A, b.kp_wt, kpo, M, mid, 15 * mid, 0, 1, b.kp_b, nn, q.seg, sp.S, g, stc, s)
                                   : lcr_gemm_f32(A, b.kp_w, kpo, M, mid, 15 * mid, 0, 0, b.kp_b, nn, q.seg, sp.S, g, stc, s)))) return rc;
   }
@@ -170,6 +181,7 @@ static size_t block_ws_bytes(const LcrBlockW& b, int64_t M, int64_t Ns) {
   a.take<float>(static_cast<size_t>(M) * 15 * mid);
   a.take<float>(M);
   a.take<float>(static_cast<size_t>(M) * mid);
+  a.take<uint16_t>(static_cast<size_t>(M));
   a.take<float>(static_cast<size_t>(M) * mid);
   a.take<float>(static_cast<size_t>(M) * b.cout);
   a.take<float>(static_cast<size_t>(M) * b.cin);

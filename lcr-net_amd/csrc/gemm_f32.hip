@@ -680,9 +680,24 @@ __device__ __forceinline__ void glds16(const float* base, unsigned off, unsigned
                : "memory");
 }
 
-template <int BM, int BN, int WM, int WN>
+// the same with a per-lane 64-bit address (the masked A loads below: a lane either reads its row or the zero line)
+__device__ __forceinline__ void glds16_v(const float* addr, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(addr), "s"(lds_dst)
+               : "memory");
+}
+// 16 zero bytes in device memory (static storage: zero-initialised): the source of the masked lanes of an LDS-direct load
+__device__ __attribute__((aligned(16))) float g_zero16[4];
+
+// Row-masked A (MASK, the KPConv contraction after lcr_kpconv_aggregate_mask): the 32 columns of K-step t of row m lie in kernel-point
+// block t >> kshift; when bit (t >> kshift) of amask[m] is clear the block was never stored and reads as zeros.  The choice is a select of
+// the source address, not a branch: every load of the step is still issued, so the counted waits stay exact.
+template <int BM, int BN, int WM, int WN, bool MASK = false>
 __global__ __launch_bounds__(GM_T, (BM == 64 ? 3 : 2)) void k_gemm_f32_deep(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
-                                                            int64_t M, int N, int K, GemmEpilogue ep) {
+                                                            int64_t M, int N, int K, GemmEpilogue ep, const uint16_t* __restrict__ amask,
+                                                            int kshift) {
   static_assert(WM * WN == 4 && BM == 32 * WM && BN == 32 * WN, "one 32x32 accumulator per wavefront");
   constexpr int LA = BM / 32, LB = BN / 32, LPW = LA + LB;   // 1-KB load instructions per wavefront and tile (8 rows each)
   constexpr int STAGE_A = BM * 128, STAGE = (BM + BN) * 128;  // bytes
@@ -700,6 +715,7 @@ __global__ __launch_bounds__(GM_T, (BM == 64 ? 3 : 2)) void k_gemm_f32_deep(cons
 
   // source byte offset of this lane for each of its load instructions: LDS slot (row, physical chunk pc) <- global chunk pc ^ ((row >> 1) & 7)
   unsigned oa[LA], ob[LB];                                     // the launcher guarantees M*K*4 and N*K*4 < 2^32
+  uint32_t rmask[MASK ? LA : 1];                               // MASK: the block mask of the lane's row
 #pragma unroll
   for (int j = 0; j < LA; ++j) {
     const int row = (w * LA + j) * 8 + (lane >> 3);
@@ -707,6 +723,7 @@ __global__ __launch_bounds__(GM_T, (BM == 64 ? 3 : 2)) void k_gemm_f32_deep(cons
     int64_t gr = m0 + row;
     gr = gr < M ? gr : M - 1;                                // duplicate rows only feed outputs that are never stored
     oa[j] = static_cast<unsigned>((gr * K + c * 4) * 4);
+    if constexpr (MASK) rmask[j] = amask[gr];
   }
 #pragma unroll
   for (int j = 0; j < LB; ++j) {
@@ -719,13 +736,25 @@ __global__ __launch_bounds__(GM_T, (BM == 64 ? 3 : 2)) void k_gemm_f32_deep(cons
   const unsigned dst_a = lds_base + w * LA * 1024, dst_b = lds_base + STAGE_A + w * LB * 1024;
   const float* Ak = A;                                         // scalar bases, advanced one K-step per tile issued
   const float* Bk = B;
+  int kt = 0;                                                  // MASK: K-step of the tile being issued
   auto issue_one = [&](int stage, int j) {                     // j-th load instruction of the tile going to `stage` (A first, then B)
-    if (j < LA) glds16(Ak, oa[j], dst_a + stage * STAGE + j * 1024);
-    else glds16(Bk, ob[j - LA], dst_b + stage * STAGE + (j - LA) * 1024);
+    if (j < LA) {
+      if constexpr (MASK) {
+        const float* src = ((rmask[j] >> (kt >> kshift)) & 1u)
+                               ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(A) + (oa[j] + static_cast<unsigned>(kt * GM_BK * 4)))
+                               : g_zero16;
+        glds16_v(src, dst_a + stage * STAGE + j * 1024);
+      } else {
+        glds16(Ak, oa[j], dst_a + stage * STAGE + j * 1024);
+      }
+    } else {
+      glds16(Bk, ob[j - LA], dst_b + stage * STAGE + (j - LA) * 1024);
+    }
   };
   auto advance = [&] {                                         // after ALL load instructions of a tile
     Ak += GM_BK;
     Bk += GM_BK;
+    if constexpr (MASK) ++kt;
   };
   auto issue = [&](int stage) {
 #pragma unroll
@@ -853,9 +882,13 @@ __global__ __launch_bounds__(GM_T, (BM == 64 ? 3 : 2)) void k_gemm_f32_deep(cons
 }
 
 template <int BM, int BN, int WM, int WN>
-static int launch_gemm_deep(const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st) {
+static int launch_gemm_deep(const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st,
+                            const uint16_t* amask = nullptr, int kshift = 0) {
   const int mt8 = (div_up(M, BM) + 7) / 8 * 8;
-  LCR_LAUNCH_TIMED((k_gemm_f32_deep<BM, BN, WM, WN>), dim3(mt8 * div_up(N, BN)), dim3(GM_T), 0, st, A, B, C, M, N, K, ep);
+  if (amask)
+    LCR_LAUNCH_TIMED((k_gemm_f32_deep<BM, BN, WM, WN, true>), dim3(mt8 * div_up(N, BN)), dim3(GM_T), 0, st, A, B, C, M, N, K, ep, amask, kshift);
+  else
+    LCR_LAUNCH_TIMED((k_gemm_f32_deep<BM, BN, WM, WN>), dim3(mt8 * div_up(N, BN)), dim3(GM_T), 0, st, A, B, C, M, N, K, ep, amask, kshift);
   return check_launch("lcr_gemm_f32");
 }
 
@@ -947,9 +980,12 @@ __global__ __launch_bounds__(256) void k_split_bf16x3_tiles(const float* __restr
 // ABL: timing ablations (tools/gemm_split_bench.py --abl): 1 no MFMAs, 2 no split arithmetic, 4 no plane stores, 8 no global loads in the
 // loop, 16 no fragment reads.  0 = the product; any other value computes garbage.
 // NWM: 32-row wavefront rows of the tile (2: 64 x 64, 256 threads — the product; 4: 128 x 64, 512 threads: measured 1.08x, not instantiated).
-template <int ABL, int NWM, int D = 2>
+// MASK: row-masked A as in k_gemm_f32_deep.  The A pieces are then buffer loads whose offset is pushed out of the buffer's range for a
+// block that was never stored: the range check returns zeros without a memory access (and without a branch in the K-step).
+template <int ABL, int NWM, int D = 2, bool MASK = false>
 __global__ __launch_bounds__(128 * NWM, 2) void k_gemm_f32_bsplit_p(const float* __restrict__ A, const uint16_t* __restrict__ Bs, float* __restrict__ C,
-                                                             int64_t M, int N, int K, GemmEpilogue ep) {
+                                                             int64_t M, int N, int K, GemmEpilogue ep, const uint16_t* __restrict__ amask,
+                                                             int kshift) {
   // LDS plane tile: 64 rows x 64 B (32 bf16), no padding; the four 16-B chunks of row r are XOR-ed with (r >> 2) & 3.  A ds_write_b128 is
   // serviced in groups of 8 consecutive lanes over 32 banks (two rows x four chunks: 128 distinct bytes), a ds_read_b128 in groups of 16 lanes
   // over 64 banks (16 different rows, one logical chunk: rows r, r+4, r+8, r+12 share a 64-B bank quadrant and get four different chunks).
@@ -973,12 +1009,19 @@ __global__ __launch_bounds__(128 * NWM, 2) void k_gemm_f32_bsplit_p(const float*
   const int srow = threadIdx.x >> 3, spc = threadIdx.x & 7;
   const float* ap[2];
   int soff[2];
+  uint32_t aoff[2], rmask[2];                                  // MASK: byte offset of the piece in A (the launcher guarantees M*K*4 < 2^31), row mask
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int r = srow + j * (T / 8);
     int64_t ga = m0 + r;
     ga = ga < M ? ga : M - 1;                                  // duplicate rows only feed outputs that are never stored
     ap[j] = A + ga * K + spc * 4;
+    if constexpr (MASK) {
+      aoff[j] = static_cast<uint32_t>((ga * K + spc * 4) * 4);
+      rmask[j] = amask[ga];
+    } else {
+      aoff[j] = rmask[j] = 0;
+    }
     soff[j] = r * RS + (((spc >> 1) ^ ((r >> 2) & 3)) << 4) + (spc & 1) * 8;
   }
   // B staging: the step's 12 KB block of the tiled planes, copied verbatim (it IS the LDS image): thread t takes bytes [16 (t + T j), + 16).
@@ -1001,10 +1044,21 @@ __global__ __launch_bounds__(128 * NWM, 2) void k_gemm_f32_bsplit_p(const float*
   const int nk = K / GM_BK;
   f32x4_t ra[D][2];                                            // D register stages: tiles t+1 .. t+D in flight / parked (two pieces each)
   u32x4_t rb[D][NPB];
+  __amdgpu_buffer_rsrc_t arsrc;
+  if constexpr (MASK) arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, static_cast<int>(M * K * 4), 0x00020000);
   auto fetch = [&](auto st_c, int t) {
     constexpr int st = decltype(st_c)::value;
     const int tt = t < nk ? t : nk - 1;                         // the tail re-reads the last tile
-    ra[st][0] = *reinterpret_cast<const f32x4_t*>(ap[0] + tt * GM_BK), ra[st][1] = *reinterpret_cast<const f32x4_t*>(ap[1] + tt * GM_BK);
+    if constexpr (MASK) {
+      const int kb = tt >> kshift;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const uint32_t o = ((rmask[j] >> kb) & 1u) ? aoff[j] + static_cast<uint32_t>(tt * GM_BK * 4) : 0x80000000u;
+        ra[st][j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(arsrc, static_cast<int>(o), 0, 0));
+      }
+    } else {
+      ra[st][0] = *reinterpret_cast<const f32x4_t*>(ap[0] + tt * GM_BK), ra[st][1] = *reinterpret_cast<const f32x4_t*>(ap[1] + tt * GM_BK);
+    }
 #pragma unroll
     for (int j = 0; j < NPB; ++j) rb[st][j] = *reinterpret_cast<const u32x4_t*>(bp + static_cast<int64_t>(tt) * 12288 + bsrc[j]);
   };
@@ -1548,8 +1602,8 @@ extern "C" int lcr_split_bf16x3_tiles(const float* w, int N, int K, uint16_t* ti
 }
 
 // C = A[M,K] · B[N,K]^T with B given as the TILED bf16 planes of lcr_split_bf16x3_tiles; epilogue as lcr_gemm_f32.
-extern "C" int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
-                                   const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
+static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
+                       const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* amask, int kshift, void* stream) {
   if (!A || !Bs || !C || M < 0 || N <= 0 || K <= 0 || K % GM_BK != 0 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(Bs) % 16 != 0 ||
       K < GM_BK) {
     set_error("lcr_gemm_f32_bsplit: needs K %% 32 == 0 and 16-byte aligned operands");
@@ -1566,17 +1620,81 @@ extern "C" int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs, float* C,
   const int mt8 = (div_up(M, 64) + 7) / 8 * 8;
   static const int abl = getenv("LCR_SPLIT_ABL") ? atoi(getenv("LCR_SPLIT_ABL")) : 0;      // timing ablations only (garbage results)
   const dim3 grid(mt8 * div_up(N, 64)), block(256);
+  if (amask) {
+    LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, 2, 2, true>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift);
+    return check_launch("lcr_gemm_f32_bsplit_masked");
+  }
   switch (abl) {
-    case 1: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<1, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 2: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<2, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 4: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<4, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 8: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<8, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 16: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<16, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 23: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<23, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    case 30: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<30, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
-    default: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep); break;
+    case 1: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<1, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 2: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<2, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 4: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<4, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 8: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<8, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 16: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<16, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 23: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<23, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 30: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<30, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    default: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, 2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
   }
   return check_launch("lcr_gemm_f32_bsplit");
+}
+
+extern "C" int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
+                                   const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
+  return bsplit_impl(A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, nullptr, 0, stream);
+}
+
+// block_k (columns per mask bit) -> log2(block_k / 32), or -1 when the mask cannot describe K
+static int mask_kshift(int K, int block_k) {
+  for (int s = 0; s <= 3; ++s)
+    if (block_k == (GM_BK << s)) return K <= 16 * block_k ? s : -1;
+  return -1;
+}
+
+extern "C" int lcr_gemm_f32_bsplit_masked(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias,
+                                          const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask,
+                                          int block_k, void* stream) {
+  const int ks = mask_kshift(K, block_k);
+  if (!row_mask || ks < 0 || M * static_cast<int64_t>(K) >= (int64_t(1) << 29)) {
+    set_error("lcr_gemm_f32_bsplit_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, and M*K < 2^29");
+    return LCR_EARG;
+  }
+  return bsplit_impl(A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, row_mask, ks, stream);
+}
+
+// Whether the contraction C[M,N] = A[M,K] . B[N,K]^T of a KPConv with C_in = K / 15 can read a row-masked aggregate and still compute what
+// lcr_gemm_f32 (split = 0) / lcr_gemm_f32_bsplit (split = 1) compute on the full one: the split form always can within its offset range; the
+// fp32 form only where lcr_gemm_f32 itself takes the K-deep kernel.  Environment LCR_KP_MASK=0: never (A/B).
+extern "C" int lcr_kpconv_mask_ok(int64_t M, int N, int K, int split) {
+  static const bool off = getenv("LCR_KP_MASK") && atoi(getenv("LCR_KP_MASK")) == 0;
+  if (off || M <= 0 || N <= 0 || K % 15 != 0 || mask_kshift(K, K / 15) < 0) return 0;
+  if (split) return M * static_cast<int64_t>(K) < (int64_t(1) << 29);
+  static const int deep_env = getenv("LCR_GEMM_DEEP") ? atoi(getenv("LCR_GEMM_DEEP")) : 1;
+  const int deep_mode = g_force_deep >= 0 ? g_force_deep : deep_env;
+  const int short_k = getenv("LCR_GEMM_SHORT_K") ? atoi(getenv("LCR_GEMM_SHORT_K")) : 256;
+  const bool short_form = getenv("LCR_GEMM_NO_SHORT") == nullptr && K <= short_k;
+  return deep_mode && !g_force_tile && (deep_mode == 2 || !short_form) && M * static_cast<int64_t>(K) < (int64_t(1) << 30) &&
+         static_cast<int64_t>(N) * K < (int64_t(1) << 30);
+}
+
+// The K-deep fp32 form over a row-masked A (same tile choice as lcr_gemm_f32 makes for these shapes).
+extern "C" int lcr_gemm_f32_masked(const float* A, const float* B, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
+                                   const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask, int block_k, void* stream) {
+  const int ks = mask_kshift(K, block_k);
+  if (!A || !B || !C || !row_mask || M < 0 || N <= 0 || K <= 0 || K % GM_BK != 0 || ks < 0 || M * static_cast<int64_t>(K) >= (int64_t(1) << 30) ||
+      static_cast<int64_t>(N) * K >= (int64_t(1) << 30) || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(B) % 16 != 0) {
+    set_error("lcr_gemm_f32_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, K %% 32 == 0, M*K and N*K < 2^30, "
+              "16-byte aligned operands");
+    return LCR_EARG;
+  }
+  if (stats && (!seg_len || S < 1 || groups < 1 || N % groups != 0 || ((N / groups) & (N / groups - 1)) != 0)) {
+    set_error("lcr_gemm_f32_masked: statistics need seg_len, S >= 1 and groups dividing N into power-of-two sized groups");
+    return LCR_EARG;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KernelTimerScope timed(KT_GEMM, st, M, N, K);
+  if (M == 0) return LCR_OK;
+  GemmEpilogue ep{bias, rowdiv, seg_len, S, groups, stats};
+  if (N <= 32) return launch_gemm_deep<128, 32, 4, 1>(A, B, C, M, N, K, ep, st, row_mask, ks);
+  return launch_gemm_deep<64, 64, 2, 2>(A, B, C, M, N, K, ep, st, row_mask, ks);
 }
 
 // Batched C_z = A_z^T·B_z (transA) with per-entry K — NetVLAD's per-scan aggregation (NetVlad.py:68): one launch for S scans.

@@ -68,12 +68,17 @@ __device__ __forceinline__ float2 vmake(const float (&a)[2]) { return make_float
 
 // OFF32 (Ns * C * 4 < 2^32, chosen by the host): the list carries the BYTE offset of the neighbour's feature row instead of its index, and a
 // step's gather is scalar base + (offset + lane column): one 32-bit add instead of a 64-bit multiply-add per step.
-template <typename IdxT, int C, bool OFF32>
+// MASK: also write mask[m], bit k set when block k of the row holds a value that is not +-0 (NaN / Inf included), and store only those
+// blocks.  A clear bit means the block is all zeros, so a contraction that zero-fills it (lcr_gemm_f32_masked / _bsplit_masked) adds
+// exactly what reading it would: +-0 products leave an accumulator that started at +0 unchanged.  The test reads the accumulators
+// themselves, after the last MFMA, so it agrees with what would have been stored by construction.
+template <typename IdxT, int C, bool OFF32, bool MASK = false>
 __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const float* __restrict__ s_feats, const uint8_t* __restrict__ s_pos,
                                                                         const float* __restrict__ q_pts, const float* __restrict__ s_pts,
                                                                         const IdxT* __restrict__ idx, int64_t M, int64_t Ns, int H, KPoints kp,
                                                                         float sigma, float* __restrict__ A, float* __restrict__ nn,
-                                                                        const int32_t* __restrict__ order, int valid_first) {
+                                                                        const int32_t* __restrict__ order, int valid_first,
+                                                                        uint16_t* __restrict__ mask) {
   constexpr int V = C >= 64 ? 4 : 2;
   constexpr int NL = C / (16 * V);           // vector loads per lane per 4-neighbour step
   constexpr int D = NL == 1 ? 4 : 2;         // steps in flight (register ring)
@@ -185,11 +190,30 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const fl
       for (int d = 0; d < D - 1; ++d)                       // the last steps % D steps: their rows are already on the way
         if (s0 + d < steps) compute(s0 + d, p[d], f[d]);
     }
+    uint32_t kmask = 0x7fffu;
+    if constexpr (MASK) {
+      // lanes 16 s .. 16 s + 15 hold block 4 s + r of the row in register r: one ballot per r, folded per 16-lane group
+      uint32_t bits = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        uint32_t o = 0;
+#pragma unroll
+        for (int q = 0; q < NL; ++q)
+#pragma unroll
+          for (int v = 0; v < V; ++v) o |= __float_as_uint(acc[q][v][r]);
+        const uint64_t b = wave_ballot((o & 0x7fffffffu) != 0u);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+          if ((b >> (16 * s4)) & 0xffffull) bits |= 1u << (4 * s4 + r);
+      }
+      kmask = bits & 0x7fffu;
+      if (lane == 0) mask[m] = static_cast<uint16_t>(kmask);
+    }
     float* out = A + m * (KP_K * C) + V * col;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k = 4 * sub + r;
-      if (k < KP_K) {
+      if (k < KP_K && ((kmask >> k) & 1u)) {
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
           float a[V];
@@ -674,12 +698,17 @@ static int g_agg_force_off64 = 0;          // tests: run the 64-bit-offset form 
 template <typename IdxT>
 static int launch_aggregate(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const IdxT* idx, int64_t M,
                             int64_t Ns, int H, int C, const KPoints& kp, float sigma, float* A, float* nn, const int32_t* order, int vf,
-                            hipStream_t st) {
+                            uint16_t* mask, hipStream_t st) {
   dim3 grid(grid_for_xcd(M, KP_WAVES)), block(KP_WAVES * 64);
   const bool off32 = Ns * C < (int64_t(1) << 30) && M * H < (int64_t(1) << 30) && !g_agg_force_off64;   // feature rows / index rows addressable with 32-bit byte offsets
-#define LCR_AGG(CC)                                                                                                                          \
-  if (off32) LCR_LAUNCH_TIMED((k_kpconv_aggregate_vec<IdxT, CC, true>), grid, block, 0, st, s_feats, s_pos, q_pts, s_pts, idx, M, Ns, H, kp, sigma, A, nn, order, vf); \
-  else LCR_LAUNCH_TIMED((k_kpconv_aggregate_vec<IdxT, CC, false>), grid, block, 0, st, s_feats, s_pos, q_pts, s_pts, idx, M, Ns, H, kp, sigma, A, nn, order, vf);      \
+#define LCR_AGG_M(CC, O32, MK) \
+  LCR_LAUNCH_TIMED((k_kpconv_aggregate_vec<IdxT, CC, O32, MK>), grid, block, 0, st, s_feats, s_pos, q_pts, s_pts, idx, M, Ns, H, kp, sigma, A, nn, order, vf, mask)
+#define LCR_AGG(CC)                            \
+  if (mask) {                                  \
+    if (off32) LCR_AGG_M(CC, true, true);      \
+    else LCR_AGG_M(CC, false, true);           \
+  } else if (off32) LCR_AGG_M(CC, true, false); \
+  else LCR_AGG_M(CC, false, false);            \
   break
   switch (C) {
     case 32: LCR_AGG(32);
@@ -689,6 +718,7 @@ static int launch_aggregate(const float* s_feats, const uint8_t* s_pos, const fl
     default: set_error("lcr_kpconv_aggregate: C must be 32, 64, 128 or 256 (got %d)", C); return LCR_EARG;
   }
 #undef LCR_AGG
+#undef LCR_AGG_M
   return check_launch("lcr_kpconv_aggregate");
 }
 
@@ -707,6 +737,13 @@ extern "C" int lcr_kpconv_aggregate(const float* s_feats, const uint8_t* s_pos, 
 extern "C" int lcr_kpconv_aggregate_ex(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
                                        int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma,
                                        float* A, float* nn, const int32_t* order, int flags, void* stream) {
+  return lcr_kpconv_aggregate_mask(s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn, nullptr, order, flags,
+                                   stream);
+}
+
+extern "C" int lcr_kpconv_aggregate_mask(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
+                                         int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma,
+                                         float* A, float* nn, uint16_t* mask, const int32_t* order, int flags, void* stream) {
   if (!s_feats || !s_pos || !q_pts || !s_pts || !idx || !kernel_points_host || !A || !nn || M < 0 || Ns < 0 || H < 1 || H > KP_HMAX ||
       !(sigma > 0.f)) {
     set_error("lcr_kpconv_aggregate: bad argument (H must be in [1,%d])", KP_HMAX);
@@ -717,8 +754,8 @@ extern "C" int lcr_kpconv_aggregate_ex(const float* s_feats, const uint8_t* s_po
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_AGGREGATE, st, M, Ns, H, C, idx_is_64 ? 8 : 4);
   const int vf = (flags & LCR_KP_VALID_FIRST) ? 1 : 0;
-  return idx_is_64 ? launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int64_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, st)
-                   : launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int32_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, st);
+  return idx_is_64 ? launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int64_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st)
+                   : launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int32_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st);
 }
 
 extern "C" int lcr_kpconv_fused(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,

@@ -128,10 +128,13 @@ def _zero_stats(S, groups, device):
     return torch.zeros((GN_REPLICAS, S, groups, 2), dtype=torch.float64, device=device)
 
 
-def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=None, groups=0):
+def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=None, groups=0, row_mask=None):
     """C = A·B (+ fused epilogue).  a: [M,K] ([K,M] if trans_a); b: [K,N] ([N,K] if trans_b, i.e. an nn.Linear weight).
     Returns (C, stats) where stats is the fp64 [GN_REPLICAS,S,groups,2] GroupNorm accumulator (sum the replicas; None if
-    groups == 0)."""
+    groups == 0).  row_mask: the int16 [M] mask of kpconv_aggregate(emit_mask=True) for a = its aggregate (trans_b only): blocks
+    whose bit is clear are read as zeros (lcr_gemm_f32_masked; where kpconv_mask_ok(M, N, K, False) holds)."""
+    if row_mask is not None:
+        return _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask)
     _lib.require_cuda(a, b)
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
@@ -148,6 +151,39 @@ def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=Non
         _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, int(trans_a), int(trans_b), _lib.ptr(bias), _lib.ptr(rowdiv),
         _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)), "lcr_gemm_f32"),
         meta=(M, N, K))
+    return c, stats
+
+
+def kpconv_mask_ok(M, N, K, split):
+    """Whether the KPConv contraction [M, K = 15 C] x [K, N] may read a row-masked aggregate on the split-bf16 (split) or fp32 form and
+    compute what the unmasked call computes (lcr_kpconv_mask_ok; environment LCR_KP_MASK=0: never)."""
+    return bool(_lib.lib().lcr_kpconv_mask_ok(int(M), int(N), int(K), int(bool(split))))
+
+
+def _mask_args(a, row_mask):
+    M, K = a.shape
+    assert row_mask.dtype == torch.int16 and row_mask.is_contiguous() and row_mask.numel() == M and row_mask.device == a.device
+    assert K % 15 == 0
+    return K // 15
+
+
+def _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask):
+    _lib.require_cuda(a, b)
+    assert trans_b and not trans_a, "the masked form takes A [M,K] and B [N,K]"
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    block_k = _mask_args(a, row_mask)
+    M, K = a.shape
+    N = b.shape[0]
+    assert b.shape[1] == K, "inner dimensions differ"
+    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    stats, S = None, 0
+    if groups:
+        seg_len = _seg(seg_len, M, a.device)
+        S = seg_len.numel()
+        stats = _zero_stats(S, groups, a.device)
+    _timed("gemm", lambda: _lib.check(_lib.lib().lcr_gemm_f32_masked(
+        _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv), _lib.ptr(seg_len) if groups else None, S,
+        int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_masked"), meta=(M, N, K))
     return c, stats
 
 
@@ -240,8 +276,9 @@ def unsplit_bf16x3(tiles):
     return t[:, :tiles.lcr_n].contiguous().view(torch.bfloat16).float()
 
 
-def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0):
-    """C = A[M,K] . B[N,K]^T with B given as the planes of split_bf16x3 (same epilogue and return value as gemm())."""
+def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0, row_mask=None):
+    """C = A[M,K] . B[N,K]^T with B given as the planes of split_bf16x3 (same epilogue and return value as gemm()).  row_mask: as in
+    gemm() (lcr_gemm_f32_bsplit_masked)."""
     _lib.require_cuda(a, planes)
     assert a.dtype == torch.float32 and a.is_contiguous() and planes.dtype == torch.int16 and planes.is_contiguous() and planes.dim() == 5
     M, K = a.shape
@@ -253,6 +290,12 @@ def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0):
         seg_len = _seg(seg_len, M, a.device)
         S = seg_len.numel()
         stats = _zero_stats(S, groups, a.device)
+    if row_mask is not None:
+        block_k = _mask_args(a, row_mask)
+        _lib.check(_lib.lib().lcr_gemm_f32_bsplit_masked(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
+                                                         _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats),
+                                                         _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_bsplit_masked")
+        return c, stats
     _lib.check(_lib.lib().lcr_gemm_f32_bsplit(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
                                               _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
                "lcr_gemm_f32_bsplit")
@@ -320,8 +363,10 @@ def _kp_host(kernel_points):
     return kp
 
 
-def kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kernel_points_host, sigma, order=None):
-    """(A [M, 15*C], nn [M]) — the gather/influence/aggregate half of KPConv.forward."""
+def kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kernel_points_host, sigma, order=None, emit_mask=False):
+    """(A [M, 15*C], nn [M]) — the gather/influence/aggregate half of KPConv.forward.  emit_mask: (A, nn, mask) with mask int16 [M], bit k
+    set when the kernel-point block A[m, kC:(k+1)C] holds a value other than +-0; the other blocks of A are NOT written (read A only
+    through gemm / gemm_bsplit with row_mask=mask)."""
     _lib.require_cuda(s_feats, q_points, s_points, idx)
     M, H = idx.shape
     Ns, C = s_feats.shape
@@ -329,6 +374,13 @@ def kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kernel_points_host
     A = torch.empty((M, 15 * C), dtype=torch.float32, device=s_feats.device)
     nn = torch.empty((M,), dtype=torch.float32, device=s_feats.device)
     kp = _kp_host(kernel_points_host)
+    if emit_mask:
+        mask = torch.empty((M,), dtype=torch.int16, device=s_feats.device)
+        _timed("kpconv_aggregate", lambda: _lib.check(_lib.lib().lcr_kpconv_aggregate_mask(
+            _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
+            ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(mask), _lib.ptr(order), 0,
+            _lib.stream_ptr(s_feats.device)), "lcr_kpconv_aggregate_mask"), meta=(M, Ns, H, C, idx.element_size()))
+        return A, nn, mask
     _timed("kpconv_aggregate", lambda: _lib.check(_lib.lib().lcr_kpconv_aggregate(
         _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
         ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(order), _lib.stream_ptr(s_feats.device)),

@@ -92,11 +92,17 @@ class KPConv(nn.Module):
             # aggregate + contraction in one launch: the (M, 480) intermediate never reaches memory
             return F.kpconv_fused(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, self.weights, self.bias,
                                   seg_len=seg_len, groups=groups, order=order)
-        A, nn_cnt = F.kpconv_aggregate(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, order=order)
         wt = self.weights_t()
-        if F.gemm_split_enabled() and F.gemm_split_ok(wt.shape[0], wt.shape[1]):
-            return F.gemm_bsplit(A, self.weights_t_split(), bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups)
-        return F.gemm(A, wt, trans_b=True, bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups)
+        split = F.gemm_split_enabled() and F.gemm_split_ok(wt.shape[0], wt.shape[1])
+        # row masks (as lcr_encoder_forward): all-zero kernel-point blocks are neither stored nor read — same results
+        M = neighbor_indices.shape[0]
+        if F.kpconv_mask_ok(M, wt.shape[0], wt.shape[1], split):
+            A, nn_cnt, mask = F.kpconv_aggregate(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, order=order, emit_mask=True)
+        else:
+            (A, nn_cnt), mask = F.kpconv_aggregate(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, order=order), None
+        if split:
+            return F.gemm_bsplit(A, self.weights_t_split(), bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
+        return F.gemm(A, wt, trans_b=True, bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
 
     def forward(self, s_feats, q_points, s_points, neighbor_indices):
         return self.forward_raw(s_feats, q_points, s_points, neighbor_indices)[0]
