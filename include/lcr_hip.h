@@ -602,6 +602,44 @@ int lcr_icp_point_to_point(const float* src, const int64_t* src_len, const float
                            double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist,
                            double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream);
 
+/* Point-to-plane ICP (Open3D's RegistrationICP with TransformationEstimationPointToPlane(), no robust kernel): the arguments, outputs,
+ * loop, stopping rule, check_every, history, determinism and domain of lcr_icp_point_to_point, plus tgt_normals f32[nt,3] (stacked like
+ * tgt; lcr_estimate_normals writes them).
+ *   - Correspondence step: unchanged (the same q, partner, count, fitness, inlier_rmse and corr rows as point-to-point at any pose).
+ *   - Update: every partnered source row i whose partner j has a non-zero normal is usable.  s = T p_i in fp64 (((T00*x + T01*y) +
+ *     T02*z) + T03, not the rounded q), t = tgt_j, n = normal_j, r = ((s-t)_x n_x + (s-t)_y n_y) + (s-t)_z n_z, J = [s x n, n].
+ *     A = sum J J^T (21 unique entries) and g = sum J r in fp64, over the same fixed tree of the pair's rows as point-to-point.
+ *     A x = -g is solved by fp64 LDL^T without pivoting; dT = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] (Open3D's
+ *     TransformVector6dToMatrix4d, linearised about the target frame's origin) and T <- dT T.  T is left unchanged when fewer than 6
+ *     rows are usable or a pivot is <= 1e-12 times the largest diagonal entry of A (all usable rows on one plane, for example).
+ *   - Partners with a zero normal count for fitness and inlier_rmse, and stay out of A and g.
+ *   - ws: lcr_icp_plane_ws_bytes(S, ns, nt) (30 doubles per block row against point-to-point's 17; lcr_icp_ws_bytes does not cover it). */
+int lcr_icp_plane_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes);
+int lcr_icp_point_to_plane(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, const float* tgt_normals, int S,
+                           const double* init, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                           double relative_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr,
+                           double* T_hist, double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream);
+
+/* Surface normals (Open3D's EstimateNormals with KDTreeSearchParamHybrid(radius, max_nn), as utils/utils/open3d.py:53-58 calls it) for B
+ * stacked clouds in one call, made exact and batch-invariant.
+ *   - Input: points f32[N,3] stacked cloud-major, lengths HOST int64[B]; radius > 0; 1 <= max_nn <= 128; viewpoint f32[B,3] on the
+ *     device or NULL (the origin of every cloud's frame: the sensor).  Coordinates must be finite (not checked on the device).
+ *   - Neighbourhood of row i: the rows j of the same cloud with d2 < radius*radius (fp32 product), d2 = ((dx*dx)+dy*dy)+dz*dz in fp32
+ *     without FMA; of these the max_nn with the smallest (d2, row), row i itself included: the first max_nn rows
+ *     lcr_radius_query_ordered(q = s = the cloud, limit = max_nn) returns for i.  k = their number.
+ *   - Covariance in fp64 about the query point p_i: d = p_j - p_i per selected row, s_a = sum d_a, s_ab = sum d_a d_b (summed in
+ *     ascending row order), c_ab = s_ab / k - (s_a / k) (s_b / k): Open3D's ComputeCovariance in exact arithmetic.
+ *   - Normal: the unit eigenvector of the smallest eigenvalue lam0 <= lam1 <= lam2 (fp64 Jacobi), oriented so that n . (v - p_i) >= 0
+ *     (fp64); where that product is exactly 0, the first non-zero component of n is made positive.
+ *   - Degenerate rows (k < 3, lam2 <= 1e-30, or lam1 <= 1e-12 lam2: coincident or collinear neighbours) get the zero normal.
+ *   - Outputs: normals f32[N,3]; nullable curvature f32[N] (lam0 / (lam0 + lam1 + lam2), 0 for degenerate rows) and count i32[N] (k).
+ *   - Determinism: a cloud gives bit-identical outputs alone or at any position in any batch.
+ *   - Asynchronous and stream-ordered, no allocation; ws: lcr_normals_ws_bytes(B, N).
+ * Domain: 1 <= B <= 64, 0 < radius with radius*radius finite, 1 <= max_nn <= 128, lengths >= 0, N <= 2^31-1; LCR_EARG outside. */
+int lcr_normals_ws_bytes(int B, int64_t n, size_t* bytes);
+int lcr_estimate_normals(const float* points, const int64_t* lengths, int B, float radius, int max_nn, const float* viewpoint, float* normals,
+                         float* curvature, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

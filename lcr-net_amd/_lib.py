@@ -116,12 +116,17 @@ _SIGS = {
     "lcr_icp_ws_bytes": (c_int, [c_int, c_i64, c_i64, c_size_p]),
     "lcr_icp_point_to_point": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_float, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_vp, c_int, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_icp_plane_ws_bytes": (c_int, [c_int, c_i64, c_i64, c_size_p]),
+    "lcr_icp_point_to_plane": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_float, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_normals_ws_bytes": (c_int, [c_int, c_i64, c_size_p]),
+    "lcr_estimate_normals": (c_int, [c_vp, c_vp, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
 }
 
 
 # entry points that synchronise, compute on the host or issue long launch sequences: called with the interpreter lock RELEASED
 _RELEASES_GIL = {"lcr_roformer_forward", "lcr_precompute_batch", "lcr_precompute_batch_rows", "lcr_encoder_forward", "lcr_encoder_forward_ex", "lcr_ktimer_read",
-                 "lcr_ktimer_read2", "lcr_hashmap_order_host", "lcr_ransac_sample_host", "lcr_icp_point_to_point", "lcr_netvlad_forward", "lcr_log_sinkhorn", "lcr_log_sinkhorn_ex",
+                 "lcr_ktimer_read2", "lcr_hashmap_order_host", "lcr_ransac_sample_host", "lcr_icp_point_to_point", "lcr_icp_point_to_plane", "lcr_netvlad_forward", "lcr_log_sinkhorn", "lcr_log_sinkhorn_ex",
                  "lcr_local_global_registration", "lcr_local_global_registration_ex", "lcr_retrieval_topk", "lcr_stream_spin"}
 
 

@@ -19,6 +19,9 @@
 // re-enumeration path (DESIGN.md "Point-to-point ICP").
 // Reductions never use float atomics: every sum is a fixed tree over the pair's own row indices, so a pair gives the same bits alone or
 // at any position in any batch.
+// Point-to-plane (lcr_icp_point_to_plane) runs the same loop with k_icp_match_plane / k_icp_update_plane: the same nearest-partner search
+// (icp_nearest), a row block of ICP_PLANE_MOM doubles (count, sum d², usable rows, the 21 entries of A = sum J J^T, g = sum J r), and an
+// fp64 LDL^T solve of A x = -g in the update.
 #include <climits>
 #include <cmath>
 
@@ -31,6 +34,7 @@ namespace lcr {
 constexpr int ICP_BLOCK = 256;   // source rows (= threads) per k_icp_match workgroup; also the k_icp_update workgroup size
 constexpr int ICP_UNROLL = 4;    // candidate loads in flight per lane
 constexpr int ICP_MOM = 17;      // count, sum d², sum dp[3], sum dr[3], sum dp dr^T [9]  (dp = p - anchor_src, dr = r - anchor_tgt)
+constexpr int ICP_PLANE_MOM = 30;  // count, sum d², usable rows, A = sum J J^T [21, upper triangle row by row], g = sum J r [6]
 
 // pair table, by value in the kernel arguments (S <= GRID_MAX_B): stacked row offsets and the first k_icp_match block of every pair
 struct IcpPairs {
@@ -54,24 +58,59 @@ __device__ __forceinline__ float icp_row(const double* T, int r, double x, doubl
   return static_cast<float>(dadd(dadd(dadd(dmul(T[4 * r], x), dmul(T[4 * r + 1], y)), dmul(T[4 * r + 2], z)), T[4 * r + 3]));
 }
 
-// fixed-order sum of ICP_MOM doubles over a workgroup of ICP_BLOCK threads; the totals land in thread 0's m[]
-__device__ __forceinline__ void icp_block_sum(double (&m)[ICP_MOM], double (*s_red)[ICP_MOM]) {
+// fixed-order sum of MOM doubles over a workgroup of ICP_BLOCK threads (across the wavefront first); the totals land in thread 0's m[]
+template <int MOM>
+__device__ __forceinline__ void icp_block_sum(double (&m)[MOM], double (*s_red)[MOM]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-  for (int j = 0; j < ICP_MOM; ++j)
+  for (int j = 0; j < MOM; ++j)
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m[j] = dadd(m[j], __shfl_xor(m[j], d));
   if (lane == 0)
 #pragma unroll
-    for (int j = 0; j < ICP_MOM; ++j) s_red[w][j] = m[j];
+    for (int j = 0; j < MOM; ++j) s_red[w][j] = m[j];
   __syncthreads();
   if (threadIdx.x == 0)
 #pragma unroll
-    for (int j = 0; j < ICP_MOM; ++j) {
+    for (int j = 0; j < MOM; ++j) {
       double a = s_red[0][j];
       for (int v = 1; v < ICP_BLOCK / 64; ++v) a = dadd(a, s_red[v][j]);
       m[j] = a;
     }
+}
+
+// the partner key of q: the smallest (d², target row) with d² < r2 over the nine x-runs of q's 3x3x3 cell neighbourhood, ~0 if none
+__device__ __forceinline__ uint64_t icp_nearest(const GridCloud& c, const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
+                                                float r2, float qx, float qy, float qz) {
+  uint64_t best = ~0ull;
+  if (c.dim[0] > 0) {
+    // the cells of cell_coord() (clamped to [-2, dim+1]) and their 3x3x3 neighbourhood inside the box, as k_radius_query enumerates them
+    const int cx = cell_coord(qx, c.org[0], c.inv_cell, c.dim[0]);
+    const int cy = cell_coord(qy, c.org[1], c.inv_cell, c.dim[1]);
+    const int cz = cell_coord(qz, c.org[2], c.inv_cell, c.dim[2]);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, c.dim[0] - 1);
+    if (x0 <= x1) {
+      for (int zz = max(cz - 1, 0); zz <= min(cz + 1, c.dim[2] - 1); ++zz)
+        for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.dim[1] - 1); ++yy) {
+          const int crow = c.cell_base + (zz * c.dim[1] + yy) * c.dim[0];
+          const int e = cell_start[crow + x1 + 1];
+          // ICP_UNROLL loads in flight per trip; the tail re-reads the run's last candidate, which cannot change an arg-min
+          for (int k = cell_start[crow + x0]; k < e; k += ICP_UNROLL) {
+            float4 p[ICP_UNROLL];
+#pragma unroll
+            for (int u = 0; u < ICP_UNROLL; ++u) p[u] = sorted[min(k + u, e - 1)];
+#pragma unroll
+            for (int u = 0; u < ICP_UNROLL; ++u) {
+              const float dx = fsub(qx, p[u].x), dy = fsub(qy, p[u].y), dz = fsub(qz, p[u].z);
+              const float d2 = fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
+              const uint64_t key = (static_cast<uint64_t>(__float_as_uint(d2)) << 32) | __float_as_uint(p[u].w);
+              best = (d2 < r2 && key < best) ? key : best;
+            }
+          }
+        }
+    }
+  }
+  return best;
 }
 
 __device__ __forceinline__ int icp_pair_of_block(const IcpPairs& P, int blk) {
@@ -123,35 +162,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float
     for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
     const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
     const float qx = icp_row(Tm, 0, x, y, z), qy = icp_row(Tm, 1, x, y, z), qz = icp_row(Tm, 2, x, y, z);
-    const GridCloud& c = h->cloud[s];
-    uint64_t best = ~0ull;
-    if (c.dim[0] > 0) {
-      // the cells of cell_coord() (clamped to [-2, dim+1]) and their 3x3x3 neighbourhood inside the box, as k_radius_query enumerates them
-      const int cx = cell_coord(qx, c.org[0], c.inv_cell, c.dim[0]);
-      const int cy = cell_coord(qy, c.org[1], c.inv_cell, c.dim[1]);
-      const int cz = cell_coord(qz, c.org[2], c.inv_cell, c.dim[2]);
-      const int x0 = max(cx - 1, 0), x1 = min(cx + 1, c.dim[0] - 1);
-      if (x0 <= x1) {
-        for (int zz = max(cz - 1, 0); zz <= min(cz + 1, c.dim[2] - 1); ++zz)
-          for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.dim[1] - 1); ++yy) {
-            const int crow = c.cell_base + (zz * c.dim[1] + yy) * c.dim[0];
-            const int e = cell_start[crow + x1 + 1];
-            // ICP_UNROLL loads in flight per trip; the tail re-reads the run's last candidate, which cannot change an arg-min
-            for (int k = cell_start[crow + x0]; k < e; k += ICP_UNROLL) {
-              float4 p[ICP_UNROLL];
-#pragma unroll
-              for (int u = 0; u < ICP_UNROLL; ++u) p[u] = sorted[min(k + u, e - 1)];
-#pragma unroll
-              for (int u = 0; u < ICP_UNROLL; ++u) {
-                const float dx = fsub(qx, p[u].x), dy = fsub(qy, p[u].y), dz = fsub(qz, p[u].z);
-                const float d2 = fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
-                const uint64_t key = (static_cast<uint64_t>(__float_as_uint(d2)) << 32) | __float_as_uint(p[u].w);
-                best = (d2 < r2 && key < best) ? key : best;
-              }
-            }
-          }
-      }
-    }
+    const uint64_t best = icp_nearest(h->cloud[s], cell_start, sorted, r2, qx, qy, qz);
     int32_t j_loc = -1;
     if (best != ~0ull) {
       const int64_t j = static_cast<int64_t>(static_cast<uint32_t>(best));
@@ -173,10 +184,48 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float
     }
     if (corr) corr[i] = j_loc;
   }
-  icp_block_sum(m, s_red);
+  icp_block_sum<ICP_MOM>(m, s_red);
   if (threadIdx.x == 0)
 #pragma unroll
     for (int j = 0; j < ICP_MOM; ++j) slab[static_cast<int64_t>(blk) * ICP_MOM + j] = m[j];
+}
+
+// thread 0 of a pair's k_icp_update*: result_k (fitness, rmse) from the summed count and d², the convergence test against result_{k-1} and
+// the history row; false when the pair stops here (done)
+__device__ __forceinline__ bool icp_result(const IcpPairs& P, int s, double cnt, double d2sum, int k, int max_iter, double rel_fit, double rel_rmse,
+                                           double* __restrict__ fitness, double* __restrict__ rmse, int32_t* __restrict__ done,
+                                           double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
+  const int64_t ns = P.src_off[s + 1] - P.src_off[s];
+  const int64_t hrow = static_cast<int64_t>(s) * (max_iter + 1);
+  const double fit = cnt / static_cast<double>(ns);
+  const double rm = cnt > 0.0 ? sqrt(d2sum / cnt) : 0.0;
+  const bool conv = k > 0 && fabs(fitness[s] - fit) < rel_fit && fabs(rmse[s] - rm) < rel_rmse;
+  fitness[s] = fit;
+  rmse[s] = rm;
+  if (fit_hist) fit_hist[hrow + k] = fit;
+  if (rmse_hist) rmse_hist[hrow + k] = rm;
+  if (conv || k >= max_iter) {
+    done[s] = 1;
+    return false;
+  }
+  return true;
+}
+
+// thread 0 of a pair's k_icp_update*: T_{k+1} = Tn (rows 0..2), the iteration count, its history row, and the pair counted as running
+__device__ __forceinline__ void icp_commit(int s, int k, int max_iter, const double (&Tn)[12], double* __restrict__ T, int32_t* __restrict__ iters,
+                                           int32_t* __restrict__ running, double* __restrict__ T_hist) {
+  const int64_t hrow = static_cast<int64_t>(s) * (max_iter + 1);
+  for (int q = 0; q < 12; ++q) T[16 * s + q] = Tn[q];
+  T[16 * s + 12] = T[16 * s + 13] = T[16 * s + 14] = 0.0;
+  T[16 * s + 15] = 1.0;
+  iters[s] = k + 1;
+  if (T_hist) {
+    double* o = T_hist + 16 * (hrow + k + 1);
+    for (int q = 0; q < 12; ++q) o[q] = Tn[q];
+    o[12] = o[13] = o[14] = 0.0;
+    o[15] = 1.0;
+  }
+  atomicAdd(&running[k & 1], 1);
 }
 
 // one workgroup per pair: result_k from the slab, convergence test against result_{k-1}, then update k (T_{k+1}) unless the pair stops
@@ -196,24 +245,12 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update(IcpPairs P, const floa
   for (int b = tid; b < nb; b += ICP_BLOCK)
 #pragma unroll
     for (int j = 0; j < ICP_MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * ICP_MOM + j]);
-  icp_block_sum(m, s_red);
+  icp_block_sum<ICP_MOM>(m, s_red);
   if (tid != 0) return;
 
-  const int64_t a = P.src_off[s], ns = P.src_off[s + 1] - a, tb = P.tgt_off[s];
-  const int hist_rows = max_iter + 1;
-  const int64_t hrow = static_cast<int64_t>(s) * hist_rows;
+  const int64_t a = P.src_off[s], tb = P.tgt_off[s];
   const double cnt = m[0];
-  const double fit = cnt / static_cast<double>(ns);
-  const double rm = cnt > 0.0 ? sqrt(m[1] / cnt) : 0.0;
-  const bool conv = k > 0 && fabs(fitness[s] - fit) < rel_fit && fabs(rmse[s] - rm) < rel_rmse;
-  fitness[s] = fit;
-  rmse[s] = rm;
-  if (fit_hist) fit_hist[hrow + k] = fit;
-  if (rmse_hist) rmse_hist[hrow + k] = rm;
-  if (conv || k >= max_iter) {
-    done[s] = 1;
-    return;
-  }
+  if (!icp_result(P, s, cnt, m[1], k, max_iter, rel_fit, rel_rmse, fitness, rmse, done, fit_hist, rmse_hist)) return;
   // update k: unit-weight Kabsch on (p_i, r_j) about the anchors; T unchanged when count < 3 or H is degenerate
   double Tn[12];
 #pragma unroll
@@ -241,17 +278,155 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update(IcpPairs P, const floa
       }
     }
   }
-  for (int q = 0; q < 12; ++q) T[16 * s + q] = Tn[q];
-  T[16 * s + 12] = T[16 * s + 13] = T[16 * s + 14] = 0.0;
-  T[16 * s + 15] = 1.0;
-  iters[s] = k + 1;
-  if (T_hist) {
-    double* o = T_hist + 16 * (hrow + k + 1);
-    for (int q = 0; q < 12; ++q) o[q] = Tn[q];
-    o[12] = o[13] = o[14] = 0.0;
-    o[15] = 1.0;
+  icp_commit(s, k, max_iter, Tn, T, iters, running, T_hist);
+}
+
+// point-to-plane: one thread per source row, the partner of k_icp_match; a usable row (partner with a non-zero normal) adds J J^T and J r
+// (s = T p in fp64, J = [s x n, n], r = (s - t) . n) to its row block, reduced into slab[blockIdx.x][ICP_PLANE_MOM].  The row keeps only
+// J and r; each of the 30 block sums is formed from them and reduced on its own (the tree of icp_block_sum), so that the 30 moments are
+// never live at once: 30 doubles in flight would double the registers of the candidate loop's kernel and halve its occupancy.
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_match_plane(IcpPairs P, const float* __restrict__ src, const float* __restrict__ tgt,
+                                                               const float* __restrict__ nrm, const GridHeader* __restrict__ h,
+                                                               const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted, float r2,
+                                                               const double* __restrict__ T, const int32_t* __restrict__ done,
+                                                               double* __restrict__ slab, int32_t* __restrict__ corr) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_PLANE_MOM];
+  const int blk = blockIdx.x;
+  const int s = icp_pair_of_block(P, blk);
+  if (done[s]) return;                                         // workgroup-uniform
+  const int64_t a = P.src_off[s], n = P.src_off[s + 1] - a, tb = P.tgt_off[s];
+  const int64_t row = static_cast<int64_t>(blk - P.blk_off[s]) * ICP_BLOCK + threadIdx.x;     // pair-local
+  double found = 0.0, d2 = 0.0, use = 0.0, res = 0.0, J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (row < n) {
+    const int64_t i = a + row;
+    double Tm[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
+    const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+    const float qx = icp_row(Tm, 0, x, y, z), qy = icp_row(Tm, 1, x, y, z), qz = icp_row(Tm, 2, x, y, z);
+    const uint64_t best = icp_nearest(h->cloud[s], cell_start, sorted, r2, qx, qy, qz);
+    int32_t j_loc = -1;
+    if (best != ~0ull) {
+      const int64_t j = static_cast<int64_t>(static_cast<uint32_t>(best));
+      j_loc = static_cast<int32_t>(j - tb);
+      found = 1.0;
+      d2 = static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32)));
+      const double nv[3] = {nrm[3 * j], nrm[3 * j + 1], nrm[3 * j + 2]};
+      if (nv[0] != 0.0 || nv[1] != 0.0 || nv[2] != 0.0) {
+        double sp[3], dv[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          sp[r] = dadd(dadd(dadd(dmul(Tm[4 * r], x), dmul(Tm[4 * r + 1], y)), dmul(Tm[4 * r + 2], z)), Tm[4 * r + 3]);
+          dv[r] = sp[r] - static_cast<double>(tgt[3 * j + r]);
+        }
+        use = 1.0;
+        res = dadd(dadd(dmul(dv[0], nv[0]), dmul(dv[1], nv[1])), dmul(dv[2], nv[2]));
+        J[0] = dmul(sp[1], nv[2]) - dmul(sp[2], nv[1]);
+        J[1] = dmul(sp[2], nv[0]) - dmul(sp[0], nv[2]);
+        J[2] = dmul(sp[0], nv[1]) - dmul(sp[1], nv[0]);
+        J[3] = nv[0];
+        J[4] = nv[1];
+        J[5] = nv[2];
+      }
+    }
+    if (corr) corr[i] = j_loc;
   }
-  atomicAdd(&running[k & 1], 1);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  auto wave_sum = [&](double v, int q) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = dadd(v, __shfl_xor(v, d));
+    if (lane == 0) s_red[w][q] = v;
+  };
+  wave_sum(found, 0);
+  wave_sum(d2, 1);
+  wave_sum(use, 2);
+  int q = 3;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) wave_sum(dmul(J[r], J[c]), q++);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) wave_sum(dmul(J[r], res), 24 + r);
+  __syncthreads();
+  if (threadIdx.x < ICP_PLANE_MOM) {                              // the cross-wave step of icp_block_sum, one moment per thread
+    double v = s_red[0][threadIdx.x];
+    for (int u = 1; u < ICP_BLOCK / 64; ++u) v = dadd(v, s_red[u][threadIdx.x]);
+    slab[static_cast<int64_t>(blk) * ICP_PLANE_MOM + threadIdx.x] = v;
+  }
+}
+
+// x = solution of A x = -g by LDL^T without pivoting (A symmetric 6x6 from its upper triangle, row by row); false when a pivot is
+// <= 1e-12 times the largest diagonal entry of A
+__device__ inline bool icp_solve6(const double* au, const double* g, double x[6]) {
+  double A[6][6], L[6][6], D[6];
+  int q = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = au[q++];
+  double amax = 0.0;
+  for (int r = 0; r < 6; ++r) amax = fmax(amax, A[r][r]);
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
+    if (!(d > 1e-12 * amax)) return false;
+    D[j] = d;
+    L[j][j] = 1.0;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = A[i][j];
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k] * D[k];
+      L[i][j] = v / d;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {                                  // L y = -g
+    double v = -g[i];
+    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+    y[i] = v;
+  }
+  for (int i = 5; i >= 0; --i) {                                 // D L^T x = y
+    double v = y[i] / D[i];
+    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+    x[i] = v;
+  }
+  return true;
+}
+
+// one workgroup per pair: result_k as k_icp_update, then the point-to-plane update T <- dT(x) T
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_update_plane(IcpPairs P, const double* __restrict__ slab, int k, int max_iter, double rel_fit,
+                                                                double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
+                                                                double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ done,
+                                                                int32_t* __restrict__ running, double* __restrict__ T_hist,
+                                                                double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_PLANE_MOM];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (s == 0 && tid == 0) running[(k + 1) & 1] = 0;          // the other slot: read by the host after the previous launch, if at all
+  if (done[s]) return;
+  const int b0 = P.blk_off[s], nb = P.blk_off[s + 1] - b0;
+  double m[ICP_PLANE_MOM];
+#pragma unroll
+  for (int j = 0; j < ICP_PLANE_MOM; ++j) m[j] = 0.0;
+  for (int b = tid; b < nb; b += ICP_BLOCK)
+#pragma unroll
+    for (int j = 0; j < ICP_PLANE_MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * ICP_PLANE_MOM + j]);
+  icp_block_sum<ICP_PLANE_MOM>(m, s_red);
+  if (tid != 0) return;
+  if (!icp_result(P, s, m[0], m[1], k, max_iter, rel_fit, rel_rmse, fitness, rmse, done, fit_hist, rmse_hist)) return;
+  // update k: T unchanged when fewer than 6 rows are usable or A is (numerically) singular
+  double Tn[12];
+  for (int q = 0; q < 12; ++q) Tn[q] = T[16 * s + q];
+  double x[6];
+  if (m[2] >= 6.0 && icp_solve6(m + 3, m + 24, x)) {
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cc = cos(x[2]), sc = sin(x[2]);
+    const double R[3][3] = {{cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa},     // Rz(x2) Ry(x1) Rx(x0)
+                            {sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa},
+                            {-sb, cb * sa, cb * ca}};
+    double To[12];
+    for (int q = 0; q < 12; ++q) To[q] = Tn[q];
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 4; ++c) Tn[4 * r + c] = (R[r][0] * To[c] + R[r][1] * To[4 + c]) + R[r][2] * To[8 + c];
+      Tn[4 * r + 3] += x[3 + r];
+    }
+  }
+  icp_commit(s, k, max_iter, Tn, T, iters, running, T_hist);
 }
 
 }  // namespace lcr
@@ -263,10 +438,11 @@ constexpr int ICP_MAX_ITER = 100000;
 
 int icp_blocks_bound(int S, int64_t ns) { return div_up(ns, ICP_BLOCK) + S; }
 
-size_t icp_layout(void* ws, int S, int64_t ns, int64_t nt, size_t grid_bytes, double** slab, int32_t** done, int32_t** running, int64_t** tgt_len) {
+size_t icp_layout(void* ws, int S, int64_t ns, int64_t nt, size_t grid_bytes, int mom, double** slab, int32_t** done, int32_t** running,
+                  int64_t** tgt_len) {
   Carver c(ws, ~size_t(0));
   c.take<char>(grid_bytes);                                      // the support grid, at the workspace base
-  double* sl = c.take<double>(static_cast<size_t>(icp_blocks_bound(S, ns)) * ICP_MOM);
+  double* sl = c.take<double>(static_cast<size_t>(icp_blocks_bound(S, ns)) * mom);
   int32_t* dn = c.take<int32_t>(S);
   int32_t* rn = c.take<int32_t>(2);
   int64_t* tl = c.take<int64_t>(S);
@@ -279,34 +455,35 @@ size_t icp_layout(void* ws, int S, int64_t ns, int64_t nt, size_t grid_bytes, do
   (void)nt;
   return c.off;
 }
-}  // namespace
 
-extern "C" int lcr_icp_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes) {
+int icp_ws_bytes(const char* name, int S, int64_t ns, int64_t nt, int mom, size_t* bytes) {
   if (!bytes || S < 1 || S > GRID_MAX_B || ns < 0 || nt < 0 || ns > INT32_MAX || nt > INT32_MAX) {
-    set_error("lcr_icp_ws_bytes: outside the domain (1 <= S <= %d, 0 <= ns, nt <= 2^31-1): S=%d ns=%lld nt=%lld", GRID_MAX_B, S,
+    set_error("%s: outside the domain (1 <= S <= %d, 0 <= ns, nt <= 2^31-1): S=%d ns=%lld nt=%lld", name, GRID_MAX_B, S,
               static_cast<long long>(ns), static_cast<long long>(nt));
     return LCR_EARG;
   }
   size_t g = 0;
   if (lcr_support_grid_ws_bytes(nt, S, &g) != LCR_OK) return LCR_EARG;
-  *bytes = icp_layout(nullptr, S, ns, nt, g, nullptr, nullptr, nullptr, nullptr);
+  *bytes = icp_layout(nullptr, S, ns, nt, g, mom, nullptr, nullptr, nullptr, nullptr);
   return LCR_OK;
 }
 
-extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, int S, const double* init,
-                                      float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
-                                      double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist,
-                                      double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
+// the host loop of both estimators (tgt_normals == nullptr: point-to-point)
+template <bool PLANE>
+int icp_run(const char* name, const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, const float* tgt_normals, int S,
+            const double* init, float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse, double* T,
+            double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist, double* rmse_hist,
+            int check_every, void* ws, size_t ws_bytes, void* stream) {
   const float r = max_correspondence_distance;
   if (S < 1 || S > GRID_MAX_B || max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
       !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0)) {
-    set_error("lcr_icp_point_to_point: outside the domain (1 <= S <= %d, 0 <= max_iteration <= %d, r > 0 with r*r finite, relative "
-              "criteria >= 0, check_every >= 0): S=%d max_iteration=%d r=%g check_every=%d", GRID_MAX_B, ICP_MAX_ITER, S, max_iteration,
+    set_error("%s: outside the domain (1 <= S <= %d, 0 <= max_iteration <= %d, r > 0 with r*r finite, relative "
+              "criteria >= 0, check_every >= 0): S=%d max_iteration=%d r=%g check_every=%d", name, GRID_MAX_B, ICP_MAX_ITER, S, max_iteration,
               static_cast<double>(r), check_every);
     return LCR_EARG;
   }
   if (!src_len || !tgt_len || !init || !T || !fitness || !inlier_rmse || !iterations || !ws) {
-    set_error("lcr_icp_point_to_point: null pointer");
+    set_error("%s: null pointer", name);
     return LCR_EARG;
   }
   IcpPairs P;
@@ -315,7 +492,7 @@ extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, 
   P.src_off[0] = P.tgt_off[0] = 0;
   for (int s = 0; s < S; ++s) {
     if (src_len[s] < 0 || tgt_len[s] < 0 || src_len[s] > INT32_MAX || tgt_len[s] > INT32_MAX) {
-      set_error("lcr_icp_point_to_point: pair %d has a negative or too large length (%lld, %lld)", s, static_cast<long long>(src_len[s]),
+      set_error("%s: pair %d has a negative or too large length (%lld, %lld)", name, s, static_cast<long long>(src_len[s]),
                 static_cast<long long>(tgt_len[s]));
       return LCR_EARG;
     }
@@ -324,51 +501,87 @@ extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, 
     P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
   }
   const int64_t ns = P.src_off[S], nt = P.tgt_off[S];
-  if (ns > INT32_MAX || nt > INT32_MAX || (ns > 0 && !src) || (nt > 0 && !tgt)) {
-    set_error("lcr_icp_point_to_point: more than 2^31-1 rows, or a null point array (ns=%lld nt=%lld)", static_cast<long long>(ns),
-              static_cast<long long>(nt));
+  if (ns > INT32_MAX || nt > INT32_MAX || (ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals)))) {
+    set_error("%s: more than 2^31-1 rows, or a null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
     return LCR_EARG;
   }
+  constexpr int mom = PLANE ? ICP_PLANE_MOM : ICP_MOM;
   size_t need = 0, grid_bytes = 0;
-  lcr_icp_ws_bytes(S, ns, nt, &need);
+  icp_ws_bytes(name, S, ns, nt, mom, &need);
   lcr_support_grid_ws_bytes(nt, S, &grid_bytes);
   if (need > ws_bytes) {
-    set_error("lcr_icp_point_to_point: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    set_error("%s: workspace of %zu bytes, %zu needed", name, ws_bytes, need);
     return LCR_ESPACE;
   }
   double* slab;
   int32_t *done, *running;
   int64_t* tgt_len_dev;
-  icp_layout(ws, S, ns, nt, grid_bytes, &slab, &done, &running, &tgt_len_dev);
+  icp_layout(ws, S, ns, nt, grid_bytes, mom, &slab, &done, &running, &tgt_len_dev);
   const GridLayout L = grid_layout(ws, nt, S);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, P, init, max_iteration + 1, T, fitness, inlier_rmse, iterations, done, running, tgt_len_dev,
                      T_hist, fitness_hist, rmse_hist);
   if (corr && ns > 0 && hipMemsetAsync(corr, 0xff, static_cast<size_t>(ns) * sizeof(int32_t), st) != hipSuccess) {   // -1 for pairs that never run
-    set_error("lcr_icp_point_to_point: clearing corr failed");
+    set_error("%s: clearing corr failed", name);
     return LCR_EHIP;
   }
-  int rc = check_launch("lcr_icp_point_to_point (init)");
+  int rc = check_launch(name);
   if (rc) return rc;
   rc = lcr_support_grid_build(tgt, tgt_len_dev, S, nt, r, nullptr, ws, grid_bytes, stream);
   if (rc) return rc;
   const int nblk = P.blk_off[S];
   const float r2 = r * r;                                        // fp32 product, as lcr_radius_query
   for (int k = 0; k <= max_iteration; ++k) {
-    if (nblk > 0)
-      hipLaunchKernelGGL(k_icp_match, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, tgt, L.hdr, L.cell_start, L.sorted, r2, T, done, slab, corr);
-    hipLaunchKernelGGL(k_icp_update, dim3(S), dim3(ICP_BLOCK), 0, st, P, src, tgt, slab, k, max_iteration, relative_fitness, relative_rmse, T,
-                       fitness, inlier_rmse, iterations, done, running, T_hist, fitness_hist, rmse_hist);
-    if ((rc = check_launch("lcr_icp_point_to_point"))) return rc;
+    if constexpr (PLANE) {
+      if (nblk > 0)
+        hipLaunchKernelGGL(k_icp_match_plane, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, tgt, tgt_normals, L.hdr, L.cell_start, L.sorted, r2, T,
+                           done, slab, corr);
+      hipLaunchKernelGGL(k_icp_update_plane, dim3(S), dim3(ICP_BLOCK), 0, st, P, slab, k, max_iteration, relative_fitness, relative_rmse, T,
+                         fitness, inlier_rmse, iterations, done, running, T_hist, fitness_hist, rmse_hist);
+    } else {
+      if (nblk > 0)
+        hipLaunchKernelGGL(k_icp_match, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, tgt, L.hdr, L.cell_start, L.sorted, r2, T, done, slab, corr);
+      hipLaunchKernelGGL(k_icp_update, dim3(S), dim3(ICP_BLOCK), 0, st, P, src, tgt, slab, k, max_iteration, relative_fitness, relative_rmse, T,
+                         fitness, inlier_rmse, iterations, done, running, T_hist, fitness_hist, rmse_hist);
+    }
+    if ((rc = check_launch(name))) return rc;
     if (check_every > 0 && k < max_iteration && (k + 1) % check_every == 0) {
       int32_t still = 0;
       if (hipMemcpyAsync(&still, running + (k & 1), sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
           hipStreamSynchronize(st) != hipSuccess) {
-        set_error("lcr_icp_point_to_point: read-back of the running count failed");
+        set_error("%s: read-back of the running count failed", name);
         return LCR_EHIP;
       }
       if (still == 0) break;
     }
   }
   return LCR_OK;
+}
+}  // namespace
+
+extern "C" int lcr_icp_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes) {
+  return icp_ws_bytes("lcr_icp_ws_bytes", S, ns, nt, ICP_MOM, bytes);
+}
+
+extern "C" int lcr_icp_plane_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes) {
+  return icp_ws_bytes("lcr_icp_plane_ws_bytes", S, ns, nt, ICP_PLANE_MOM, bytes);
+}
+
+extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, int S, const double* init,
+                                      float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
+                                      double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist,
+                                      double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
+  return icp_run<false>("lcr_icp_point_to_point", src, src_len, tgt, tgt_len, nullptr, S, init, max_correspondence_distance, max_iteration,
+                        relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist, fitness_hist, rmse_hist, check_every,
+                        ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_icp_point_to_plane(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, const float* tgt_normals,
+                                      int S, const double* init, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                                      double relative_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr,
+                                      double* T_hist, double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  return icp_run<true>("lcr_icp_point_to_plane", src, src_len, tgt, tgt_len, tgt_normals, S, init, max_correspondence_distance, max_iteration,
+                       relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist, fitness_hist, rmse_hist, check_every,
+                       ws, ws_bytes, stream);
 }

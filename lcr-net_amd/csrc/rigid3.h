@@ -1,4 +1,5 @@
-// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (pose_tail.hip) and the RANSAC hypotheses (ransac.hip).
+// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (pose_tail.hip) and the RANSAC hypotheses (ransac.hip), and the
+// fp64 symmetric 3x3 eigen-solver of the surface normals (normals.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,5 +93,61 @@ __device__ inline void rotation_from_H_impl(const double H[3][3], double R[3][3]
 
 __device__ inline void rotation_from_H(const double H[3][3], double R[3][3]) { rotation_from_H_impl<false>(H, R, nullptr); }
 __device__ inline void rotation_from_H_sv(const double H[3][3], double R[3][3], double sv[3]) { rotation_from_H_impl<true>(H, R, sv); }
+
+// Eigen-decomposition of a symmetric 3x3 matrix by cyclic Jacobi rotations in fp64: A = V diag(lam) V^T with lam ascending and the
+// eigenvectors in the columns of V (orthonormal up to rounding).  Sweeps stop once the off-diagonal mass is below 1e-36 of the diagonal's
+// (or zero), at most 50.
+__device__ inline void sym3_eigen(const double A[3][3], double lam[3], double V[3][3]) {
+  double a[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      a[i][j] = A[i][j];
+      V[i][j] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 50; ++sweep) {
+    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+    const double dia = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
+    if (off == 0.0 || off <= 1e-36 * dia) break;
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 3; ++k) {             // a <- a J (columns p, q)
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = c * akp - s * akq;
+          a[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 3; ++k) {             // a <- J^T a (rows p, q)
+          const double apk = a[p][k], aqk = a[q][k];
+          a[p][k] = c * apk - s * aqk;
+          a[q][k] = s * apk + c * aqk;
+        }
+        a[p][q] = a[q][p] = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int ord[3] = {0, 1, 2};
+  for (int x = 0; x < 2; ++x)
+    for (int y = x + 1; y < 3; ++y)
+      if (a[ord[y]][ord[y]] < a[ord[x]][ord[x]]) {
+        const int tmp = ord[x];
+        ord[x] = ord[y];
+        ord[y] = tmp;
+      }
+  double W[3][3];
+  for (int j = 0; j < 3; ++j) {
+    lam[j] = a[ord[j]][ord[j]];
+    for (int k = 0; k < 3; ++k) W[k][j] = V[k][ord[j]];
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int j = 0; j < 3; ++j) V[k][j] = W[k][j];
+}
 
 }  // namespace lcr

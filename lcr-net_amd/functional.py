@@ -840,18 +840,38 @@ def icp_point_to_point(src, src_len, tgt, tgt_len, init, max_correspondence_dist
     stacked pair-major with host lengths src_len / tgt_len (S ints), init f64 [S,4,4] (source onto target) on the device ->
     dict(T f64 [S,4,4], fitness f64 [S], inlier_rmse f64 [S], iterations int32 [S]; with want_corr corr int32 [ns] (pair-local target row or -1);
     with want_history T_hist f64 [S, max_iteration+1, 4, 4], fitness_hist / rmse_hist f64 [S, max_iteration+1], NaN after `iterations`)."""
-    _lib.require_cuda(src, tgt, init)
+    return _icp("icp_point_to_point", src, src_len, tgt, tgt_len, None, init, max_correspondence_distance, max_iteration, relative_fitness,
+                relative_rmse, check_every, want_corr, want_history)
+
+
+def icp_point_to_plane(src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6,
+                       relative_rmse=1e-6, check_every=16, want_corr=False, want_history=False):
+    """Point-to-plane ICP (include/lcr_hip.h, lcr_icp_point_to_plane): icp_point_to_point's arguments and outputs, plus the target normals
+    tgt_normals f32 [nt,3] on the device (estimate_normals writes them; zero rows stay out of the update)."""
+    if tgt_normals is None:
+        raise ValueError("icp_point_to_plane: the target needs normals")
+    return _icp("icp_point_to_plane", src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, max_iteration, relative_fitness,
+                relative_rmse, check_every, want_corr, want_history)
+
+
+def _icp(name, src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+         check_every, want_corr, want_history):
+    plane = tgt_normals is not None
+    _lib.require_cuda(src, tgt, init, *([tgt_normals] if plane else []))
     dev = src.device
     S, iters = len(src_len), int(max_iteration)
     sl = np.ascontiguousarray(np.asarray(src_len, dtype=np.int64).reshape(-1))
     tl = np.ascontiguousarray(np.asarray(tgt_len, dtype=np.int64).reshape(-1))
     if len(tl) != S or init.shape != (S, 4, 4) or init.dtype != torch.float64:
-        raise ValueError("icp_point_to_point: src_len, tgt_len and init [S,4,4] float64 must describe the same S pairs")
+        raise ValueError("%s: src_len, tgt_len and init [S,4,4] float64 must describe the same S pairs" % name)
     if src.shape[0] != int(sl.sum()) or tgt.shape[0] != int(tl.sum()):
-        raise ValueError("icp_point_to_point: the point arrays do not hold sum(src_len) / sum(tgt_len) rows")
+        raise ValueError("%s: the point arrays do not hold sum(src_len) / sum(tgt_len) rows" % name)
+    if plane and (tuple(tgt_normals.shape) != tuple(tgt.shape) or tgt_normals.dtype != torch.float32):
+        raise ValueError("%s: tgt_normals must be float32 with the shape of tgt" % name)
     src, tgt, init = src.contiguous(), tgt.contiguous(), init.contiguous()
     nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_icp_ws_bytes(S, src.shape[0], tgt.shape[0], ctypes.byref(nbytes)), "lcr_icp_ws_bytes")
+    ws_fn = "lcr_icp_plane_ws_bytes" if plane else "lcr_icp_ws_bytes"
+    _lib.check(getattr(_L(), ws_fn)(S, src.shape[0], tgt.shape[0], ctypes.byref(nbytes)), ws_fn)
     ws = _lib.workspace(nbytes.value, dev)
     f64 = dict(dtype=torch.float64, device=dev)
     out = {"T": torch.empty((S, 4, 4), **f64), "fitness": torch.empty((S,), **f64), "inlier_rmse": torch.empty((S,), **f64),
@@ -859,13 +879,56 @@ def icp_point_to_point(src, src_len, tgt, tgt_len, init, max_correspondence_dist
     corr = torch.empty((src.shape[0],), dtype=torch.int32, device=dev) if want_corr else None
     hist = [torch.full((S, iters + 1, 4, 4), float("nan"), **f64), torch.full((S, iters + 1), float("nan"), **f64),
             torch.full((S, iters + 1), float("nan"), **f64)] if want_history else [None, None, None]
-    _lib.check(_L().lcr_icp_point_to_point(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, S, _lib.ptr(init),
-                                           float(max_correspondence_distance), iters, float(relative_fitness), float(relative_rmse),
-                                           _lib.ptr(out["T"]), _lib.ptr(out["fitness"]), _lib.ptr(out["inlier_rmse"]), _lib.ptr(out["iterations"]),
-                                           _lib.ptr(corr), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]), int(check_every),
-                                           _lib.ptr(ws), ws.numel(), _sp(src)), "lcr_icp_point_to_point")
+    tail = (float(max_correspondence_distance), iters, float(relative_fitness), float(relative_rmse), _lib.ptr(out["T"]), _lib.ptr(out["fitness"]),
+            _lib.ptr(out["inlier_rmse"]), _lib.ptr(out["iterations"]), _lib.ptr(corr), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
+            int(check_every), _lib.ptr(ws), ws.numel(), _sp(src))
+    if plane:
+        nrm = tgt_normals.contiguous()
+        _lib.check(_L().lcr_icp_point_to_plane(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, _lib.ptr(nrm), S, _lib.ptr(init), *tail),
+                   "lcr_icp_point_to_plane")
+    else:
+        _lib.check(_L().lcr_icp_point_to_point(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, S, _lib.ptr(init), *tail),
+                   "lcr_icp_point_to_point")
     if want_corr:
         out["corr"] = corr
     if want_history:
         out["T_hist"], out["fitness_hist"], out["rmse_hist"] = hist
+    return out
+
+
+NORMALS_MAX_CLOUDS = 64   # clouds per lcr_estimate_normals call (the support grid's limit)
+NORMALS_MAX_NN = 128
+
+
+def estimate_normals(points, lengths, radius, max_nn, viewpoint=None, want_curvature=False, want_count=False):
+    """Surface normals (include/lcr_hip.h, lcr_estimate_normals; Open3D's EstimateNormals(KDTreeSearchParamHybrid(radius, max_nn))) for
+    B <= 64 clouds in one native call: points f32 [N,3] on the device stacked cloud-major, lengths host ints [B], viewpoint f32 [B,3] (or
+    None: each cloud's origin) -> dict(normals f32 [N,3] (zero rows where degenerate); with want_curvature curvature f32 [N]; with
+    want_count count int32 [N], the neighbours used).  Asynchronous on the current stream."""
+    _lib.require_cuda(points)
+    dev = points.device
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    B = len(ln)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or points.shape[0] != int(ln.sum()):
+        raise ValueError("estimate_normals: points must be float32 [sum(lengths), 3]")
+    points = points.contiguous()
+    vp = None
+    if viewpoint is not None:
+        vp = (viewpoint if torch.is_tensor(viewpoint) else torch.from_numpy(np.asarray(viewpoint, dtype=np.float32)))
+        vp = vp.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        if vp.shape[0] != B:
+            raise ValueError("estimate_normals: viewpoint must be [B,3] for the B clouds")
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_normals_ws_bytes(B, points.shape[0], ctypes.byref(nbytes)), "lcr_normals_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    n = points.shape[0]
+    out = {"normals": torch.empty((n, 3), dtype=torch.float32, device=dev)}
+    curv = torch.empty((n,), dtype=torch.float32, device=dev) if want_curvature else None
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev) if want_count else None
+    _lib.check(_L().lcr_estimate_normals(_lib.ptr(points), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(vp), _lib.ptr(out["normals"]),
+                                         _lib.ptr(curv), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_estimate_normals")
+    if want_curvature:
+        out["curvature"] = curv
+    if want_count:
+        out["count"] = cnt
     return out

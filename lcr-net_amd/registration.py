@@ -9,7 +9,10 @@ SSE, then smaller h).  The exact definition is in include/lcr_hip.h (lcr_ransac_
 
 Point-to-point ICP on the dense clouds (Open3D's registration_icp with TransformationEstimationPointToPoint, which the reference's pair
 generators run for their ground truth, data/Kitti/generate_kitti_pairs.py:145-147): `registration_icp` (Open3D's call shape) and
-`icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states."""
+`icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states.
+Both also run point-to-plane ICP (estimation_method="point_to_plane", Open3D's TransformationEstimationPointToPlane), which needs target
+normals: `estimate_normals` / `estimate_normals_batched` compute them on the GPU (csrc/normals.hip; utils/utils/open3d.py:53-58 with a
+radius, KDTreeSearchParamHybrid)."""
 import numpy as np
 import torch
 
@@ -58,12 +61,25 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
 ICP_MAX_PAIRS_PER_CALL = 64          # S per native call (the support grid's cloud limit); icp_batched splits larger batches
 
 
+ICP_ESTIMATION_METHODS = ("point_to_point", "point_to_plane")
+
+
+def _estimation(method, normals):
+    if method not in ICP_ESTIMATION_METHODS:
+        raise ValueError("estimation_method must be one of %s, not %r" % (ICP_ESTIMATION_METHODS, method))
+    if method == "point_to_plane" and normals is None:
+        raise ValueError("point-to-plane ICP needs target normals (estimate_normals computes them)")
+    return method == "point_to_plane"
+
+
 def icp_batched(src, src_len, tgt, tgt_len, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                check_every=16, want_history=False, want_corr=False):
+                check_every=16, want_history=False, want_corr=False, estimation_method="point_to_point", tgt_normals=None):
     """ICP for S pairs on the GPU.  src f32 [ns,3] / tgt f32 [nt,3]: device tensors stacked pair-major, src_len / tgt_len: host sequences
     of S ints, init: [S,4,4] source onto target (any float dtype, any device).  -> dict of device tensors (T f64 [S,4,4], fitness f64 [S],
     inlier_rmse f64 [S], iterations int32 [S], and with want_corr / want_history the corr rows and the per-step history; see
-    functional.icp_point_to_point).  Batches of more than 64 pairs are split into chunks; every pair's result is the same in any chunk."""
+    functional.icp_point_to_point).  estimation_method "point_to_plane" needs tgt_normals f32 [nt,3] on the device (stacked like tgt).
+    Batches of more than 64 pairs are split into chunks; every pair's result is the same in any chunk."""
+    plane = _estimation(estimation_method, tgt_normals)
     src_len = [int(x) for x in np.asarray(src_len).reshape(-1)]
     tgt_len = [int(x) for x in np.asarray(tgt_len).reshape(-1)]
     S = len(src_len)
@@ -74,9 +90,14 @@ def icp_batched(src, src_len, tgt, tgt_len, init, max_correspondence_distance, m
     parts = []
     for c0 in range(0, S, ICP_MAX_PAIRS_PER_CALL):
         c1 = min(S, c0 + ICP_MAX_PAIRS_PER_CALL)
-        parts.append(F.icp_point_to_point(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1], init[c0:c1],
-                                          max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, check_every,
-                                          want_corr=want_corr, want_history=want_history))
+        if plane:
+            parts.append(F.icp_point_to_plane(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1],
+                                              tgt_normals[to[c0]:to[c1]], init[c0:c1], max_correspondence_distance, max_iteration,
+                                              relative_fitness, relative_rmse, check_every, want_corr=want_corr, want_history=want_history))
+        else:
+            parts.append(F.icp_point_to_point(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1], init[c0:c1],
+                                              max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, check_every,
+                                              want_corr=want_corr, want_history=want_history))
     if len(parts) == 1:
         return parts[0]
     return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
@@ -95,10 +116,13 @@ class ICPResult:
             self.fitness, self.inlier_rmse, len(self.correspondence_set), self.iterations)
 
 
-def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
-    """Open3D's call shape, registration_icp(source, target, max_correspondence_distance, init, TransformationEstimationPointToPoint(),
-    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)), on the GPU.  source / target: numpy arrays or torch tensors
-    [N,3] / [M,3].  Returns an ICPResult."""
+def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                     estimation_method="point_to_point", target_normals=None):
+    """Open3D's call shape, registration_icp(source, target, max_correspondence_distance, init, TransformationEstimationPointToPoint() or
+    TransformationEstimationPointToPlane(), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)), on the GPU.
+    source / target: numpy arrays or torch tensors [N,3] / [M,3]; estimation_method "point_to_plane" needs target_normals [M,3] (as Open3D
+    refuses a target without normals; estimate_normals computes them).  Returns an ICPResult."""
+    _estimation(estimation_method, target_normals)
     if torch.is_tensor(target) and target.is_cuda:
         dev = target.device
     elif torch.is_tensor(source) and source.is_cuda:
@@ -107,9 +131,49 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
         dev = torch.device("cuda", torch.cuda.current_device())
     src, tgt = _device_points(source, dev), _device_points(target, dev)
     T0 = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init, dtype=np.float64))).to(device=dev, dtype=torch.float64).reshape(1, 4, 4)
+    nrm = _device_points(target_normals, dev) if target_normals is not None else None
     r = icp_batched(src, [src.shape[0]], tgt, [tgt.shape[0]], T0, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
-                    want_corr=True)
+                    want_corr=True, estimation_method=estimation_method, tgt_normals=nrm)
     corr = r["corr"].cpu().numpy().astype(np.int64)
     rows = np.nonzero(corr >= 0)[0]
     return ICPResult(r["T"][0].cpu().numpy(), float(r["fitness"][0].item()), float(r["inlier_rmse"][0].item()),
                      np.stack([rows, corr[rows]], axis=1).astype(np.int64), int(r["iterations"][0].item()))
+
+
+# ---- surface normals (utils/utils/open3d.py:53-58 with KDTreeSearchParamHybrid(radius, max_nn)) ----
+def estimate_normals_batched(points, lengths, radius, max_nn=30, viewpoint=None, want_curvature=False, want_count=False):
+    """Normals for B clouds on the GPU.  points f32 [N,3]: a device tensor stacked cloud-major, lengths: host sequence of B ints,
+    viewpoint: None (every cloud's origin) or [B,3].  -> dict of device tensors (normals f32 [N,3], and curvature / count on request;
+    see functional.estimate_normals).  Batches of more than 64 clouds are split; every cloud's result is the same in any chunk."""
+    lengths = [int(x) for x in np.asarray(lengths).reshape(-1)]
+    B = len(lengths)
+    dev = points.device
+    if viewpoint is not None:
+        viewpoint = (viewpoint if torch.is_tensor(viewpoint) else torch.from_numpy(np.asarray(viewpoint, dtype=np.float32)))
+        viewpoint = viewpoint.to(device=dev, dtype=torch.float32).reshape(B, 3)
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    parts = []
+    for c0 in range(0, B, F.NORMALS_MAX_CLOUDS):
+        c1 = min(B, c0 + F.NORMALS_MAX_CLOUDS)
+        parts.append(F.estimate_normals(points[off[c0]:off[c1]], lengths[c0:c1], radius, max_nn, viewpoint[c0:c1] if viewpoint is not None else None,
+                                        want_curvature=want_curvature, want_count=want_count))
+    if len(parts) == 1:
+        return parts[0]
+    return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+def estimate_normals(points, radius, max_nn=30, viewpoint=(0.0, 0.0, 0.0)):
+    """Normals of one cloud, as utils/utils/open3d.py:estimate_normals computes them with a radius (Open3D's
+    KDTreeSearchParamHybrid(radius, max_nn)), oriented toward `viewpoint` (default the sensor at the origin).  points: numpy array or torch
+    tensor [N,3]; returns the same kind (numpy float32, or a float32 tensor on the GPU).  A radius is required: Open3D's parameterless
+    default (KDTreeSearchParamKNN(30)) is not offered.  Degenerate rows (fewer than 3 neighbours, coincident or collinear ones) get the
+    zero normal."""
+    if radius is None:
+        raise ValueError("estimate_normals needs a search radius")
+    dev = points.device if torch.is_tensor(points) and points.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    pts = _device_points(points, dev)
+    vp = torch.tensor(np.asarray(viewpoint, dtype=np.float32).reshape(1, 3), device=dev)
+    n = estimate_normals_batched(pts, [pts.shape[0]], radius, max_nn, vp)["normals"]
+    if torch.is_tensor(points):
+        return n
+    return n.cpu().numpy()

@@ -3,7 +3,8 @@
 
     python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd] [--num_corr K] [--seed S] [--pairs-per-call P]
                                       [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000] [--write-back]
-                                      [--refine icp [--icp-distance 0.5] [--icp-iterations 30]]
+                                      [--refine icp|icp_plane [--icp-distance 0.5] [--icp-iterations 30]
+                                                              [--normal-radius 1.0] [--normal-max-nn 30]]
 
 Reads every `{seq}_{anc}_{pos}.npz` of FEATURES_DIR (what io_formats.save_registration / demo.py write; both the pos_/anc_ and the
 ref_/src_ key families of eval.py:96-110 are accepted), keeps the top --num_corr correspondences by corr_scores (:114-118), and
@@ -15,6 +16,8 @@ registers the anchor onto the positive:
   svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group.
 --refine icp (opt-in) then refines every estimate by point-to-point ICP of the dense anchor cloud (`anc_points_f`) onto the positive's
 (`pos_points_f`), Open3D's criteria with --icp-distance / --icp-iterations, batched on the GPU (lcrnet_amd.registration.icp_batched).
+--refine icp_plane does the same with point-to-plane ICP, on normals of `pos_points_f` computed on the GPU (radius --normal-radius,
+at most --normal-max-nn neighbours; lcrnet_amd.registration.estimate_normals_batched).
 Prints the reference's Fine Matching line (FMR / IR at acceptance_radius 0.6 with inlier_ratio_threshold 0.05, IR@0.3, IR@0.1,
 num_Corr; config_reg.py:64-65) and Registration line (RR, RRE, RTE, Rx, Ry, Rz: evaluation.registration_summary), then one JSON line.
 Coarse-matching metrics are not computed: the shipped model writes empty gt_node_corr_indices (io_formats.save_registration).
@@ -81,9 +84,10 @@ def estimate_group(method, items, args, device):
 
 
 def refine_icp(pairs, est, args, device):
-    """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each."""
+    """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each.
+    --refine icp_plane: point-to-plane, on normals of pos_points_f estimated on the GPU first."""
     import torch
-    from lcrnet_amd.registration import icp_batched
+    from lcrnet_amd.registration import estimate_normals_batched, icp_batched
     out = []
     for g in range(0, len(pairs), args.pairs_per_call):
         group = pairs[g:g + args.pairs_per_call]
@@ -91,7 +95,13 @@ def refine_icp(pairs, est, args, device):
         tgts = [np.ascontiguousarray(d["pos_points_f"], np.float32).reshape(-1, 3) for _, d, _, _, _ in group]
         cat = lambda xs: torch.from_numpy(np.concatenate(xs)).to(device)
         init = torch.from_numpy(np.stack([np.asarray(T, np.float64) for T in est[g:g + args.pairs_per_call]])).to(device)
-        r = icp_batched(cat(srcs), [len(x) for x in srcs], cat(tgts), [len(x) for x in tgts], init, args.icp_distance, args.icp_iterations)
+        tgt, tl = cat(tgts), [len(x) for x in tgts]
+        if args.refine == "icp_plane":
+            nrm = estimate_normals_batched(tgt, tl, args.normal_radius, args.normal_max_nn)["normals"]
+            r = icp_batched(cat(srcs), [len(x) for x in srcs], tgt, tl, init, args.icp_distance, args.icp_iterations,
+                            estimation_method="point_to_plane", tgt_normals=nrm)
+        else:
+            r = icp_batched(cat(srcs), [len(x) for x in srcs], tgt, tl, init, args.icp_distance, args.icp_iterations)
         out += list(r["T"].cpu().numpy())
     return out
 
@@ -107,9 +117,12 @@ def main(argv=None):
     p.add_argument("--ransac-n", type=int, default=4)
     p.add_argument("--num-iterations", type=int, default=50000)
     p.add_argument("--write-back", action="store_true", help="store estimated_transform_ransac in each file (eval.py:184-185)")
-    p.add_argument("--refine", choices=["icp"], default=None, help="refine each estimate by point-to-point ICP of the dense clouds")
+    p.add_argument("--refine", choices=["icp", "icp_plane"], default=None,
+                   help="refine each estimate by point-to-point (icp) or point-to-plane (icp_plane) ICP of the dense clouds")
     p.add_argument("--icp-distance", type=float, default=0.5)
     p.add_argument("--icp-iterations", type=int, default=30)
+    p.add_argument("--normal-radius", type=float, default=1.0, help="--refine icp_plane: normal search radius on pos_points_f")
+    p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane: neighbours per normal at most")
     args = p.parse_args(argv)
     if args.pairs_per_call < 1:
         p.error("--pairs-per-call must be >= 1")
@@ -134,7 +147,7 @@ def main(argv=None):
             group = pairs[g:g + args.pairs_per_call]
             est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
     scored = est                                          # --write-back stores the method's own estimate, refined or not
-    if args.refine == "icp":
+    if args.refine:
         import torch
         scored = refine_icp(pairs, est, args, torch.device("cuda", torch.cuda.current_device()))
     seconds = time.perf_counter() - t0
@@ -158,8 +171,10 @@ def main(argv=None):
            "num_corr": args.num_corr, "seed": args.seed, "pairs_per_call": args.pairs_per_call}
     if args.method == "ransac":
         out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
-    if args.refine == "icp":
-        out["refine"] = {"method": "icp", "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
+    if args.refine:
+        out["refine"] = {"method": args.refine, "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
+        if args.refine == "icp_plane":
+            out["refine"].update(normal_radius=args.normal_radius, normal_max_nn=args.normal_max_nn)
     print(json.dumps(out))
     return out
 
