@@ -105,6 +105,40 @@ int lcr_grid_subsample_rows(const float* xyz, int row_floats, const int64_t* len
  * std::unordered_map<size_t,...> visits after inserting the n distinct keys in the given order — the serial mirror of
  * the device kernel that fixes lcr_grid_subsample's output order (grid_subsampling_cpu.cpp:26,45-47). */
 int lcr_hashmap_order_host(const uint64_t* keys_host, int64_t n, int64_t* order_host);
+/* HOST helper (no GPU): out_host[i] = codes_host[i] mod the phase-th bucket count of libstdc++'s prime schedule (13, 29, ..., phase
+ * 0..27), through the exact multiply-high reduction the device replay uses for keys of 2^52 and more. */
+int lcr_hashmap_bucket_host(const uint64_t* codes_host, int64_t n, int phase, int64_t* out_host);
+
+/* ------------------------------------------------------------------------------------------------
+ * a-1o  Open3D voxel down-sampling — replaces PointCloud::VoxelDownSample (legacy Open3D, with AccumulatedPoint and
+ *       utility::hash_eigen), the offline step of data/Kitti/downsample_pcd.py:29, data/Kitti_360/downsample_pcd.py and
+ *       data/mulran/downsample_pcd_mulran.py, and of the helper voxel_downsample (utils/utils/open3d.py:61-69).
+ * Per cloud, on rows of R = row_floats (3 .. 64) floats with x, y, z first and a voxel size v given as a DOUBLE:
+ *   m      = component-wise min of the cloud's xyz (fp32 -> fp64 is exact);
+ *   o      = m - v * 0.5 in fp64;
+ *   i_d    = (int) floor((p_d - o_d) / v): fp64 subtract, then a true fp64 division (no reciprocal, no contraction);
+ *   code   = hash_eigen(ix, iy, iz): s = 0, then for e in (ix, iy, iz): s ^= (uint64)(int64)e + 0x9e3779b9 + (s << 6) + (s >> 2) mod 2^64;
+ *   voxel  = count n and fp64 sums of x, y, z and of every other output column, added in input-row order;
+ *   output = sum / (double) n (a true division), rounded to fp32 (RNE) in out_f32; out_f64 (nullable) gets the unrounded averages;
+ *   order  = libstdc++ std::unordered_map iteration order with the voxels inserted in first-occurrence order, bucket = code mod
+ *            bucket_count.
+ * Columns 3 .. out_cols-1 are averaged like an Open3D colour channel: [N,4] -> [M,4] is the KITTI `downsampled_xyzi` record
+ * (intensity carried as colour channel 0), [N,4] -> [M,3] MulRan's xyz-only file.
+ * hash_eigen CODES COLLIDE: it is boost's hash_combine on small integers, e.g. (1, 65, z) and (2, 2, z) share a code for every z; on
+ * synthetic raw scans 4-25 % of the voxels share their code with another voxel (groups of up to 5).  Voxels are identified by their index triple (the sort key packs
+ * ix + NX iy + NX NY iz with the cloud id), never by the code; distinct voxels with equal codes share a bucket, and libstdc++ puts a
+ * new node at the front of its bucket whatever the codes are, which the replay reproduces.
+ *   rows     f32[n_cap, row_floats]   stacked clouds (first sum(len) rows are used); len i64[B], B <= 64
+ *   out_f32  f32[n_cap, out_cols]     3 <= out_cols <= row_floats; first sum(out_len) rows are written
+ *   out_f64  f64[n_cap, out_cols]     or NULL
+ *   status   u32[1]  LCR_STATUS_KEY_OVERFLOW when a cloud's packed index key with the cloud id needs more than key_bits_hint bits
+ *            (retry with 0) or more than 64, or an axis spans INT_MAX voxels or more (Open3D refuses such clouds too): the rows are
+ *            then not meaningful.  LCR_STATUS_LEN_MISMATCH: sum(len) > n_cap.
+ * ------------------------------------------------------------------------------------------------ */
+int lcr_voxel_down_sample_ws_bytes(int64_t n_cap, int B, size_t* bytes);
+int lcr_voxel_down_sample(const float* rows, int row_floats, int out_cols, const int64_t* len, int B, int64_t n_cap, double voxel,
+                          int key_bits_hint, float* out_f32, double* out_f64, int64_t* out_len, uint32_t* status,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a-2  radius search — replaces utils.ext.radius_neighbors + the [:, :limit] slice of
@@ -195,6 +229,13 @@ int lcr_precompute_batch(const float* points0, const int64_t* lengths0, const Lc
 int lcr_precompute_batch_rows(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* layout,
                               float voxel_size, float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws,
                               size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream);
+/* Raw-scan mode with a choice of voxeliser: raw_method 0 = grid subsampling (lcr_precompute_batch_rows, raw_voxel narrowed to
+ * float), 1 = Open3D VoxelDownSample (lcr_voxel_down_sample with raw_voxel as given, stage 0 = its fp32 [M,3] rows).  The workspace
+ * must hold lcr_precompute_ws_bytes_ex(layout, raw_method) bytes (layout->ws_bytes is the raw_method 0 size). */
+int lcr_precompute_ws_bytes_ex(const LcrPrecomputeLayout* layout, int raw_method, size_t* bytes);
+int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* layout,
+                                 float voxel_size, float radius, double raw_voxel, int raw_method, int key_bits_hint, void* out,
+                                 size_t out_bytes, void* ws, size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a-4 / a-5 / a-6  KPConv encoder building blocks (fp32).  Index tensors are [M,H] int32 or int64 (idx_is_64),

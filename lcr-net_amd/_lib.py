@@ -25,6 +25,9 @@ _SIGS = {
     "lcr_precompute_layout": (c_int, [c_i64, c_int, c_int, c_vp, c_int, c_i64, c_vp]),
     "lcr_precompute_batch": (c_int, [c_vp, c_vp, c_vp, c_float, c_float, c_float, c_int, c_vp, c_size_t, c_vp, c_size_t, c_vp, c_vp, c_vp]),
     "lcr_precompute_batch_rows": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_int, c_vp, c_size_t, c_vp, c_size_t, c_vp, c_vp, c_vp]),
+    "lcr_precompute_ws_bytes_ex": (c_int, [c_vp, c_int, c_size_p]),
+    "lcr_precompute_batch_rows_ex": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, ctypes.c_double, c_int, c_int, c_vp, c_size_t, c_vp, c_size_t,
+                                             c_vp, c_vp, c_vp]),
     "lcr_radius_query_multi": (c_int, [c_vp, c_int, c_int, c_vp]),
     "lcr_radius_query": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_float, c_int, c_vp, c_vp, c_vp, c_vp]),
     "lcr_stream_spin": (c_int, [c_int, c_vp]),
@@ -37,6 +40,10 @@ _SIGS = {
     "lcr_grid_subsample_ex": (c_int, [c_vp, c_vp, c_int, c_i64, c_float, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_grid_subsample_rows": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_float, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_hashmap_order_host": (c_int, [c_vp, c_i64, c_vp]),
+    "lcr_hashmap_bucket_host": (c_int, [c_vp, c_i64, c_int, c_vp]),
+    "lcr_voxel_down_sample_ws_bytes": (c_int, [c_i64, c_int, c_size_p]),
+    "lcr_voxel_down_sample": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_i64, ctypes.c_double, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t,
+                                      c_vp]),
     "lcr_gemm_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "lcr_gemm_f32_anorm": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_float, c_float, c_vp, c_int,
                                    c_int, c_vp, c_vp]),
@@ -125,7 +132,7 @@ _SIGS = {
 
 
 # entry points that synchronise, compute on the host or issue long launch sequences: called with the interpreter lock RELEASED
-_RELEASES_GIL = {"lcr_roformer_forward", "lcr_precompute_batch", "lcr_precompute_batch_rows", "lcr_encoder_forward", "lcr_encoder_forward_ex", "lcr_ktimer_read",
+_RELEASES_GIL = {"lcr_roformer_forward", "lcr_precompute_batch", "lcr_precompute_batch_rows", "lcr_precompute_batch_rows_ex", "lcr_hashmap_bucket_host", "lcr_encoder_forward", "lcr_encoder_forward_ex", "lcr_ktimer_read",
                  "lcr_ktimer_read2", "lcr_hashmap_order_host", "lcr_ransac_sample_host", "lcr_icp_point_to_point", "lcr_icp_point_to_plane", "lcr_netvlad_forward", "lcr_log_sinkhorn", "lcr_log_sinkhorn_ex",
                  "lcr_local_global_registration", "lcr_local_global_registration_ex", "lcr_retrieval_topk", "lcr_stream_spin"}
 

@@ -36,6 +36,33 @@ static const int64_t h_sched[] = {13,        29,        59,         127,        
                                   1447153,   2938679,   5967347,    12117689,   24607243, 49969847, 101473717,
                                   206062531, 418453099, 849745171, 1725584621, 3504127453};
 
+// Exact `x % d` for any 64-bit x with one precomputed constant per divisor (Barrett / Granlund-Montgomery): m = floor((2^64-1) / d)
+// gives q = mulhi(x, m) in {floor(x/d) - 1, floor(x/d)}, so one conditional subtract fixes the remainder.  The same function runs
+// on the host (tests/test_voxel_down_sample_cpu.py checks it against `%` for every prime of the schedule) and on the device, where a
+// generic 64-bit urem expands to ~100 instructions.
+__host__ __device__ constexpr uint64_t hm_magic(uint64_t d) { return ~0ull / d; }
+__host__ __device__ inline uint64_t hm_mod(uint64_t x, uint64_t d, uint64_t m) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const uint64_t q = __umul64hi(x, m);
+#else
+  const uint64_t q = static_cast<uint64_t>((static_cast<unsigned __int128>(x) * m) >> 64);
+#endif
+  const uint64_t r = x - q * d;
+  return r >= d ? r - d : r;
+}
+#define HM_MAGIC(d) hm_magic(d##ull)
+#define HM_MAGIC_TABLE \
+  { \
+   HM_MAGIC(13), HM_MAGIC(29), HM_MAGIC(59), HM_MAGIC(127), HM_MAGIC(257), HM_MAGIC(541), HM_MAGIC(1109), \
+   HM_MAGIC(2357), HM_MAGIC(5087), HM_MAGIC(10273), HM_MAGIC(20753), HM_MAGIC(42043), HM_MAGIC(85229), HM_MAGIC(172933), \
+   HM_MAGIC(351061), HM_MAGIC(712697), HM_MAGIC(1447153), HM_MAGIC(2938679), HM_MAGIC(5967347), HM_MAGIC(12117689), HM_MAGIC(24607243), \
+   HM_MAGIC(49969847), HM_MAGIC(101473717), HM_MAGIC(206062531), HM_MAGIC(418453099), HM_MAGIC(849745171), HM_MAGIC(1725584621), HM_MAGIC(3504127453) \
+  }
+static const uint64_t h_magic[N_SCHED] = HM_MAGIC_TABLE;
+__constant__ const uint64_t c_magic[N_SCHED] = HM_MAGIC_TABLE;
+#undef HM_MAGIC_TABLE
+#undef HM_MAGIC
+
 struct GsHeader {
   RadixCtl rx;                       // n, num_passes (must be first: radix kernels read it)
   int      B;
@@ -386,8 +413,9 @@ __device__ void hm_scan_inplace(E* a, int n, int* lds) {
 // consumed — one workgroup per cloud is latency-bound, so the number of DEPENDENT memory round trips per pass is what counts.
 
 // key % nb for nb < 2^31: 32-bit remainder when the key fits, else floor(key * (1/nb)) in fp64 (exact quotient within +-1 for
-// keys < 2^53, fixed up), else the 64-bit division.  The generic 64-bit urem costs ~100 instructions per element and phase.
-__device__ __forceinline__ int hm_bucket(uint64_t key, uint64_t nb64, double inv_nb) {
+// keys < 2^53, fixed up), else the exact reduction hm_mod with the phase's constant mg (the generic 64-bit urem costs ~100
+// instructions per element and phase).
+__device__ __forceinline__ int hm_bucket(uint64_t key, uint64_t nb64, double inv_nb, uint64_t mg) {
   if ((key >> 32) == 0 && (nb64 >> 32) == 0) return static_cast<int>(static_cast<uint32_t>(key) % static_cast<uint32_t>(nb64));
   if ((key >> 52) == 0 && (nb64 >> 31) == 0) {
     int64_t q = static_cast<int64_t>(static_cast<double>(key) * inv_nb);
@@ -396,7 +424,7 @@ __device__ __forceinline__ int hm_bucket(uint64_t key, uint64_t nb64, double inv
     if (r >= static_cast<int64_t>(nb64)) r -= static_cast<int64_t>(nb64);
     return static_cast<int>(r);
   }
-  return static_cast<int>(key % nb64);
+  return static_cast<int>(hm_mod(key, nb64, mg));
 }
 
 // One phase of the replay with nb buckets: elements [0, hi) are in the table, those below `lo` carry their list position after
@@ -431,7 +459,7 @@ template <int HU, typename ET, typename EM, typename EA, typename ES, bool CNT16
 __device__ __forceinline__ void hm_phase(const uint64_t* __restrict__ key, ET* __restrict__ t, ET* __restrict__ bk,
                                          EM* __restrict__ memt, ET* __restrict__ arrv, EA* __restrict__ at,
                                          int32_t* __restrict__ gmin, typename HmCnt<CNT16>::type* cnt, ES* start, int lo,
-                                         int hi, int nb, uint64_t nb64, int* lds) {
+                                         int hi, int nb, uint64_t nb64, uint64_t mg, int* lds) {
   using E = ET;
   const int tid = threadIdx.x;
   const double inv_nb = 1.0 / static_cast<double>(nb64);
@@ -459,7 +487,7 @@ __device__ __forceinline__ void hm_phase(const uint64_t* __restrict__ key, ET* _
     for (int k = 0; k < HU; ++k) {
       const int e = e0 + k * HM_T;
       if (e < hi) {
-        bb[k] = hm_bucket(kk[k], nb64, inv_nb);
+        bb[k] = hm_bucket(kk[k], nb64, inv_nb, mg);
         atomicMin(&gmin[bb[k]], tt[k]);
         arr[k] = hm_cnt_fetch_inc(cnt, bb[k]);
       }
@@ -616,12 +644,28 @@ constexpr size_t HM_LDS_SMALL = static_cast<size_t>(HM_LC) * (2 * sizeof(int32_t
 constexpr size_t HM_LDS_BYTES = 160 * 1024 - 1024;   // the whole CU's LDS but the static part: the 10273- / 20753-bucket phases keep their scattered arrays there
 static_assert(HM_LDS_SMALL <= HM_LDS_BYTES, "LDS phases do not fit");
 
+// What the replay hands on, per cloud: pos[e] = list position of the e-th inserted voxel.  Grid subsampling gathers the barycentres
+// into the output rows; the Open3D voxeliser (k_vd_reduce) only needs every voxel's destination row.
+struct HmEmitBary {
+  const float* bary;
+  float*       out_xyz;
+  template <typename E>
+  __device__ __forceinline__ void operator()(const E* pos, const int32_t* ins_seg, int64_t o, int n) const { hm_emit(pos, ins_seg, bary, out_xyz, o, n); }
+};
+struct HmEmitRow {
+  int32_t* seg_row;      // [segments] output row of every voxel run
+  template <typename E>
+  __device__ __forceinline__ void operator()(const E* pos, const int32_t* ins_seg, int64_t o, int n) const {
+    for (int e = threadIdx.x; e < n; e += HM_T) seg_row[ins_seg[o + e]] = static_cast<int32_t>(o + static_cast<int>(pos[e]));
+  }
+};
+
+template <class Emit>
 __global__ __launch_bounds__(HM_T) void k_gs_hashorder(const GsHeader* __restrict__ h, const uint64_t* __restrict__ ins_key,
-                                                       const int32_t* __restrict__ ins_seg, const float* __restrict__ bary,
-                                                       int32_t* __restrict__ hm_t, int32_t* __restrict__ hm_bk,
+                                                       const int32_t* __restrict__ ins_seg, int32_t* __restrict__ hm_t, int32_t* __restrict__ hm_bk,
                                                        int32_t* __restrict__ hm_mem, int32_t* __restrict__ hm_at,
                                                        int32_t* __restrict__ hm_arr, int32_t* __restrict__ hm_gmin, int32_t* __restrict__ hm_cnt,
-                                                       int32_t* __restrict__ hm_start, float* __restrict__ out_xyz) {
+                                                       int32_t* __restrict__ hm_start, Emit emit) {
   __shared__ int lds[HM_T / 64];
   extern __shared__ __align__(16) unsigned char hm_dyn[];
   const int b = blockIdx.x;
@@ -649,7 +693,7 @@ __global__ __launch_bounds__(HM_T) void k_gs_hashorder(const GsHeader* __restric
     for (; p < HM_LDS_PHASES; ++p) {
       const int nb = static_cast<int>(c_sched[p]);
       const int hi = min(n, nb);
-      hm_phase<4, uint16_t, uint16_t, uint16_t, uint16_t>(lkey, lt, lbk, lmem, larr, lat, lgmin, lcnt, lstart, lo, hi, nb, static_cast<uint64_t>(nb), lds);
+      hm_phase<4, uint16_t, uint16_t, uint16_t, uint16_t>(lkey, lt, lbk, lmem, larr, lat, lgmin, lcnt, lstart, lo, hi, nb, static_cast<uint64_t>(nb), c_magic[p], lds);
       uint16_t* sw = lt;                         // the new positions become the next phase's timestamps
       lt = lbk;
       lbk = sw;
@@ -660,7 +704,7 @@ __global__ __launch_bounds__(HM_T) void k_gs_hashorder(const GsHeader* __restric
       }
     }
     if (done) {
-      hm_emit(lt, ins_seg, bary, out_xyz, o, n);
+      emit(lt, ins_seg, o, n);
       return;
     }
     for (int e = tid; e < lo; e += HM_T) hm_t[o + e] = static_cast<int32_t>(lt[e]);
@@ -690,14 +734,14 @@ __global__ __launch_bounds__(HM_T) void k_gs_hashorder(const GsHeader* __restric
       uint16_t* lstart = reinterpret_cast<uint16_t*>(lcnt + nbe);
       uint16_t* lat = lstart + nbe;
       uint16_t* lmem = lat + hie;
-      hm_phase<4, int32_t, uint16_t, uint16_t, uint16_t>(key, t, bk, lmem, arrv, lat, lgmin, lcnt, lstart, lo, hi, nb, static_cast<uint64_t>(nb64), lds);
+      hm_phase<4, int32_t, uint16_t, uint16_t, uint16_t>(key, t, bk, lmem, arrv, lat, lgmin, lcnt, lstart, lo, hi, nb, static_cast<uint64_t>(nb64), c_magic[p], lds);
     } else if (nb64 < 65536 && need_part <= HM_LDS_BYTES) {
       int32_t* lgmin = reinterpret_cast<int32_t*>(hm_dyn);
       uint16_t* lcnt = reinterpret_cast<uint16_t*>(lgmin + nbe);     // becomes `start` in place
       uint16_t* lat = lcnt + nbe;
-      hm_phase<4, int32_t, int32_t, uint16_t, uint16_t, true>(key, t, bk, memt, arrv, lat, lgmin, lcnt, lcnt, lo, hi, nb, static_cast<uint64_t>(nb64), lds);
+      hm_phase<4, int32_t, int32_t, uint16_t, uint16_t, true>(key, t, bk, memt, arrv, lat, lgmin, lcnt, lcnt, lo, hi, nb, static_cast<uint64_t>(nb64), c_magic[p], lds);
     } else {
-      hm_phase<4, int32_t, int32_t, int32_t, int32_t>(key, t, bk, memt, arrv, at, gmin, cnt, start, lo, hi, nb, static_cast<uint64_t>(nb64), lds);
+      hm_phase<4, int32_t, int32_t, int32_t, int32_t>(key, t, bk, memt, arrv, at, gmin, cnt, start, lo, hi, nb, static_cast<uint64_t>(nb64), c_magic[p], lds);
     }
     int32_t* sw = t;
     t = bk;
@@ -705,7 +749,164 @@ __global__ __launch_bounds__(HM_T) void k_gs_hashorder(const GsHeader* __restric
     lo = hi;
     if (hi >= n) break;
   }
-  hm_emit(t, ins_seg, bary, out_xyz, o, n);
+  emit(t, ins_seg, o, n);
+}
+
+// ---- Open3D PointCloud::VoxelDownSample (lcr_voxel_down_sample) -----------------------------------------------------------------
+// Same chain as a-1 with Open3D's arithmetic (include/lcr_hip.h states the contract): fp64 origin min - v/2 and indices
+// floor((p - o) / v); the sort key packs the INDEX triple (ix + NX iy + NX NY iz, never negative, no escape range) with the cloud id,
+// so runs are voxels even where hash_eigen codes collide; the replay gets one hash_eigen code per voxel (duplicates allowed: it
+// only reads each element's bucket and insertion rank) and writes every voxel's output row; k_vd_reduce then sums each run in
+// fp64 in input order and divides once.
+struct VdLayout {
+  GsLayout g;
+  double*  org;          // [GS_MAX_B][3] fp64 voxel origin per cloud
+  int32_t* seg_row;      // [n] output row of every voxel run
+  size_t   bytes;
+};
+
+static VdLayout vd_layout(void* ws, int64_t n_cap, int B) {
+  VdLayout V;
+  V.g = gs_layout(ws, n_cap, B);
+  Carver c(ws, ~size_t(0));
+  c.off = V.g.bytes;
+  V.org = c.take<double>(3 * GS_MAX_B);
+  V.seg_row = c.take<int32_t>(static_cast<size_t>(n_cap > 0 ? n_cap : 1));
+  V.bytes = c.off;
+  return V;
+}
+
+__device__ __forceinline__ int64_t vd_index(float p, double o, double voxel) { return static_cast<int64_t>(floor((static_cast<double>(p) - o) / voxel)); }
+
+// utility::hash_eigen<Eigen::Vector3i>: boost hash_combine over std::hash<int> (identity, sign-extended to size_t)
+__device__ __forceinline__ uint64_t vd_hash_eigen(int64_t ix, int64_t iy, int64_t iz) {
+  uint64_t s = 0;
+  s ^= static_cast<uint64_t>(ix) + 0x9e3779b9ull + (s << 6) + (s >> 2);
+  s ^= static_cast<uint64_t>(iy) + 0x9e3779b9ull + (s << 6) + (s >> 2);
+  s ^= static_cast<uint64_t>(iz) + 0x9e3779b9ull + (s << 6) + (s >> 2);
+  return s;
+}
+
+__global__ void k_vd_params(GsHeader* h, double* __restrict__ org, double voxel, int key_bits_hint, uint32_t* status) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int B = h->B;
+  int kbits = 1;
+  for (int b = 0; b < B; ++b) {
+    h->top[b] = 0;
+    if (h->in_off[b + 1] <= h->in_off[b]) {
+      h->NX[b] = h->NY[b] = 1;
+      continue;
+    }
+    uint64_t nn[3];
+    bool wide = false;
+    for (int d = 0; d < 3; ++d) {
+      const double o = static_cast<double>(ord2f(h->bb_min[b][d])) - voxel * 0.5;
+      org[3 * b + d] = o;
+      const double top = floor((static_cast<double>(ord2f(h->bb_max[b][d])) - o) / voxel);   // largest index on this axis
+      wide |= !(top < 2147483647.0);                                                          // Open3D keeps indices in an int
+      nn[d] = wide ? 1 : static_cast<uint64_t>(top) + 1;
+    }
+    h->NX[b] = nn[0];
+    h->NY[b] = nn[1];
+    const unsigned __int128 cells = static_cast<unsigned __int128>(nn[0]) * nn[1] * nn[2];
+    const int kb = wide || (cells >> 64) != 0 ? 65 : max(bits_of(static_cast<uint64_t>(cells) - 1), 1);
+    kbits = max(kbits, kb);
+  }
+  const int cbits = bits_of(static_cast<uint64_t>(B - 1));
+  int total = kbits + cbits;
+  if (total > 64 || (key_bits_hint > 0 && total > key_bits_hint)) {
+    atomicOr(status, LCR_STATUS_KEY_OVERFLOW);
+    total = min(total, 64);
+    if (key_bits_hint > 0) total = min(total, key_bits_hint);
+    kbits = max(total - cbits, 1);
+  }
+  h->kbits = kbits;
+  h->rx.num_passes = radix_passes(total);
+}
+
+__global__ __launch_bounds__(256) void k_vd_keys(GsHeader* h, const double* __restrict__ org, const float* __restrict__ xyz, int rs, double voxel,
+                                                 uint64_t* __restrict__ keyA, uint32_t* __restrict__ valA, uint32_t* status) {
+  const int B = h->B;
+  const int64_t n = h->rx.n;
+  const int kbits = h->kbits;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int b = cloud_of(h->in_off, B, i);
+    const uint64_t ix = static_cast<uint64_t>(vd_index(xyz[rs * i + 0], org[3 * b + 0], voxel));
+    const uint64_t iy = static_cast<uint64_t>(vd_index(xyz[rs * i + 1], org[3 * b + 1], voxel));
+    const uint64_t iz = static_cast<uint64_t>(vd_index(xyz[rs * i + 2], org[3 * b + 2], voxel));
+    const uint64_t key = ix + h->NX[b] * (iy + h->NY[b] * iz);
+    // as in k_gs_keys: a key beyond the promised bits is reported and truncated, the cloud field stays intact
+    if (kbits < 64 && (key >> kbits) != 0) atomicOr(status, LCR_STATUS_KEY_OVERFLOW);
+    const uint64_t kmask = kbits < 64 ? ((1ull << kbits) - 1ull) : ~0ull;
+    keyA[i] = (kbits < 64 ? (static_cast<uint64_t>(b) << kbits) : 0ull) | (key & kmask);
+    valA[i] = static_cast<uint32_t>(i);
+  }
+}
+
+// one lane per voxel run: its hash_eigen code (from the indices of its first row) and first row, the first-occurrence flag
+__global__ __launch_bounds__(256) void k_vd_segs(GsHeader* h, const double* __restrict__ org, const float* __restrict__ xyz, int rs, double voxel,
+                                                 const uint32_t* __restrict__ vA, const uint32_t* __restrict__ vB,
+                                                 const int32_t* __restrict__ head_scan, const int32_t* __restrict__ seg_start,
+                                                 uint64_t* __restrict__ seg_key, uint32_t* __restrict__ seg_first, int32_t* __restrict__ first_flag,
+                                                 int64_t* __restrict__ out_len) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) gs_offsets(h, head_scan, out_len);
+  const int64_t n = h->rx.n;
+  const int64_t nseg = n > 0 ? head_scan[n] : 0;
+  const uint32_t* v = sorted_vals(h, vA, vB);
+  const int B = h->B;
+  for (int64_t seg = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; seg < nseg; seg += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const uint32_t f = v[seg_start[seg]];   // stable sort => first element of the run is the first occurrence
+    const int b = cloud_of(h->in_off, B, static_cast<int64_t>(f));
+    const float* p = xyz + rs * static_cast<int64_t>(f);
+    seg_key[seg] = vd_hash_eigen(vd_index(p[0], org[3 * b + 0], voxel), vd_index(p[1], org[3 * b + 1], voxel), vd_index(p[2], org[3 * b + 2], voxel));
+    seg_first[seg] = f;
+    first_flag[f] = 1;
+  }
+}
+
+// one lane per voxel run: fp64 sums of the first `cols` columns in input order (AccumulatedPoint::AddPoint), sum / n
+// (GetAveragePoint), written to the run's row of the replayed order — fp32 (RNE) and optionally the fp64 value itself
+constexpr int VD_CU = 4;   // columns per walk of a run
+__global__ __launch_bounds__(256) void k_vd_reduce(const GsHeader* __restrict__ h, const float* __restrict__ xyz, int rs, int cols,
+                                                   const uint32_t* __restrict__ vA, const uint32_t* __restrict__ vB,
+                                                   const int32_t* __restrict__ head_scan, const int32_t* __restrict__ seg_start,
+                                                   const int32_t* __restrict__ seg_row, float* __restrict__ out_f32, double* __restrict__ out_f64) {
+  const int64_t n = h->rx.n;
+  const int64_t nseg = n > 0 ? head_scan[n] : 0;
+  const uint32_t* v = sorted_vals(h, vA, vB);
+  for (int64_t seg = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; seg < nseg; seg += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t i = seg_start[seg];
+    const int64_t end = seg + 1 < nseg ? seg_start[seg + 1] : n;
+    const double cnt = static_cast<double>(end - i);
+    const int64_t dst = static_cast<int64_t>(seg_row[seg]) * cols;
+    for (int c0 = 0; c0 < cols; c0 += VD_CU) {
+      double s[VD_CU] = {0.0, 0.0, 0.0, 0.0};
+      // chunks of 8 rows: the loads of a chunk are issued together, the additions stay serial (the order is part of the contract)
+      for (int64_t j = i; j < end; j += 8) {
+        uint32_t r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r[u] = v[j + u < end ? j + u : end - 1];
+        float x[8][VD_CU];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+          for (int c = 0; c < VD_CU; ++c) x[u][c] = c0 + c < cols ? xyz[rs * static_cast<int64_t>(r[u]) + c0 + c] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (j + u < end) {
+#pragma unroll
+            for (int c = 0; c < VD_CU; ++c) s[c] = s[c] + static_cast<double>(x[u][c]);
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < VD_CU; ++c)
+        if (c0 + c < cols) {
+          const double a = s[c] / cnt;
+          out_f32[dst + c0 + c] = static_cast<float>(a);
+          if (out_f64) out_f64[dst + c0 + c] = a;
+        }
+    }
+  }
 }
 
 }  // namespace lcr
@@ -774,18 +975,89 @@ extern "C" int lcr_grid_subsample_rows(const float* xyz, int row_floats, const i
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_insertion, dim3(nblk), dim3(256), 0, st, L.hdr, L.first, L.seg_key, L.seg_first, L.ins_key, L.ins_seg);
   static DynLds hm_opt_in;
-  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder), HM_LDS_BYTES) != hipSuccess) {
+  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitBary>), HM_LDS_BYTES) != hipSuccess) {
     set_error("lcr_grid_subsample: cannot reserve %zu B of LDS for the hash-order kernel", HM_LDS_BYTES);
     return LCR_EHIP;
   }
-  hipLaunchKernelGGL(k_gs_hashorder, dim3(B), dim3(HM_T), HM_LDS_BYTES, st, L.hdr, L.ins_key, L.ins_seg, L.bary, L.hm_t, L.hm_bk, L.hm_mem, L.hm_at, L.hm_arr,
-                     L.hm_gmin, L.hm_cnt, L.hm_start, out_xyz);
+  hipLaunchKernelGGL(k_gs_hashorder<HmEmitBary>, dim3(B), dim3(HM_T), HM_LDS_BYTES, st, L.hdr, L.ins_key, L.ins_seg, L.hm_t, L.hm_bk, L.hm_mem, L.hm_at,
+                     L.hm_arr, L.hm_gmin, L.hm_cnt, L.hm_start, HmEmitBary{L.bary, out_xyz});
   return check_launch("lcr_grid_subsample");
 }
 
 extern "C" int lcr_grid_subsample(const float* xyz, const int64_t* len, int B, int64_t n_cap, float voxel, float* out_xyz,
                                   int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
   return lcr_grid_subsample_ex(xyz, len, B, n_cap, voxel, 0, out_xyz, out_len, status, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_voxel_down_sample_ws_bytes(int64_t n_cap, int B, size_t* bytes) {
+  if (!bytes || n_cap < 0 || B < 1 || B > GS_MAX_B) return LCR_EARG;
+  *bytes = vd_layout(nullptr, n_cap, B).bytes;
+  return LCR_OK;
+}
+
+extern "C" int lcr_voxel_down_sample(const float* rows, int row_floats, int out_cols, const int64_t* len, int B, int64_t n_cap, double voxel,
+                                     int key_bits_hint, float* out_f32, double* out_f64, int64_t* out_len, uint32_t* status, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  if (row_floats < 3 || row_floats > 64 || out_cols < 3 || out_cols > row_floats) {
+    set_error("lcr_voxel_down_sample: rows of %d floats, %d output columns (3 <= out_cols <= row_floats <= 64)", row_floats, out_cols);
+    return LCR_EARG;
+  }
+  if (!len || !out_f32 || !out_len || !status || !ws || B < 1 || B > GS_MAX_B || n_cap < 0 || !(voxel > 0.0) || !(voxel < 1e300) ||
+      key_bits_hint < 0 || key_bits_hint > 64) {
+    set_error("lcr_voxel_down_sample: bad argument");
+    return LCR_EARG;
+  }
+  if (n_cap > (int64_t(1) << 31) - 2) {
+    set_error("lcr_voxel_down_sample: more than 2^31-2 points");
+    return LCR_EARG;
+  }
+  VdLayout V = vd_layout(ws, n_cap, B);
+  if (V.bytes > ws_bytes) {
+    set_error("lcr_voxel_down_sample: workspace too small (%zu < %zu)", ws_bytes, V.bytes);
+    return LCR_ESPACE;
+  }
+  const GsLayout& L = V.g;
+  const int rs = row_floats;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nblk = n_cap > 0 ? min(div_up(n_cap, 256), 2048) : 1;
+  hipLaunchKernelGGL(k_gs_init, dim3(1), dim3(64), 0, st, L.hdr, len, B, n_cap, status);
+  if (n_cap == 0) {
+    hipLaunchKernelGGL(k_gs_offsets, dim3(1), dim3(64), 0, st, L.hdr, static_cast<const int32_t*>(nullptr), out_len);
+    return check_launch("lcr_voxel_down_sample");
+  }
+  hipLaunchKernelGGL(k_gs_bbox, dim3(min(div_up(n_cap, 1024), 512)), dim3(256), 0, st, L.hdr, rows, rs);
+  hipLaunchKernelGGL(k_vd_params, dim3(1), dim3(64), 0, st, L.hdr, V.org, voxel, key_bits_hint, status);
+  hipLaunchKernelGGL(k_vd_keys, dim3(nblk), dim3(256), 0, st, L.hdr, V.org, rows, rs, voxel, L.keyA, L.valA, status);
+  const int max_passes = radix_passes(key_bits_hint > 0 ? key_bits_hint : 64);
+  int rc = radix_sort_pairs(&L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, max_passes, L.hist, L.scan_ws, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gs_heads, dim3(nblk), dim3(256), 0, st, L.hdr, L.keyA, L.keyB, L.head, L.first, n_cap);
+  rc = exclusive_scan_i32(L.head, L.head, n_cap + 1, nullptr, L.scan_ws, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gs_seg_starts, dim3(nblk), dim3(256), 0, st, L.hdr, L.head, L.seg_start);
+  hipLaunchKernelGGL(k_vd_segs, dim3(nblk), dim3(256), 0, st, L.hdr, V.org, rows, rs, voxel, L.valA, L.valB, L.head, L.seg_start, L.seg_key,
+                     L.seg_first, L.first, out_len);
+  rc = exclusive_scan_i32(L.first, L.first, n_cap + 1, nullptr, L.scan_ws, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gs_insertion, dim3(nblk), dim3(256), 0, st, L.hdr, L.first, L.seg_key, L.seg_first, L.ins_key, L.ins_seg);
+  static DynLds hm_opt_in;
+  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitRow>), HM_LDS_BYTES) != hipSuccess) {
+    set_error("lcr_voxel_down_sample: cannot reserve %zu B of LDS for the hash-order kernel", HM_LDS_BYTES);
+    return LCR_EHIP;
+  }
+  hipLaunchKernelGGL(k_gs_hashorder<HmEmitRow>, dim3(B), dim3(HM_T), HM_LDS_BYTES, st, L.hdr, L.ins_key, L.ins_seg, L.hm_t, L.hm_bk, L.hm_mem, L.hm_at,
+                     L.hm_arr, L.hm_gmin, L.hm_cnt, L.hm_start, HmEmitRow{V.seg_row});
+  hipLaunchKernelGGL(k_vd_reduce, dim3(nblk), dim3(256), 0, st, L.hdr, rows, rs, out_cols, L.valA, L.valB, L.head, L.seg_start, V.seg_row, out_f32,
+                     out_f64);
+  return check_launch("lcr_voxel_down_sample");
+}
+
+// Host: out[i] = codes[i] mod (the phase-th bucket count of the schedule), through the exact reduction hm_mod that hm_bucket uses.
+extern "C" int lcr_hashmap_bucket_host(const uint64_t* codes, int64_t n, int phase, int64_t* out) {
+  if (n < 0 || phase < 0 || phase >= N_SCHED || (n > 0 && (!codes || !out))) return LCR_EARG;
+  const uint64_t d = static_cast<uint64_t>(h_sched[phase]);
+  for (int64_t i = 0; i < n; ++i) out[i] = static_cast<int64_t>(hm_mod(codes[i], d, h_magic[phase]));
+  return LCR_OK;
 }
 
 // Host mirror of the phase algorithm of k_gs_hashorder (same steps, serial): order[j] = insertion rank of the j-th

@@ -95,7 +95,8 @@ struct PreWs {
   size_t    bytes;
 };
 
-static int carve_ws(void* ws, const LcrPrecomputeLayout& L, PreWs* W) {
+// raw_method: 0 = grid subsampling (lcr_grid_subsample_rows), 1 = Open3D VoxelDownSample (lcr_voxel_down_sample)
+static int carve_ws(void* ws, const LcrPrecomputeLayout& L, PreWs* W, int raw_method = 0) {
   Carver c(ws, ~size_t(0));
   W->status = c.take<uint32_t>(64);
   W->packed = c.take<int64_t>(LCR_MAX_STAGES * 64 + 8);
@@ -103,7 +104,7 @@ static int carve_ws(void* ws, const LcrPrecomputeLayout& L, PreWs* W) {
   W->raw_ws = nullptr;
   W->raw_bytes = 0;
   if (L.n_raw > 0) {
-    int rc = lcr_grid_subsample_ws_bytes(L.n_raw, L.B, &W->raw_bytes);
+    int rc = raw_method == 1 ? lcr_voxel_down_sample_ws_bytes(L.n_raw, L.B, &W->raw_bytes) : lcr_grid_subsample_ws_bytes(L.n_raw, L.B, &W->raw_bytes);
     if (rc) return rc;
     W->raw_ws = c.take<char>(W->raw_bytes);
   }
@@ -185,6 +186,29 @@ extern "C" int lcr_precompute_batch(const float* points0, const int64_t* lengths
 extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
                                          float voxel_size, float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws,
                                          size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  return lcr_precompute_batch_rows_ex(points0, raw_row_floats, lengths0, L, voxel_size, radius, static_cast<double>(raw_voxel), 0, key_bits_hint, out,
+                                      out_bytes, ws, ws_bytes, lengths_host, status_host, stream);
+}
+
+extern "C" int lcr_precompute_ws_bytes_ex(const LcrPrecomputeLayout* L, int raw_method, size_t* bytes) {
+  if (!L || !bytes || raw_method < 0 || raw_method > 1) {
+    set_error("lcr_precompute_ws_bytes_ex: bad argument");
+    return LCR_EARG;
+  }
+  PreWs W;
+  int rc = carve_ws(nullptr, *L, &W, raw_method);
+  if (rc) return rc;
+  *bytes = W.bytes;
+  return LCR_OK;
+}
+
+extern "C" int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
+                                            float voxel_size, float radius, double raw_voxel, int raw_method, int key_bits_hint, void* out,
+                                            size_t out_bytes, void* ws, size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  if (raw_method < 0 || raw_method > 1) {
+    set_error("lcr_precompute_batch: raw_method %d (0 = grid subsampling, 1 = Open3D VoxelDownSample)", raw_method);
+    return LCR_EARG;
+  }
   if (L && raw_row_floats != 3 && !(L->n_raw > 0)) {
     set_error("lcr_precompute_batch: rows of %d floats need raw mode (stage-0 points are then produced as [n,3] inside the call)", raw_row_floats);
     return LCR_EARG;
@@ -193,8 +217,13 @@ extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_float
     set_error("lcr_precompute_batch: bad argument");
     return LCR_EARG;
   }
-  if (out_bytes < L->out_bytes || ws_bytes < L->ws_bytes) {
-    set_error("lcr_precompute_batch: arena too small (out %zu < %zu or ws %zu < %zu)", out_bytes, L->out_bytes, ws_bytes, L->ws_bytes);
+  size_t ws_need = L->ws_bytes;
+  if (raw_method != 0 && L->n_raw > 0) {
+    int rc = lcr_precompute_ws_bytes_ex(L, raw_method, &ws_need);
+    if (rc) return rc;
+  }
+  if (out_bytes < L->out_bytes || ws_bytes < ws_need) {
+    set_error("lcr_precompute_batch: arena too small (out %zu < %zu or ws %zu < %zu)", out_bytes, L->out_bytes, ws_bytes, ws_need);
     return LCR_ESPACE;
   }
   const int S = L->num_stages, B = L->B;
@@ -210,7 +239,7 @@ extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_float
   static HostStats hs;
   const auto t_in = std::chrono::steady_clock::now();
   PreWs W;
-  int rc = carve_ws(ws, *L, &W);
+  int rc = carve_ws(ws, *L, &W, raw_method);
   if (rc) return rc;
   CtxLease lease;                      // returned to the pool on every exit path (all work is joined into `stream` first)
   PreCtx& C = *lease.c;
@@ -219,7 +248,7 @@ extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_float
   const float* pts[LCR_MAX_STAGES];
   const int64_t* lens[LCR_MAX_STAGES];
   const bool raw = L->n_raw > 0;
-  if (raw && !(raw_voxel > 0.f)) {
+  if (raw && !(raw_voxel > 0.0)) {
     set_error("lcr_precompute_batch: raw mode needs raw_voxel > 0");
     return LCR_EARG;
   }
@@ -237,8 +266,12 @@ extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_float
     ~PoolLoan() { scan_state_pool(nullptr, 0); }
   } loan(W.scan_pool, PRE_SCAN_POOL);
   if (raw) {
-    rc = TURN(lcr_grid_subsample_rows(points0, raw_row_floats, lengths0, B, L->n_raw, raw_voxel, key_bits_hint, const_cast<float*>(pts[0]),
+    if (raw_method == 1)   // Open3D's voxeliser: x, y, z averaged in fp64, rounded to the f32[n, 3] stage-0 rows
+      rc = TURN(lcr_voxel_down_sample(points0, raw_row_floats, 3, lengths0, B, L->n_raw, raw_voxel, key_bits_hint, const_cast<float*>(pts[0]), nullptr,
                                       const_cast<int64_t*>(lens[0]), W.status, W.raw_ws, W.raw_bytes, main));
+    else
+      rc = TURN(lcr_grid_subsample_rows(points0, raw_row_floats, lengths0, B, L->n_raw, static_cast<float>(raw_voxel), key_bits_hint,
+                                        const_cast<float*>(pts[0]), const_cast<int64_t*>(lens[0]), W.status, W.raw_ws, W.raw_bytes, main));
     if (rc) return rc;
   }
   float v = voxel_size, r = radius;

@@ -131,15 +131,27 @@ def _workspace(nbytes, dev, stream):
     return ws
 
 
+RAW_METHODS = {"grid": 0, "open3d": 1}
+
+
+def _raw_method_id(method):
+    if method not in RAW_METHODS:
+        raise ValueError("raw voxeliser must be one of %s, not %r" % (sorted(RAW_METHODS), method))
+    return RAW_METHODS[method]
+
+
 def precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling=True, key_bits_hint=32,
-                           raw_voxel=None, capacity=None):
-    """The native pre-processing call (csrc/precompute.hip) without the tensor views: returns a PrecomputedArena."""
+                           raw_voxel=None, capacity=None, raw_method="grid"):
+    """The native pre-processing call (csrc/precompute.hip) without the tensor views: returns a PrecomputedArena.
+    raw_method: the raw-scan voxeliser — "grid" (the collate's grid subsampling) or "open3d" (Open3D's VoxelDownSample,
+    downsample.py)."""
     _lib.require_cuda(points, lengths)
     assert points.dtype == torch.float32 and points.is_contiguous() and lengths.dtype == torch.int64 and num_stages == len(neighbor_limits)
     dev = points.device
     lengths = lengths.contiguous()
     B, S = lengths.numel(), num_stages
     raw = raw_voxel is not None
+    method = _raw_method_id(raw_method)
     n_raw = points.shape[0] if raw else 0
     row_floats = int(points.shape[1]) if points.dim() == 2 else 3      # raw mode takes [N, C >= 3] rows (x, y, z first; 4 = KITTI xyzi)
     if points.dim() != 2 or row_floats < 3 or (row_floats != 3 and not raw):
@@ -148,19 +160,29 @@ def precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neig
     lay = _layout_for(n0, B, S, neighbor_limits, upsampling, n_raw)
     stream = _lib.stream_ptr(dev)
     out = torch.empty(max(lay.out_bytes, 256), dtype=torch.uint8, device=dev)
-    ws = _workspace(lay.ws_bytes, dev, stream)
     lens_host = (ctypes.c_int64 * (S * B))()
     status = ctypes.c_uint32(0)
-    _lib.check(_lib.lib().lcr_precompute_batch_rows(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
-                                                    float(radius), float(raw_voxel) if raw else 0.0, int(key_bits_hint), _lib.ptr(out), out.numel(),
-                                                    _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host), ctypes.addressof(status), stream),
-               "lcr_precompute_batch")
+    if method == 0:
+        ws = _workspace(lay.ws_bytes, dev, stream)
+        _lib.check(_lib.lib().lcr_precompute_batch_rows(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
+                                                        float(radius), float(raw_voxel) if raw else 0.0, int(key_bits_hint), _lib.ptr(out),
+                                                        out.numel(), _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host), ctypes.addressof(status),
+                                                        stream), "lcr_precompute_batch")
+    else:
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(_lib.lib().lcr_precompute_ws_bytes_ex(ctypes.addressof(lay), method, ctypes.byref(nbytes)), "lcr_precompute_ws_bytes_ex")
+        ws = _workspace(nbytes.value, dev, stream)
+        _lib.check(_lib.lib().lcr_precompute_batch_rows_ex(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
+                                                           float(radius), float(raw_voxel) if raw else 0.0, method, int(key_bits_hint), _lib.ptr(out),
+                                                           out.numel(), _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host),
+                                                           ctypes.addressof(status), stream), "lcr_precompute_batch")
     st = status.value
     if st & STATUS_KEY_OVERFLOW and key_bits_hint:
-        return precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling, 0, raw_voxel, capacity)
+        return precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling, 0, raw_voxel, capacity,
+                                      raw_method)
     if raw and st & STATUS_LEN_MISMATCH and n0 < n_raw:
         return precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling, key_bits_hint,
-                                      raw_voxel, n_raw)             # the voxel count exceeded the guessed capacity
+                                      raw_voxel, n_raw, raw_method)   # the voxel count exceeded the guessed capacity
     if st:
         raise RuntimeError("precompute_batch: device status 0x%x" % st)
     flat = list(lens_host)
@@ -168,15 +190,15 @@ def precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neig
 
 
 def precompute_batch_native(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling=True, key_bits_hint=32,
-                            raw_voxel=None, capacity=None):
+                            raw_voxel=None, capacity=None, raw_method="grid"):
     """precompute_batch as ONE native call (csrc/precompute.hip): same dictionary, int32 indices.  The ~140 launches and the
     length read-back are issued by C++ with the interpreter lock released throughout.
 
     raw_voxel: `points` are RAW scans, voxelised at this size inside the same call (no extra host round trip); `capacity` is
     the row capacity assumed for the voxelised stack (default: a quarter of the raw points; a too small guess is detected on
-    the device and the call is repeated with the safe bound)."""
+    the device and the call is repeated with the safe bound); raw_method: "grid" or "open3d" (precompute_batch_arena)."""
     return precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling, key_bits_hint,
-                                  raw_voxel, capacity).views()
+                                  raw_voxel, capacity, raw_method).views()
 
 
 def precompute_batch(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling=True,
@@ -360,9 +382,14 @@ def all_collate_fn_stack_mode(data_dicts, num_stages, voxel_size, search_radius,
     return _precompute_or_keep(merged, feats[0], points, lengths, B, num_stages, voxel_size, search_radius, neighbor_limits, precompute_data, device)
 
 
-def voxelize_raw_scans(points, lengths, voxel_size, key_bits_hint=32):
-    """Raw-scan ingest (replaces the offline Open3D voxel_down_sample(0.3) of data/Kitti/downsample_pcd.py:29
-    with the a-1 kernel): stacked raw scans -> stacked voxel barycentres; returns (points, lengths_dev, lengths_host)."""
+def voxelize_raw_scans(points, lengths, voxel_size, key_bits_hint=32, method="grid"):
+    """Raw-scan ingest (the offline Open3D voxel_down_sample(0.3) of data/Kitti/downsample_pcd.py:29): stacked raw
+    scans -> stacked voxel barycentres [M,3]; returns (points, lengths_dev, lengths_host).  method "grid" runs the a-1 kernel (the
+    collate's grid subsampling), "open3d" Open3D's VoxelDownSample itself (downsample.py)."""
+    if _raw_method_id(method) == 1:
+        from .downsample import voxel_down_sample
+        pts, _, lens, lh = voxel_down_sample(points.contiguous(), lengths, voxel_size, 3, key_bits_hint=key_bits_hint)
+        return pts, lens, lh
     out, out_len, status = grid_subsample_device(points, lengths, voxel_size, key_bits_hint=key_bits_hint)
     host = torch.cat([out_len, status.long()]).cpu()
     st = int(host[-1])

@@ -20,12 +20,14 @@ VOXEL, RADIUS, NUM_STAGES = 0.3, 1.275, 4
 K, EXCLUDE, START = 50, 100, 101
 
 
-def voxelise_frames(raw_frames, voxel=VOXEL, batch=8):
-    """raw scans (device f32 [N_i, >= 3]) -> the 0.3 m voxelised clouds the reference reads from `downsampled_xyzi/*.npy` (device f32 [n_i,3])."""
+def voxelise_frames(raw_frames, voxel=VOXEL, batch=8, method="grid"):
+    """raw scans (device f32 [N_i, >= 3]) -> the 0.3 m voxelised clouds the reference reads from `downsampled_xyzi/*.npy` (device f32 [n_i,3]).
+    method: "grid" (the collate's grid subsampling) or "open3d" (Open3D's VoxelDownSample, what wrote those files)."""
     out = []
     for f0 in range(0, len(raw_frames), batch):
         chunk = [f[:, :3].contiguous() for f in raw_frames[f0:f0 + batch]]
-        pts, _, lh = voxelize_raw_scans(torch.cat(chunk), torch.tensor([len(c) for c in chunk], dtype=torch.int64, device=chunk[0].device), voxel)
+        pts, _, lh = voxelize_raw_scans(torch.cat(chunk), torch.tensor([len(c) for c in chunk], dtype=torch.int64, device=chunk[0].device), voxel,
+                                         method=method)
         off = 0
         for n in lh:
             out.append(pts[off:off + n].contiguous())
@@ -67,10 +69,11 @@ def register_pairs(pair_model, clouds, pairs, limits, pairs_per_call=16, workers
 
 
 def run(desc_model, pair_model, raw_frames, thres, out_dir, seq=0, desc_limits=(64, 65, 74, 80), pair_limits=(74, 68, 70, 67), pairs_per_call=16,
-        max_pairs=None, write_descriptors=True):
+        max_pairs=None, write_descriptors=True, voxelizer="grid"):
     """The whole chain; writes `{out_dir}/features/{seq}_{idx}.npz`, `{out_dir}/features/predicted_des_L2_dis.npz`,
-    `{out_dir}/result/top1_with_thres_%.2f/%02d.txt` and `{out_dir}/registration/{seq}_pose`.  -> dict with the in-memory results."""
-    clouds = voxelise_frames(raw_frames)
+    `{out_dir}/result/top1_with_thres_%.2f/%02d.txt` and `{out_dir}/registration/{seq}_pose`.  -> dict with the in-memory results.
+    voxelizer: the raw-scan voxeliser of voxelise_frames ("grid" or "open3d")."""
+    clouds = voxelise_frames(raw_frames, method=voxelizer)
     desc = sequence_descriptors(desc_model, clouds, list(desc_limits))
     feat_dir = os.path.join(out_dir, "features")
     os.makedirs(feat_dir, exist_ok=True)

@@ -13,7 +13,7 @@ import time
 
 import torch
 
-from .data import precompute_batch, precompute_batch_arena, voxelize_raw_scans
+from .data import _raw_method_id, precompute_batch, precompute_batch_arena, voxelize_raw_scans
 
 
 _HIP = None
@@ -230,13 +230,17 @@ class HostIngest:
 
 class DescriptorPipeline:
     def __init__(self, model, voxel_size=0.3, radius=1.275, num_stages=4, neighbor_limits=(64, 65, 74, 80), upsampling=False,
-                 raw_voxel=None, overlap=True, producer_thread=True, depth=2, pre_workers=2):
+                 raw_voxel=None, overlap=True, producer_thread=True, depth=2, pre_workers=2, raw_method="grid"):
         """raw_voxel: voxel size of the raw-scan ingest step (None = inputs are already voxelised like the reference's
-        downsampled .npy scans; 0.3 = BASELINE configs[1]).  upsampling: also compute the 3 decoder-only upsampling lists."""
+        downsampled .npy scans; 0.3 = BASELINE configs[1]).  raw_method: its voxeliser, "grid" (the collate's grid subsampling)
+        or "open3d" (Open3D's VoxelDownSample, what produced the reference's downsampled scans).  upsampling: also compute the 3
+        decoder-only upsampling lists."""
         self.model = model
         self.voxel_size, self.radius, self.num_stages = voxel_size, radius, num_stages
         self.limits = list(neighbor_limits)
         self.upsampling, self.raw_voxel, self.overlap = upsampling, raw_voxel, overlap
+        _raw_method_id(raw_method)
+        self.raw_method = raw_method
         dev = next(model.parameters()).device
         self.device = dev
         # The pre-processing chain is latency-bound (~130 dependent short launches per batch).  With ONE chain in flight it needs the
@@ -291,9 +295,9 @@ class DescriptorPipeline:
         if self.raw_voxel is not None and not os.environ.get("LCR_PRE_TWO_CALLS"):
             # raw scans -> everything, one native call and ONE host round trip (the voxelisation's own read-back is gone)
             return precompute_batch_arena(points.contiguous(), lengths.to(points.device), self.num_stages, self.voxel_size, self.radius,
-                                          self.limits, upsampling=self.upsampling, raw_voxel=self.raw_voxel)
+                                          self.limits, upsampling=self.upsampling, raw_voxel=self.raw_voxel, raw_method=self.raw_method)
         if self.raw_voxel is not None:
-            points, lengths, _ = voxelize_raw_scans(points, lengths, self.raw_voxel)
+            points, lengths, _ = voxelize_raw_scans(points, lengths, self.raw_voxel, method=self.raw_method)
         return precompute_batch(points.contiguous(), lengths, self.num_stages, self.voxel_size, self.radius, self.limits,
                                 upsampling=self.upsampling)
 

@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--target-pairs", type=int, default=64)
     ap.add_argument("--pairs-per-call", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--voxelizer", choices=["grid", "open3d"], default="grid",
+                    help="raw-scan voxeliser: the collate's grid subsampling, or Open3D's VoxelDownSample (what wrote the reference's downsampled scans)")
     args = ap.parse_args()
     import lcrnet_amd.synthetic as synthetic
     from lcrnet_amd import io_formats as io
@@ -87,7 +89,7 @@ def main():
     torch.cuda.synchronize()
     t = {}
     t0 = time.perf_counter()
-    clouds = lc.voxelise_frames(frames)
+    clouds = lc.voxelise_frames(frames, method=args.voxelizer)
     torch.cuda.synchronize()
     t["voxelise_s"] = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -125,7 +127,7 @@ def main():
         if rev.get(anc) == pos:
             T = o["estimated_transform"].cpu().numpy()
             errs.append((float(np.abs(T[:3, :3] - Tp[:3, :3]).max()), float(np.linalg.norm(T[:3, 3] - Tp[:3, 3]))))
-    print(json.dumps({"metric": "loop detection -> registration, chained on one GPU", "frames": args.frames, "raw_points_per_frame": int(np.mean([len(f) for f in frames])),
+    print(json.dumps({"metric": "loop detection -> registration, chained on one GPU", "voxelizer": args.voxelizer, "frames": args.frames, "raw_points_per_frame": int(np.mean([len(f) for f in frames])),
                       "voxel_points_per_frame": int(np.mean([len(c) for c in clouds])), "threshold": round(thres, 6), "loop_rows": int(len(kept)),
                       "pairs_registered": len(outs), "pairs_per_call": args.pairs_per_call, **{k: round(v, 4) for k, v in t.items()},
                       "descriptor_scans_per_s": round(args.frames / t["descriptors_s"], 1),

@@ -43,6 +43,8 @@ def parse():
     ap.add_argument("--revisit-every", type=int, default=1500)
     ap.add_argument("--host-rows", action="store_true", help="feed the scans as host [N,4] velodyne rows through the ingest leg (upload inside the timed region)")
     ap.add_argument("--out", default=None, help="directory for the npz files (default: a temporary one, removed afterwards)")
+    ap.add_argument("--voxelizer", choices=["grid", "open3d"], default="grid",
+                    help="raw-scan voxeliser of the ingest leg: the collate's grid subsampling, or Open3D's VoxelDownSample")
     ap.add_argument("--dump", default=None, help="rank 0 writes the gathered descriptors and the rows to this .npz (strong-scaling identity check of tools/scale_run.sh; small corpora only)")
     return ap.parse_args()
 
@@ -120,7 +122,7 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    with DescriptorPipeline(model, VOXEL, RADIUS, NUM_STAGES, LIMITS, upsampling=False, raw_voxel=VOXEL) as pipe:
+    with DescriptorPipeline(model, VOXEL, RADIUS, NUM_STAGES, LIMITS, upsampling=False, raw_voxel=VOXEL, raw_method=args.voxelizer) as pipe:
         pipe.enable_dual_encoder(2)
         for _ in pipe.run(staged[:4]):
             pass
@@ -179,7 +181,7 @@ def main():
         top1, top45 = ev.compute_topN(pair, gt, 1), ev.compute_topN(pair, gt, 45)
         P, R = ev.compute_PR_overlap(pair, gt)
         f1, _ = ev.compute_F1(P, R)
-        print(json.dumps({"metric": "loop detection over a sequence, end to end", "frames": C, "n_gpus": world,
+        print(json.dumps({"metric": "loop detection over a sequence, end to end", "voxelizer": args.voxelizer, "frames": C, "n_gpus": world,
                           "descriptor_scans_per_s": round(C / t_desc, 1), "descriptor_s": round(t_desc, 3), "inputs": "host [N,4] rows through the ingest leg" if args.host_rows else "resident in HBM",
                           "retrieval_ms_slowest_rank": round(t_ret * 1e3, 2), "retrieval_ms_per_rank": t_ret_all, "query_rows_per_rank": q_rows_all,
                           "wall_s_descriptors_plus_retrieval": round(t_desc + t_ret, 3), "gathered_descriptors_sha1": desc_sha1, "rows_sha1": rows_sha1,
