@@ -611,6 +611,62 @@ int lcr_ransac_correspondences(const float* src, const float* ref, const int32_t
 /* The sampler on the host: idx_host[k * ransac_n + j] = draw j of hypothesis h0 + k for a pair of n rows (1 <= n <= 2^31 - 1,
  * 1 <= ransac_n <= 8, 0 <= h0, h0 + count <= 1e6). */
 int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, int ransac_n, int64_t n, int32_t* idx_host);
+/* Correspondence RANSAC with Open3D's correspondence checkers (utils/utils/open3d.py:109-142 passes
+ * CorrespondenceCheckerBasedOnEdgeLength(0.9) and CorrespondenceCheckerBasedOnDistance(distance_threshold)).  Sampler, hypothesis, score
+ * and selection are those of lcr_ransac_correspondences (one code path: that entry is this one with both checks off and no corr, and
+ * returns the same bits); a hypothesis that fails a check is INVALID exactly like a collinear sample: never selected, counts_all = -1,
+ * sse_all = 0, the identity in T_all.
+ *   - edge_similarity (<= 0: off), before the fit: for every two draws a < b of the sample, on the fp32 rows, ls2 = |s_a - s_b|^2 and
+ *     lr2 = |r_a - r_b|^2 in the exact fp32 form (dx*dx + dy*dy) + dz*dz (every operation rounded), k2 = edge_similarity *
+ *     edge_similarity (fp32 product); the sample passes iff ls2 >= k2 * lr2 and lr2 >= k2 * ls2 (fp32 products) for all of them.
+ *     Squared lengths on purpose: no square root enters the definition.  A sample that fails is not fitted.
+ *   - checker_distance (<= 0: off), after the fit: every sampled row must satisfy the scoring rule's own d2 < checker_distance *
+ *     checker_distance (the fma form above on the stored fp32 transform, fp32 product on the right).
+ *   - reject_all (nullable) uint8 [S*iterations]: 0 valid, 1 degenerate (collinear or coincident sample, or n_s < ransac_n), 2 edge check,
+ *     3 distance check; the first check that fires in the order edge, degenerate, distance names the code.
+ *   - With a check on, the surviving hypotheses of every pair are listed in ascending h (a fourth launch, one workgroup per pair) and
+ *     the scoring pass runs over that list only: a rejected hypothesis streams no correspondence.  Selection's tie-break on h and the
+ *     index s*iterations+h of the per-hypothesis outputs are those of the original h.
+ *   - Index form: corr int32 [n_corr,2] non-null (pair-local src row, ref row; start [S+1] then offsets the rows of corr, and n_corr >=
+ *     start[S] is the capacity of corr): src / ref are the pairs' point clouds, stacked pair-major with src_start / ref_start int32 [S+1].
+ *     The rows are gathered by a kernel of its own into the workspace (12 B per row and side) and the rest of the call sees the layout of
+ *     lcr_ransac_correspondences, so the two forms give the same bits.  An index outside its cloud yields a NaN row (never an inlier).
+ *     corr null: src / ref are the correspondence rows themselves; src_start, ref_start and n_corr are not read.
+ * ws: lcr_ransac_ex_ws_bytes(S, iterations, n_corr) (n_corr = 0 without corr).  Domain: that of lcr_ransac_correspondences, the squares
+ * of the two checker parameters finite, 0 <= n_corr <= 2^31-1; LCR_EARG outside. */
+int lcr_ransac_ex_ws_bytes(int S, int iterations, int64_t n_corr, size_t* bytes);
+int lcr_ransac_correspondences_ex(const float* src, const float* ref, const int32_t* start, int S, const int32_t* corr, const int32_t* src_start,
+                                  const int32_t* ref_start, int64_t n_corr, float thr, int ransac_n, int iterations, uint64_t seed,
+                                  float edge_similarity, float checker_distance, float* T, int32_t* inliers, float* rmse, int32_t* best_h,
+                                  float* T_all, int32_t* counts_all, float* sse_all, uint8_t* reject_all, void* ws, size_t ws_bytes, void* stream);
+
+/* Exact nearest neighbour in feature space (what Open3D's registration_ransac_based_on_feature_matching asks of a KD-tree over the
+ * features), for S pairs in one call.
+ *   - Pairs: queries qf f32[nq,C] and database df f32[nd,C] stacked pair-major; pair s = query rows [q_start[s], q_start[s+1]) and
+ *     database rows [d_start[s], d_start[s+1]) (int32 [S+1] on the device).  A query only sees the database of its own pair.
+ *   - d2(i, j), fp32 with every operation rounded (no contraction): acc = 0; for c = 0 .. C-1: t = q[c] - d[c]; acc = acc + t * t.
+ *   - nn(i) = the pair-local database row j that minimises (d2(i, j), j) lexicographically: ties go to the smaller row.  A total order,
+ *     so the result depends on no tile, slice or launch order, and a pair gives the same bits alone or in any batch.
+ *   - Non-finite features: a NaN distance never wins (+inf is an ordinary value and can).  A row whose every distance is NaN, and every
+ *     row of a pair with an empty database, gets nn = -1 and d2 = NaN (0x7fc00000).
+ *   - Outputs per query row: nn int32 [nq], d2 f32 [nq] (the minimum itself).
+ *   - Every (i, j) is evaluated by the chain above on the vector unit (no screening pass, so nothing rests on an error bound):
+ *     3 nq nd C rounded operations.  Three stream-ordered launches and a scan over the pairs, no host synchronisation, no allocation; the workspace holds one
+ *     (d2, row) per query and database slice (at most 16 slices), never an nq x nd matrix.
+ * Domain: 1 <= S <= 65535, 1 <= C <= 1024, 0 <= nq, nd <= 2^31-1 (the row counts of qf / df); LCR_EARG outside. */
+int lcr_feature_nn_ws_bytes(int S, int64_t nq, int64_t nd, size_t* bytes);
+int lcr_feature_nn(const float* qf, const float* df, const int32_t* q_start, const int32_t* d_start, int S, int C, int64_t nq, int64_t nd,
+                   int32_t* nn, float* d2, void* ws, size_t ws_bytes, void* stream);
+/* Correspondences from nearest-neighbour rows, per pair: the rows (i, nn_sr[i]) in ascending i (both pair-local), keeping i iff
+ * 0 <= nn_sr[i] < the pair's ref rows and (nn_rs null, or nn_rs[nn_sr[i]] == i: the mutual filter).  As Open3D does, a pair whose mutual
+ * set has fewer than min_rows (= ransac_n) rows falls back to its unfiltered set, decided on the device.  nn_sr int32 [ns] stacked with
+ * src_start [S+1], nn_rs int32 [nr] stacked with ref_start [S+1].  Outputs: corr int32 [ns,2] (capacity: one row per source row; the first
+ * start[S] are written), start int32 [S+1] (exclusive scan of the pairs' counts), nullable mutual_used int32 [S] (1 where the filter held).
+ * Ordered compaction by wavefront ballot and prefix, no atomics; three launches and a scan, no host synchronisation.
+ * Domain: 1 <= S <= 65535, min_rows >= 0; LCR_EARG outside. */
+int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes);
+int lcr_feature_correspondences(const int32_t* nn_sr, const int32_t* src_start, const int32_t* nn_rs, const int32_t* ref_start, int S, int min_rows,
+                                int32_t* corr, int32_t* start, int32_t* mutual_used, void* ws, size_t ws_bytes, void* stream);
 
 /* Point-to-point ICP (Open3D's RegistrationICP with TransformationEstimationPointToPoint(with_scaling=False), as the reference's pair
  * generators run it: data/Kitti/generate_kitti_pairs.py:145-147) for S pairs in one call, made exact and batch-invariant.

@@ -9,6 +9,10 @@
 //                    (hypothesis, correspondence): 9 FMA for R s + t, 3 subtracts, 1 mul + 2 FMA for d², a compare and two accumulates —
 //                    VALU-issue bound, nothing else close (DESIGN.md "Correspondence RANSAC").  Each wavefront writes its best candidate;
 //   k_ransac_select  one workgroup per pair reduces the candidates in the total order (count desc, SSE asc, h asc).
+// lcr_ransac_correspondences_ex adds Open3D's correspondence checkers (edge length before the fit, distance after it; k_ransac_hyp) and,
+// when one of them is on, k_ransac_compact: one workgroup per pair lists the surviving hypotheses in ascending h (ballot + prefix), and
+// k_ransac_score gives its lanes to that list, so that a rejected hypothesis never streams a correspondence.  Its index form (corr rows
+// into the pairs' point clouds) is a gather kernel of its own in front (k_ransac_gather): everything after it sees today's layout.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -51,8 +55,13 @@ __device__ __forceinline__ void rs_wave_best(int& c, float& s, int& h) {
 }
 
 // one thread per (pair blockIdx.y, hypothesis h): hyp[(s * iters + h) * 16 + 0..11] = R|t, [12] = 1 valid / 0 invalid (R = I, t = 0)
+// edge_k2 > 0: the edge-length check (before the fit); check_d2 > 0: the distance check (after it, on the stored fp32 transform); reject
+// (nullable): 0 valid, 1 degenerate, 2 edge, 3 distance.  checked: counts_all / sse_all of the invalid hypotheses are written here (-1, 0),
+// because the compacted scoring pass never visits them.
 __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ src, const float* __restrict__ ref, const int32_t* __restrict__ start,
-                                                    int iters, int rn, uint64_t seed, float* __restrict__ hyp, float* __restrict__ T_all) {
+                                                    int iters, int rn, uint64_t seed, float edge_k2, float check_d2, bool checked,
+                                                    float* __restrict__ hyp, float* __restrict__ T_all, uint8_t* __restrict__ reject,
+                                                    int32_t* __restrict__ counts_all, float* __restrict__ sse_all) {
   const int s = blockIdx.y;
   const int h = blockIdx.x * blockDim.x + threadIdx.x;
   if (h >= iters) return;
@@ -60,7 +69,33 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ sr
   const int64_t g = static_cast<int64_t>(s) * iters + h;
   double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
   bool ok = false;
-  if (n >= rn) {
+  int code = 1;
+  bool edge_ok = true;
+  if (n >= rn && edge_k2 > 0.f) {                         // CorrespondenceCheckerBasedOnEdgeLength on the fp32 rows, squared lengths
+    float fs[RS_MAX_N][3], fr[RS_MAX_N][3];
+#pragma unroll
+    for (int j = 0; j < RS_MAX_N; ++j)
+      if (j < rn) {
+        const int64_t i = a + static_cast<int64_t>(ransac_draw(seed, h, j, static_cast<uint32_t>(n)));
+        for (int d = 0; d < 3; ++d) {
+          fs[j][d] = src[3 * i + d];
+          fr[j][d] = ref[3 * i + d];
+        }
+      }
+#pragma unroll
+    for (int j = 0; j < RS_MAX_N; ++j)
+#pragma unroll
+      for (int k = j + 1; k < RS_MAX_N; ++k)
+        if (k < rn) {
+          const float sx = fsub(fs[j][0], fs[k][0]), sy = fsub(fs[j][1], fs[k][1]), sz = fsub(fs[j][2], fs[k][2]);
+          const float rx = fsub(fr[j][0], fr[k][0]), ry = fsub(fr[j][1], fr[k][1]), rz = fsub(fr[j][2], fr[k][2]);
+          const float ls2 = fadd(fadd(fmul(sx, sx), fmul(sy, sy)), fmul(sz, sz));
+          const float lr2 = fadd(fadd(fmul(rx, rx), fmul(ry, ry)), fmul(rz, rz));
+          edge_ok = edge_ok && ls2 >= fmul(edge_k2, lr2) && lr2 >= fmul(edge_k2, ls2);
+        }
+    if (!edge_ok) code = 2;
+  }
+  if (n >= rn && edge_ok) {
     double ps[RS_MAX_N][3], pr[RS_MAX_N][3], cs[3] = {0, 0, 0}, cr[3] = {0, 0, 0};
 #pragma unroll
     for (int j = 0; j < RS_MAX_N; ++j) {
@@ -95,7 +130,36 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ sr
           t[r] -= Rf[r][c] * cs[c];
         }
       }
+      if (check_d2 > 0.f) {                               // CorrespondenceCheckerBasedOnDistance: the scoring rule on the sampled rows
+        float m[12];
+        for (int r = 0; r < 3; ++r) {
+          for (int c = 0; c < 3; ++c) m[4 * r + c] = static_cast<float>(R[r][c]);
+          m[4 * r + 3] = static_cast<float>(t[r]);
+        }
+#pragma unroll
+        for (int j = 0; j < RS_MAX_N; ++j)
+          if (j < rn) {
+            const float px = static_cast<float>(ps[j][0]), py = static_cast<float>(ps[j][1]), pz = static_cast<float>(ps[j][2]);
+            const float dx = fmaf(m[2], pz, fmaf(m[1], py, fmaf(m[0], px, m[3]))) - static_cast<float>(pr[j][0]);
+            const float dy = fmaf(m[6], pz, fmaf(m[5], py, fmaf(m[4], px, m[7]))) - static_cast<float>(pr[j][1]);
+            const float dz = fmaf(m[10], pz, fmaf(m[9], py, fmaf(m[8], px, m[11]))) - static_cast<float>(pr[j][2]);
+            ok = ok && fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < check_d2;
+          }
+        if (!ok) {
+          code = 3;
+          for (int r = 0; r < 3; ++r) {
+            t[r] = 0;
+            for (int c = 0; c < 3; ++c) R[r][c] = r == c ? 1 : 0;
+          }
+        }
+      }
     }
+  }
+  if (ok) code = 0;
+  if (reject) reject[g] = static_cast<uint8_t>(code);
+  if (checked && !ok) {
+    if (counts_all) counts_all[g] = -1;
+    if (sse_all) sse_all[g] = 0.f;
   }
   float* o = hyp + RS_HYP * g;
   for (int r = 0; r < 3; ++r) {
@@ -111,15 +175,65 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ sr
   }
 }
 
-// one wavefront per (tile blockIdx.x of 64 hypotheses, pair blockIdx.y); writes the tile's best (count, sse, h) candidate
+// one workgroup per pair: surv[s * iters + k] = the k-th valid hypothesis in ascending h, nsurv[s] = their number
+__global__ __launch_bounds__(256) void k_ransac_compact(const float* __restrict__ hyp, int iters, int32_t* __restrict__ surv,
+                                                        int32_t* __restrict__ nsurv) {
+  __shared__ int s_w[4];
+  const int s = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  const int64_t g0 = static_cast<int64_t>(s) * iters;
+  int base = 0;
+  for (int h0 = 0; h0 < iters; h0 += 256) {               // block-uniform trip count
+    const int h = h0 + tid;
+    const bool keep = h < iters && hyp[RS_HYP * (g0 + h) + 12] != 0.f;
+    const uint64_t m = wave_ballot(keep);
+    __syncthreads();
+    if ((tid & 63) == 0) s_w[w] = __popcll(m);
+    __syncthreads();
+    int off = base + mbcnt_lt(m);
+    for (int k = 0; k < w; ++k) off += s_w[k];
+    if (keep) surv[g0 + off] = h;
+    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  }
+  if (tid == 0) nsurv[s] = base;
+}
+
+// index form: row i of pair s (start[s] <= i < start[s+1]) = (cloud_src[src_start[s] + corr[i][0]], cloud_ref[ref_start[s] + corr[i][1]]);
+// an index outside its cloud is not read: the row becomes NaN, which is an inlier of no hypothesis and gives a hypothesis no inlier
+__global__ __launch_bounds__(256) void k_ransac_gather(const float* __restrict__ csrc, const float* __restrict__ cref, const int32_t* __restrict__ corr,
+                                                       const int32_t* __restrict__ start, const int32_t* __restrict__ src_start,
+                                                       const int32_t* __restrict__ ref_start, int S, int64_t cap, float* __restrict__ gs,
+                                                       float* __restrict__ gr) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= cap || i >= start[S]) return;
+  int lo = 0, hi = S - 1;                                 // the last s with start[s] <= i
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (start[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int a = corr[2 * i], b = corr[2 * i + 1];
+  const int ns = src_start[lo + 1] - src_start[lo], nr = ref_start[lo + 1] - ref_start[lo];
+  const float nan = __uint_as_float(0x7fc00000u);
+  for (int d = 0; d < 3; ++d) {
+    gs[3 * i + d] = a >= 0 && a < ns ? csrc[3 * (static_cast<int64_t>(src_start[lo]) + a) + d] : nan;
+    gr[3 * i + d] = b >= 0 && b < nr ? cref[3 * (static_cast<int64_t>(ref_start[lo]) + b) + d] : nan;
+  }
+}
+
+// one wavefront per (tile blockIdx.x of 64 hypotheses, pair blockIdx.y); writes the tile's best (count, sse, h) candidate.
+// surv != nullptr: the tile's lanes take the pair's surviving hypotheses surv[s * iters + tile * 64 + lane] (all valid) instead of h itself
 __global__ __launch_bounds__(RS_TILE) void k_ransac_score(const float* __restrict__ src, const float* __restrict__ ref, const int32_t* __restrict__ start,
                                                           int iters, float thr2, const float* __restrict__ hyp, int32_t* __restrict__ cand_count,
                                                           float* __restrict__ cand_sse, int32_t* __restrict__ cand_h, int32_t* __restrict__ counts_all,
-                                                          float* __restrict__ sse_all) {
+                                                          float* __restrict__ sse_all, const int32_t* __restrict__ surv,
+                                                          const int32_t* __restrict__ nsurv) {
   __shared__ float4 sh[2 * RS_CHUNK];
   const int s = blockIdx.y, lane = threadIdx.x;
-  const int h = blockIdx.x * RS_TILE + lane;
-  const bool live = h < iters;
+  int h = blockIdx.x * RS_TILE + lane;
+  bool live = h < iters;
+  if (surv) {
+    live = h < nsurv[s];
+    h = live ? surv[static_cast<int64_t>(s) * iters + h] : INT_MAX;
+  }
   const int a = start[s], n = start[s + 1] - a;
   const int64_t g = static_cast<int64_t>(s) * iters + (live ? h : 0);
   float m[12];
@@ -245,42 +359,99 @@ extern "C" int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, 
   return LCR_OK;
 }
 
+// workspace layout shared by the two entries: the old one has no survivor list and no gathered rows
+static size_t ransac_carve(Carver& c, int S, int iterations, bool checked, int64_t n_gather, float** hyp, int32_t** cc, float** cs, int32_t** ch,
+                           int32_t** surv, int32_t** nsurv, float** gs, float** gr) {
+  const size_t tiles = static_cast<size_t>(div_up(iterations, RS_TILE));
+  float* a = c.take<float>(static_cast<size_t>(S) * iterations * RS_HYP);   // hypotheses + valid flags
+  int32_t* b = c.take<int32_t>(S * tiles);                                  // per-tile best count
+  float* d = c.take<float>(S * tiles);                                      // its SSE
+  int32_t* e = c.take<int32_t>(S * tiles);                                  // its hypothesis index
+  int32_t* f = checked ? c.take<int32_t>(static_cast<size_t>(S) * iterations) : nullptr;   // surviving hypotheses per pair, ascending h
+  int32_t* g = checked ? c.take<int32_t>(static_cast<size_t>(S)) : nullptr;
+  float* p = n_gather > 0 ? c.take<float>(3 * static_cast<size_t>(n_gather)) : nullptr;    // index form: the gathered rows
+  float* q = n_gather > 0 ? c.take<float>(3 * static_cast<size_t>(n_gather)) : nullptr;
+  if (hyp) *hyp = a, *cc = b, *cs = d, *ch = e, *surv = f, *nsurv = g, *gs = p, *gr = q;
+  return c.off;
+}
+
 extern "C" int lcr_ransac_ws_bytes(int S, int iterations, size_t* bytes) {
   if (!bytes) return LCR_EARG;
   if (ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ws_bytes") != LCR_OK) return LCR_EARG;
-  const size_t tiles = static_cast<size_t>(div_up(iterations, RS_TILE));
   Carver c(nullptr, ~size_t(0));
-  c.take<float>(static_cast<size_t>(S) * iterations * RS_HYP);   // hypotheses + valid flags
-  c.take<int32_t>(S * tiles);                                     // per-tile best count
-  c.take<float>(S * tiles);                                       // its SSE
-  c.take<int32_t>(S * tiles);                                     // its hypothesis index
-  *bytes = c.off;
+  *bytes = ransac_carve(c, S, iterations, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   return LCR_OK;
+}
+
+extern "C" int lcr_ransac_ex_ws_bytes(int S, int iterations, int64_t n_corr, size_t* bytes) {
+  if (!bytes) return LCR_EARG;
+  if (ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ex_ws_bytes") != LCR_OK) return LCR_EARG;
+  if (n_corr < 0 || n_corr > INT32_MAX) {
+    set_error("lcr_ransac_ex_ws_bytes: n_corr outside 0..2^31-1 (%lld)", static_cast<long long>(n_corr));
+    return LCR_EARG;
+  }
+  Carver c(nullptr, ~size_t(0));
+  *bytes = ransac_carve(c, S, iterations, true, n_corr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return LCR_OK;
+}
+
+static int ransac_run(const char* what, const float* src, const float* ref, const int32_t* start, int S, const int32_t* corr,
+                      const int32_t* src_start, const int32_t* ref_start, int64_t n_corr, float thr, int ransac_n, int iterations, uint64_t seed,
+                      float edge_similarity, float checker_distance, float* T, int32_t* inliers, float* rmse, int32_t* best_h, float* T_all,
+                      int32_t* counts_all, float* sse_all, uint8_t* reject_all, void* ws, size_t ws_bytes, void* stream) {
+  if (ransac_domain(S, ransac_n, iterations, what) != LCR_OK) return LCR_EARG;
+  if (!src || !ref || !start || !T || !inliers || !rmse || !ws || !(thr > 0.f) || !std::isfinite(thr) || !std::isfinite(thr * thr)) {
+    set_error("%s: null pointer or distance threshold not finite and > 0 (thr=%g)", what, static_cast<double>(thr));
+    return LCR_EARG;
+  }
+  const float edge_k2 = edge_similarity > 0.f ? edge_similarity * edge_similarity : 0.f;
+  const float check_d2 = checker_distance > 0.f ? checker_distance * checker_distance : 0.f;
+  if (std::isnan(edge_similarity) || std::isnan(checker_distance) || !std::isfinite(edge_k2) || !std::isfinite(check_d2) ||
+      (corr && (!src_start || !ref_start || n_corr < 0 || n_corr > INT32_MAX))) {
+    set_error("%s: checker parameter not finite when squared (edge_similarity=%g checker_distance=%g), or the index form without "
+              "src_start / ref_start or with n_corr outside 0..2^31-1", what, static_cast<double>(edge_similarity),
+              static_cast<double>(checker_distance));
+    return LCR_EARG;
+  }
+  const bool checked = edge_k2 > 0.f || check_d2 > 0.f;
+  const int64_t n_gather = corr ? n_corr : 0;
+  float *hyp, *cs, *gs, *gr;
+  int32_t *cc, *ch, *surv, *nsurv;
+  Carver c(ws, ws_bytes);
+  const size_t need = ransac_carve(c, S, iterations, checked, n_gather, &hyp, &cc, &cs, &ch, &surv, &nsurv, &gs, &gr);
+  if (need > ws_bytes) {
+    set_error("%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
+    return LCR_ESPACE;
+  }
+  const int tiles = div_up(iterations, RS_TILE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n_gather > 0) {
+    hipLaunchKernelGGL(k_ransac_gather, dim3(div_up(n_gather, 256)), dim3(256), 0, st, src, ref, corr, start, src_start, ref_start, S, n_gather, gs,
+                       gr);
+    src = gs;
+    ref = gr;
+  }
+  hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iterations, 256), S), dim3(256), 0, st, src, ref, start, iterations, ransac_n, seed, edge_k2, check_d2,
+                     checked, hyp, T_all, reject_all, counts_all, sse_all);
+  if (checked) hipLaunchKernelGGL(k_ransac_compact, dim3(S), dim3(256), 0, st, hyp, iterations, surv, nsurv);
+  hipLaunchKernelGGL(k_ransac_score, dim3(tiles, S), dim3(RS_TILE), 0, st, src, ref, start, iterations, thr * thr, hyp, cc, cs, ch, counts_all, sse_all,
+                     checked ? surv : nullptr, checked ? nsurv : nullptr);
+  hipLaunchKernelGGL(k_ransac_select, dim3(S), dim3(256), 0, st, hyp, iterations, tiles, cc, cs, ch, T, inliers, rmse, best_h);
+  return check_launch(what);
+}
+
+extern "C" int lcr_ransac_correspondences_ex(const float* src, const float* ref, const int32_t* start, int S, const int32_t* corr,
+                                             const int32_t* src_start, const int32_t* ref_start, int64_t n_corr, float thr, int ransac_n,
+                                             int iterations, uint64_t seed, float edge_similarity, float checker_distance, float* T,
+                                             int32_t* inliers, float* rmse, int32_t* best_h, float* T_all, int32_t* counts_all, float* sse_all,
+                                             uint8_t* reject_all, void* ws, size_t ws_bytes, void* stream) {
+  return ransac_run("lcr_ransac_correspondences_ex", src, ref, start, S, corr, src_start, ref_start, n_corr, thr, ransac_n, iterations, seed,
+                    edge_similarity, checker_distance, T, inliers, rmse, best_h, T_all, counts_all, sse_all, reject_all, ws, ws_bytes, stream);
 }
 
 extern "C" int lcr_ransac_correspondences(const float* src, const float* ref, const int32_t* start, int S, float thr, int ransac_n, int iterations,
                                           uint64_t seed, float* T, int32_t* inliers, float* rmse, int32_t* best_h, float* T_all, int32_t* counts_all,
                                           float* sse_all, void* ws, size_t ws_bytes, void* stream) {
-  if (ransac_domain(S, ransac_n, iterations, "lcr_ransac_correspondences") != LCR_OK) return LCR_EARG;
-  if (!src || !ref || !start || !T || !inliers || !rmse || !ws || !(thr > 0.f) || !std::isfinite(thr) || !std::isfinite(thr * thr)) {
-    set_error("lcr_ransac_correspondences: null pointer or distance threshold not finite and > 0 (thr=%g)", static_cast<double>(thr));
-    return LCR_EARG;
-  }
-  size_t need = 0;
-  lcr_ransac_ws_bytes(S, iterations, &need);
-  if (need > ws_bytes) {
-    set_error("lcr_ransac_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    return LCR_ESPACE;
-  }
-  const int tiles = div_up(iterations, RS_TILE);
-  Carver c(ws, ws_bytes);
-  float* hyp = c.take<float>(static_cast<size_t>(S) * iterations * RS_HYP);
-  int32_t* cc = c.take<int32_t>(static_cast<size_t>(S) * tiles);
-  float* cs = c.take<float>(static_cast<size_t>(S) * tiles);
-  int32_t* ch = c.take<int32_t>(static_cast<size_t>(S) * tiles);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iterations, 256), S), dim3(256), 0, st, src, ref, start, iterations, ransac_n, seed, hyp, T_all);
-  hipLaunchKernelGGL(k_ransac_score, dim3(tiles, S), dim3(RS_TILE), 0, st, src, ref, start, iterations, thr * thr, hyp, cc, cs, ch, counts_all, sse_all);
-  hipLaunchKernelGGL(k_ransac_select, dim3(S), dim3(256), 0, st, hyp, iterations, tiles, cc, cs, ch, T, inliers, rmse, best_h);
-  return check_launch("lcr_ransac_correspondences");
+  return ransac_run("lcr_ransac_correspondences", src, ref, start, S, nullptr, nullptr, nullptr, 0, thr, ransac_n, iterations, seed, 0.f, 0.f, T,
+                    inliers, rmse, best_h, T_all, counts_all, sse_all, nullptr, ws, ws_bytes, stream);
 }

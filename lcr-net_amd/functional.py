@@ -826,6 +826,94 @@ def ransac_correspondences(src, ref, start, distance_threshold, ransac_n, num_it
     return T, inliers, rmse, best
 
 
+def ransac_correspondences_ex(src, ref, start, distance_threshold, ransac_n, num_iterations, seed=0, edge_similarity=0.0, checker_distance=0.0,
+                              corr=None, src_start=None, ref_start=None, want_details=False, want_reject=False):
+    """Correspondence RANSAC with Open3D's correspondence checkers (include/lcr_hip.h, lcr_ransac_correspondences_ex): the arguments and
+    outputs of ransac_correspondences, plus edge_similarity / checker_distance (<= 0: off) and the index form: with corr int32 [n,2]
+    (pair-local src row, ref row; start [S+1] offsets its rows) src / ref are the pairs' point clouds stacked with src_start / ref_start.
+    want_reject appends reject_all uint8 [S*iters] (0 valid, 1 degenerate, 2 edge check, 3 distance check).  Both checks off and no corr:
+    the bits of ransac_correspondences."""
+    _lib.require_cuda(src, ref, start)
+    dev = src.device
+    S, iters = start.numel() - 1, int(num_iterations)
+    n_corr = 0
+    if corr is not None:
+        if src_start is None or ref_start is None:
+            raise ValueError("ransac_correspondences_ex: corr needs src_start and ref_start")
+        _lib.require_cuda(corr, src_start, ref_start)
+        if corr.dtype != torch.int32 or corr.dim() != 2 or corr.shape[1] != 2 or src_start.numel() != S + 1 or ref_start.numel() != S + 1:
+            raise ValueError("ransac_correspondences_ex: corr must be int32 [n,2] and src_start / ref_start int32 [S+1]")
+        corr, src_start, ref_start = corr.contiguous(), src_start.contiguous(), ref_start.contiguous()
+        n_corr = corr.shape[0]
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_ransac_ex_ws_bytes(S, iters, n_corr, ctypes.byref(nbytes)), "lcr_ransac_ex_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty((S,), dtype=torch.int32, device=dev)
+    rmse = torch.empty((S,), dtype=torch.float32, device=dev)
+    best = torch.empty((S,), dtype=torch.int32, device=dev)
+    T_all = torch.empty((S * iters, 4, 4), dtype=torch.float32, device=dev) if want_details else None
+    counts = torch.empty((S * iters,), dtype=torch.int32, device=dev) if want_details else None
+    sse = torch.empty((S * iters,), dtype=torch.float32, device=dev) if want_details else None
+    reject = torch.empty((S * iters,), dtype=torch.uint8, device=dev) if want_reject else None
+    _lib.check(_L().lcr_ransac_correspondences_ex(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S,
+                                                  _lib.ptr(corr), _lib.ptr(src_start), _lib.ptr(ref_start), n_corr, float(distance_threshold),
+                                                  int(ransac_n), iters, int(seed) & 0xFFFFFFFFFFFFFFFF, float(edge_similarity),
+                                                  float(checker_distance), _lib.ptr(T), _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best),
+                                                  _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse), _lib.ptr(reject), _lib.ptr(ws), ws.numel(),
+                                                  _sp(src)), "lcr_ransac_correspondences_ex")
+    out = (T, inliers, rmse, best) + ((T_all, counts, sse) if want_details else ())
+    return out + ((reject,) if want_reject else ())
+
+
+def feature_nn(qf, df, q_start, d_start):
+    """Exact nearest neighbour in feature space (include/lcr_hip.h, lcr_feature_nn) for S pairs in one native call: qf f32 [nq,C] /
+    df f32 [nd,C] stacked pair-major, q_start / d_start int32 [S+1] -> (nn int32 [nq]: the pair-local database row with the smallest
+    (d2, row), -1 where the pair's database is empty or every distance is NaN; d2 f32 [nq])."""
+    _lib.require_cuda(qf, df, q_start, d_start)
+    if qf.dim() != 2 or df.dim() != 2 or qf.shape[1] != df.shape[1] or qf.dtype != torch.float32 or df.dtype != torch.float32:
+        raise ValueError("feature_nn: qf [nq,C] and df [nd,C] must be float32 with the same C")
+    if q_start.dtype != torch.int32 or d_start.dtype != torch.int32 or q_start.numel() != d_start.numel():
+        raise ValueError("feature_nn: q_start and d_start must be int32 [S+1]")
+    dev = qf.device
+    S, C, nq, nd = q_start.numel() - 1, qf.shape[1], qf.shape[0], df.shape[0]
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_feature_nn_ws_bytes(S, nq, nd, ctypes.byref(nbytes)), "lcr_feature_nn_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    nn = torch.empty((nq,), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nq,), dtype=torch.float32, device=dev)
+    _lib.check(_L().lcr_feature_nn(_lib.ptr(qf.contiguous()), _lib.ptr(df.contiguous()), _lib.ptr(q_start.contiguous()),
+                                   _lib.ptr(d_start.contiguous()), S, C, nq, nd, _lib.ptr(nn), _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _sp(qf)),
+               "lcr_feature_nn")
+    return nn, d2
+
+
+def feature_correspondences(nn_sr, src_start, ref_start, nn_rs=None, min_rows=3):
+    """Correspondences from nearest-neighbour rows (include/lcr_hip.h, lcr_feature_correspondences): nn_sr int32 [ns] (src -> ref, stacked
+    with src_start [S+1]) and, for the mutual filter, nn_rs int32 [nr] (ref -> src, stacked with ref_start [S+1]) -> (corr int32 [ns,2] of
+    which the first start[S] rows are written: (src row, ref row) pair-local in ascending src row; start int32 [S+1]; mutual_used
+    int32 [S]).  A pair whose mutual set has fewer than min_rows rows falls back to its unfiltered set."""
+    _lib.require_cuda(nn_sr, src_start, ref_start, *([nn_rs] if nn_rs is not None else []))
+    for t in (nn_sr, src_start, ref_start) + ((nn_rs,) if nn_rs is not None else ()):
+        if t.dtype != torch.int32:
+            raise ValueError("feature_correspondences: int32 tensors expected")
+    dev = nn_sr.device
+    S = src_start.numel() - 1
+    if ref_start.numel() != S + 1:
+        raise ValueError("feature_correspondences: src_start and ref_start must both be int32 [S+1]")
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_feature_correspondences_ws_bytes(S, ctypes.byref(nbytes)), "lcr_feature_correspondences_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    corr = torch.empty((nn_sr.numel(), 2), dtype=torch.int32, device=dev)
+    start = torch.empty((S + 1,), dtype=torch.int32, device=dev)
+    used = torch.empty((S,), dtype=torch.int32, device=dev)
+    _lib.check(_L().lcr_feature_correspondences(_lib.ptr(nn_sr.contiguous()), _lib.ptr(src_start.contiguous()),
+                                                _lib.ptr(nn_rs.contiguous() if nn_rs is not None else None), _lib.ptr(ref_start.contiguous()), S,
+                                                int(min_rows), _lib.ptr(corr), _lib.ptr(start), _lib.ptr(used), _lib.ptr(ws), ws.numel(),
+                                                _sp(nn_sr)), "lcr_feature_correspondences")
+    return corr, start, used
+
+
 def ransac_sample_host(seed, h0, count, ransac_n, n):
     """The RANSAC sampler on the host (no GPU): int32 [count, ransac_n] row indices of hypotheses h0 .. h0+count-1 for a pair of n rows."""
     out = np.empty((int(count), int(ransac_n)), dtype=np.int32)

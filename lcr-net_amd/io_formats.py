@@ -94,9 +94,15 @@ def _to_numpy(v):
     return np.asarray(v)
 
 
-def save_registration(output_dir, seq_id, anchor_idx, positive_idx, output_dict, transform):
+# the dense per-point descriptors next to pos_points_f / anc_points_f (LCRNet.forward leaves them in its output dict): what
+# tools/registration_eval.py --method ransac_featurematch matches.  The reference's test_registration.py:74-91 does not store them.
+REGISTRATION_FEAT_KEYS = ("pos_feats_f", "anc_feats_f")
+
+
+def save_registration(output_dir, seq_id, anchor_idx, positive_idx, output_dict, transform, with_feats=False):
     """`{seq_id}_{anchor_idx}_{positive_idx}.npz` with the 15 arrays of demo/demo.py:86-105 (the model's output dict + the
-    ground-truth `transform` of the data dict + both global descriptors).  Returns the path."""
+    ground-truth `transform` of the data dict + both global descriptors).  with_feats (opt-in) adds `pos_feats_f` / `anc_feats_f`
+    [N,256] for feature-matching RANSAC; with the default the file keeps the reference's key set.  Returns the path."""
     # gt_node_corr_indices / gt_node_corr_overlaps are written by demo.py:97-98 but are NOT produced by the shipped
     # LCRNet.forward (LCRNet.py:161-321 never sets them; only the training-time loss path reads them, loss_reg.py:175,256): when the
     # output dict has none they are stored empty, (0,2) int64 / (0,) f32, so that experiments/registration/eval.py:97-98 can open the file
@@ -105,6 +111,9 @@ def save_registration(output_dir, seq_id, anchor_idx, positive_idx, output_dict,
     arrays["transform"] = _to_numpy(transform)
     arrays["pos_feature_global"] = _to_numpy(output_dict["pos_feature_global"])
     arrays["anc_feature_global"] = _to_numpy(output_dict["anc_feature_global"])
+    if with_feats:
+        for k in REGISTRATION_FEAT_KEYS:
+            arrays[k] = _to_numpy(output_dict[k])
     path = os.path.join(output_dir, f"{seq_id}_{anchor_idx}_{positive_idx}.npz")
     np.savez_compressed(path, **arrays)
     return path

@@ -7,6 +7,11 @@ scored in fp32 against every correspondence of its pair, and the winner is the h
 SSE, then smaller h).  The exact definition is in include/lcr_hip.h (lcr_ransac_correspondences).  All of it runs in HIP kernels
 (csrc/ransac.hip); a pair gives the same bits alone or inside a batch.
 
+Feature-matching RANSAC (utils/utils/open3d.py:109-142, `registration_with_ransac_from_feats`: Open3D's
+registration_ransac_based_on_feature_matching with an edge-length checker at 0.9 and a distance checker, eval.py's `ransac_featurematch`):
+`ransac_from_feats_batched` / `registration_with_ransac_from_feats`.  Exact nearest neighbours in feature space (csrc/feature_nn.hip),
+the correspondence list with the optional mutual filter, and the RANSAC above with both checkers, all on the device.
+
 Point-to-point ICP on the dense clouds (Open3D's registration_icp with TransformationEstimationPointToPoint, which the reference's pair
 generators run for their ground truth, data/Kitti/generate_kitti_pairs.py:145-147): `registration_icp` (Open3D's call shape) and
 `icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states.
@@ -55,6 +60,71 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
     start = torch.tensor([0, src.shape[0]], dtype=torch.int32, device=dev)
     T, _, _ = ransac_batched(src, ref, start, distance_threshold, ransac_n, num_iterations, seed)
     return T[0].cpu().numpy().astype(np.float64)
+
+
+# ---- feature-matching RANSAC (utils/utils/open3d.py:109-142) ----
+REF_EDGE_SIMILARITY = 0.9            # CorrespondenceCheckerBasedOnEdgeLength(0.9), utils/utils/open3d.py:131
+
+
+def _starts(lengths, device):
+    """int32 [S+1] row offsets on the device from per-pair lengths (a host sequence, or a device tensor: no synchronisation)."""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        z = torch.zeros((1,), dtype=torch.int32, device=device)
+        return torch.cat([z, torch.cumsum(lengths.to(device=device, dtype=torch.int64).reshape(-1), 0).to(torch.int32)])
+    ln = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+    return torch.from_numpy(np.concatenate([[0], np.cumsum(ln)]).astype(np.int32)).to(device)
+
+
+def ransac_from_feats_batched(src_points, ref_points, src_feats, ref_feats, src_len, ref_len, distance_threshold=REF_DISTANCE_THRESHOLD,
+                              ransac_n=REF_RANSAC_N, num_iterations=REF_NUM_ITERATIONS, seed=0, mutual_filter=False,
+                              edge_similarity=REF_EDGE_SIMILARITY, want_corr=False, want_reject=False):
+    """Feature-matching RANSAC for S pairs, everything on the device and nothing synchronised.  src_points f32 [ns,3] / ref_points
+    f32 [nr,3] and src_feats f32 [ns,C] / ref_feats f32 [nr,C]: device tensors stacked pair-major; src_len / ref_len: S lengths (host
+    sequences or device tensors).  Per pair: every source row is matched to its exact nearest reference row in feature space
+    (functional.feature_nn), with mutual_filter only rows whose match points back are kept (a pair left with fewer than ransac_n rows
+    falls back to all of them, as Open3D does), and the checked RANSAC (edge-length similarity `edge_similarity`, distance checker at
+    `distance_threshold`) runs on those correspondences.  -> dict of device tensors: T f32 [S,4,4] (src onto ref), inliers int32 [S],
+    rmse f32 [S], best_h int32 [S], num_corr int32 [S]; with want_corr also corr int32 [ns,2] (pair-local rows; the first start[S] are
+    valid) and start int32 [S+1]; with want_reject reject_all uint8 [S*num_iterations] (0 valid, 1 degenerate, 2 edge, 3 distance)."""
+    dev = src_points.device
+    src_start, ref_start = _starts(src_len, dev), _starts(ref_len, dev)
+    nn_sr, _ = F.feature_nn(src_feats, ref_feats, src_start, ref_start)
+    nn_rs = F.feature_nn(ref_feats, src_feats, ref_start, src_start)[0] if mutual_filter else None
+    corr, start, _ = F.feature_correspondences(nn_sr, src_start, ref_start, nn_rs, min_rows=ransac_n)
+    out = F.ransac_correspondences_ex(src_points, ref_points, start, distance_threshold, ransac_n, num_iterations, seed,
+                                      edge_similarity=edge_similarity, checker_distance=distance_threshold, corr=corr, src_start=src_start,
+                                      ref_start=ref_start, want_reject=want_reject)
+    res = {"T": out[0], "inliers": out[1], "rmse": out[2], "best_h": out[3], "num_corr": start[1:] - start[:-1]}
+    if want_corr:
+        res.update(corr=corr, start=start)
+    if want_reject:
+        res["reject_all"] = out[4]
+    return res
+
+
+def _device_feats(x, device):
+    if torch.is_tensor(x):
+        return x.detach().to(device=device, dtype=torch.float32).reshape(x.shape[0], -1).contiguous()
+    x = np.asarray(x, dtype=np.float32)
+    return torch.from_numpy(np.ascontiguousarray(x.reshape(x.shape[0], -1))).to(device)
+
+
+def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_feats, distance_threshold=0.05, ransac_n=3, num_iterations=50000,
+                                        val_iterations=1000, seed=0, mutual_filter=False):
+    """The reference helper's name, argument order and defaults (utils/utils/open3d.py:109-118), plus `seed` and `mutual_filter` (False:
+    the reference calls the Open3D signature that has none).  src_points / ref_points: numpy arrays or torch tensors [N,3] / [M,3],
+    src_feats / ref_feats [N,C] / [M,C].  Edge-length checker at 0.9 and distance checker at distance_threshold, as the reference sets
+    them.  `val_iterations` (Open3D's validation budget of RANSACConvergenceCriteria) is accepted and ignored: every one of the
+    num_iterations hypotheses runs, as for registration_with_ransac_from_correspondences.  Returns the float64 (4,4) ndarray transform
+    from src to ref."""
+    dev = ref_points.device if torch.is_tensor(ref_points) and ref_points.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    src, ref = _device_points(src_points, dev), _device_points(ref_points, dev)
+    sf, rf = _device_feats(src_feats, dev), _device_feats(ref_feats, dev)
+    if sf.shape[0] != src.shape[0] or rf.shape[0] != ref.shape[0] or sf.shape[1] != rf.shape[1]:
+        raise ValueError("one feature row per point and the same feature width on both sides are needed")
+    r = ransac_from_feats_batched(src, ref, sf, rf, [src.shape[0]], [ref.shape[0]], distance_threshold, ransac_n, num_iterations, seed,
+                                  mutual_filter=mutual_filter)
+    return r["T"][0].cpu().numpy().astype(np.float64)
 
 
 # ---- point-to-point ICP (Open3D's registration_icp with TransformationEstimationPointToPoint; data/Kitti/generate_kitti_pairs.py:145-147) ----

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Registration evaluation over saved pair files: the counterpart of experiments/registration/eval.py.
 
-    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd] [--num_corr K] [--seed S] [--pairs-per-call P]
-                                      [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000] [--write-back]
+    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|ransac_featurematch] [--num_corr K] [--seed S]
+                                      [--pairs-per-call P] [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000]
+                                      [--write-back] [--mutual-filter] [--edge-similarity 0.9]
                                       [--refine icp|icp_plane [--icp-distance 0.5] [--icp-iterations 30]
                                                               [--normal-radius 1.0] [--normal-max-nn 30]]
 
@@ -13,7 +14,13 @@ registers the anchor onto the positive:
   ransac  the deterministic GPU RANSAC of lcrnet_amd.registration with src = anchor, ref = positive and the reference's settings
           (config_reg.py:69-73: 0.3 m, 4 points, 50 000 iterations); --pairs-per-call pairs go into one native call;
           --write-back stores `estimated_transform_ransac` in the file as :184-185 do;
-  svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group.
+  svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group;
+  ransac_featurematch
+          eval.py's fourth choice (utils/utils/open3d.py:109-142): every point of `anc_points_f` is matched to its exact nearest
+          neighbour among `pos_feats_f` in feature space (--mutual-filter keeps only matches that point back), and the RANSAC runs on
+          those correspondences with Open3D's edge-length checker (--edge-similarity, 0.9) and its distance checker at
+          --distance-threshold (lcrnet_amd.registration.ransac_from_feats_batched).  Needs `pos_feats_f` / `anc_feats_f` in the pair
+          files (io_formats.save_registration(..., with_feats=True)); a file without them ends the run with a non-zero exit.
 --refine icp (opt-in) then refines every estimate by point-to-point ICP of the dense anchor cloud (`anc_points_f`) onto the positive's
 (`pos_points_f`), Open3D's criteria with --icp-distance / --icp-iterations, batched on the GPU (lcrnet_amd.registration.icp_batched).
 --refine icp_plane does the same with point-to-plane ICP, on normals of `pos_points_f` computed on the GPU (radius --normal-radius,
@@ -83,6 +90,23 @@ def estimate_group(method, items, args, device):
     return T.cpu().numpy().astype(np.float64)
 
 
+def estimate_featurematch(group, args, device):
+    """Feature-matching RANSAC for a group of pairs in one native call sequence: (transforms (S,4,4) float64, num_corr [S],
+    reject codes uint8 [S, iterations])."""
+    import torch
+    from lcrnet_amd.registration import ransac_from_feats_batched
+    pts = lambda k: [np.ascontiguousarray(d[k], np.float32).reshape(-1, 3) for _, d, _, _, _ in group]
+    fts = lambda k: [np.ascontiguousarray(d[k], np.float32).reshape(len(d[k]), -1) for _, d, _, _, _ in group]
+    cat = lambda xs: torch.from_numpy(np.concatenate(xs)).to(device)
+    sp, rp, sf, rf = pts("anc_points_f"), pts("pos_points_f"), fts("anc_feats_f"), fts("pos_feats_f")
+    r = ransac_from_feats_batched(cat(sp), cat(rp), cat(sf), cat(rf), [len(x) for x in sp], [len(x) for x in rp], args.distance_threshold,
+                                  args.ransac_n, args.num_iterations, args.seed, mutual_filter=args.mutual_filter,
+                                  edge_similarity=args.edge_similarity, want_reject=True)
+    torch.cuda.synchronize(device)
+    return (r["T"].cpu().numpy().astype(np.float64), r["num_corr"].cpu().numpy(),
+            r["reject_all"].cpu().numpy().reshape(len(group), args.num_iterations))
+
+
 def refine_icp(pairs, est, args, device):
     """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each.
     --refine icp_plane: point-to-plane, on normals of pos_points_f estimated on the GPU first."""
@@ -109,7 +133,7 @@ def refine_icp(pairs, est, args, device):
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("features_dir")
-    p.add_argument("--method", choices=["lgr", "ransac", "svd"], default="lgr")
+    p.add_argument("--method", choices=["lgr", "ransac", "svd", "ransac_featurematch"], default="lgr")
     p.add_argument("--num_corr", type=int, default=None)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--pairs-per-call", type=int, default=16)
@@ -117,6 +141,8 @@ def main(argv=None):
     p.add_argument("--ransac-n", type=int, default=4)
     p.add_argument("--num-iterations", type=int, default=50000)
     p.add_argument("--write-back", action="store_true", help="store estimated_transform_ransac in each file (eval.py:184-185)")
+    p.add_argument("--mutual-filter", action="store_true", help="ransac_featurematch: keep only mutual nearest neighbours")
+    p.add_argument("--edge-similarity", type=float, default=0.9, help="ransac_featurematch: edge-length checker (<= 0: off)")
     p.add_argument("--refine", choices=["icp", "icp_plane"], default=None,
                    help="refine each estimate by point-to-point (icp) or point-to-plane (icp_plane) ICP of the dense clouds")
     p.add_argument("--icp-distance", type=float, default=0.5)
@@ -134,6 +160,11 @@ def main(argv=None):
         if seq == 8 and anc == 15 and pos == 58:          # eval.py:92-94 ("delete bad data")
             continue
         d, pos_pts, anc_pts, scores = load_pair(f, args.num_corr)
+        if args.method == "ransac_featurematch":
+            missing = [k for k in io.REGISTRATION_FEAT_KEYS + ("pos_points_f", "anc_points_f") if k not in d]
+            if missing:
+                sys.exit("registration_eval: --method ransac_featurematch needs %s in %s; write the pair files with "
+                         "io_formats.save_registration(..., with_feats=True)" % (", ".join(missing), f))
         pairs.append((f, d, pos_pts, anc_pts, scores))
 
     t0 = time.perf_counter()
@@ -142,10 +173,16 @@ def main(argv=None):
     else:
         import torch
         device = torch.device("cuda", torch.cuda.current_device())
-        est = []
+        est, fm_corr, fm_reject = [], [], []
         for g in range(0, len(pairs), args.pairs_per_call):
             group = pairs[g:g + args.pairs_per_call]
-            est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
+            if args.method == "ransac_featurematch":
+                T, nc, rej = estimate_featurematch(group, args, device)
+                est += list(T)
+                fm_corr += list(nc)
+                fm_reject.append(rej)
+            else:
+                est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
     scored = est                                          # --write-back stores the method's own estimate, refined or not
     if args.refine:
         import torch
@@ -171,6 +208,14 @@ def main(argv=None):
            "num_corr": args.num_corr, "seed": args.seed, "pairs_per_call": args.pairs_per_call}
     if args.method == "ransac":
         out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
+    if args.method == "ransac_featurematch":
+        rej = np.concatenate(fm_reject) if fm_reject else np.zeros((0, args.num_iterations), np.uint8)
+        share = lambda code: float((rej == code).mean()) if rej.size else float("nan")
+        out["ransac_featurematch"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n,
+                                      "num_iterations": args.num_iterations, "mutual_filter": args.mutual_filter,
+                                      "edge_similarity": args.edge_similarity,
+                                      "num_corr": float(np.mean(fm_corr)) if fm_corr else float("nan"),
+                                      "rejected": {"degenerate": share(1), "edge_length": share(2), "distance": share(3)}}
     if args.refine:
         out["refine"] = {"method": args.refine, "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
         if args.refine == "icp_plane":
