@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #endif
@@ -48,6 +49,9 @@ struct Carver {
 };
 
 inline int div_up(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
+// grid size of a grid-stride kernel over n items: `per` items per workgroup, at least one and at most `cap` workgroups
+inline int blocks_for(int64_t n, int per = 256, int cap = 4096) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, cap))); }
+inline hipStream_t ST(void* stream) { return static_cast<hipStream_t>(stream); }      // the C ABI carries streams as void*
 
 // Opt-in to more than 64 KB of dynamic LDS for one kernel.  Function attributes are PER DEVICE and this library is called from several
 // host threads (pipeline workers), so the "already done" state is one atomic per (kernel, device): racing callers both set the
@@ -93,6 +97,15 @@ __device__ __forceinline__ float fmul(float a, float b) {
 __device__ __forceinline__ float fdiv(float a, float b) {
 #pragma clang fp contract(off)
   return __fdiv_rn(a, b);
+}
+// the same for fp64 (the ICP moments and the normals' covariance sums: the CPU restatements round every product and sum)
+__device__ __forceinline__ double dadd(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double dmul(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -260,16 +260,29 @@ static int fnn_split(int S, int64_t nq, int64_t nd) {
   return static_cast<int>(std::max<int64_t>(z, 1));
 }
 
+struct FnnLayout {
+  int32_t *tiles, *pj;   // tiles [S+1]: query tiles per pair, scanned in place; pd / pj [Z, nq]: per-slice minima and their rows
+  float*   pd;
+  void*    scan_ws;
+  int      Z;            // database slices (fnn_split)
+  size_t   bytes;
+};
+static FnnLayout fnn_layout(void* ws, int S, int64_t nq, int64_t nd) {
+  FnnLayout L;
+  Carver c(ws, ~size_t(0));
+  L.tiles = c.take<int32_t>(static_cast<size_t>(S) + 1);
+  L.scan_ws = c.take<char>(scan_ws_bytes(S + 2));
+  L.Z = fnn_split(S, nq, nd);
+  L.pd = c.take<float>(static_cast<size_t>(L.Z) * nq);
+  L.pj = c.take<int32_t>(static_cast<size_t>(L.Z) * nq);
+  L.bytes = c.off;
+  return L;
+}
+
 extern "C" int lcr_feature_nn_ws_bytes(int S, int64_t nq, int64_t nd, size_t* bytes) {
   if (!bytes) return LCR_EARG;
   if (fnn_domain(S, 1, nq, nd, "lcr_feature_nn_ws_bytes") != LCR_OK) return LCR_EARG;
-  Carver c(nullptr, ~size_t(0));
-  c.take<int32_t>(static_cast<size_t>(S) + 1);                        // query tiles per pair, scanned in place
-  c.take<char>(scan_ws_bytes(S + 2));
-  const size_t Z = static_cast<size_t>(fnn_split(S, nq, nd));
-  c.take<float>(Z * nq);                                              // per-slice minima
-  c.take<int32_t>(Z * nq);
-  *bytes = c.off;
+  *bytes = fnn_layout(nullptr, S, nq, nd).bytes;
   return LCR_OK;
 }
 
@@ -280,27 +293,35 @@ extern "C" int lcr_feature_nn(const float* qf, const float* df, const int32_t* q
     set_error("lcr_feature_nn: null pointer");
     return LCR_EARG;
   }
-  size_t need = 0;
-  lcr_feature_nn_ws_bytes(S, nq, nd, &need);
-  if (need > ws_bytes) {
-    set_error("lcr_feature_nn: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  const FnnLayout L = fnn_layout(ws, S, nq, nd);
+  if (L.bytes > ws_bytes) {
+    set_error("lcr_feature_nn: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
     return LCR_ESPACE;
   }
   if (nq == 0) return LCR_OK;
-  Carver c(ws, ws_bytes);
-  int32_t* tiles = c.take<int32_t>(static_cast<size_t>(S) + 1);
-  void* sws = c.take<char>(scan_ws_bytes(S + 2));
-  const int Z = fnn_split(S, nq, nd);
-  float* pd = c.take<float>(static_cast<size_t>(Z) * nq);
-  int32_t* pj = c.take<int32_t>(static_cast<size_t>(Z) * nq);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_fnn_count_tiles, dim3(div_up(S + 1, 256)), dim3(256), 0, st, q_start, S, tiles);
-  int rc = exclusive_scan_i32(tiles, tiles, S + 1, nullptr, sws, st);
+  hipLaunchKernelGGL(k_fnn_count_tiles, dim3(div_up(S + 1, 256)), dim3(256), 0, st, q_start, S, L.tiles);
+  int rc = exclusive_scan_i32(L.tiles, L.tiles, S + 1, nullptr, L.scan_ws, st);
   if (rc != LCR_OK) return rc;
   const int64_t wgs = (nq + FN_TQ - 1) / FN_TQ + S;                   // upper bound of sum ceil(nq_s / 128); the surplus exits at once
-  hipLaunchKernelGGL(k_fnn_tiles, dim3(static_cast<unsigned>(wgs), Z), dim3(256), 0, st, qf, df, q_start, d_start, tiles, S, C, nq, pd, pj);
-  hipLaunchKernelGGL(k_fnn_merge, dim3(div_up(nq, 256)), dim3(256), 0, st, pd, pj, Z, nq, nn, d2);
+  hipLaunchKernelGGL(k_fnn_tiles, dim3(static_cast<unsigned>(wgs), L.Z), dim3(256), 0, st, qf, df, q_start, d_start, L.tiles, S, C, nq, L.pd, L.pj);
+  hipLaunchKernelGGL(k_fnn_merge, dim3(div_up(nq, 256)), dim3(256), 0, st, L.pd, L.pj, L.Z, nq, nn, d2);
   return check_launch("lcr_feature_nn");
+}
+
+struct FcLayout {
+  int32_t *count, *use;   // count [S+1]: correspondences per pair; use [S]: 1 = the pair uses its mutual matches
+  void*    scan_ws;
+  size_t   bytes;
+};
+static FcLayout fc_layout(void* ws, int S) {
+  FcLayout L;
+  Carver c(ws, ~size_t(0));
+  L.count = c.take<int32_t>(static_cast<size_t>(S) + 1);
+  L.use = c.take<int32_t>(static_cast<size_t>(S));
+  L.scan_ws = c.take<char>(scan_ws_bytes(S + 2));
+  L.bytes = c.off;
+  return L;
 }
 
 extern "C" int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes) {
@@ -308,11 +329,7 @@ extern "C" int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes) {
     set_error("lcr_feature_correspondences_ws_bytes: null pointer or S outside 1..65535 (S=%d)", S);
     return LCR_EARG;
   }
-  Carver c(nullptr, ~size_t(0));
-  c.take<int32_t>(static_cast<size_t>(S) + 1);
-  c.take<int32_t>(static_cast<size_t>(S));
-  c.take<char>(scan_ws_bytes(S + 2));
-  *bytes = c.off;
+  *bytes = fc_layout(nullptr, S).bytes;
   return LCR_OK;
 }
 
@@ -323,20 +340,15 @@ extern "C" int lcr_feature_correspondences(const int32_t* nn_sr, const int32_t* 
     set_error("lcr_feature_correspondences: null pointer or outside the domain (1 <= S <= 65535, min_rows >= 0): S=%d min_rows=%d", S, min_rows);
     return LCR_EARG;
   }
-  size_t need = 0;
-  lcr_feature_correspondences_ws_bytes(S, &need);
-  if (need > ws_bytes) {
-    set_error("lcr_feature_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  const FcLayout L = fc_layout(ws, S);
+  if (L.bytes > ws_bytes) {
+    set_error("lcr_feature_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
     return LCR_ESPACE;
   }
-  Carver c(ws, ws_bytes);
-  int32_t* count = c.take<int32_t>(static_cast<size_t>(S) + 1);
-  int32_t* use = c.take<int32_t>(static_cast<size_t>(S));
-  void* sws = c.take<char>(scan_ws_bytes(S + 2));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_fc_count, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, S, min_rows, count, use);
-  int rc = exclusive_scan_i32(count, start, S + 1, nullptr, sws, st);
+  hipLaunchKernelGGL(k_fc_count, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, S, min_rows, L.count, L.use);
+  int rc = exclusive_scan_i32(L.count, start, S + 1, nullptr, L.scan_ws, st);
   if (rc != LCR_OK) return rc;
-  hipLaunchKernelGGL(k_fc_write, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, start, use, corr, mutual_used);
+  hipLaunchKernelGGL(k_fc_write, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, start, L.use, corr, mutual_used);
   return check_launch("lcr_feature_correspondences");
 }

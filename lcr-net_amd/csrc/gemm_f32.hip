@@ -1467,7 +1467,7 @@ using namespace lcr;
 // tuning hook (tools/gemm_bench.py): 0 = heuristic, 1..5 = force a tile shape
 static int g_force_tile = 0;
 extern "C" void lcr_gemm_debug_force_tile(int t) { g_force_tile = t; }
-// tuning / test hook: -1 = LCR_GEMM_STREAMK (default 1 = heuristic), 0 = never, 2 = whenever the stream-K kernel is legal
+// tuning / test hook: -1 = LCR_GEMM_STREAMK (default 0 = never), 0 = never, 1 = heuristic, 2 = whenever the stream-K kernel is legal
 static int g_force_streamk = -1;
 // tuning / test hook: -1 = LCR_GEMM_DEEP (default on), 0 = never, 1 = wherever legal
 static int g_force_deep = -1;
@@ -1476,6 +1476,35 @@ extern "C" void lcr_gemm_debug_streamk(int mode) { g_force_streamk = mode; }
 
 static int gemm_impl(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const float* bias,
                      const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, void* stream);
+
+// Which form lcr_gemm_f32 takes for a shape (vec: both leading dimensions multiples of 4 floats and 16-byte aligned bases).  gemm_impl
+// dispatches on it and lcr_kpconv_mask_ok asks it; every switch is read here, once.
+// LCR_GEMM_NO_SHORT set: no light form; LCR_GEMM_SHORT_K: its largest K (256); LCR_GEMM_DEEP 0: off, 1: K beyond the light form (default),
+// 2: every legal K; LCR_GEMM_STREAMK 0: off (default), 1: heuristic, 2: whenever legal.
+static int env_int(const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; }
+enum GemmForm { GF_SCALAR, GF_FORCED_TILE, GF_SHORT, GF_DEEP, GF_STREAMK, GF_TILE };
+static GemmForm gemm_form(int64_t M, int N, int K, int transA, int transB, bool vec) {
+  static const bool no_short = getenv("LCR_GEMM_NO_SHORT") != nullptr;   // A/B switch while the light form is being evaluated
+  static const int short_k = env_int("LCR_GEMM_SHORT_K", 256);
+  static const int deep_env = env_int("LCR_GEMM_DEEP", 1);
+  static const int sk_env = env_int("LCR_GEMM_STREAMK", 0);
+  if (!vec) return GF_SCALAR;
+  if (g_force_tile >= 1 && g_force_tile <= 5) return GF_FORCED_TILE;
+  // K-deep form (LDS-direct loads + cross-step fragment prefetch) wherever both operands are k-contiguous and K is a multiple of the K-step
+  const int deep_mode = g_force_deep >= 0 ? g_force_deep : deep_env;
+  const bool deep_ok = !transA && transB && K % GM_BK == 0 && !g_force_tile && M * K < (int64_t(1) << 30) && static_cast<int64_t>(N) * K < (int64_t(1) << 30);
+  if (deep_mode == 2 && deep_ok) return GF_DEEP;
+  if (!no_short && K <= short_k && !transA) return GF_SHORT;
+  if (deep_mode && deep_ok) return GF_DEEP;
+  if (N <= 32) return GF_TILE;
+  // Stream-K is opt-in: measured +3 / +5 / +7 % on the three deepest KPConv contractions alone (93.6 vs 96, 121 vs 128, 153 vs
+  // 164 us) — far from the 20 % a CU-count model predicts, because one or two workgroups per CU already reach 40 / 60 % of the
+  // matrix-pipe rate that three reach (65 %), so an unevenly loaded CU is slower per tile but not idle pro rata.
+  const int sk_mode = g_force_streamk >= 0 ? g_force_streamk : sk_env;
+  const bool sk_legal = !transA && !transB && K >= 64 && static_cast<int64_t>(div_up(M, 64)) * div_up(N, 64) <= SK_MAX_TILES;
+  if (sk_mode && sk_legal && (sk_mode == 2 || sk_worth(M, N, K))) return GF_STREAMK;
+  return GF_TILE;
+}
 
 // C = leaky(GroupNorm(A)) · B^T (+ bias, + statistics of C): the light GEMM with normalise-on-load (ANorm above).  The caller
 // guarantees that every segment holds at least 64 rows (a row block then touches at most two segments); shapes outside the
@@ -1538,44 +1567,30 @@ static int gemm_impl(const float* A, const float* B, float* C, int64_t M, int N,
   // row offsets inside them are multiples of the leading dimension)
   const int64_t lda = transA ? M : K, ldb = transB ? K : N;
   const bool vec = (lda % 4 == 0) && (ldb % 4 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (reinterpret_cast<uintptr_t>(B) % 16 == 0);
-  if (!vec) return launch_gemm<128, 64, 4, 1, false>(A, B, C, M, N, K, transA, transB, ep, st);
-  switch (g_force_tile) {
-    case 1: return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    case 2: return launch_gemm<128, 64, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    case 3: return launch_gemm<128, 32, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    case 4: return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    case 5: return launch_gemm<64, 128, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    default: break;
+  switch (gemm_form(M, N, K, transA, transB, vec)) {
+    case GF_SCALAR: return launch_gemm<128, 64, 4, 1, false>(A, B, C, M, N, K, transA, transB, ep, st);
+    case GF_FORCED_TILE:
+      switch (g_force_tile) {
+        case 1: return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
+        case 2: return launch_gemm<128, 64, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
+        case 3: return launch_gemm<128, 32, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
+        case 4: return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
+        default: return launch_gemm<64, 128, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
+      }
+    case GF_SHORT:
+      if (N <= 32) return launch_gemm<128, 32, 4, 1, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
+      return launch_gemm<64, 64, 2, 2, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
+    case GF_DEEP:
+      if (N <= 32) return launch_gemm_deep<128, 32, 4, 1>(A, B, C, M, N, K, ep, st);
+      return launch_gemm_deep<64, 64, 2, 2>(A, B, C, M, N, K, ep, st);
+    case GF_STREAMK: return launch_gemm_sk(A, B, C, M, N, K, ep, st);
+    case GF_TILE: break;
   }
   // Tile choice from tools/gemm_bench.py --tiles on MI355X: 64x64 (2x2 wavefronts) wins or ties on every encoder shape with
   // N >= 64 (enough workgroups for two per CU matters more than per-tile reuse at these M); N = 32 wants the 128-row tile;
   // only large, deep problems (>= 512 tiles of 128x128 and K >= 512) pay for the big tile.
-  const int64_t b128 = (M + 127) / 128, nb128 = (N + 127) / 128;
-  static const bool no_short = getenv("LCR_GEMM_NO_SHORT") != nullptr;   // A/B switch while the light form is being evaluated
-  static const int short_k = getenv("LCR_GEMM_SHORT_K") ? atoi(getenv("LCR_GEMM_SHORT_K")) : 256;
-  // K-deep form (LDS-direct loads + cross-step fragment prefetch) wherever both operands are k-contiguous and K is a multiple of the
-  // K-step (LCR_GEMM_DEEP=0: off; 1: K beyond the light form; 2: every such K)
-  static const int deep_env = getenv("LCR_GEMM_DEEP") ? atoi(getenv("LCR_GEMM_DEEP")) : 1;
-  const int deep_mode = g_force_deep >= 0 ? g_force_deep : deep_env;
-  const bool deep_ok = !transA && transB && K % GM_BK == 0 && !g_force_tile && M * K < (int64_t(1) << 30) && static_cast<int64_t>(N) * K < (int64_t(1) << 30);
-  auto deep = [&] {
-    if (N <= 32) return launch_gemm_deep<128, 32, 4, 1>(A, B, C, M, N, K, ep, st);
-    return launch_gemm_deep<64, 64, 2, 2>(A, B, C, M, N, K, ep, st);
-  };
-  if (deep_mode == 2 && deep_ok) return deep();
-  if (!no_short && K <= short_k && !transA) {
-    if (N <= 32) return launch_gemm<128, 32, 4, 1, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    return launch_gemm<64, 64, 2, 2, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
-  }
-  if (deep_mode && deep_ok) return deep();
   if (N <= 32) return launch_gemm<128, 32, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-  // Stream-K is opt-in: measured +3 / +5 / +7 % on the three deepest KPConv contractions alone (93.6 vs 96, 121 vs 128, 153 vs
-  // 164 us) — far from the 20 % a CU-count model predicts, because one or two workgroups per CU already reach 40 / 60 % of the
-  // matrix-pipe rate that three reach (65 %), so an unevenly loaded CU is slower per tile but not idle pro rata.
-  static const int sk_env = getenv("LCR_GEMM_STREAMK") ? atoi(getenv("LCR_GEMM_STREAMK")) : 0;   // 0 off, 1 heuristic, 2 whenever legal
-  const int sk_mode = g_force_streamk >= 0 ? g_force_streamk : sk_env;
-  const bool sk_legal = !transA && !transB && K >= 64 && static_cast<int64_t>(div_up(M, 64)) * div_up(N, 64) <= SK_MAX_TILES;
-  if (sk_mode && sk_legal && (sk_mode == 2 || sk_worth(M, N, K))) return launch_gemm_sk(A, B, C, M, N, K, ep, st);
+  const int64_t b128 = (M + 127) / 128, nb128 = (N + 127) / 128;
   if (K >= 512 && b128 * nb128 >= 512) return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
   return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
 }
@@ -1667,12 +1682,7 @@ extern "C" int lcr_kpconv_mask_ok(int64_t M, int N, int K, int split) {
   static const bool off = getenv("LCR_KP_MASK") && atoi(getenv("LCR_KP_MASK")) == 0;
   if (off || M <= 0 || N <= 0 || K % 15 != 0 || mask_kshift(K, K / 15) < 0) return 0;
   if (split) return M * static_cast<int64_t>(K) < (int64_t(1) << 29);
-  static const int deep_env = getenv("LCR_GEMM_DEEP") ? atoi(getenv("LCR_GEMM_DEEP")) : 1;
-  const int deep_mode = g_force_deep >= 0 ? g_force_deep : deep_env;
-  const int short_k = getenv("LCR_GEMM_SHORT_K") ? atoi(getenv("LCR_GEMM_SHORT_K")) : 256;
-  const bool short_form = getenv("LCR_GEMM_NO_SHORT") == nullptr && K <= short_k;
-  return deep_mode && !g_force_tile && (deep_mode == 2 || !short_form) && M * static_cast<int64_t>(K) < (int64_t(1) << 30) &&
-         static_cast<int64_t>(N) * K < (int64_t(1) << 30);
+  return gemm_form(M, N, K, 0, 1, true) == GF_DEEP;      // A [M,K] and B [N,K] row-major with K % 32 == 0 (mask_kshift): the vector forms
 }
 
 // The K-deep fp32 form over a row-masked A (same tile choice as lcr_gemm_f32 makes for these shapes).
@@ -1750,9 +1760,9 @@ extern "C" int lcr_gemm_f32_strided_batched(const float* A, const float* B, floa
   // LCR_GEMM_BATCH_TILE=128: ONE 128 x 128 tile per problem instead of four 64 x 64 ones for the 128 x 128 x 256 patch products.  Looked like
   // +4 % pairs/s across two gpurun sessions (590 -> 616), is -3 % in a same-session A/B (648 / 644 vs 632 / 623 pairs/s at 16 pairs per call) and
   // 1.29 vs 0.96 ms per call alone: off by default, kept as the switch that measured it
-  static const int batch_tile = getenv("LCR_GEMM_BATCH_TILE") ? atoi(getenv("LCR_GEMM_BATCH_TILE")) : 64;
+  static const int batch_tile = env_int("LCR_GEMM_BATCH_TILE", 64);
   if (batch_tile == 128 && M >= 128 && N >= 128) return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
-  static const bool batch_short = !(getenv("LCR_GEMM_BATCH_SHORT") && atoi(getenv("LCR_GEMM_BATCH_SHORT")) == 0);
+  static const bool batch_short = env_int("LCR_GEMM_BATCH_SHORT", 1) != 0;
   if (batch_short && K <= 256 && !transA) return launch_gemm<64, 64, 2, 2, true, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
   return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
 }

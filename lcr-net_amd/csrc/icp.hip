@@ -44,15 +44,6 @@ struct IcpPairs {
   int64_t tgt_off[GRID_MAX_B + 1];
 };
 
-__device__ __forceinline__ double dadd(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ double dmul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
 // fp32(((T[4r] * x + T[4r+1] * y) + T[4r+2] * z) + T[4r+3]), no contraction
 __device__ __forceinline__ float icp_row(const double* T, int r, double x, double y, double z) {
   return static_cast<float>(dadd(dadd(dadd(dmul(T[4 * r], x), dmul(T[4 * r + 1], y)), dmul(T[4 * r + 2], z)), T[4 * r + 3]));
@@ -77,6 +68,17 @@ __device__ __forceinline__ void icp_block_sum(double (&m)[MOM], double (*s_red)[
       for (int v = 1; v < ICP_BLOCK / 64; ++v) a = dadd(a, s_red[v][j]);
       m[j] = a;
     }
+}
+
+// the moments of a pair for its k_icp_update*: the slab rows of its nb row blocks (from b0) summed in a fixed order, totals in thread 0's m[]
+template <int MOM>
+__device__ __forceinline__ void icp_slab_sum(const double* __restrict__ slab, int b0, int nb, double (&m)[MOM], double (*s_red)[MOM]) {
+#pragma unroll
+  for (int j = 0; j < MOM; ++j) m[j] = 0.0;
+  for (int b = threadIdx.x; b < nb; b += ICP_BLOCK)
+#pragma unroll
+    for (int j = 0; j < MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * MOM + j]);
+  icp_block_sum<MOM>(m, s_red);
 }
 
 // the partner key of q: the smallest (d², target row) with d² < r2 over the nine x-runs of q's 3x3x3 cell neighbourhood, ~0 if none
@@ -119,6 +121,25 @@ __device__ __forceinline__ int icp_pair_of_block(const IcpPairs& P, int blk) {
   return s;
 }
 
+// the shared head of k_icp_match*: source row i of pair s under the pair's current T.  Tm = rows 0..2 of T, p = the row in fp64; the partner
+// (icp_nearest of fp32(T p)) comes back as its stacked target row j and d² (0 without one); corr[i] gets the pair-local partner (-1: none).  False: no partner.
+__device__ __forceinline__ bool icp_match_row(const double* __restrict__ T, int s, const float* __restrict__ src, int64_t i, int64_t tb,
+                                              const GridHeader* __restrict__ h, const int32_t* __restrict__ cell_start,
+                                              const float4* __restrict__ sorted, float r2, int32_t* __restrict__ corr, double (&Tm)[12],
+                                              double (&p)[3], int64_t& j, double& d2) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) p[d] = src[3 * i + d];
+  const float qx = icp_row(Tm, 0, p[0], p[1], p[2]), qy = icp_row(Tm, 1, p[0], p[1], p[2]), qz = icp_row(Tm, 2, p[0], p[1], p[2]);
+  const uint64_t best = icp_nearest(h->cloud[s], cell_start, sorted, r2, qx, qy, qz);
+  const bool found = best != ~0ull;
+  j = static_cast<int64_t>(static_cast<uint32_t>(best));
+  d2 = found ? static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) : 0.0;
+  if (corr) corr[i] = found ? static_cast<int32_t>(j - tb) : -1;
+  return found;
+}
+
 __global__ void k_icp_init(IcpPairs P, const double* __restrict__ init, int hist_rows, double* __restrict__ T, double* __restrict__ fitness,
                            double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ done, int32_t* __restrict__ running,
                            int64_t* __restrict__ tgt_len, double* __restrict__ T_hist, double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
@@ -157,17 +178,10 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float
   for (int j = 0; j < ICP_MOM; ++j) m[j] = 0.0;
   if (row < n) {
     const int64_t i = a + row;
-    double Tm[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
-    const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
-    const float qx = icp_row(Tm, 0, x, y, z), qy = icp_row(Tm, 1, x, y, z), qz = icp_row(Tm, 2, x, y, z);
-    const uint64_t best = icp_nearest(h->cloud[s], cell_start, sorted, r2, qx, qy, qz);
-    int32_t j_loc = -1;
-    if (best != ~0ull) {
-      const int64_t j = static_cast<int64_t>(static_cast<uint32_t>(best));
-      j_loc = static_cast<int32_t>(j - tb);
-      const double d2 = static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32)));
+    double Tm[12], p[3], d2;
+    int64_t j;
+    if (icp_match_row(T, s, src, i, tb, h, cell_start, sorted, r2, corr, Tm, p, j, d2)) {
+      const double x = p[0], y = p[1], z = p[2];
       const double dp[3] = {x - static_cast<double>(src[3 * a]), y - static_cast<double>(src[3 * a + 1]), z - static_cast<double>(src[3 * a + 2])};
       const double dr[3] = {static_cast<double>(tgt[3 * j]) - static_cast<double>(tgt[3 * tb]),
                             static_cast<double>(tgt[3 * j + 1]) - static_cast<double>(tgt[3 * tb + 1]),
@@ -182,7 +196,6 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float
         for (int q = 0; q < 3; ++q) m[8 + 3 * r + q] = dmul(dp[r], dr[q]);
       }
     }
-    if (corr) corr[i] = j_loc;
   }
   icp_block_sum<ICP_MOM>(m, s_red);
   if (threadIdx.x == 0)
@@ -240,12 +253,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update(IcpPairs P, const floa
   if (done[s]) return;
   const int b0 = P.blk_off[s], nb = P.blk_off[s + 1] - b0;
   double m[ICP_MOM];
-#pragma unroll
-  for (int j = 0; j < ICP_MOM; ++j) m[j] = 0.0;
-  for (int b = tid; b < nb; b += ICP_BLOCK)
-#pragma unroll
-    for (int j = 0; j < ICP_MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * ICP_MOM + j]);
-  icp_block_sum<ICP_MOM>(m, s_red);
+  icp_slab_sum<ICP_MOM>(slab, b0, nb, m, s_red);
   if (tid != 0) return;
 
   const int64_t a = P.src_off[s], tb = P.tgt_off[s];
@@ -299,18 +307,11 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match_plane(IcpPairs P, const
   double found = 0.0, d2 = 0.0, use = 0.0, res = 0.0, J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (row < n) {
     const int64_t i = a + row;
-    double Tm[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) Tm[k] = T[16 * s + k];
-    const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
-    const float qx = icp_row(Tm, 0, x, y, z), qy = icp_row(Tm, 1, x, y, z), qz = icp_row(Tm, 2, x, y, z);
-    const uint64_t best = icp_nearest(h->cloud[s], cell_start, sorted, r2, qx, qy, qz);
-    int32_t j_loc = -1;
-    if (best != ~0ull) {
-      const int64_t j = static_cast<int64_t>(static_cast<uint32_t>(best));
-      j_loc = static_cast<int32_t>(j - tb);
+    double Tm[12], p[3];
+    int64_t j;
+    if (icp_match_row(T, s, src, i, tb, h, cell_start, sorted, r2, corr, Tm, p, j, d2)) {
+      const double x = p[0], y = p[1], z = p[2];
       found = 1.0;
-      d2 = static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32)));
       const double nv[3] = {nrm[3 * j], nrm[3 * j + 1], nrm[3 * j + 2]};
       if (nv[0] != 0.0 || nv[1] != 0.0 || nv[2] != 0.0) {
         double sp[3], dv[3];
@@ -329,7 +330,6 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match_plane(IcpPairs P, const
         J[5] = nv[2];
       }
     }
-    if (corr) corr[i] = j_loc;
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   auto wave_sum = [&](double v, int q) {
@@ -402,12 +402,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update_plane(IcpPairs P, cons
   if (done[s]) return;
   const int b0 = P.blk_off[s], nb = P.blk_off[s + 1] - b0;
   double m[ICP_PLANE_MOM];
-#pragma unroll
-  for (int j = 0; j < ICP_PLANE_MOM; ++j) m[j] = 0.0;
-  for (int b = tid; b < nb; b += ICP_BLOCK)
-#pragma unroll
-    for (int j = 0; j < ICP_PLANE_MOM; ++j) m[j] = dadd(m[j], slab[static_cast<int64_t>(b0 + b) * ICP_PLANE_MOM + j]);
-  icp_block_sum<ICP_PLANE_MOM>(m, s_red);
+  icp_slab_sum<ICP_PLANE_MOM>(slab, b0, nb, m, s_red);
   if (tid != 0) return;
   if (!icp_result(P, s, m[0], m[1], k, max_iter, rel_fit, rel_rmse, fitness, rmse, done, fit_hist, rmse_hist)) return;
   // update k: T unchanged when fewer than 6 rows are usable or A is (numerically) singular

@@ -213,17 +213,26 @@ __global__ __launch_bounds__(NV_D) void k_netvlad_tail(const float* __restrict__
 
 using namespace lcr;
 
-
+struct NetvladLayout {   // xn [n_rows, NV_F] unit-norm rows, act [n_rows, NV_K] soft assignments, V [S, NV_F, NV_K], asum [S, NV_K],
+  float *xn, *act, *V, *asum, *partial;   // partial [NV_SPLIT, S, NV_D] split-K partials of the hidden projection
+  size_t bytes;
+};
+static NetvladLayout netvlad_layout(void* ws, int64_t n_rows, int S) {
+  NetvladLayout L;
+  Carver c(ws, ~size_t(0));
+  const size_t rows = static_cast<size_t>(n_rows > 0 ? n_rows : 1);
+  L.xn = c.take<float>(rows * NV_F);
+  L.act = c.take<float>(rows * NV_K);
+  L.V = c.take<float>(static_cast<size_t>(S) * NV_F * NV_K);
+  L.asum = c.take<float>(static_cast<size_t>(S) * NV_K);
+  L.partial = c.take<float>(static_cast<size_t>(NV_SPLIT) * S * NV_D);
+  L.bytes = c.off;
+  return L;
+}
 
 extern "C" int lcr_netvlad_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
   if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
-  Carver c(nullptr, ~size_t(0));
-  c.take<float>(static_cast<size_t>(n_rows > 0 ? n_rows : 1) * NV_F);
-  c.take<float>(static_cast<size_t>(n_rows > 0 ? n_rows : 1) * NV_K);
-  c.take<float>(static_cast<size_t>(S) * NV_F * NV_K);
-  c.take<float>(static_cast<size_t>(S) * NV_K);
-  c.take<float>(static_cast<size_t>(NV_SPLIT) * S * NV_D);
-  *bytes = c.off;
+  *bytes = netvlad_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
 }
 
@@ -242,25 +251,18 @@ extern "C" int lcr_netvlad_forward(const float* feats, const int64_t* seg_len_ho
     }
     N += seg_len_host[s];
   }
-  size_t need = 0;
-  lcr_netvlad_ws_bytes(N, S, &need);
-  if (need > ws_bytes) {
-    set_error("lcr_netvlad_forward: workspace too small (%zu < %zu)", ws_bytes, need);
+  const NetvladLayout L = netvlad_layout(ws, N, S);
+  if (L.bytes > ws_bytes) {
+    set_error("lcr_netvlad_forward: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
     return LCR_ESPACE;
   }
-  Carver c(ws, ws_bytes);
-  float* xn = c.take<float>(static_cast<size_t>(N) * NV_F);
-  float* act = c.take<float>(static_cast<size_t>(N) * NV_K);
-  float* V = c.take<float>(static_cast<size_t>(S) * NV_F * NV_K);
-  float* asum = c.take<float>(static_cast<size_t>(S) * NV_K);
-  float* partial = c.take<float>(static_cast<size_t>(NV_SPLIT) * S * NV_D);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float bn_eps = 1e-5f;
   const int nblk = static_cast<int>(std::min<int64_t>((N + 3) / 4, 256 * 16));
-  hipLaunchKernelGGL(k_row_l2norm, dim3(nblk), dim3(256), 0, st, feats, N, NV_F, 1e-12f, xn);
-  int rc = lcr_gemm_f32(xn, wt->cluster_weights, act, N, NV_K, NV_F, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+  hipLaunchKernelGGL(k_row_l2norm, dim3(nblk), dim3(256), 0, st, feats, N, NV_F, 1e-12f, L.xn);
+  int rc = lcr_gemm_f32(L.xn, wt->cluster_weights, L.act, N, NV_K, NV_F, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_bn_softmax64, dim3(nblk), dim3(256), 0, st, act, N, BnParams{wt->bn1_w, wt->bn1_b, wt->bn1_mean, wt->bn1_var}, bn_eps);
+  hipLaunchKernelGGL(k_bn_softmax64, dim3(nblk), dim3(256), 0, st, L.act, N, BnParams{wt->bn1_w, wt->bn1_b, wt->bn1_mean, wt->bn1_var}, bn_eps);
   // V_s (1024 x 64) = xn_s^T (1024 x n_s) · act_s (n_s x 64) for all scans, 64 scans per launch: A is stored K-major -> transA
   for (int s0 = 0; s0 < S; s0 += 64) {
     const int cnt = std::min(64, S - s0);
@@ -280,14 +282,14 @@ extern "C" int lcr_netvlad_forward(const float* feats, const int64_t* seg_len_ho
       r0 += n;
     }
     seg.off[cnt] = r0;
-    rc = lcr_gemm_f32_batched_ta(xn, act, V, NV_F, NV_K, cnt, kk, ao, bo, co, stream);
+    rc = lcr_gemm_f32_batched_ta(L.xn, L.act, L.V, NV_F, NV_K, cnt, kk, ao, bo, co, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_colsum64, dim3(cnt), dim3(1024), 0, st, act, seg, asum + s0 * NV_K);
+    hipLaunchKernelGGL(k_colsum64, dim3(cnt), dim3(1024), 0, st, L.act, seg, L.asum + s0 * NV_K);
   }
-  hipLaunchKernelGGL(k_vlad_finalize, dim3(S), dim3(1024), 0, st, V, asum, wt->cluster_weights2);
+  hipLaunchKernelGGL(k_vlad_finalize, dim3(S), dim3(1024), 0, st, L.V, L.asum, wt->cluster_weights2);
   for (int s0 = 0; s0 < S; s0 += 8)
-    hipLaunchKernelGGL((k_hidden_splitk<8>), dim3(NV_SPLIT), dim3(NV_D), 0, st, V, wt->hidden1_weights, S, s0, partial);
-  hipLaunchKernelGGL(k_netvlad_tail, dim3(S), dim3(NV_D), 0, st, partial, S, BnParams{wt->bn2_w, wt->bn2_b, wt->bn2_mean, wt->bn2_var},
+    hipLaunchKernelGGL((k_hidden_splitk<8>), dim3(NV_SPLIT), dim3(NV_D), 0, st, L.V, wt->hidden1_weights, S, s0, L.partial);
+  hipLaunchKernelGGL(k_netvlad_tail, dim3(S), dim3(NV_D), 0, st, L.partial, S, BnParams{wt->bn2_w, wt->bn2_b, wt->bn2_mean, wt->bn2_var},
                      wt->gating_weights, BnParams{wt->gbn_w, wt->gbn_b, wt->gbn_mean, wt->gbn_var}, bn_eps, out);
   return check_launch("lcr_netvlad_forward");
 }

@@ -40,14 +40,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ double nadd(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ double nmul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 __global__ void k_normals_init(NormClouds C, int64_t* __restrict__ len) {
   for (int b = threadIdx.x; b < C.B; b += blockDim.x) len[b] = C.off[b + 1] - C.off[b];
@@ -206,33 +198,33 @@ __global__ __launch_bounds__(NRM_WAVES * 64) void k_normals_cov(NormClouds C, co
       const float4 p = ord[e];
       const double d[3] = {static_cast<double>(p.x) - static_cast<double>(qx), static_cast<double>(p.y) - static_cast<double>(qy),
                            static_cast<double>(p.z) - static_cast<double>(qz)};
-      m[0] = nadd(m[0], d[0]);
-      m[1] = nadd(m[1], d[1]);
-      m[2] = nadd(m[2], d[2]);
-      m[3] = nadd(m[3], nmul(d[0], d[0]));
-      m[4] = nadd(m[4], nmul(d[0], d[1]));
-      m[5] = nadd(m[5], nmul(d[0], d[2]));
-      m[6] = nadd(m[6], nmul(d[1], d[1]));
-      m[7] = nadd(m[7], nmul(d[1], d[2]));
-      m[8] = nadd(m[8], nmul(d[2], d[2]));
+      m[0] = dadd(m[0], d[0]);
+      m[1] = dadd(m[1], d[1]);
+      m[2] = dadd(m[2], d[2]);
+      m[3] = dadd(m[3], dmul(d[0], d[0]));
+      m[4] = dadd(m[4], dmul(d[0], d[1]));
+      m[5] = dadd(m[5], dmul(d[0], d[2]));
+      m[6] = dadd(m[6], dmul(d[1], d[1]));
+      m[7] = dadd(m[7], dmul(d[1], d[2]));
+      m[8] = dadd(m[8], dmul(d[2], d[2]));
     }
   }
 #pragma unroll
   for (int j = 0; j < 9; ++j)
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m[j] = nadd(m[j], __shfl_xor(m[j], d));
+    for (int d = 32; d >= 1; d >>= 1) m[j] = dadd(m[j], __shfl_xor(m[j], d));
   if (lane == 0) {
     cnt_out[i] = k;
     double* o = cov + 6 * i;
     if (k > 0) {
       const double kk = static_cast<double>(k);
       const double mu[3] = {m[0] / kk, m[1] / kk, m[2] / kk};
-      o[0] = m[3] / kk - nmul(mu[0], mu[0]);
-      o[1] = m[4] / kk - nmul(mu[0], mu[1]);
-      o[2] = m[5] / kk - nmul(mu[0], mu[2]);
-      o[3] = m[6] / kk - nmul(mu[1], mu[1]);
-      o[4] = m[7] / kk - nmul(mu[1], mu[2]);
-      o[5] = m[8] / kk - nmul(mu[2], mu[2]);
+      o[0] = m[3] / kk - dmul(mu[0], mu[0]);
+      o[1] = m[4] / kk - dmul(mu[0], mu[1]);
+      o[2] = m[5] / kk - dmul(mu[0], mu[2]);
+      o[3] = m[6] / kk - dmul(mu[1], mu[1]);
+      o[4] = m[7] / kk - dmul(mu[1], mu[2]);
+      o[5] = m[8] / kk - dmul(mu[2], mu[2]);
     } else {
       for (int j = 0; j < 6; ++j) o[j] = 0.0;
     }
@@ -263,12 +255,12 @@ __global__ __launch_bounds__(256) void k_normals_finish(NormClouds C, const floa
         for (int r = 0; r < 3; ++r) v[r] = viewpoint[3 * b + r];
       const double w[3] = {v[0] - static_cast<double>(pts[3 * i]), v[1] - static_cast<double>(pts[3 * i + 1]),
                            v[2] - static_cast<double>(pts[3 * i + 2])};
-      const double dot = nadd(nadd(nmul(n[0], w[0]), nmul(n[1], w[1])), nmul(n[2], w[2]));
+      const double dot = dadd(dadd(dmul(n[0], w[0]), dmul(n[1], w[1])), dmul(n[2], w[2]));
       // dot == 0 (the viewpoint in the tangent plane): the first non-zero component of n is made positive
       const double lead = n[0] != 0.0 ? n[0] : (n[1] != 0.0 ? n[1] : n[2]);
       if (dot < 0.0 || (dot == 0.0 && lead < 0.0))
         for (int r = 0; r < 3; ++r) n[r] = -n[r];
-      curv = lam[0] / nadd(nadd(lam[0], lam[1]), lam[2]);
+      curv = lam[0] / dadd(dadd(lam[0], lam[1]), lam[2]);
     }
   }
   for (int r = 0; r < 3; ++r) normals[3 * i + r] = static_cast<float>(n[r]);

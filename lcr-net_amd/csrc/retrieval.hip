@@ -163,13 +163,23 @@ using namespace lcr;
 extern "C" int lcr_gemm_f32(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const float* bias,
                             const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, void* stream);
 
+struct RetrievalLayout {   // dots [min(Q, RT_ROWS), C]: one block of products; qn [Q], dn [C]: squared norms of queries / database rows
+  float *dots, *qn, *dn;
+  size_t bytes;
+};
+static RetrievalLayout retrieval_layout(void* ws, int64_t Q, int64_t C) {
+  RetrievalLayout L;
+  Carver c(ws, ~size_t(0));
+  L.dots = c.take<float>(static_cast<size_t>(std::max<int64_t>(std::min<int64_t>(Q, RT_ROWS) * C, 1)));
+  L.qn = c.take<float>(static_cast<size_t>(std::max<int64_t>(Q, 1)));
+  L.dn = c.take<float>(static_cast<size_t>(std::max<int64_t>(C, 1)));
+  L.bytes = c.off;
+  return L;
+}
+
 extern "C" int lcr_retrieval_ws_bytes(int64_t Q, int64_t C, size_t* bytes) {
   if (!bytes || Q < 0 || C < 0) return LCR_EARG;
-  Carver c(nullptr, ~size_t(0));
-  c.take<float>(static_cast<size_t>(std::max<int64_t>(std::min<int64_t>(Q, RT_ROWS) * C, 1)));   // one block of products
-  c.take<float>(static_cast<size_t>(std::max<int64_t>(Q, 1)));
-  c.take<float>(static_cast<size_t>(std::max<int64_t>(C, 1)));
-  *bytes = c.off;
+  *bytes = retrieval_layout(nullptr, Q, C).bytes;
   return LCR_OK;
 }
 
@@ -184,29 +194,24 @@ extern "C" int lcr_retrieval_topk(const float* queries, int64_t Q, int64_t q0, c
     set_error("lcr_retrieval_topk: more than 2^31-1 database rows");
     return LCR_EARG;
   }
-  size_t need = 0;
-  lcr_retrieval_ws_bytes(Q, C, &need);
-  if (need > ws_bytes) {
-    set_error("lcr_retrieval_topk: workspace too small (%zu < %zu)", ws_bytes, need);
+  const RetrievalLayout L = retrieval_layout(ws, Q, C);
+  if (L.bytes > ws_bytes) {
+    set_error("lcr_retrieval_topk: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
     return LCR_ESPACE;
   }
   if (Q == 0) return LCR_OK;
-  Carver c(ws, ws_bytes);
-  float* dots = c.take<float>(static_cast<size_t>(std::min<int64_t>(Q, RT_ROWS) * C));
-  float* qn = c.take<float>(static_cast<size_t>(Q));
-  float* dn = c.take<float>(static_cast<size_t>(C));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_row_sqnorm, dim3(static_cast<int>(std::min<int64_t>((Q + 3) / 4, 4096))), dim3(256), 0, st, queries, Q, D, qn);
-  hipLaunchKernelGGL(k_row_sqnorm, dim3(static_cast<int>(std::min<int64_t>((C + 3) / 4, 4096))), dim3(256), 0, st, database, C, D, dn);
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(static_cast<int>(std::min<int64_t>((Q + 3) / 4, 4096))), dim3(256), 0, st, queries, Q, D, L.qn);
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(static_cast<int>(std::min<int64_t>((C + 3) / 4, 4096))), dim3(256), 0, st, database, C, D, L.dn);
   for (int64_t r0 = 0; r0 < Q; r0 += RT_ROWS) {
     const int64_t rows = std::min<int64_t>(RT_ROWS, Q - r0);
     // columns the block's last row may see (the window is causal: earlier rows see fewer; every row masks by its own bound)
     const int64_t nb = std::max<int64_t>(0, std::min<int64_t>(C, q0 + r0 + rows - 1 - exclude));
     if (nb > 0) {
-      int rc = lcr_gemm_f32(queries + r0 * D, database, dots, rows, static_cast<int>(nb), D, 0, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+      int rc = lcr_gemm_f32(queries + r0 * D, database, L.dots, rows, static_cast<int>(nb), D, 0, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_row_topk, dim3(static_cast<int>(rows)), dim3(TK_T), 0, st, dots, nb, qn + r0, dn, q0 + r0, exclude, nb, k, out_idx + r0 * k,
+    hipLaunchKernelGGL(k_row_topk, dim3(static_cast<int>(rows)), dim3(TK_T), 0, st, L.dots, nb, L.qn + r0, L.dn, q0 + r0, exclude, nb, k, out_idx + r0 * k,
                        out_d2 + r0 * k);
   }
   return check_launch("lcr_retrieval_topk");

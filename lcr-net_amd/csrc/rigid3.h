@@ -1,4 +1,4 @@
-// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (pose_tail.hip) and the RANSAC hypotheses (ransac.hip), and the
+// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (lgr.hip) and the RANSAC hypotheses (ransac.hip), and the
 // fp64 symmetric 3x3 eigen-solver of the surface normals (normals.hip).
 #pragma once
 #include <hip/hip_runtime.h>

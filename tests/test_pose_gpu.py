@@ -68,6 +68,24 @@ def test_point_to_node_partition():
     assert (p2n.cpu().long() == wp2n).float().mean().item() > 0.999
     assert torch.equal(nm.cpu(), wnm)
     assert (knn.cpu() == wknn).float().mean().item() > 0.998 and (km.cpu() == wkm).float().mean().item() > 0.999   # exact-up-to-fp64-near-ties is asserted on the reference's own nodes in test_pose_chain_gpu.py (stage D1)
+    # a few hundred points on 7 nodes, one of which owns no point, and more columns than the largest membership: the padding (knn = N,
+    # mask 0) and node_mask == 0.  Coordinates are multiples of 1/8 below 64, so every product and sum of the distance is exact in fp32 in
+    # the kernel and in the restatement alike, and points at equal distance from their node are dropped: the comparison is exact.
+    centres = torch.tensor([[0.0, 0, 0], [10, 0, 0], [0, 10, 0], [0, 0, 10], [10, 10, 0], [50, 50, 50], [10, 0, 10]])
+    own = torch.tensor([0, 1, 2, 3, 4, 6]).repeat_interleave(torch.tensor([90, 31, 64, 1, 77, 40]))      # node 5 owns nobody
+    off = torch.round(torch.randn(len(own), 3, generator=g) * 8) / 8
+    d2 = (off ** 2).sum(1)
+    first = [i for i in range(len(own)) if not ((own[:i] == own[i]) & (d2[:i] == d2[i])).any()]
+    few = (centres[own] + off)[first]
+    few = few[torch.randperm(len(few), generator=g)]
+    assert len(few) > 200
+    K = 128
+    wp2n, wnm, wknn, wkm = torch_ref.point_to_node_partition(few, centres, K)
+    assert wkm.sum(1).max().item() < K and not wnm[5] and wnm.sum().item() == 6
+    p2n, nm, knn, km = F.point_to_node_partition(few.cuda(), centres.cuda(), K)
+    assert torch.equal(p2n.cpu().long(), wp2n.long()) and torch.equal(nm.cpu(), wnm) and torch.equal(km.cpu(), wkm)
+    assert torch.equal(knn.cpu(), wknn)
+    assert (knn.cpu()[~wkm] == len(few)).all() and not km.cpu()[5].any()
 
 
 def test_point_to_node_partition_of_a_stack_equals_the_per_cloud_calls():
@@ -142,6 +160,75 @@ def test_log_sinkhorn_and_top1_matching():
             assert set(zip(wi.tolist(), wj.tolist())) == set(zip(bij[:, 1].tolist(), bij[:, 2].tolist()))
             assert bij[:, 1].tolist() == wi.tolist()                       # row-major order
             assert (sc.cpu() - ws).abs().max().item() < 1e-4 * ws.abs().max().item() + 1e-6
+
+
+# One problem set per Sinkhorn form of the library (lcr_log_sinkhorn_form: 0 register resident, 1 LDS resident, 2 persistent row slabs,
+# 3 one launch per half-iteration), the smallest shapes that reach each: 8 x 8; just past 132 lines; one problem just past 150 KiB of
+# matrix + vectors; and 33 of those, where the 2 row slabs per problem would need more than the 64 workgroups the persistent form may
+# hold.  "legacy" is lcr_log_sinkhorn on the form-2 problem: its short workspace cannot hold the hand-off buffers, so it runs form 3.
+SINKHORN_FORM_CASES = {"form0": (0, 3, 8, 8), "form1": (1, 2, 132, 131), "form2": (2, 1, 193, 193), "form3": (3, 33, 193, 193),
+                       "legacy": (2, 1, 193, 193)}
+
+
+@pytest.fixture(scope="module")
+def sinkhorn_form_problems():
+    """(raw, row mask, column mask, fp32 oracle, fp64 oracle) per distinct (M, N), computed once at the largest B of the cases that share it
+    (the problems of a set are independent: a case with a smaller B takes the leading ones)."""
+    g = torch.Generator().manual_seed(4)
+    out = {}
+    for _, B, M, N in SINKHORN_FORM_CASES.values():
+        if (M, N) in out and out[(M, N)][0].shape[0] >= B:
+            continue
+        raw = torch.randn(B, M, N, generator=g) * 3
+        rm = torch.rand(B, M, generator=g) > 0.15
+        cm = torch.rand(B, N, generator=g) > 0.15
+        rm[:, 0] = cm[:, 0] = True
+        alpha = torch.tensor(0.7)
+        out[(M, N)] = (raw, rm, cm, torch_ref.log_optimal_transport(raw * 0.5, rm, cm, alpha, iters=100),
+                       torch_ref.log_optimal_transport(raw.double() * 0.5, rm, cm, alpha.double(), iters=100))
+    return out
+
+
+@pytest.mark.parametrize("case", list(SINKHORN_FORM_CASES))
+def test_log_sinkhorn_every_form(case, sinkhorn_form_problems):
+    """Every form of the Sinkhorn plan against the oracles and the tolerances of test_log_sinkhorn_and_top1_matching (1e-4 against the fp32
+    restatement; its loosest bound against fp64, 7e-5, set there for a node-level problem with a wider score spread than these).  The form
+    is asserted first, so a case cannot silently test another kernel if a threshold moves."""
+    import ctypes
+    from lcrnet_amd import _lib
+    from lcrnet_amd import functional as F
+    if os.environ.get("LCR_SINKHORN_COOP") == "0" and case in ("form2", "legacy"):
+        pytest.skip("the persistent form is switched off (LCR_SINKHORN_COOP=0)")
+    form, B, M, N = SINKHORN_FORM_CASES[case]
+    L = _lib.lib()
+    got_form = ctypes.c_int(-1)
+    _lib.check(L.lcr_log_sinkhorn_form(B, M, N, ctypes.byref(got_form)), "lcr_log_sinkhorn_form")
+    assert got_form.value == form, (case, got_form.value)
+    raw, rm, cm, want32, want64 = (t[:B] for t in sinkhorn_form_problems[(M, N)])
+    alpha = torch.tensor(0.7).cuda()
+    if case == "legacy":
+        rm8, cm8 = rm.to(torch.uint8).cuda(), cm.to(torch.uint8).cuda()
+        S = torch.empty((B, M + 1, N + 1), dtype=torch.float32, device="cuda")
+        a1, rawg = alpha.reshape(1).float(), raw.cuda().contiguous()
+        _lib.check(L.lcr_build_padded_scores(_lib.ptr(rawg), _lib.ptr(rm8), _lib.ptr(cm8), B, M, N, 0.5, _lib.ptr(a1), 1e12, _lib.ptr(S),
+                                             _lib.stream_ptr(S.device)), "lcr_build_padded_scores")
+        uv = torch.empty(B * (2 * (M + N + 2) + 1), dtype=torch.float32, device="cuda")      # what the legacy entry documents
+        _lib.check(L.lcr_log_sinkhorn(_lib.ptr(S), _lib.ptr(rm8), _lib.ptr(cm8), B, M, N, 100, 1e12, _lib.ptr(uv), _lib.stream_ptr(S.device)),
+                   "lcr_log_sinkhorn")
+        got = S.cpu()
+    else:
+        got = F.log_optimal_transport(raw.cuda(), rm.cuda(), cm.cuda(), alpha, scale=0.5, iters=100).cpu()
+        F.check_transport_status()
+    valid = torch.ones(B, M + 1, N + 1, dtype=torch.bool)
+    valid[:, :M, :] &= rm[:, :, None]
+    valid[:, :, :N] &= cm[:, None, :]
+    assert torch.isfinite(got).all()
+    e64 = (got.double() - want64)[valid].abs().max().item()
+    e32 = (got - want32)[valid].abs().max().item()
+    floor = (want32.double() - want64)[valid].abs().max().item()
+    print("sinkhorn %s %s: HIP vs fp64 %.2e, vs fp32 torch %.2e (fp32 torch vs fp64 %.2e)" % (case, (B, M, N), e64, e32, floor))
+    assert e64 < 7e-5, (case, e64)
+    assert e32 < 1e-4, (case, e32)
 
 
 # spread -> bound on |HIP - fp64| (scores spread over +-3*spread).  Measured: 2.7e-6 / 1.0e-4 / 5.5e-4 for the HIP kernel and
