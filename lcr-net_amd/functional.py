@@ -457,6 +457,26 @@ def netvlad_forward(feats, seg_len_host, weights_struct):
     return out
 
 
+def gemm_batched_ta(a, b, c, M, N, k, a_off, b_off, c_off):
+    """c[c_off[z] : c_off[z] + M*N] <- A_z^T · B_z for every entry z, in place, where A_z = a[a_off[z]:] read as [k[z], M] and
+    B_z = b[b_off[z]:] as [k[z], N] (lcr_gemm_f32_batched_ta: a, b, c flat fp32 device buffers; k and the ELEMENT offsets are host sequences,
+    at most 64 entries; offsets into a and b and M, N are multiples of 4).  The entry point's own refusals surface as RuntimeError."""
+    _lib.require_cuda(a, b, c)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (a, b, c))
+    kk = np.ascontiguousarray(k, dtype=np.int32)
+    ao, bo, co = (np.ascontiguousarray(v, dtype=np.int64) for v in (a_off, b_off, c_off))
+    count = int(kk.shape[0])
+    assert ao.shape == bo.shape == co.shape == (count,)
+    for i in range(count):                                  # nothing outside the three buffers is addressed, whatever the entry point accepts
+        assert 0 <= ao[i] and ao[i] + max(int(kk[i]), 0) * M <= a.numel(), "A entry out of range"
+        assert 0 <= bo[i] and bo[i] + max(int(kk[i]), 0) * N <= b.numel(), "B entry out of range"
+        assert 0 <= co[i] and co[i] + M * N <= c.numel(), "C entry out of range"
+    _lib.check(_lib.lib().lcr_gemm_f32_batched_ta(_lib.ptr(a), _lib.ptr(b), _lib.ptr(c), int(M), int(N), count, ctypes.c_void_p(kk.ctypes.data),
+                                                  ctypes.c_void_p(ao.ctypes.data), ctypes.c_void_p(bo.ctypes.data),
+                                                  ctypes.c_void_p(co.ctypes.data), _lib.stream_ptr(a.device)), "lcr_gemm_f32_batched_ta")
+    return c
+
+
 def linear(x, weight, bias=None, relu=False):
     """nn.Linear (weight [out,in]) on the MFMA GEMM, optional ReLU."""
     y = gemm(x.contiguous(), weight, trans_b=True, bias=bias)[0]
