@@ -249,14 +249,21 @@ __device__ __forceinline__ void gemm_epilogue(floatx16 (&acc)[NT], float* __rest
   // the fp32 sums of its 16 values per column in LDS, one thread per column folds the 2*WM row slices in fp64, the gs lanes of
   // a group are folded with shuffles in the BN/64 wavefronts that hold the columns, and the workgroup issues one pair of
   // global fp64 atomics per group into the statistics replica (row block % GN_REPLICAS).  (A version with fp64 shuffles in
-  // every wavefront + LDS fp64 atomics cost 8-9 us per unary GEMM.)  Slow path (a segment boundary inside the tile): per
-  // wavefront, per segment present in its 32 rows, straight to global memory.
+  // every wavefront + LDS fp64 atomics cost 8-9 us per unary GEMM.)  Slow path (a segment boundary inside the tile, or a segment
+  // of fewer than GN_EXACT_ROWS rows): per wavefront, per segment present in its 32 rows, straight to global memory.
+  // The fp32 partials cost sum x^2 / n - mean^2 a relative 1e-7 (|mean| / std)^2, and fp64 atomics of fp32 values add exactly, so the
+  // table does not depend on the order in which the wavefronts arrive.  A group of a few values can have next to no variance, and
+  // there the rounding of x^2 to fp32 was all that was left of it: segments of fewer than GN_EXACT_ROWS rows (groups of <= 32
+  // columns) are summed in fp64 from the first addition.  Such a segment meets at most two wavefronts per column block, two
+  // atomics per table entry, and a + b = b + a: still independent of the order.
   if (want_stats) {
     __shared__ float s_part[2][2 * WM][BN];
     double* rep = ep.stats + static_cast<int64_t>(m_tile % GN_REPLICAS) * ep.S * ep.groups * 2;
     int64_t seg_start = blk_seg_start, seg_end = blk_seg_end;
     const int64_t blk_last_row = min(m0 + BM - 1, M - 1);
-    const bool uniform = blk_last_row < seg_end;      // block-uniform
+    constexpr int GN_EXACT_ROWS = 32;
+    auto exact_segment = [&](int64_t rows) { return rows < GN_EXACT_ROWS && gs <= 32; };      // the one rule for "summed in fp64"; wave-uniform
+    const bool uniform = blk_last_row < seg_end && !exact_segment(seg_end - seg_start);       // block-uniform
     if (uniform) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
@@ -304,15 +311,31 @@ __device__ __forceinline__ void gemm_epilogue(floatx16 (&acc)[NT], float* __rest
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
           const int col = n0 + wn * (32 * NT) + j * 32 + (lane & 31);
-          float s = 0.f, ss = 0.f;
+          double ds, dss;
+          if (exact_segment(seg_end - seg_start)) {
+            ds = dss = 0.0;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int64_t row = wrow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const float v = (whole || (row >= seg_start && row < seg_end)) ? acc[j][r] : 0.f;
-            s += v;
-            ss = fmaf(v, v, ss);
+            for (int r = 0; r < 16; ++r) {
+              const int64_t row = wrow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+              float vf = (row >= seg_start && row < seg_end) ? acc[j][r] : 0.f;
+              // converted here, one at a time.  Without the barrier the sixteen conversions are hoisted out of the segment loop and held
+              // as doubles: the light-form kernels (cap 80 registers) then spill 8-12 bytes to scratch; with it they need no more than before.
+              asm volatile("" : "+v"(vf));
+              const double v = vf;
+              ds += v;
+              dss = fma(v, v, dss);
+            }
+          } else {
+            float s = 0.f, ss = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int64_t row = wrow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+              const float v = (whole || (row >= seg_start && row < seg_end)) ? acc[j][r] : 0.f;
+              s += v;
+              ss = fmaf(v, v, ss);
+            }
+            ds = s, dss = ss;
           }
-          double ds = s, dss = ss;
           // fold the two row-halves, then the lanes of one group (gs consecutive columns, capped at the 32-column tile)
           ds += __shfl_xor(ds, 32);
           dss += __shfl_xor(dss, 32);

@@ -7,6 +7,9 @@
 //     y = act( GN(x) [+ res | + GN_res(res)] ),   act = LeakyReLU(slope) or identity,
 // which covers UnaryBlock / ConvBlock (modules.py:78-84, 140-145) and the tail of ResidualBlock (:207-225) in one pass.
 // Optionally emits pos[n] = (sum_c y[n][c] > 0), the flag KPConv's neighbour count is built from (kpconv.py:113-114).
+// GN(x) is evaluated in the centred form (x - mean) * (rstd * gamma) + beta with the mean carried as two floats.  The scale / shift
+// form x * a + (beta - mean * a) rounds at the size of mean * a, and that is the whole answer where a group's variance is small
+// against its mean: a one-row segment with one channel per group has variance 0, a = gamma / sqrt(eps) ~ 316 gamma and y = beta.
 #include <algorithm>
 
 #include <type_traits>
@@ -44,9 +47,13 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
                                                   float eps, float slope, int act, uint8_t* __restrict__ pos) {
   // Every workgroup owns a CONTIGUOUS range of rows, so it touches one segment (two or three at scan boundaries) and only
   // folds the statistics replicas of those: (mean, rstd) per (segment, group) of the range, finalised in fp64 once per block.
-  extern __shared__ __attribute__((aligned(16))) float2 s_tab[];   // [2][S * groups]: sized by the launch, 4 KB for 8 scans
+  // LDS table, sized by the launch (6 KB for 8 scans): [2][S * groups] (mean, rstd), then [2][S * groups] floats — what each mean lost
+  // when it was rounded to fp32
+  extern __shared__ __attribute__((aligned(16))) float2 s_tab[];
   float2* s_x = s_tab;
   float2* s_r = s_tab + S * groups;
+  float* s_xl = reinterpret_cast<float*>(s_tab + 2 * S * groups);
+  float* s_rl = s_xl + S * groups;
   __shared__ int64_t s_start[GN_MAX_SEG + 1];       // first row of every segment (prefix of seg_len)
   const int gs = C / groups;
   const int c4n = C >> 2;                           // float4 pieces per row
@@ -84,10 +91,12 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
     const double m = sx / cnt;
     const double var = fmax(sxx / cnt - m * m, 0.0);
     s_x[i] = make_float2(static_cast<float>(m), static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps))));
+    s_xl[i] = static_cast<float>(m - static_cast<double>(static_cast<float>(m)));
     if (RM == 2) {
       const double rm = rx / cnt;
       const double rv = fmax(rxx / cnt - rm * rm, 0.0);
       s_r[i] = make_float2(static_cast<float>(rm), static_cast<float>(1.0 / sqrt(rv + static_cast<double>(eps))));
+      s_rl[i] = static_cast<float>(rm - static_cast<double>(static_cast<float>(rm)));
     }
   }
   __syncthreads();
@@ -109,7 +118,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
   }
   const int64_t t_end = ((t_hi - t_lo + 63) & ~int64_t(63)) + t_lo;
   // FAST (block-uniform; every block of this model except the B - 1 that straddle a scan boundary): one segment in the range, C / 4 and the
-  // group size powers of two, fixed channel offset — the row is a shift of the element index, and the thread's four (mean, rstd) pairs sit in
+  // group size powers of two, fixed channel offset — the row is a shift of the element index, and the thread's four (scale, mean, shift) triples sit in
   // registers.  The general form spends ~170 VALU instructions per 16-B element on a 64-bit division (row = t / (C/4)), four 32-bit
   // divisions (group = channel / gs), the segment walk and eight LDS reads (PMC: 97 M of a step's 601 M VALU instructions for 2 % of its
   // flops); the arithmetic on the values is the same in both forms, operation for operation.
@@ -119,20 +128,24 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
   auto run = [&](auto fast_c) {
     constexpr bool FAST = decltype(fast_c)::value;
     float2 mx[4], mrs[4];
+    float bx[4], brs[4];
     if (FAST) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {                  // (scale, shift) of this thread's four channels
+      for (int u = 0; u < 4; ++u) {                  // (scale, mean) and the shift of this thread's four channels
         const int gi = (c0_f + u) >> shg;
         const float g = u == 0 ? gam_f.x : u == 1 ? gam_f.y : u == 2 ? gam_f.z : gam_f.w, b = u == 0 ? bet_f.x : u == 1 ? bet_f.y : u == 2 ? bet_f.z : bet_f.w;
         const float2 mr = s_x[gi];
         const float a = mr.y * g;
-        mx[u] = make_float2(a, fmaf(-mr.x, a, b));
+        mx[u] = make_float2(a, mr.x);
+        bx[u] = fmaf(-s_xl[gi], a, b);
         mrs[u] = make_float2(1.f, 0.f);
+        brs[u] = 0.f;
         if (RM == 2) {
           const float rg = u == 0 ? rgam_f.x : u == 1 ? rgam_f.y : u == 2 ? rgam_f.z : rgam_f.w, rbv = u == 0 ? rbet_f.x : u == 1 ? rbet_f.y : u == 2 ? rbet_f.z : rbet_f.w;
           const float2 rr = s_r[gi];
           const float a2 = rr.y * rg;
-          mrs[u] = make_float2(a2, fmaf(-rr.x, a2, rbv));
+          mrs[u] = make_float2(a2, rr.x);
+          brs[u] = fmaf(-s_rl[gi], a2, rbv);
         }
       }
     }
@@ -186,25 +199,27 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
         float rowsum = 0.f;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          // y = x * (rstd * gamma) + (beta - mean * rstd * gamma): the scale / shift form of lcr_gemm_f32_anorm's table (and of torch's
-          // own GroupNorm kernels); FAST: the thread's four (scale, shift) pairs are loop constants
-          float xa, xb, ra = 1.f, rb = 0.f;
+          // y = (x - mean_hi) * (rstd * gamma) + (beta - mean_lo * rstd * gamma): centred, so nothing of the size of mean * rstd * gamma is
+          // ever rounded; FAST: the thread's four (scale, mean_hi, shift) triples are loop constants
+          float xa, xm, xb, ra = 1.f, rm = 0.f, rb = 0.f;
           if (FAST) {
-            xa = mx[u].x, xb = mx[u].y;
-            ra = mrs[u].x, rb = mrs[u].y;
+            xa = mx[u].x, xm = mx[u].y, xb = bx[u];
+            ra = mrs[u].x, rm = mrs[u].y, rb = brs[u];
           } else {
             const int gi = (s - seg_lo) * groups + (c0 + u) / gs;
             const float2 mr = s_x[gi];
             xa = mr.y * g4[u];
-            xb = fmaf(-mr.x, xa, b4[u]);
+            xm = mr.x;
+            xb = fmaf(-s_xl[gi], xa, b4[u]);
             if (RM == 2) {
               const float2 rr = s_r[gi];
               ra = rr.y * rg4[u];
-              rb = fmaf(-rr.x, ra, rb4[u]);
+              rm = rr.x;
+              rb = fmaf(-s_rl[gi], ra, rb4[u]);
             }
           }
-          float v = fmaf(xin[u], xa, xb);
-          if (RM == 2) v += fmaf(rin[u], ra, rb);
+          float v = fmaf(xin[u] - xm, xa, xb);
+          if (RM == 2) v += fmaf(rin[u] - rm, ra, rb);
           else if (RM == 1) v += rin[u];
           if (act) v = v > 0.f ? v : v * slope;
           out[u] = v;
@@ -225,7 +240,14 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
 
 // plain segmented statistics for tensors that do not come out of lcr_gemm_f32 (e.g. the fused C_in = 1 KPConv):
 // a wavefront walks 64 consecutive rows with lanes = channels (coalesced rows), folds the lanes of a group and issues one
-// pair of fp64 atomics per (segment, group, wavefront).
+// pair of fp64 atomics per (segment, group, wavefront).  Two sets of sums run side by side and the segment's length picks one:
+//   * >= 64 rows: fp32 partials over the wavefront's rows.  fp64 atomics of fp32 values add exactly, so the table does not depend on the order
+//     in which the wavefronts arrive; sum x^2 / n - mean^2 pays a relative 1e-7 (|mean| / std)^2 for the partials, over >= 64 values a group;
+//   * shorter, with groups of at most 64 channels: fp64 from the first addition (the square of an fp32 value is exact in fp64).  A group of
+//     one or two values can have next to no variance, and the rounding of x^2 to fp32 was all that was left of it.  Such a segment reaches
+//     at most two wavefronts, each with one atomic per table entry, and a + b = b + a: the table stays independent of their order here
+//     too.  (A wider group takes one atomic per 64-channel slice, more than two inexact addends; it holds >= 128 values and keeps the
+//     fp32 partials.)
 __global__ __launch_bounds__(256) void k_gn_stats(const float* __restrict__ x, int64_t N, int C, int groups, const int64_t* __restrict__ seg_len,
                                                   int S, double* __restrict__ stats) {
   const int gs = C / groups;
@@ -236,12 +258,14 @@ __global__ __launch_bounds__(256) void k_gn_stats(const float* __restrict__ x, i
   for (int c0 = 0; c0 < C; c0 += 64) {
     const int c = c0 + lane;
     float s = 0.f, ss = 0.f;
+    double s64 = 0.0, ss64 = 0.0;
     int64_t slen;
     int cur = seg_of(seg_len, S, r0, &slen);
     int64_t seg_end = 0;
     for (int i = 0; i <= cur; ++i) seg_end += seg_len[i];
     auto flush = [&](int sg) {
-      double ds = s, dss = ss;
+      const bool exact = seg_len[sg] < 64 && gs <= 64;        // wave-uniform
+      double ds = exact ? s64 : static_cast<double>(s), dss = exact ? ss64 : static_cast<double>(ss);
       const int span = gs < 64 ? gs : 64;
       for (int d = 1; d < span; d <<= 1) {
         ds += __shfl_xor(ds, d);
@@ -253,6 +277,7 @@ __global__ __launch_bounds__(256) void k_gn_stats(const float* __restrict__ x, i
         atomicAdd(&rep[(static_cast<int64_t>(sg) * groups + c / gs) * 2 + 1], dss);
       }
       s = ss = 0.f;
+      s64 = ss64 = 0.0;
     };
     constexpr int RB = 8;                       // rows requested per trip (clamped addresses, masked afterwards: branch-free loads)
     const int cc = c < C ? c : C - 1;
@@ -275,6 +300,9 @@ __global__ __launch_bounds__(256) void k_gn_stats(const float* __restrict__ x, i
           const float v = c < C ? vv[u] : 0.f;
           s += v;
           ss = fmaf(v, v, ss);
+          const double v64 = v;
+          s64 += v64;
+          ss64 = fma(v64, v64, ss64);
         }
       }
     }
@@ -310,7 +338,7 @@ extern "C" int lcr_groupnorm_apply(const float* x, const double* stats, const fl
   }
   // contiguous row ranges per workgroup, >= 2048 float4 pieces each (the per-block statistics fold is amortised over them)
   const int nblk = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((N * c4n + 2047) / 2048, 256 * 8)));
-  const size_t tab_bytes = sizeof(float2) * 2 * static_cast<size_t>(S) * groups;
+  const size_t tab_bytes = (sizeof(float2) + sizeof(float)) * 2 * static_cast<size_t>(S) * groups;
   const int rm = res ? (res_stats ? 2 : 1) : 0;
   act = (act & 255) | (g_gn_force_general ? 256 : 0);
 #define LCR_GN(P, R)                                                                                                                       \
@@ -332,6 +360,11 @@ extern "C" int lcr_groupnorm_apply(const float* x, const double* stats, const fl
 extern "C" int lcr_groupnorm_stats(const float* x, int64_t N, int C, int groups, const int64_t* seg_len, int S, double* stats, void* stream) {
   if (!x || !stats || !seg_len || N < 0 || C < 1 || groups < 1 || C % groups != 0 || S < 1) {
     set_error("lcr_groupnorm_stats: bad argument");
+    return LCR_EARG;
+  }
+  const int gs = C / groups;
+  if ((gs & (gs - 1)) != 0) {               // k_gn_stats folds the lanes of a group with xor shuffles, like the GEMM epilogues
+    set_error("lcr_groupnorm_stats: channels per group must be a power of two");
     return LCR_EARG;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
