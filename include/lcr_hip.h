@@ -668,6 +668,39 @@ int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes);
 int lcr_feature_correspondences(const int32_t* nn_sr, const int32_t* src_start, const int32_t* nn_rs, const int32_t* ref_start, int S, int min_rows,
                                 int32_t* corr, int32_t* start, int32_t* mutual_used, void* ws, size_t ws_bytes, void* stream);
 
+/* Ground-truth node correspondences (patch overlaps) under the ground-truth transform, for P pairs in one call: the labels behind the
+ * coarse-matching metrics (reference: modules/registration/matching.py:252-349, one pair at a time in torch).
+ *   - Inputs: what lcr_point_to_node_partition_stack emits for the 2P clouds [pos_0, anc_0, pos_1, anc_1, ...]: points f32[sum N,3] with
+ *     HOST point_off i64[2P+1], nodes f32[sum M,3] with HOST node_off i64[2P+1] (rows point_off[c] .. of points and node_off[c] .. of
+ *     nodes belong to cloud c; knn and the masks start at the first cloud's first node), knn i64[sum M,K] cloud-local, knn_mask
+ *     u8[sum M,K], node_mask u8[sum M]; transforms f32[P,16] on the device, row-major 4x4, anc (src) onto pos (ref).  The node centres
+ *     are not read: the definition has no use for them.
+ *   - A patch entry (node, k) is valid iff node_mask[node] and knn_mask[node,k] are set and 0 <= knn[node,k] < the cloud's point count.
+ *   - r2 = (float)(pos_radius * pos_radius).  Each anc point (x, y, z) is moved once: q' = ((R0*x + R1*y) + R2*z) + t per component
+ *     (R0 R1 R2 t = that row of the 4x4), every operation fp32 and rounded, no contraction.
+ *   - A point pair (p of the ref patch, q' of the src patch) is NEAR iff ((dx*dx + dy*dy) + dz*dz) < r2 with d = p - q', fp32, every
+ *     operation rounded, the comparison strict.  A non-finite coordinate is therefore never near.
+ *   - For ref node i (pos) and src node j (anc): cr = valid points of patch i near at least one valid point of patch j, cs = the converse,
+ *     nr / ns = the valid counts.  (i, j) is a correspondence iff cr > 0 (equivalently cs > 0);
+ *     overlap = ((float)cr / (float)nr + (float)cs / (float)ns) / 2 with IEEE fp32 divisions.  A node without a valid point never appears.
+ *   - The reference's enclosing-sphere screen (matching.py:311-321) is NOT part of the definition; the screen used here (axis-aligned boxes
+ *     of the valid finite points, tested with a radius whose rounded square is >= r2) cannot drop a near pair.  The reference decides
+ *     nearness on |x|^2 - 2 x.y + |y|^2, whose rounding at 80 m coordinates is of the order of r2's last digits: DESIGN.md section 8.
+ *   - Outputs: corr i32[cap,2] pair-local (ref node, src node), row-major within a pair, pairs in order; overlap f32[cap]; start i32[P+1],
+ *     the exclusive scan of the pairs' counts; status u32[1], written (not or-ed): LCR_STATUS_CAP_EXCEEDED iff start[P] > cap, else 0.
+ *     start always holds the true counts; rows at or beyond cap are not written.  cap = sum M_p * N_p can never overflow.
+ *   - Stream-ordered launches only (six and a scan), no host synchronisation, no allocation, no atomics; ordered compaction by wavefront
+ *     ballot and prefix.  A pair gives the same bytes alone or in any batch.
+ * Domain: 1 <= P <= 32, 1 <= K <= 2048, non-decreasing offsets, at most 2^31-1 points, nodes and sum M_p * N_p, cap >= 0, pos_radius >= 0
+ * with a finite fp32 square; empty clouds and empty node lists are legal and give zero rows.  LCR_EARG outside.  The partition itself
+ * takes any K >= 1; a patch wider than 2048 points does not fit the wavefront's LDS. */
+#define LCR_STATUS_CAP_EXCEEDED 4u
+int lcr_node_correspondences_ws_bytes(const int64_t* point_off, const int64_t* node_off, int P, int K, size_t* bytes);
+int lcr_node_correspondences(const float* points, const int64_t* point_off, const float* nodes, const int64_t* node_off, const int64_t* knn,
+                             const uint8_t* knn_mask, const uint8_t* node_mask, const float* transforms, int P, int K, double pos_radius,
+                             int64_t cap, int32_t* corr, float* overlap, int32_t* start, uint32_t* status, void* ws, size_t ws_bytes,
+                             void* stream);
+
 /* Point-to-point ICP (Open3D's RegistrationICP with TransformationEstimationPointToPoint(with_scaling=False), as the reference's pair
  * generators run it: data/Kitti/generate_kitti_pairs.py:145-147) for S pairs in one call, made exact and batch-invariant.
  *   - Pairs: source rows stacked pair-major in src f32[ns,3], target rows in tgt f32[nt,3]; src_len / tgt_len are HOST int64[S].

@@ -128,6 +128,9 @@ _SIGS = {
     "lcr_feature_nn": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_feature_correspondences_ws_bytes": (c_int, [c_int, c_size_p]),
     "lcr_feature_correspondences": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_node_correspondences_ws_bytes": (c_int, [c_vp, c_vp, c_int, c_int, c_size_p]),
+    "lcr_node_correspondences": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_icp_ws_bytes": (c_int, [c_int, c_i64, c_i64, c_size_p]),
     "lcr_icp_point_to_point": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_float, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_vp, c_int, c_vp, ctypes.c_size_t, c_vp]),

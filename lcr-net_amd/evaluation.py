@@ -189,3 +189,54 @@ def fine_matching_metrics(ref_corr_points, src_corr_points, transform, acceptanc
     return {"IR": ir, "IR@0.3": inlier_ratio(ref_corr_points, src_corr_points, transform, 0.3),
             "IR@0.1": inlier_ratio(ref_corr_points, src_corr_points, transform, 0.1), "FMR": float(ir >= inlier_ratio_threshold),
             "num_corr": int(np.asarray(ref_corr_points).shape[0])}
+
+
+# ---- coarse-matching metrics of experiments/registration/eval.py:117-133, 249-255 (utils/utils/registration.py:319-347, 196-202) ---------
+def coarse_matching_metrics(ref_nodes, src_nodes, ref_corr_indices, src_corr_indices, gt_corr_indices):
+    """One pair's precision / recall / hit_ratio of the predicted node correspondences against the ground-truth ones
+    (evaluate_sparse_correspondences): both lists become 0/1 matrices over (ref nodes, src nodes), so duplicate rows count once;
+    precision = hits / (predicted + 1e-12), recall = hits / (ground truth + 1e-12), hit_ratio = the mean of the shares of ground-truth
+    ref rows and src columns that hold a hit, each with the same 1e-12 in the denominator."""
+    gt_idx = np.asarray(gt_corr_indices).reshape(-1, 2).astype(np.int64)
+    gt = np.zeros((np.asarray(ref_nodes).shape[0], np.asarray(src_nodes).shape[0]))
+    gt[gt_idx[:, 0], gt_idx[:, 1]] = 1.0
+    pred = np.zeros_like(gt)
+    pred[np.asarray(ref_corr_indices).astype(np.int64), np.asarray(src_corr_indices).astype(np.int64)] = 1.0
+    hit = gt * pred
+    precision = hit.sum() / (pred.sum() + 1e-12)
+    recall = hit.sum() / (gt.sum() + 1e-12)
+    hit, gt = hit > 0, gt > 0
+    ref_hits = np.any(hit, axis=1).sum() / (np.any(gt, axis=1).sum() + 1e-12)
+    src_hits = np.any(hit, axis=0).sum() / (np.any(gt, axis=0).sum() + 1e-12)
+    return {"precision": float(precision), "recall": float(recall), "hit_ratio": float(0.5 * (ref_hits + src_hits))}
+
+
+def coarse_matching_summary(nums, metrics):
+    """The Coarse Matching line of eval.py:249-255 over the pairs: nums = predicted node correspondences per pair (eval.py:129),
+    metrics = coarse_matching_metrics per pair.  NUM, PIR, RECALL, HIT_RATIO = means; PMR>0 = share of pairs with precision > 0
+    (eval.py:133).  NaN without pairs, like the reference's meter."""
+    mean = lambda xs: float(np.mean(xs)) if len(xs) else float("nan")
+    return {"NUM": mean([float(n) for n in nums]), "PIR": mean([m["precision"] for m in metrics]),
+            "RECALL": mean([m["recall"] for m in metrics]), "HIT_RATIO": mean([m["hit_ratio"] for m in metrics]),
+            "PMR>0": mean([float(m["precision"] > 0) for m in metrics])}
+
+
+def correspondence_overlap(ref_points, src_points, transform=None, positive_radius=0.1):
+    """compute_overlap (registration.py:196-202), the `overlap` entry of evaluate_correspondences: the share of ref points whose nearest
+    src point (after `transform`, applied as points @ R^T + t) is closer than positive_radius.  The nearest neighbour is the exact
+    GPU search of functional.feature_nn on the three coordinates (fp32: d2 = ((dx*dx) + dy*dy) + dz*dz, every operation rounded), where
+    the reference asks a KD-tree; the distance is sqrt(d2) in fp32."""
+    import torch
+    from . import functional as F
+    ref = np.ascontiguousarray(ref_points, dtype=np.float32).reshape(-1, 3)
+    src = np.asarray(src_points).reshape(-1, 3)
+    if transform is not None:
+        T = np.asarray(transform)
+        src = src @ T[:3, :3].T + T[:3, 3]
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    if ref.shape[0] == 0:
+        return float("nan")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    start = lambda n: torch.tensor([0, n], dtype=torch.int32, device=dev)
+    _, d2 = F.feature_nn(torch.from_numpy(ref).to(dev), torch.from_numpy(src).to(dev), start(ref.shape[0]), start(src.shape[0]))
+    return float(np.mean(np.sqrt(d2.cpu().numpy()) < np.float32(positive_radius)))

@@ -934,6 +934,61 @@ def feature_correspondences(nn_sr, src_start, ref_start, nn_rs=None, min_rows=3)
     return corr, start, used
 
 
+def node_correspondences_ws_bytes(point_off, node_off, K):
+    """Workspace bytes of lcr_node_correspondences for these host offset lists (2P+1 entries each)."""
+    po, mo = np.ascontiguousarray(point_off, dtype=np.int64), np.ascontiguousarray(node_off, dtype=np.int64)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_node_correspondences_ws_bytes(po.ctypes.data, mo.ctypes.data, (len(po) - 1) // 2, int(K), ctypes.byref(nbytes)),
+               "lcr_node_correspondences_ws_bytes")
+    return nbytes.value
+
+
+def node_correspondences_raw(points_f, point_off, nodes, node_off, knn, knn_mask, node_mask, transforms, pos_radius, cap=None, ws=None, corr=None,
+                             overlap=None, start=None, status=None):
+    """lcr_node_correspondences (include/lcr_hip.h) as it is: no host synchronisation.  -> (corr int32 [cap,2], overlap f32 [cap],
+    start int32 [P+1], status int32 [1]); rows at or beyond start[P] are not written.  cap defaults to sum M_p * N_p, which cannot
+    overflow; ws / corr / overlap / start / status may be caller-owned buffers (uint8 / int32 / float32 / int32 / int32)."""
+    po, mo = np.ascontiguousarray(point_off, dtype=np.int64), np.ascontiguousarray(node_off, dtype=np.int64)
+    if len(po) != len(mo) or len(po) < 3 or len(po) % 2 == 0:
+        raise ValueError("node_correspondences: point_off and node_off must have 2P+1 entries, P >= 1")
+    P = (len(po) - 1) // 2
+    _lib.require_cuda(points_f, nodes, knn, knn_mask, node_mask, transforms)
+    if points_f.dtype != torch.float32 or transforms.dtype != torch.float32 or knn.dtype != torch.int64 or knn.dim() != 2:
+        raise ValueError("node_correspondences: points_f / transforms float32, knn int64 [M,K]")
+    if transforms.numel() != 16 * P or knn.shape[0] != mo[-1] - mo[0] or knn_mask.shape != knn.shape or node_mask.numel() != knn.shape[0]:
+        raise ValueError("node_correspondences: one 4x4 transform per pair, knn / knn_mask [sum M, K], node_mask [sum M]")
+    if points_f.shape[0] < po[-1] or nodes.shape[0] < mo[-1]:
+        raise ValueError("node_correspondences: offsets beyond the stacked rows")
+    dev = points_f.device
+    K = knn.shape[1]
+    as_u8 = lambda t: (t.to(torch.uint8) if t.dtype != torch.uint8 else t).contiguous()
+    km, nm = as_u8(knn_mask), as_u8(node_mask)
+    m = np.diff(mo)
+    if cap is None:
+        cap = int((m[0::2] * m[1::2]).sum())
+    if ws is None:
+        ws = _lib.workspace(node_correspondences_ws_bytes(po, mo, K), dev)
+    corr = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev) if corr is None else corr
+    overlap = torch.empty((max(cap, 1),), dtype=torch.float32, device=dev) if overlap is None else overlap
+    start = torch.empty((P + 1,), dtype=torch.int32, device=dev) if start is None else start
+    status = torch.empty((1,), dtype=torch.int32, device=dev) if status is None else status
+    _lib.check(_L().lcr_node_correspondences(_lib.ptr(points_f.contiguous()), po.ctypes.data, _lib.ptr(nodes.contiguous()), mo.ctypes.data,
+                                             _lib.ptr(knn.contiguous()), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(transforms.contiguous()), P, K,
+                                             float(pos_radius), int(cap), _lib.ptr(corr), _lib.ptr(overlap), _lib.ptr(start), _lib.ptr(status),
+                                             _lib.ptr(ws), ws.numel(), _sp(points_f)), "lcr_node_correspondences")
+    return corr, overlap, start, status
+
+
+def node_correspondences(points_f, point_off, nodes, node_off, knn, knn_mask, node_mask, transforms, pos_radius):
+    """Ground-truth node correspondences of P pairs in one native call (include/lcr_hip.h, lcr_node_correspondences): the stacked outputs
+    of `point_to_node_partition_stack` for the clouds [pos_0, anc_0, pos_1, anc_1, ...] (host offset lists of 2P+1 entries), transforms
+    f32 [P,4,4] (anc onto pos) -> (corr int64 [C,2]: pair-local (ref node, src node) rows, row-major within a pair, pairs in order;
+    overlaps f32 [C]; start int32 [P+1]: pair p owns rows start[p] .. start[p+1]).  One host synchronisation, to size the result."""
+    corr, overlap, start, _ = node_correspondences_raw(points_f, point_off, nodes, node_off, knn, knn_mask, node_mask, transforms, pos_radius)
+    C = int(start[-1].item())
+    return corr[:C].long(), overlap[:C].clone(), start
+
+
 def ransac_sample_host(seed, h0, count, ransac_n, n):
     """The RANSAC sampler on the host (no GPU): int32 [count, ransac_n] row indices of hypotheses h0 .. h0+count-1 for a pair of n rows."""
     out = np.empty((int(count), int(ransac_n)), dtype=np.int32)

@@ -1,1 +1,2 @@
 from .matching import get_node_correspondences  # noqa: F401
+from .matching import get_node_correspondences_batched  # noqa: F401

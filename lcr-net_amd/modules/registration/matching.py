@@ -47,3 +47,44 @@ def get_node_correspondences(ref_nodes, src_nodes, ref_knn_points, src_knn_point
         overlaps[a:a + chunk] = (ref_cov + src_cov) / 2
     keep = overlaps > 0
     return torch.stack([ri[keep], si[keep]], dim=1), overlaps[keep]
+
+
+@torch.no_grad()
+def get_node_correspondences_batched(outs, transforms, pos_radius=0.45):
+    """The labels of every pair of a `forward_pairs` call in ONE native call (functional.node_correspondences; include/lcr_hip.h,
+    lcr_node_correspondences): `outs` is the list of dicts `LCRNet.forward_pairs` returns (pos/anc_points_f, pos/anc_points_c,
+    pos/anc_node_knn_indices, pos/anc_node_knn_masks and, when present, pos/anc_node_masks), `transforms` (P, 4, 4) or a list of
+    (4, 4), anchor onto positive.  Stores gt_node_corr_indices i64 (C, 2) and gt_node_corr_overlaps f32 (C,) in each dict (what
+    io_formats.save_registration writes) and returns them as a list of pairs.  More than 32 pairs go in slices of 32.
+    Unlike `get_node_correspondences` above, nearness is decided on direct coordinate differences: the labels are a
+    pure function of the inputs.  A dict without node masks (the plain LCRNet drops them) uses "the node has a valid patch point", which
+    is what the partition's own node mask says."""
+    from ... import functional as F
+    outs = list(outs)
+    T = torch.stack([torch.as_tensor(t) for t in transforms]) if isinstance(transforms, (list, tuple)) else transforms
+    T = T.detach().reshape(-1, 4, 4)
+    if T.shape[0] != len(outs):
+        raise RuntimeError("one transform per pair: got %d for %d pairs" % (T.shape[0], len(outs)))
+    result = []
+    for g0 in range(0, len(outs), 32):
+        group = outs[g0:g0 + 32]
+        dev = group[0]["pos_points_f"].device
+        pts, nodes, knn, km, nm, po, mo = [], [], [], [], [], [0], [0]
+        for o in group:
+            for side in ("pos", "anc"):
+                k = o[side + "_node_knn_indices"]
+                m = o[side + "_node_knn_masks"]
+                pts.append(o[side + "_points_f"])
+                nodes.append(o[side + "_points_c"])
+                knn.append(k)
+                km.append(m)
+                nm.append(o[side + "_node_masks"] if side + "_node_masks" in o else m.bool().any(1))
+                po.append(po[-1] + pts[-1].shape[0])
+                mo.append(mo[-1] + k.shape[0])
+        corr, ov, start = F.node_correspondences(torch.cat(pts).float(), po, torch.cat(nodes).float(), mo, torch.cat(knn), torch.cat(km),
+                                                 torch.cat(nm), T[g0:g0 + 32].to(dev).float().contiguous(), pos_radius)
+        s = start.tolist()
+        for p, o in enumerate(group):
+            o["gt_node_corr_indices"], o["gt_node_corr_overlaps"] = corr[s[p]:s[p + 1]], ov[s[p]:s[p + 1]]
+            result.append((o["gt_node_corr_indices"], o["gt_node_corr_overlaps"]))
+    return result

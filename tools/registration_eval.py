@@ -27,7 +27,9 @@ registers the anchor onto the positive:
 at most --normal-max-nn neighbours; lcrnet_amd.registration.estimate_normals_batched).
 Prints the reference's Fine Matching line (FMR / IR at acceptance_radius 0.6 with inlier_ratio_threshold 0.05, IR@0.3, IR@0.1,
 num_Corr; config_reg.py:64-65) and Registration line (RR, RRE, RTE, Rx, Ry, Rz: evaluation.registration_summary), then one JSON line.
-Coarse-matching metrics are not computed: the shipped model writes empty gt_node_corr_indices (io_formats.save_registration).
+When at least one pair file carries non-empty `gt_node_corr_indices` (modules.registration.get_node_correspondences_batched stores
+them before io_formats.save_registration), the reference's Coarse Matching line (NUM, PIR, RECALL, HIT_RATIO, PMR>0: eval.py:117-133,
+249-255, over all pairs) comes first and its values go into the JSON line as "coarse_matching"; without labels the output is as before.
 Like eval.py:92-94 the pair seq 8, anchor 15, positive 58 is skipped."""
 import argparse
 import glob
@@ -130,6 +132,22 @@ def refine_icp(pairs, est, args, device):
     return out
 
 
+def coarse_block(dicts):
+    """The coarse-matching block (eval.py:117-133, 249-255) over the loaded pair files, or None when none of them carries labels."""
+    labelled = [d for d in dicts if "gt_node_corr_indices" in d and np.asarray(d["gt_node_corr_indices"]).shape[0] > 0]
+    if not labelled:
+        return None
+    nums, ms = [], []
+    for d in dicts:
+        fam = "pos" if "pos_node_corr_indices" in d else "ref"
+        side = {"pos": "anc", "ref": "src"}[fam]
+        gt = d["gt_node_corr_indices"] if "gt_node_corr_indices" in d else np.zeros((0, 2), np.int64)
+        ms.append(ev.coarse_matching_metrics(d[fam + "_points_c"], d[side + "_points_c"], d[fam + "_node_corr_indices"],
+                                             d[side + "_node_corr_indices"], gt))
+        nums.append(np.asarray(d[fam + "_node_corr_indices"]).shape[0])
+    return ev.coarse_matching_summary(nums, ms)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("features_dir")
@@ -199,6 +217,10 @@ def main(argv=None):
     fm = {k: float(np.mean([x[k] for x in fine])) if fine else float("nan") for k in ("FMR", "IR", "IR@0.3", "IR@0.1", "num_corr")}
     reg = ev.registration_summary([d["transform"] for _, d, _, _, _ in pairs], scored)
     print("Pairs: %d" % len(files))
+    coarse = coarse_block([d for _, d, _, _, _ in pairs])
+    if coarse is not None:
+        print("  Coarse Matching, NUM: {:.3f}, PIR: {:.3f}, RECALL: {:.3f}, HIT_RATIO: {:.3f}, PMR>0: {:.3f}".format(
+            coarse["NUM"], coarse["PIR"], coarse["RECALL"], coarse["HIT_RATIO"], coarse["PMR>0"]))
     print("  Fine Matching, FMR: {:.4f}, IR: {:.3f}, IR@0.3: {:.3f}, IR@0.1: {:.3f}, num_Corr: {:.3f}".format(
         fm["FMR"], fm["IR"], fm["IR@0.3"], fm["IR@0.1"], fm["num_corr"]))
     print("  Registration, RR: {:.4f}, RRE: {:.3f}, RTE: {:.3f}, Rx: {:.3f}, Ry: {:.3f}, Rz: {:.3f}".format(
@@ -206,6 +228,8 @@ def main(argv=None):
     out = {"method": args.method, "pairs": reg["pairs"], "accepted": reg["accepted"], "fine_matching": fm,
            "registration": {k: reg[k] for k in ("RR", "RRE", "RTE", "Rx", "Ry", "Rz")}, "seconds": seconds,
            "num_corr": args.num_corr, "seed": args.seed, "pairs_per_call": args.pairs_per_call}
+    if coarse is not None:
+        out["coarse_matching"] = coarse
     if args.method == "ransac":
         out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
     if args.method == "ransac_featurematch":
