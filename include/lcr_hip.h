@@ -555,7 +555,8 @@ int lcr_upsample_concat(const float* x, int64_t Nx, int C1, const void* idx, int
 /* out[r] = src[idx[r]] (zeros where idx == pad): index_select on a zero-padded tensor */
 int lcr_gather_rows(const float* src, int64_t pad, int C, const int64_t* idx, int64_t R, float* out, void* stream);
 /* weighted_procrustes (modules/registration/procrustes.py:6-73), batched: problem p = correspondences [start[p],start[p+1]);
- * 3x3 SVD on the device (one-sided Jacobi, fp64); T f32[P,4,4]. */
+ * 3x3 SVD on the device (one-sided Jacobi, fp64); T f32[P,4,4].  An empty range or all-zero weights (H == 0) give the identity, as torch.svd
+ * does; rank <= 1 inputs give some proper rotation of least residual. */
 int lcr_procrustes_batched(const float* src, const float* ref, const float* w, const int32_t* start, int P, float eps, float* T, void* stream);
 /* counts[p] = #{ |ref - T_p src| < radius } (-1 if the hypothesis came from < min_count correspondences); best = first argmax */
 int lcr_inlier_count(const float* T, int P, const float* src, const float* ref, int n, float radius, const int32_t* start,

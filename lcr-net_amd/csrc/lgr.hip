@@ -258,7 +258,7 @@ extern "C" int lcr_procrustes_batched(const float* src, const float* ref, const 
 
 extern "C" int lcr_inlier_count(const float* T, int P, const float* src, const float* ref, int n, float radius, const int32_t* start, int min_count,
                                 int32_t* counts, int32_t* best, void* stream) {
-  if (!T || !src || !ref || !counts || P < 1 || n < 0) return LCR_EARG;
+  if (!T || !counts || P < 1 || n < 0 || (n > 0 && (!src || !ref))) return LCR_EARG;       // no rows: nothing to read, null src / ref allowed
   hipLaunchKernelGGL(k_inlier_count, dim3(P), dim3(256), 0, ST(stream), T, src, ref, n, radius, start, min_count, counts);
   if (best) hipLaunchKernelGGL(k_argmax_i32, dim3(1), dim3(64), 0, ST(stream), counts, P, best);
   return check_launch("lcr_inlier_count");
@@ -266,8 +266,8 @@ extern "C" int lcr_inlier_count(const float* T, int P, const float* src, const f
 
 extern "C" int lcr_inlier_weights(const float* T_all, const int32_t* sel, const float* src, const float* ref, const float* score, int n, float radius,
                                   float* w_out, void* stream) {
+  if (n == 0) return LCR_OK;                               // no rows: nothing to read or write, null pointers allowed
   if (!T_all || !src || !ref || !score || !w_out || n < 0) return LCR_EARG;
-  if (n == 0) return LCR_OK;
   hipLaunchKernelGGL(k_inlier_weights, dim3(blocks_for(n)), dim3(256), 0, ST(stream), T_all, sel, src, ref, score, n, radius, w_out);
   return check_launch("lcr_inlier_weights");
 }

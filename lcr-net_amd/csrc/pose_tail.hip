@@ -306,8 +306,9 @@ __global__ __launch_bounds__(256) void k_gather_rows_vec(const float* __restrict
 using namespace lcr;
 
 extern "C" int lcr_vote_shift(const float* xyz, const float* offsets, int64_t N, float max_range, float* out, void* stream) {
+  if (N == 0) return LCR_OK;                               // no points: nothing to read or write, null pointers allowed
   if (!xyz || !offsets || !out || N < 0) return LCR_EARG;
-  if (N) hipLaunchKernelGGL(k_vote_shift, dim3(blocks_for(N)), dim3(256), 0, ST(stream), xyz, offsets, N, max_range, out);
+  hipLaunchKernelGGL(k_vote_shift, dim3(blocks_for(N)), dim3(256), 0, ST(stream), xyz, offsets, N, max_range, out);
   return check_launch("lcr_vote_shift");
 }
 
@@ -327,8 +328,8 @@ extern "C" int lcr_greedy_nms(const float* pts, const int64_t* len, int B, int64
 }
 
 extern "C" int lcr_neighbor_mean(const float* pts, const void* idx, int idx_is_64, int64_t M, int H, int64_t pad, float* out, void* stream) {
+  if (M == 0) return LCR_OK;                               // no rows: nothing to read or write, null pointers allowed
   if (!pts || !idx || !out || M < 0 || H < 1) return LCR_EARG;
-  if (M == 0) return LCR_OK;
   if (idx_is_64) hipLaunchKernelGGL((k_neighbor_mean<int64_t>), dim3(blocks_for(M)), dim3(256), 0, ST(stream), pts, static_cast<const int64_t*>(idx), M, H, pad, out);
   else hipLaunchKernelGGL((k_neighbor_mean<int32_t>), dim3(blocks_for(M)), dim3(256), 0, ST(stream), pts, static_cast<const int32_t*>(idx), M, H, pad, out);
   return check_launch("lcr_neighbor_mean");

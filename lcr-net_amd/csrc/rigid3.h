@@ -58,6 +58,9 @@ __device__ inline void rotation_from_H_impl(const double H[3][3], double R[3][3]
       U[k][j] = sig[c] > 1e-300 ? A[k][c] / sig[c] : 0.0;
     }
   }
+  // H == 0 (no correspondence, or every weight zero): no direction at all.  Start U from the canonical basis; the completion below then
+  // gives U = I, and V = I (no rotation was applied) gives R = I exactly, as torch.svd of a zero matrix does.
+  if (!(sig[ord[0]] > 1e-300)) U[0][0] = 1.0;
   // complete U if rank deficient: third column = u0 x u1 (and second from any orthogonal vector if needed)
   if (sig[ord[1]] <= 1e-12 * sig[ord[0]] || sig[ord[1]] <= 1e-300) {
     // pick an axis least aligned with u0
