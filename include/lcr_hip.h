@@ -771,6 +771,36 @@ int lcr_normals_ws_bytes(int B, int64_t n, size_t* bytes);
 int lcr_estimate_normals(const float* points, const int64_t* lengths, int B, float radius, int max_nn, const float* viewpoint, float* normals,
                          float* curvature, int32_t* count, void* ws, size_t ws_bytes, void* stream);
 
+/* FPFH descriptors (Open3D's compute_fpfh_feature with KDTreeSearchParamHybrid(radius, max_nn): the 33-bin hand-crafted feature that
+ * registration_ransac_based_on_feature_matching is documented with) for B stacked clouds in one call, from the points and normals alone.
+ *   - Input: points f32[N,3] and normals f32[N,3] stacked cloud-major (lcr_estimate_normals writes such normals), lengths HOST int64[B].
+ *   - Neighbourhood of row i: the first max_nn rows lcr_radius_query_ordered(q = s = the cloud, limit = max_nn) returns for i, that is
+ *     the rows of the same cloud with d2 < radius*radius (fp32 product), d2 = ((dx*dx)+dy*dy)+dz*dz in fp32 without FMA, ascending by
+ *     (d2, row); row i itself is then removed from that list WHEREVER it stands.  Open3D drops the first entry, which is the row itself
+ *     unless the cloud has coincident points, where its choice depends on the KD-tree's order: this is the one place where the
+ *     definition is made canonical.  m = the number of remaining rows; count = m.  m == 0 gives an all-zero feature and SPFH row.
+ *   - Pair features, all arithmetic in fp64 on the fp32 inputs promoted, (p1, n1) = row i and (p2, n2) = the neighbour:
+ *       dp = p2 - p1, d = |dp|; d == 0: f = (0, 0, 0).
+ *       a1 = n1.dp / d, a2 = n2.dp / d.  Swap iff |a1| < |a2|; on a swap n1 <-> n2, dp = -dp, f2 = -a2; otherwise f2 = a1.
+ *       (Open3D writes the swap as acos(|a1|) > acos(|a2|); the two agree whenever both cosines are <= 1.  An fp32-rounded normal can
+ *       push a cosine past 1, where Open3D compares with a NaN: comparing the cosines is a deliberate canonical choice.)
+ *       v = dp x n1; |v| == 0: f = (0, 0, 0).  Otherwise v /= |v|, w = n1 x v, f1 = v.n2, f0 = atan2(w.n2, n1.n2).
+ *   - Bins: b0 = floor(11 (f0 + pi) / (2 pi)), b1 = floor(11 (f1 + 1) / 2), b2 = floor(11 (f2 + 1) / 2), each clamped to 0..10.  A
+ *     zero-feature pair still votes, as in Open3D: bin 5 of each block (coincident points, zero (degenerate) normals).
+ *   - SPFH: spfh(i, 11 k + b_k) = (votes * 100) / m in fp64, one rounding.  The votes are integers: SPFH depends on no summation order.
+ *   - FPFH: over the same list in its order, skipping neighbours with d2 == 0: acc_j = sum spfh(nb, j) / d2(nb), d2 the search's fp32
+ *     value promoted, every division and sum rounded in fp64, in list order (which depends on the row's own list alone).  Per block of
+ *     11: s = sum acc_j (ascending j); feature_j = acc_j * (s != 0 ? 100 / s : 0) + spfh(i, j), written rounded to fp32.
+ *   - Outputs: features f32[N,33]; nullable spfh f32[N,33] (SPFH rounded to fp32) and count i32[N] (m).
+ *   - Determinism: a cloud gives bit-identical outputs alone or at any position in any batch.  No float atomics.
+ *   - Asynchronous and stream-ordered, no allocation, no host synchronisation; ws: lcr_fpfh_ws_bytes(B, N, max_nn) (the support grid, the
+ *     int32 [N, max_nn] neighbour table and the fp64 SPFH rows).  The argument checks and lcr_fpfh_ws_bytes are host-only.
+ * Parity against Open3D's own binary is unpinned; tests/fpfh_restatement.py restates exactly the text above.
+ * Domain: 1 <= B <= 64, 0 < radius with radius*radius finite, 2 <= max_nn <= 128, lengths >= 0, N <= 2^31-1; LCR_EARG outside. */
+int lcr_fpfh_ws_bytes(int B, int64_t n, int max_nn, size_t* bytes);
+int lcr_fpfh(const float* points, const float* normals, const int64_t* lengths, int B, float radius, int max_nn, float* features, float* spfh,
+             int32_t* count, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

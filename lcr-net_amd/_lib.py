@@ -139,6 +139,8 @@ _SIGS = {
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_normals_ws_bytes": (c_int, [c_int, c_i64, c_size_p]),
     "lcr_estimate_normals": (c_int, [c_vp, c_vp, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_fpfh_ws_bytes": (c_int, [c_int, c_i64, c_int, c_size_p]),
+    "lcr_fpfh": (c_int, [c_vp, c_vp, c_vp, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
 }
 
 

@@ -1095,3 +1095,38 @@ def estimate_normals(points, lengths, radius, max_nn, viewpoint=None, want_curva
     if want_count:
         out["count"] = cnt
     return out
+
+
+FPFH_MAX_CLOUDS = 64      # clouds per lcr_fpfh call (the support grid's limit)
+FPFH_MAX_NN = 128
+FPFH_BINS = 33
+
+
+def fpfh(points, normals, lengths, radius, max_nn, want_spfh=False, want_count=False):
+    """FPFH descriptors (include/lcr_hip.h, lcr_fpfh; Open3D's compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn))) for B <= 64
+    clouds in one native call: points / normals f32 [N,3] on the device stacked cloud-major, lengths host ints [B] -> dict(features f32
+    [N,33]; with want_spfh spfh f32 [N,33]; with want_count count int32 [N], the neighbours that voted).  Asynchronous on the current
+    stream."""
+    _lib.require_cuda(points, normals)
+    dev = points.device
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    B = len(ln)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or points.shape[0] != int(ln.sum()):
+        raise ValueError("fpfh: points must be float32 [sum(lengths), 3]")
+    if tuple(normals.shape) != tuple(points.shape) or normals.dtype != torch.float32 or normals.device != dev:
+        raise ValueError("fpfh: normals must be float32 with the shape and device of points")
+    points, normals = points.contiguous(), normals.contiguous()
+    n = points.shape[0]
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_fpfh_ws_bytes(B, n, int(max_nn), ctypes.byref(nbytes)), "lcr_fpfh_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    out = {"features": torch.empty((n, FPFH_BINS), dtype=torch.float32, device=dev)}
+    spfh = torch.empty((n, FPFH_BINS), dtype=torch.float32, device=dev) if want_spfh else None
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev) if want_count else None
+    _lib.check(_L().lcr_fpfh(_lib.ptr(points), _lib.ptr(normals), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(out["features"]),
+                             _lib.ptr(spfh), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_fpfh")
+    if want_spfh:
+        out["spfh"] = spfh
+    if want_count:
+        out["count"] = cnt
+    return out

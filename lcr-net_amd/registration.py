@@ -247,3 +247,46 @@ def estimate_normals(points, radius, max_nn=30, viewpoint=(0.0, 0.0, 0.0)):
     if torch.is_tensor(points):
         return n
     return n.cpu().numpy()
+
+
+# ---- FPFH descriptors (Open3D's compute_fpfh_feature) and the learning-free chain normals -> FPFH -> feature-matching RANSAC ----
+def compute_fpfh_feature_batched(points, normals, lengths, radius, max_nn=100):
+    """FPFH for B clouds on the GPU.  points / normals f32 [N,3]: device tensors stacked cloud-major, lengths: host sequence of B ints.
+    -> device f32 [N,33] (see functional.fpfh and include/lcr_hip.h, lcr_fpfh).  Batches of more than 64 clouds are split; every cloud's
+    result is the same in any chunk."""
+    lengths = [int(x) for x in np.asarray(lengths).reshape(-1)]
+    B = len(lengths)
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    parts = []
+    for c0 in range(0, B, F.FPFH_MAX_CLOUDS):
+        c1 = min(B, c0 + F.FPFH_MAX_CLOUDS)
+        parts.append(F.fpfh(points[off[c0]:off[c1]], normals[off[c0]:off[c1]], lengths[c0:c1], radius, max_nn)["features"])
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def compute_fpfh_feature(points, normals, radius, max_nn=100):
+    """FPFH of one cloud: Open3D's compute_fpfh_feature(cloud, KDTreeSearchParamHybrid(radius, max_nn)), as an (N,33) array, which is the
+    (N,C) layout registration_with_ransac_from_feats and the reference's make_open3d_registration_feature take (Open3D's own Feature.data
+    is the transpose).  points / normals: numpy arrays or torch tensors [N,3]; returns the same kind as points (numpy float32, or a
+    float32 tensor on the GPU)."""
+    dev = points.device if torch.is_tensor(points) and points.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    pts, nrm = _device_points(points, dev), _device_points(normals, dev)
+    if pts.shape != nrm.shape:
+        raise ValueError("compute_fpfh_feature needs one normal per point")
+    f = compute_fpfh_feature_batched(pts, nrm, [pts.shape[0]], radius, max_nn)
+    if torch.is_tensor(points):
+        return f
+    return f.cpu().numpy()
+
+
+def fpfh_ransac_batched(src, src_len, ref, ref_len, normal_radius, normal_max_nn, feature_radius, feature_max_nn, src_viewpoint=None,
+                        ref_viewpoint=None, **ransac_kw):
+    """The learning-free registration chain for S pairs, everything on the device: normals of every cloud (oriented toward its viewpoint;
+    None = each cloud's origin, the sensor) -> FPFH -> ransac_from_feats_batched (exact feature nearest neighbours, checked RANSAC;
+    ransac_kw are its keyword arguments).  src f32 [ns,3] / ref f32 [nr,3]: device tensors stacked pair-major, src_len / ref_len: host
+    sequences of S ints.  -> the dict of ransac_from_feats_batched (T f32 [S,4,4] maps src onto ref)."""
+    feats = []
+    for pts, ln, vp in ((src, src_len, src_viewpoint), (ref, ref_len, ref_viewpoint)):
+        nrm = estimate_normals_batched(pts, ln, normal_radius, normal_max_nn, vp)["normals"]
+        feats.append(compute_fpfh_feature_batched(pts, nrm, ln, feature_radius, feature_max_nn))
+    return ransac_from_feats_batched(src, ref, feats[0], feats[1], src_len, ref_len, **ransac_kw)

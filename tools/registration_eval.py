@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """Registration evaluation over saved pair files: the counterpart of experiments/registration/eval.py.
 
-    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|ransac_featurematch] [--num_corr K] [--seed S]
+    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|ransac_featurematch|fpfh_ransac] [--num_corr K] [--seed S]
                                       [--pairs-per-call P] [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000]
                                       [--write-back] [--mutual-filter] [--edge-similarity 0.9]
                                       [--refine icp|icp_plane [--icp-distance 0.5] [--icp-iterations 30]
                                                               [--normal-radius 1.0] [--normal-max-nn 30]]
+                                      [--fpfh-radius 2.5] [--fpfh-max-nn 100]
 
 Reads every `{seq}_{anc}_{pos}.npz` of FEATURES_DIR (what io_formats.save_registration / demo.py write; both the pos_/anc_ and the
 ref_/src_ key families of eval.py:96-110 are accepted), keeps the top --num_corr correspondences by corr_scores (:114-118), and
@@ -21,6 +22,11 @@ registers the anchor onto the positive:
           those correspondences with Open3D's edge-length checker (--edge-similarity, 0.9) and its distance checker at
           --distance-threshold (lcrnet_amd.registration.ransac_from_feats_batched).  Needs `pos_feats_f` / `anc_feats_f` in the pair
           files (io_formats.save_registration(..., with_feats=True)); a file without them ends the run with a non-zero exit.
+  fpfh_ransac
+          the learning-free baseline: normals of `anc_points_f` / `pos_points_f` (--normal-radius, --normal-max-nn, oriented toward each
+          cloud's origin) -> FPFH descriptors (--fpfh-radius, --fpfh-max-nn) -> the feature-matching RANSAC above, all on the GPU
+          (lcrnet_amd.registration.fpfh_ransac_batched).  Needs only `pos_points_f` / `anc_points_f` (and `transform`) in the pair
+          files; where a file has no correspondences the Fine Matching line averages over the files that have.
 --refine icp (opt-in) then refines every estimate by point-to-point ICP of the dense anchor cloud (`anc_points_f`) onto the positive's
 (`pos_points_f`), Open3D's criteria with --icp-distance / --icp-iterations, batched on the GPU (lcrnet_amd.registration.icp_batched).
 --refine icp_plane does the same with point-to-plane ICP, on normals of `pos_points_f` computed on the GPU (radius --normal-radius,
@@ -56,8 +62,10 @@ def parse_name(path):
     return seq, int(anc), int(pos)
 
 
-def load_pair(path, num_corr):
+def load_pair(path, num_corr, need_corr=True):
     d = io.load_registration(path)
+    if not need_corr and not ("corr_scores" in d and ("pos_corr_points" in d or "ref_corr_points" in d)):
+        return d, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0,), np.float32)
     if "pos_corr_points" in d:
         pos, anc = d["pos_corr_points"], d["anc_corr_points"]
     else:
@@ -109,6 +117,21 @@ def estimate_featurematch(group, args, device):
             r["reject_all"].cpu().numpy().reshape(len(group), args.num_iterations))
 
 
+def estimate_fpfh(group, args, device):
+    """normals -> FPFH -> feature-matching RANSAC for a group of pairs: (transforms (S,4,4) float64, num_corr [S])."""
+    import torch
+    from lcrnet_amd.registration import fpfh_ransac_batched
+    pts = lambda k: [np.ascontiguousarray(d[k], np.float32).reshape(-1, 3) for _, d, _, _, _ in group]
+    cat = lambda xs: torch.from_numpy(np.concatenate(xs)).to(device)
+    sp, rp = pts("anc_points_f"), pts("pos_points_f")
+    r = fpfh_ransac_batched(cat(sp), [len(x) for x in sp], cat(rp), [len(x) for x in rp], args.normal_radius, args.normal_max_nn,
+                            args.fpfh_radius, args.fpfh_max_nn, distance_threshold=args.distance_threshold, ransac_n=args.ransac_n,
+                            num_iterations=args.num_iterations, seed=args.seed, mutual_filter=args.mutual_filter,
+                            edge_similarity=args.edge_similarity)
+    torch.cuda.synchronize(device)
+    return r["T"].cpu().numpy().astype(np.float64), r["num_corr"].cpu().numpy()
+
+
 def refine_icp(pairs, est, args, device):
     """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each.
     --refine icp_plane: point-to-plane, on normals of pos_points_f estimated on the GPU first."""
@@ -151,7 +174,7 @@ def coarse_block(dicts):
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("features_dir")
-    p.add_argument("--method", choices=["lgr", "ransac", "svd", "ransac_featurematch"], default="lgr")
+    p.add_argument("--method", choices=["lgr", "ransac", "svd", "ransac_featurematch", "fpfh_ransac"], default="lgr")
     p.add_argument("--num_corr", type=int, default=None)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--pairs-per-call", type=int, default=16)
@@ -165,8 +188,10 @@ def main(argv=None):
                    help="refine each estimate by point-to-point (icp) or point-to-plane (icp_plane) ICP of the dense clouds")
     p.add_argument("--icp-distance", type=float, default=0.5)
     p.add_argument("--icp-iterations", type=int, default=30)
-    p.add_argument("--normal-radius", type=float, default=1.0, help="--refine icp_plane: normal search radius on pos_points_f")
-    p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane: neighbours per normal at most")
+    p.add_argument("--normal-radius", type=float, default=1.0, help="--refine icp_plane / fpfh_ransac: normal search radius")
+    p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane / fpfh_ransac: neighbours per normal at most")
+    p.add_argument("--fpfh-radius", type=float, default=2.5, help="fpfh_ransac: FPFH search radius")
+    p.add_argument("--fpfh-max-nn", type=int, default=100, help="fpfh_ransac: neighbours per FPFH row at most")
     args = p.parse_args(argv)
     if args.pairs_per_call < 1:
         p.error("--pairs-per-call must be >= 1")
@@ -177,7 +202,11 @@ def main(argv=None):
         seq, anc, pos = parse_name(f)
         if seq == 8 and anc == 15 and pos == 58:          # eval.py:92-94 ("delete bad data")
             continue
-        d, pos_pts, anc_pts, scores = load_pair(f, args.num_corr)
+        d, pos_pts, anc_pts, scores = load_pair(f, args.num_corr, need_corr=args.method != "fpfh_ransac")
+        if args.method == "fpfh_ransac":
+            missing = [k for k in ("pos_points_f", "anc_points_f", "transform") if k not in d]
+            if missing:
+                sys.exit("registration_eval: --method fpfh_ransac needs %s in %s" % (", ".join(missing), f))
         if args.method == "ransac_featurematch":
             missing = [k for k in io.REGISTRATION_FEAT_KEYS + ("pos_points_f", "anc_points_f") if k not in d]
             if missing:
@@ -199,6 +228,10 @@ def main(argv=None):
                 est += list(T)
                 fm_corr += list(nc)
                 fm_reject.append(rej)
+            elif args.method == "fpfh_ransac":
+                T, nc = estimate_fpfh(group, args, device)
+                est += list(T)
+                fm_corr += list(nc)
             else:
                 est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
     scored = est                                          # --write-back stores the method's own estimate, refined or not
@@ -213,7 +246,7 @@ def main(argv=None):
             modified["estimated_transform_ransac"] = T
             np.savez(f, **modified)
 
-    fine = [ev.fine_matching_metrics(b, a, d["transform"]) for _, d, b, a, _ in pairs]
+    fine = [ev.fine_matching_metrics(b, a, d["transform"]) for _, d, b, a, _ in pairs if args.method != "fpfh_ransac" or len(b)]
     fm = {k: float(np.mean([x[k] for x in fine])) if fine else float("nan") for k in ("FMR", "IR", "IR@0.3", "IR@0.1", "num_corr")}
     reg = ev.registration_summary([d["transform"] for _, d, _, _, _ in pairs], scored)
     print("Pairs: %d" % len(files))
@@ -240,6 +273,11 @@ def main(argv=None):
                                       "edge_similarity": args.edge_similarity,
                                       "num_corr": float(np.mean(fm_corr)) if fm_corr else float("nan"),
                                       "rejected": {"degenerate": share(1), "edge_length": share(2), "distance": share(3)}}
+    if args.method == "fpfh_ransac":
+        out["fpfh_ransac"] = {"normal_radius": args.normal_radius, "normal_max_nn": args.normal_max_nn, "fpfh_radius": args.fpfh_radius,
+                              "fpfh_max_nn": args.fpfh_max_nn, "distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n,
+                              "num_iterations": args.num_iterations, "mutual_filter": args.mutual_filter,
+                              "edge_similarity": args.edge_similarity, "num_corr": float(np.mean(fm_corr)) if fm_corr else float("nan")}
     if args.refine:
         out["refine"] = {"method": args.refine, "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
         if args.refine == "icp_plane":
