@@ -801,6 +801,53 @@ int lcr_fpfh_ws_bytes(int B, int64_t n, int max_nn, size_t* bytes);
 int lcr_fpfh(const float* points, const float* normals, const int64_t* lengths, int B, float radius, int max_nn, float* features, float* spfh,
              int32_t* count, void* ws, size_t ws_bytes, void* stream);
 
+/* Range-image scan overlap: the labels "frame j overlaps frame i by more than 0.3" of the loop-detection evaluation, for B stacked scans
+ * and P pairs of them per call.  The kernels emit integers only; the ratio is taken by the caller.
+ *   Parameters (defaults of a 64-beam sensor): H = 64, W = 900, fov_up = 3 (degrees), fov_down = -25 (degrees), max_range = 50, eps = 1.
+ *   Derived angles: fu = fov_up*pi/180, fd = fov_down*pi/180, fov = |fu| + |fd|.
+ *   Projection of one point: (x, y, z) is fp32 and promoted to fp64.  The rigid transform M is f64[3,4], applied in fp64 with every
+ *   operation rounded, no FMA, in this order: x' = ((M00*x + M01*y) + M02*z) + M03, and likewise for y' and z'.
+ *     - d = sqrt((x'x' + y'y') + z'z').
+ *     - The point is kept iff 0 < d < max_range.
+ *     - yaw = -atan2(y', x').
+ *     - pitch = asin(clamp(z'/d, -1, 1)).
+ *     - u = 0.5*(yaw/pi + 1)*W.
+ *     - v = (1 - (pitch + |fd|)/fov)*H.
+ *     - Column = floor(u) clamped to 0..W-1.
+ *     - Row = floor(v) clamped to 0..H-1.
+ *     - Points outside the vertical field of view therefore land in the edge rows.
+ *   Range image: a pixel holds the minimum over its points of d rounded to fp32.  Rounding is monotone, so this equals the minimum of
+ *   the rounded values.  An empty pixel holds -1.
+ *
+ * lcr_range_images: points f32[N,3] stacked cloud-major, lengths HOST int64[B] -> images f32[B,H,W] with M = identity (applied like any
+ * M, so a negative zero coordinate comes out as +0), and valid i32[B], the count of non-empty pixels.
+ *
+ * lcr_scan_overlap: for each of P pairs (i, j) = pairs[p] (device i32[P,2]) with rel[p] (device f64[P,3,4]; the caller passes
+ * rel = inv(T_i)*T_j, computed on the host in fp64): cloud j is projected through rel[p] into a scratch image, which is compared with
+ * images[i] (as lcr_range_images wrote it, with valid).  counts i32[P,3] =
+ *     matches   the number of pixels non-empty in both images with |double(a) - double(b)| < eps,
+ *     valid_cur = valid[i],
+ *     valid_ref the number of non-empty pixels of the projected image.
+ *   i == j is allowed.  A pair with an index outside 0..B-1 reads nothing, gets counts (-1, -1, -1) and raises status i32[1] (device) to
+ *   the largest such p + 1; status is 0 after a call without one.
+ *   - Determinism: the only atomics are integer ones (an integer minimum on the fp32 bit pattern of a positive depth is order-free).  A
+ *     pair gives the same bytes alone or at any position in any call.  No float atomics.
+ *   - Both entries are asynchronous and stream-ordered, no allocation, no host synchronisation; ws: lcr_range_images_ws_bytes(B) /
+ *     lcr_scan_overlap_ws_bytes(B, P) (the clouds' prefix offsets: the images being built live in LDS, in bands of rows).  The argument
+ *     checks and the _ws_bytes helpers are host-only.  P == 0 returns LCR_OK before every other check and launches nothing (status is
+ *     then not written).
+ * The definition is restated in tests/scan_overlap_restatement.py and is not pinned against the script that produced the reference's
+ * seq-00 labels.
+ * Domain: 1 <= B <= 64, 0 <= P <= 2^31-1, 1 <= H <= 128, 1 <= W <= 4096, 0 < max_range, 0 < eps, fov > 0 and finite, lengths >= 0,
+ * N <= 2^31-1; LCR_EARG outside. */
+int lcr_range_images_ws_bytes(int B, size_t* bytes);
+int lcr_range_images(const float* points, const int64_t* lengths, int B, int H, int W, double fov_up, double fov_down, double max_range,
+                     float* images, int32_t* valid, void* ws, size_t ws_bytes, void* stream);
+int lcr_scan_overlap_ws_bytes(int B, int64_t P, size_t* bytes);
+int lcr_scan_overlap(const float* points, const int64_t* lengths, int B, const float* images, const int32_t* valid, const int32_t* pairs,
+                     const double* rel, int64_t P, int H, int W, double fov_up, double fov_down, double max_range, double eps, int32_t* counts,
+                     int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,12 @@ _SIGS = {
     "lcr_estimate_normals": (c_int, [c_vp, c_vp, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "lcr_fpfh_ws_bytes": (c_int, [c_int, c_i64, c_int, c_size_p]),
     "lcr_fpfh": (c_int, [c_vp, c_vp, c_vp, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_range_images_ws_bytes": (c_int, [c_int, c_size_p]),
+    "lcr_range_images": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp,
+                                 ctypes.c_size_t, c_vp]),
+    "lcr_scan_overlap_ws_bytes": (c_int, [c_int, c_i64, c_size_p]),
+    "lcr_scan_overlap": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_double, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
 }
 
 

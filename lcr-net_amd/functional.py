@@ -1130,3 +1130,58 @@ def fpfh(points, normals, lengths, radius, max_nn, want_spfh=False, want_count=F
     if want_count:
         out["count"] = cnt
     return out
+
+
+SCAN_OVERLAP_MAX_CLOUDS = 64   # clouds per lcr_range_images / lcr_scan_overlap call
+SCAN_OVERLAP_PROJ = dict(H=64, W=900, fov_up=3.0, fov_down=-25.0, max_range=50.0)    # the 64-beam defaults of include/lcr_hip.h
+
+
+def _scan_clouds(who, points, lengths):
+    _lib.require_cuda(points)
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or points.shape[0] != int(ln.sum()):
+        raise ValueError("%s: points must be float32 [sum(lengths), 3]" % who)
+    return points.contiguous(), ln
+
+
+def range_images(points, lengths, H=64, W=900, fov_up=3.0, fov_down=-25.0, max_range=50.0):
+    """Spherical range images (include/lcr_hip.h, lcr_range_images) of B <= 64 clouds in one native call: points f32 [N,3] on the device
+    stacked cloud-major, lengths host ints [B] -> (images f32 [B,H,W] with -1 in empty pixels, valid int32 [B]).  Asynchronous on the
+    current stream."""
+    points, ln = _scan_clouds("range_images", points, lengths)
+    dev, B = points.device, len(ln)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_range_images_ws_bytes(B, ctypes.byref(nbytes)), "lcr_range_images_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    images = torch.empty((B, int(H), int(W)), dtype=torch.float32, device=dev)
+    valid = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(_L().lcr_range_images(_lib.ptr(points), ln.ctypes.data, B, int(H), int(W), float(fov_up), float(fov_down), float(max_range),
+                                     _lib.ptr(images), _lib.ptr(valid), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_range_images")
+    return images, valid
+
+
+def scan_overlap(points, lengths, images, valid, pairs, rel, H=64, W=900, fov_up=3.0, fov_down=-25.0, max_range=50.0, eps=1.0):
+    """Range-image overlap counts (include/lcr_hip.h, lcr_scan_overlap) of P pairs of the B <= 64 clouds in one native call: images / valid
+    as range_images returned them for the same clouds and projection, pairs int32 [P,2] (i, j) and rel f64 [P,3,4] = inv(T_i) T_j on the
+    device -> (counts int32 [P,3] = (matches, valid_cur, valid_ref), status int32 [1]: 0, or p + 1 of a pair with an index outside
+    0..B-1, whose counts are -1).  Raw form: asynchronous on the current stream, the status is not read here."""
+    points, ln = _scan_clouds("scan_overlap", points, lengths)
+    dev, B = points.device, len(ln)
+    _lib.require_cuda(images, valid, pairs, rel)
+    if tuple(images.shape) != (B, int(H), int(W)) or images.dtype != torch.float32 or tuple(valid.shape) != (B,) or valid.dtype != torch.int32:
+        raise ValueError("scan_overlap: images must be float32 [B,H,W] and valid int32 [B]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+        raise ValueError("scan_overlap: pairs must be int32 [P,2]")
+    P = pairs.shape[0]
+    if tuple(rel.shape) != (P, 3, 4) or rel.dtype != torch.float64:
+        raise ValueError("scan_overlap: rel must be float64 [P,3,4]")
+    images, valid, pairs, rel = images.contiguous(), valid.contiguous(), pairs.contiguous(), rel.contiguous()
+    counts = torch.empty((P, 3), dtype=torch.int32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_scan_overlap_ws_bytes(B, P, ctypes.byref(nbytes)), "lcr_scan_overlap_ws_bytes")
+    ws = _lib.workspace(nbytes.value, dev)
+    _lib.check(_L().lcr_scan_overlap(_lib.ptr(points), ln.ctypes.data, B, _lib.ptr(images), _lib.ptr(valid), _lib.ptr(pairs), _lib.ptr(rel), P,
+                                     int(H), int(W), float(fov_up), float(fov_down), float(max_range), float(eps), _lib.ptr(counts),
+                                     _lib.ptr(status), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_scan_overlap")
+    return counts, status

@@ -162,8 +162,16 @@ def save_top1_with_threshold(dataset_root, seq, rows3, thres):
 
 def load_loop_pairs(path):
     """The reference's reader of that file (datasets/loop_closure/kitti/dataset.py:48-57): per line anc_idx = field 0 (the query frame),
-    pos_idx = field 1 (its match) -> [(pos_idx, anc_idx)] = (ref frame, src frame) of the registration pair."""
+    pos_idx = field 1 (its match) -> [(pos_idx, anc_idx)] = (ref frame, src frame) of the registration pair.
+
+    A path ending in `.npz` is read as the distance-based loop-pair file of the reference's generate_*_loop_pairs_distance_npz (key `data`:
+    dicts with `anc_idx`, the query frame, and `pos_idx`, all its matches; loop_gt.save_loop_pairs writes it): one (pos_idx, anc_idx) per
+    match, in file order."""
     out = []
+    if str(path).endswith(".npz"):
+        for d in np.load(path, allow_pickle=True)["data"]:
+            out.extend((int(k), int(d["anc_idx"])) for k in np.asarray(d["pos_idx"]).reshape(-1))
+        return out
     with open(path) as f:
         for line in f.readlines():
             s = line.split()

@@ -45,6 +45,7 @@ def parse():
     ap.add_argument("--out", default=None, help="directory for the npz files (default: a temporary one, removed afterwards)")
     ap.add_argument("--voxelizer", choices=["grid", "open3d"], default="grid",
                     help="raw-scan voxeliser of the ingest leg: the collate's grid subsampling, or Open3D's VoxelDownSample")
+    ap.add_argument("--gt-labels", default=None, help="overlap labels .npz (tools/loop_gt_run.py writes them; one entry per frame) instead of the KITTI 00 asset / the synthetic revisits")
     ap.add_argument("--dump", default=None, help="rank 0 writes the gathered descriptors and the rows to this .npz (strong-scaling identity check of tools/scale_run.sh; small corpora only)")
     return ap.parse_args()
 
@@ -169,7 +170,12 @@ def main():
         back = np.load(os.path.join(out_dir, "predicted_des_L2_dis.npz"))["arr_0"]
         assert back.shape == ((C - 102) * 50, 1, 3)
         gt_file = os.path.join(ROOT, "tests", "golden", "loop_gt_seq00_0.3overlap_inactive.npz")
-        if C == 4541 and os.path.exists(gt_file):
+        if args.gt_labels:
+            from lcrnet_amd.loop_gt import load_loop_labels
+            gt, gt_name = load_loop_labels(args.gt_labels), "labels of %s" % os.path.basename(args.gt_labels)
+            if len(gt) != C:
+                raise SystemExit("--gt-labels holds %d frames, --frames is %d" % (len(gt), C))
+        elif C == 4541 and os.path.exists(gt_file):
             gt, gt_name = np.load(gt_file, allow_pickle=True)["arr_0"], "reference asset loop_gt_seq00_0.3overlap_inactive.npz (KITTI 00)"
         else:
             gt = np.empty(C, dtype=object)
