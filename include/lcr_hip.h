@@ -848,6 +848,68 @@ int lcr_scan_overlap(const float* points, const int64_t* lengths, int B, const f
                      const double* rel, int64_t P, int H, int W, double fov_up, double fov_down, double max_range, double eps, int32_t* counts,
                      int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* Registration loss terms (the reference's experiments/lcrnet/loss_reg.py: gap :96-159, node_gap :163-231, SingleSideChamferLoss_Brute
+ * :21-45, VoteLoss_new :48-92) with the gradients a training step needs: to the scores and to the shifted nodes.  Restated in
+ * tests/losses_restatement.py.
+ *
+ * lcr_gap_loss: B score slices grouped into P pairs.  Slice b is S[soff[b] ...], (n_b+1) x (m_b+1) row-major fp32 log-transport scores,
+ * the last row and column being the dustbin; n_b = roff[b+1]-roff[b], m_b = coff[b+1]-coff[b]; row i of slice b is entry roff[b]+i of
+ * every per-row table (p_pts, pmask, the first `rows` line statistics), column j entry coff[b]+j of every per-column table (q_pts, qmask,
+ * the line statistics from `rows` on).  soff / roff / coff are DEVICE i64[B+1]; seg_start is DEVICE i32[P+1], pair p owning slices
+ * seg_start[p] .. seg_start[p+1]-1.  The host passes the extents it allocated for: n_max, m_max, elems (S and labels), rows, cols.  A slice
+ * or segment that does not fit them is skipped by every kernel and raises LCR_STATUS_LEN_MISMATCH: nothing outside the extents is touched.
+ *   - Labels, two bits per score (bit 0 positive, bit 1 negative), for the inner (i < n, j < m) entries from one of two sources:
+ *     LCR_GAP_LABELS_POINTS: q' = ((R0*x + R1*y) + R2*z) + t per component with the pair's row-major 4x4 (transforms f32[P,16]),
+ *       d = p - q', d2 = ((dx*dx + dy*dy) + dz*dz), fp32, every operation rounded.  positive iff d2 < (float)(r*r) and pmask[i] and
+ *       qmask[j]; negative iff d2 > (float)((2r)*(2r)), whatever the masks say (the reference does not mask its negatives).
+ *     LCR_GAP_LABELS_OVERLAPS: corr i64[C,2] pair-local (i, j) with overlaps f32[C], pair p's entries being corr_start[p] ..
+ *       corr_start[p+1]-1 (DEVICE i32[P+1]; c_max = the host's bound on a pair's count), written into the pair's FIRST slice.  An entry is
+ *       positive iff overlap > (float)positive_overlap and both masks, negative iff its overlap is exactly 0; a node pair that is not
+ *       listed is negative.  A pair's entries must be distinct node pairs; an index outside the slice is skipped and raises
+ *       LCR_STATUS_INDEX_RANGE.
+ *   - A line is a row i < n of a slice (candidates j = 0..m, the dustbin column included) or a column j < m (candidates i = 0..n).  Its
+ *     dustbin entry is positive iff the line has no inner positive, else negative.  pos = the mean of -S over the line's positives
+ *     (count >= 1); hinge = the sum over the line's NEGATIVES of max(pos + S + gamma, 0), an argument >= 0 counting as active; every
+ *     other entry stands for the reference's constant 1e12 and contributes nothing.  fp64 on the fp32 scores.
+ *   - A line is dropped iff (float)pos == 1e12f exactly (the reference's own test: the padded lines, whose dustbin score is -1e12).
+ *   - Per pair: terms f32[P,3] = (mean over kept rows of log(hinge + 1), the same over kept columns, their mean), NaN where a pair keeps
+ *     no line; kept i32[P,2].  Saved for the gradient: labels u8[elems] (the dustbin entries hold their line's dustbin label, the corner
+ *     0); line_pos f64, line_hinge f64, line_count i32 (positives), line_active i32 (-1 on a dropped line), each [rows + cols], rows first.
+ *   - status u32[1] is written, not or-ed.
+ * lcr_gap_loss_grad: upstream f32[P,2] (d loss / d row term, d column term) -> dS, the layout of S, every element written once by one
+ * thread: w_line * ([negative and active] - [positive] * active / count) summed over the element's row line and column line, w_line =
+ * upstream / (kept * (hinge + 1)); zero on dropped lines, on the constant entries and at the corner.  Points and transforms get none.
+ *
+ * lcr_min_dist: stacked queries A f32[na,3] and data D f32[nd,3] in P segments (DEVICE i32[P+1] a_start / d_start; q_max = the host's
+ * bound on a segment's query count; a segment that does not fit na / nd is skipped).  dist[q] = sqrt(max(d2, 1e-12f)) of the nearest
+ * data point of q's segment, d2 by differences as above; arg i32[na] its segment-local row, the lower row on a tie, -1 (and dist = inf)
+ * for an empty segment; mean f32[P] = the mean of dist over the queries with valid[q] != 0 (all of them when valid is NULL), NaN when
+ * there is none; count i32[P] = their number.
+ * lcr_min_dist_grad: dA[q] = upstream[p] * (a - d*) / dist / count for a valid query whose d2 >= 1e-12f, zero elsewhere.
+ *
+ * All four are asynchronous, stream-ordered, allocate nothing, use no atomics and give a pair the same bytes alone or in any batch.
+ * Domain: 1 <= P <= B <= 65535, n_max, m_max <= 32767, radius >= 0 with (2r)^2 finite in fp32, positive_overlap >= 0; min_dist:
+ * 1 <= P <= 65535, na, nd <= (2^31-1)/3.  LCR_EARG outside. */
+#define LCR_STATUS_INDEX_RANGE 8u
+#define LCR_GAP_LABELS_POINTS 0
+#define LCR_GAP_LABELS_OVERLAPS 1
+int lcr_gap_loss_ws_bytes(int64_t rows, int64_t cols, size_t* bytes);
+int lcr_gap_loss(const float* S, const int64_t* soff, const int64_t* roff, const int64_t* coff, const int32_t* seg_start, int64_t B, int P,
+                 int n_max, int m_max, int64_t elems, int64_t rows, int64_t cols, int source, const float* p_pts, const float* q_pts,
+                 const float* transforms, double positive_radius, const int64_t* corr, const float* overlaps, const int32_t* corr_start,
+                 int64_t C, int64_t c_max, double positive_overlap, const uint8_t* pmask, const uint8_t* qmask, double gamma, float* terms,
+                 int32_t* kept, uint8_t* labels, double* line_pos, double* line_hinge, int32_t* line_count, int32_t* line_active,
+                 uint32_t* status, void* ws, size_t ws_bytes, void* stream);
+int lcr_gap_loss_grad(const float* S, const int64_t* soff, const int64_t* roff, const int64_t* coff, const int32_t* seg_start, int64_t B,
+                      int P, int n_max, int m_max, int64_t elems, int64_t rows, int64_t cols, double gamma, const float* upstream,
+                      const int32_t* kept, const uint8_t* labels, const double* line_pos, const double* line_hinge,
+                      const int32_t* line_count, const int32_t* line_active, float* dS, void* stream);
+int lcr_min_dist(const float* A, const int32_t* a_start, int64_t na, const float* D, const int32_t* d_start, int64_t nd,
+                 const uint8_t* valid, int P, int64_t q_max, float* dist, int32_t* arg, float* mean, int32_t* count, void* stream);
+int lcr_min_dist_grad(const float* A, const int32_t* a_start, int64_t na, const float* D, const int32_t* d_start, int64_t nd,
+                      const uint8_t* valid, int P, int64_t q_max, const int32_t* arg, const float* dist, const int32_t* count,
+                      const float* upstream, float* dA, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,3 +9,4 @@ GPU is missing.
 __version__ = "0.1.0"
 
 from . import _lib  # noqa: F401
+from . import losses  # noqa: F401,E402

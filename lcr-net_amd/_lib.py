@@ -147,6 +147,14 @@ _SIGS = {
     "lcr_scan_overlap_ws_bytes": (c_int, [c_int, c_i64, c_size_p]),
     "lcr_scan_overlap": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_gap_loss_ws_bytes": (c_int, [c_i64, c_i64, c_size_p]),
+    "lcr_gap_loss": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp,
+                             ctypes.c_double, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_double, c_vp, c_vp, ctypes.c_double, c_vp, c_vp, c_vp,
+                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "lcr_gap_loss_grad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_i64, ctypes.c_double, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lcr_min_dist": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lcr_min_dist_grad": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -10,9 +10,17 @@ def make_cfg():
                      "init_radius": 4.25 * init_voxel, "init_sigma": 2.0 * init_voxel, "group_norm": 32, "input_dim": 1,
                      "init_dim": 64, "output_dim": 256},
         "GAT": {"input_dim": 1024, "hidden_dim": 128, "output_dim": 256, "num_heads": 4, "num_layers": 4, "k": None},
-        "model": {"num_points_in_patch": 128, "num_sinkhorn_iterations": 100, "ground_truth_matching_radius": 0.45},
+        "model": {"num_points_in_patch": 128, "num_sinkhorn_iterations": 100, "ground_truth_matching_radius": 0.45,
+                  "ground_truth_corres_radius": 2.4},
         "Vote": {"MAX_TRANSLATE_RANGE": 4.2, "MLPS": [512, 256], "NMS_radius": 2.4},
         "fine_matching": {"acceptance_radius": 0.45, "mutual": False, "topk": 1, "confidence_threshold": 0, "use_dustbin": True,
                           "use_global_score": False, "correspondence_threshold": 3, "correspondence_limit": None, "num_refinement_steps": 5},
         "neighbor_limits": [64, 65, 74, 80],     # dataset_loop_detection.py:25,80 (training default)
+        # the loss terms (config_model.py:95-122), read by losses.py
+        "coarse_loss": {"positive_margin": 0.1, "negative_margin": 1.4, "positive_optimal": 0.1, "negative_optimal": 1.4, "log_scale": 40,
+                        "positive_overlap": 0.1},
+        "fine_loss": {"positive_radius": 0.45},
+        "distribution_loss": {"triplet_loss_gamma": 0.5},
+        "triplet_loss": {"margin": 0.5},
+        "loss": {"weight_coarse_loss": 1.0, "weight_vote_loss": 0.25, "weight_gap_loss": 5},
     }

@@ -1,5 +1,7 @@
 """Thin tensor-level wrappers over the C ABI (include/lcr_hip.h).  No arithmetic happens in Python: every function
-allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd)."""
+allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd), with one exception:
+gap_loss / min_dist have the gradient launchers gap_loss_grad / min_dist_grad beside them, which losses.py wraps in
+torch.autograd.Functions (gradients to the scores and to the queries only)."""
 import ctypes
 import os
 import threading
@@ -1185,3 +1187,160 @@ def scan_overlap(points, lengths, images, valid, pairs, rel, H=64, W=900, fov_up
                                      int(H), int(W), float(fov_up), float(fov_down), float(max_range), float(eps), _lib.ptr(counts),
                                      _lib.ptr(status), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_scan_overlap")
     return counts, status
+
+
+# ------------------------------------------------------------------------------------------------ registration loss terms
+class GapGeometry:
+    """The slice tables of lcr_gap_loss (include/lcr_hip.h) for B score slices of (n_b + 1) x (m_b + 1) grouped into pairs: n, m = host
+    lists of the slices' inner sizes, seg = the host list [P+1] of every pair's first slice.  Device tables are built once per object."""
+
+    def __init__(self, n, m, seg, device):
+        n, m, seg = np.asarray(n, dtype=np.int64).reshape(-1), np.asarray(m, dtype=np.int64).reshape(-1), np.asarray(seg, dtype=np.int64)
+        if len(n) != len(m) or len(n) < 1 or len(seg) < 2 or seg[0] != 0 or seg[-1] != len(n) or (np.diff(seg) < 1).any() or (n < 0).any() \
+                or (m < 0).any():
+            raise ValueError("GapGeometry: n and m per slice (>= 0), seg = [P+1] increasing slice offsets from 0 to B")
+        self.B, self.P, self.device = len(n), len(seg) - 1, device
+        self.n, self.m, self.seg = n, m, seg
+        pre = lambda x: np.concatenate([[0], np.cumsum(x)])
+        self.soff_h, self.roff_h, self.coff_h = pre((n + 1) * (m + 1)), pre(n), pre(m)
+        self.elems, self.rows, self.cols = int(self.soff_h[-1]), int(self.roff_h[-1]), int(self.coff_h[-1])
+        self.n_max, self.m_max = int(n.max()), int(m.max())
+        tab = host_values(np.stack([self.soff_h, self.roff_h, self.coff_h]), torch.int64, device)
+        self.soff, self.roff, self.coff = tab[0], tab[1], tab[2]
+        self.seg_start = host_values(seg, torch.int32, device)
+
+    @classmethod
+    def uniform(cls, B, N, M, device, seg=None):
+        return cls([N] * B, [M] * B, [0, B] if seg is None else seg, device)
+
+
+def _gap_u8(t, n, what):
+    if t is None or t.numel() != n:
+        raise ValueError("gap_loss: %s must have %d entries" % (what, n))
+    return (t.to(torch.uint8) if t.dtype != torch.uint8 else t).contiguous().view(-1)
+
+
+def gap_loss(scores, geom, gamma, pmask, qmask, points=None, overlaps=None, out=None, ws=None):
+    """lcr_gap_loss (include/lcr_hip.h): scores f32 [geom.elems] (the slices back to back), pmask [rows], qmask [cols] and ONE label source:
+    points = (p_pts f32 [rows,3], q_pts f32 [cols,3], transforms f32 [P,4,4], positive_radius) or
+    overlaps = (corr int64 [C,2], overlap f32 [C], counts: host list of the pairs' entry counts, positive_overlap).
+    -> dict: terms f32 [P,3] (row term, column term, mean), kept int32 [P,2], labels uint8 [elems], line_pos / line_hinge f64 and
+    line_count / line_active int32 [rows + cols], status int32 [1] (not read here: no host synchronisation).  out / ws: caller-owned
+    buffers under the same names."""
+    if (points is None) == (overlaps is None):
+        raise ValueError("gap_loss: exactly one of points / overlaps")
+    _lib.require_cuda(scores, pmask, qmask)
+    dev, g = scores.device, geom
+    if scores.dtype != torch.float32 or scores.numel() != g.elems:
+        raise ValueError("gap_loss: scores must be float32 with %d elements" % g.elems)
+    scores = scores.contiguous().view(-1)
+    pm, qm = _gap_u8(pmask, g.rows, "pmask"), _gap_u8(qmask, g.cols, "qmask")
+    null = None
+    pp = qp = T = corr = ov = cstart = null
+    radius = thr = 0.0
+    C = c_max = 0
+    if points is not None:
+        pp, qp, T, radius = points
+        _lib.require_cuda(pp, qp, T)
+        if pp.dtype != torch.float32 or qp.dtype != torch.float32 or T.dtype != torch.float32 or pp.numel() != 3 * g.rows \
+                or qp.numel() != 3 * g.cols or T.numel() != 16 * g.P:
+            raise ValueError("gap_loss: points f32 [rows,3] / [cols,3] and one f32 4x4 transform per pair")
+        pp, qp, T = pp.contiguous(), qp.contiguous(), T.contiguous()
+        source = 0
+    else:
+        corr, ov, counts, thr = overlaps
+        _lib.require_cuda(corr, ov)
+        counts = [int(c) for c in counts]
+        C = corr.shape[0]
+        if corr.dtype != torch.int64 or corr.dim() != 2 or corr.shape[1] != 2 or ov.dtype != torch.float32 or ov.numel() != C \
+                or len(counts) != g.P or sum(counts) != C:
+            raise ValueError("gap_loss: corr int64 [C,2], overlap f32 [C], one entry count per pair summing to C")
+        corr, ov = corr.contiguous(), ov.contiguous()
+        cstart = host_values(np.concatenate([[0], np.cumsum(counts)]), torch.int32, dev)
+        c_max = max(counts)
+        source = 1
+    out = {} if out is None else out
+    lines = g.rows + g.cols
+    for name, shape, dt in (("terms", (g.P, 3), torch.float32), ("kept", (g.P, 2), torch.int32), ("labels", (g.elems,), torch.uint8),
+                            ("line_pos", (lines,), torch.float64), ("line_hinge", (lines,), torch.float64),
+                            ("line_count", (lines,), torch.int32), ("line_active", (lines,), torch.int32), ("status", (1,), torch.int32)):
+        if name not in out:
+            out[name] = torch.empty(shape, dtype=dt, device=dev)
+    if ws is None:
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(_L().lcr_gap_loss_ws_bytes(g.rows, g.cols, ctypes.byref(nbytes)), "lcr_gap_loss_ws_bytes")
+        ws = _lib.workspace(nbytes.value, dev)
+    P = _lib.ptr
+    _lib.check(_L().lcr_gap_loss(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows, g.cols,
+                                 source, P(pp), P(qp), P(T), float(radius), P(corr), P(ov), P(cstart), C, c_max, float(thr), P(pm), P(qm),
+                                 float(gamma), P(out["terms"]), P(out["kept"]), P(out["labels"]), P(out["line_pos"]), P(out["line_hinge"]),
+                                 P(out["line_count"]), P(out["line_active"]), P(out["status"]), P(ws), ws.numel(), _sp(scores)), "lcr_gap_loss")
+    return out
+
+
+def gap_loss_grad(scores, geom, gamma, saved, upstream, dS=None):
+    """lcr_gap_loss_grad: saved = what gap_loss returned for the same scores, upstream f32 [P,2] (d loss / d row term, d column term)
+    -> dS f32 [geom.elems], every element written once."""
+    g = geom
+    _lib.require_cuda(scores, upstream)
+    if scores.dtype != torch.float32 or scores.numel() != g.elems or upstream.dtype != torch.float32 or upstream.numel() != 2 * g.P:
+        raise ValueError("gap_loss_grad: scores f32 [elems], upstream f32 [P,2]")
+    scores, upstream = scores.contiguous().view(-1), upstream.contiguous()
+    dS = torch.empty((g.elems,), dtype=torch.float32, device=scores.device) if dS is None else dS
+    P = _lib.ptr
+    _lib.check(_L().lcr_gap_loss_grad(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows,
+                                      g.cols, float(gamma), P(upstream), P(saved["kept"]), P(saved["labels"]), P(saved["line_pos"]),
+                                      P(saved["line_hinge"]), P(saved["line_count"]), P(saved["line_active"]), P(dS), _sp(scores)),
+               "lcr_gap_loss_grad")
+    return dS
+
+
+def _md_args(who, A, D, a_counts, d_counts, valid):
+    _lib.require_cuda(A, D, valid)
+    a_counts, d_counts = [int(c) for c in a_counts], [int(c) for c in d_counts]
+    if A.dtype != torch.float32 or D.dtype != torch.float32 or A.dim() != 2 or D.dim() != 2 or A.shape[1] != 3 or D.shape[1] != 3:
+        raise ValueError("%s: A [na,3] and D [nd,3] must be float32" % who)
+    if len(a_counts) != len(d_counts) or len(a_counts) < 1 or sum(a_counts) != A.shape[0] or sum(d_counts) != D.shape[0]:
+        raise ValueError("%s: one query count and one data count per segment, summing to the stacked rows" % who)
+    if valid is not None:
+        if valid.numel() != A.shape[0]:
+            raise ValueError("%s: valid must have one entry per query" % who)
+        valid = (valid.to(torch.uint8) if valid.dtype != torch.uint8 else valid).contiguous().view(-1)
+    return a_counts, d_counts, valid
+
+
+def min_dist(A, D, a_counts, d_counts, valid=None, starts=None, out=None):
+    """lcr_min_dist (include/lcr_hip.h): stacked queries A f32 [na,3] against stacked data D f32 [nd,3] in P segments given by the host
+    lists a_counts / d_counts -> dict: dist f32 [na], arg int32 [na] (segment-local, lower row on a tie), mean f32 [P] over the queries
+    with valid != 0, count int32 [P], and the device offset tables a_start / d_start for min_dist_grad.  out: caller-owned buffers under the same names."""
+    a_counts, d_counts, valid = _md_args("min_dist", A, D, a_counts, d_counts, valid)
+    dev, P_ = A.device, len(a_counts)
+    A, D = A.contiguous(), D.contiguous()
+    if starts is None:
+        tab = host_values(np.stack([np.concatenate([[0], np.cumsum(a_counts)]), np.concatenate([[0], np.cumsum(d_counts)])]), torch.int32, dev)
+        starts = (tab[0], tab[1])
+    out = {} if out is None else out
+    for name, shape, dt in (("dist", (A.shape[0],), torch.float32), ("arg", (A.shape[0],), torch.int32), ("mean", (P_,), torch.float32),
+                            ("count", (P_,), torch.int32)):
+        if name not in out:
+            out[name] = torch.empty(shape, dtype=dt, device=dev)
+    out.update({"a_start": starts[0], "d_start": starts[1], "valid": valid})
+    P = _lib.ptr
+    _lib.check(_L().lcr_min_dist(P(A), P(starts[0]), A.shape[0], P(D), P(starts[1]), D.shape[0], P(valid), P_, max(a_counts), P(out["dist"]),
+                                 P(out["arg"]), P(out["mean"]), P(out["count"]), _sp(A)), "lcr_min_dist")
+    return out
+
+
+def min_dist_grad(A, D, a_counts, d_counts, saved, upstream, dA=None):
+    """lcr_min_dist_grad: saved = what min_dist returned for the same inputs, upstream f32 [P] -> dA f32 [na,3]."""
+    a_counts, d_counts, _ = _md_args("min_dist_grad", A, D, a_counts, d_counts, None)
+    _lib.require_cuda(upstream)
+    if upstream.dtype != torch.float32 or upstream.numel() != len(a_counts):
+        raise ValueError("min_dist_grad: upstream must be float32 [P]")
+    A, D, upstream = A.contiguous(), D.contiguous(), upstream.contiguous()
+    dA = torch.empty_like(A) if dA is None else dA
+    P = _lib.ptr
+    _lib.check(_L().lcr_min_dist_grad(P(A), P(saved["a_start"]), A.shape[0], P(D), P(saved["d_start"]), D.shape[0], P(saved["valid"]),
+                                      len(a_counts), max(a_counts), P(saved["arg"]), P(saved["dist"]), P(saved["count"]), P(upstream), P(dA),
+                                      _sp(A)), "lcr_min_dist_grad")
+    return dA
