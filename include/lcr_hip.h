@@ -910,6 +910,51 @@ int lcr_min_dist_grad(const float* A, const int32_t* a_start, int64_t na, const 
                       const uint8_t* valid, int P, int64_t q_max, const int32_t* arg, const float* dist, const int32_t* count,
                       const float* upstream, float* dA, void* stream);
 
+/* The Adan optimiser (the reference's experiments/lcrnet/adan.py, arXiv 2208.06677) as ONE pass over a list of fp32 tensors, and the
+ * global gradient norm it clips by.  Restated in tests/adan_restatement.py; the Python side is lcrnet_amd.adan.Adan.
+ *
+ * LcrAdanTensor is a HOST array of T entries: the six DEVICE arrays of one tensor (parameter p, gradient g, exp_avg m, exp_avg_sq n,
+ * exp_avg_diff d, pre_grad pg), each numel floats, and `fresh` != 0 for a tensor without a previous gradient (the group's first step, or
+ * a parameter that has just gained a gradient).  The table is consumed before the call returns: it is packed into kernel arguments, a
+ * few dozen tensors per launch, so nothing is copied to the device, nothing outlives the call and the host never waits.  Pointers need
+ * 4-byte alignment only; a tensor whose arrays are all 16-byte aligned moves in 16-byte accesses.  The arrays of a call must not overlap.
+ *
+ * lcr_adan_grad_norm (g and numel of the entries only): the list is cut into chunks of 4096 elements, tensor after tensor, a tensor's
+ *   last chunk being short.  One workgroup per chunk sums (double)g * (double)g in a fixed order into partial[chunk] (ws, fp64); one
+ *   workgroup then sums the partials in a fixed order (thread k takes k, k + 256, ... ascending; the 256 sums by a fixed tree) and writes
+ *   norm_clip[0] = (float)sqrt(sum) and norm_clip[1] = fminf((float)max_grad_norm / (norm + (float)eps), 1.0f), or 1 when
+ *   max_grad_norm == 0 (no clipping).  No atomics: the same gradients give the same bytes on every run, however the launches are cut.
+ * lcr_adan_step, per element, fp32 with every operation rounded; the doubles of LcrAdanHyper and 1 - beta_k, 1 -/+ lr * weight_decay
+ *   (formed in double) are rounded to fp32 once:
+ *     c = clip ? *clip : 1;   g' = c < 1 ? g * c : g            (when c < 1, g' is also stored to g: the reference clips p.grad in place)
+ *     diff = fresh ? 0 : g' - pg;   pg = g'
+ *     u = g' + beta2 * diff
+ *     m = m * beta1 + (1 - beta1) * g';   d = d * beta2 + (1 - beta2) * diff;   n = n * beta3 + ((1 - beta3) * u) * u
+ *     den = sqrt(n) / bias3_sqrt + eps
+ *     upd = (m / bias1 + (beta2 * d) / bias2) / den
+ *     no_prox ?  p = p * (1 - lr * wd) - lr * upd   :   p = (p - lr * upd) / (1 + lr * wd)
+ *   bias1 = 1 - beta1^step, bias2 = 1 - beta2^step, bias3_sqrt = sqrt(1 - beta3^step), computed by the caller.  On a fresh tensor pg is
+ *   written and never read, and d becomes exactly d * beta2.  clip is a DEVICE float (norm_clip + 1), or NULL for no clipping.
+ * Every element is read and written by one thread, so a tensor's result does not depend on the tensors around it.
+ * All entries are asynchronous and stream-ordered.  LCR_EARG, launching nothing, for T < 0, numel < 0 or > 2^35, a null pointer with
+ * numel > 0, a pointer that is not 4-byte aligned, a negative or NaN max_grad_norm / eps; LCR_ESPACE for a workspace below
+ * lcr_adan_ws_bytes.  T == 0 and numel == 0 are legal: no work (the norm of nothing is 0). */
+typedef struct {
+  float *p, *g, *m, *n, *d, *pg;
+  int64_t numel;
+  int32_t fresh;
+  int32_t pad;
+} LcrAdanTensor;
+typedef struct {
+  double beta1, beta2, beta3, bias1, bias2, bias3_sqrt, lr, weight_decay, eps;
+  int32_t no_prox;
+  int32_t pad;
+} LcrAdanHyper;
+int lcr_adan_ws_bytes(const LcrAdanTensor* t, int T, size_t* bytes);
+int lcr_adan_grad_norm(const LcrAdanTensor* t, int T, double max_grad_norm, double eps, float* norm_clip, void* ws, size_t ws_bytes,
+                       void* stream);
+int lcr_adan_step(const LcrAdanTensor* t, int T, const LcrAdanHyper* h, const float* clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,4 @@ __version__ = "0.1.0"
 
 from . import _lib  # noqa: F401
 from . import losses  # noqa: F401,E402
+from . import adan  # noqa: F401,E402

@@ -155,6 +155,9 @@ _SIGS = {
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lcr_min_dist": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "lcr_min_dist_grad": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "lcr_adan_ws_bytes": (c_int, [c_vp, c_int, c_size_p]),
+    "lcr_adan_grad_norm": (c_int, [c_vp, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_size_t, c_vp]),
+    "lcr_adan_step": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
 }
 
 

@@ -23,4 +23,7 @@ def make_cfg():
         "distribution_loss": {"triplet_loss_gamma": 0.5},
         "triplet_loss": {"margin": 0.5},
         "loss": {"weight_coarse_loss": 1.0, "weight_vote_loss": 0.25, "weight_gap_loss": 5},
+        # the Adan optimiser of the loop-detection trainer (config_ld.py:69-79), read by adan.Adan.from_cfg
+        "optimadan": {"lr": 1e-4, "lr_decay": 0.95, "lr_decay_steps": 4, "weight_decay": 1e-6, "opt_betas": None, "opt_eps": None,
+                      "max_grad_norm": 0, "no_prox": False},
     }

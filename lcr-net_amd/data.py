@@ -307,7 +307,7 @@ test_loop_detection_collate_fn_stack_mode_online.__test__ = False     # a collat
 # ---- training-time collates (experiments/lcrnet/data.py:130-348), mirrored by name ------------------------------------------------
 # Host logic only (stacking order, which keys are popped / unwrapped); the collate proper is the same device-side
 # precompute_data_stack_mode.  They exist so that the reference's trainval_* scripts can keep their DataLoader code when the
-# pre-processing moves to the GPU; the training loop itself (losses, optimiser) is out of scope.
+# pre-processing moves to the GPU; the loss terms are in losses.py and the optimiser in adan.py, the model backward is out of scope.
 def _precompute_or_keep(merged, feats, points, lengths, batch_size, num_stages, voxel_size, search_radius, neighbor_limits, precompute_data,
                         device):
     merged["features"] = feats

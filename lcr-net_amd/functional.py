@@ -1344,3 +1344,52 @@ def min_dist_grad(A, D, a_counts, d_counts, saved, upstream, dA=None):
                                       len(a_counts), max(a_counts), P(saved["arg"]), P(saved["dist"]), P(saved["count"]), P(upstream), P(dA),
                                       _sp(A)), "lcr_min_dist_grad")
     return dA
+
+
+# ------------------------------------------------------------------------------------------------ Adan optimiser step
+class AdanHyper(ctypes.Structure):
+    """LcrAdanHyper (include/lcr_hip.h)."""
+    _fields_ = [(k, ctypes.c_double) for k in ("beta1", "beta2", "beta3", "bias1", "bias2", "bias3_sqrt", "lr", "weight_decay", "eps")] + \
+               [("no_prox", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+ADAN_TENSOR_WORDS = 8       # LcrAdanTensor as int64 words: p, g, m, n, d, pg, numel, fresh (low half; the high half is padding)
+
+
+def adan_table(params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, pre_grads, fresh):
+    """The HOST LcrAdanTensor array of lcr_adan_grad_norm / lcr_adan_step as an int64 array [T, 8].  The tensors must be CUDA, float32
+    and contiguous (checked by the caller: lcrnet_amd.adan); the table holds raw pointers, so it is only good while they live."""
+    T = len(grads)
+    tab = np.zeros((T, ADAN_TENSOR_WORDS), dtype=np.int64)
+    for col, ts in enumerate((params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, pre_grads)):
+        if ts is not None:
+            tab[:, col] = [t.data_ptr() for t in ts]
+    tab[:, 6] = [t.numel() for t in grads]
+    if fresh is not None:
+        tab[:, 7] = fresh
+    return tab
+
+
+def adan_ws_bytes(table):
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_L().lcr_adan_ws_bytes(table.ctypes.data, len(table), ctypes.byref(nbytes)), "lcr_adan_ws_bytes")
+    return nbytes.value
+
+
+def adan_grad_norm(table, max_grad_norm, eps, device, norm_clip=None, ws=None):
+    """lcr_adan_grad_norm over the gradients of `table` (adan_table; only g and numel are read) -> norm_clip f32 [2] on the device:
+    the global L2 norm and min(max_grad_norm / (norm + eps), 1).  No host synchronisation."""
+    if norm_clip is None:
+        norm_clip = torch.empty(2, dtype=torch.float32, device=device)
+    if ws is None:
+        ws = _lib.workspace(adan_ws_bytes(table), device)
+    _lib.check(_L().lcr_adan_grad_norm(table.ctypes.data, len(table), float(max_grad_norm), float(eps), _lib.ptr(norm_clip), _lib.ptr(ws),
+                                       ws.numel() * ws.element_size(), _lib.stream_ptr(device)), "lcr_adan_grad_norm")
+    return norm_clip
+
+
+def adan_step(table, hyper, clip, device):
+    """lcr_adan_step: one fused pass over the tensors of `table` (adan_table); hyper = AdanHyper, clip = a device float32 tensor of one
+    element (the second entry of adan_grad_norm's result) or None.  No host synchronisation."""
+    _lib.check(_L().lcr_adan_step(table.ctypes.data, len(table), ctypes.addressof(hyper), _lib.ptr(clip), _lib.stream_ptr(device)),
+               "lcr_adan_step")
