@@ -264,8 +264,7 @@ __global__ __launch_bounds__(256) void k_attention_topk(const float* __restrict_
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t qi = static_cast<int64_t>(blockIdx.x) * 4 + w;
   if (qi >= seg.q_off[seg.P]) return;                           // whole wavefront (no block-wide barriers below)
-  int p = 0;
-  while (p + 1 < seg.P && qi >= seg.q_off[p + 1]) ++p;
+  const int p = cloud_of(seg.q_off, seg.P, qi);
   const int head = blockIdx.y, ld = heads * AT_D;
   const int64_t ko = seg.k_off[p];
   const int m = seg.k_off[p + 1] - seg.k_off[p], kk = min(seg.kk[p], m);

@@ -22,6 +22,18 @@ constexpr int GN_REPLICAS = 8;
 
 void set_error(const char* fmt, ...);
 
+// B stacked clouds (or pairs) given by host lengths: exclusive row offsets, off[B] = total rows.  Passed by value in kernel arguments.
+constexpr int GRID_MAX_B = 64;   // clouds per call
+struct Stack {
+  int     B;
+  int64_t off[GRID_MAX_B + 1];
+};
+// The domain of every such table: 1 <= B <= GRID_MAX_B, lengths non-null, each length and the total in [0, 2^31-1].  Fills *out and
+// returns LCR_OK, or sets the error text in the name of entry point `who` and returns LCR_EARG.  No HIP call.
+int stack_from_lengths(const char* who, const int64_t* lengths, int B, Stack* out);
+// One launch of one workgroup: the table's lengths to len[B] and / or its offsets to off[B + 1], *status cleared (each may be null).
+int stack_to_device(const char* who, const Stack& C, int64_t* len, int64_t* off, int32_t* status, hipStream_t st);
+
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -119,11 +131,29 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
   return (1ull << (threadIdx.x & 63)) - 1ull;
 }
 
-// cloud that owns stacked row i, given exclusive prefix offsets off[0..B] (off[B] = total)
-__device__ __forceinline__ int cloud_of(const int64_t* off, int B, int64_t i) {
+// the fence that makes a wavefront's LDS writes visible to its own other lanes (no workgroup barrier: the data is wave-private)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// cloud that owns stacked row i, given exclusive prefix offsets off[0..B] (off[B] = total); the comparison is made in the common type
+// of the row and the offsets, as written out at the call site it replaces
+template <typename T, typename I>
+__device__ __forceinline__ int cloud_of(const T* off, int B, I i) {
   int b = 0;
   while (b + 1 < B && i >= off[b + 1]) ++b;
   return b;
+}
+
+// the device side of stack_to_device, for kernels that carry a table anyway: the lengths and / or offsets of a Stack's off[0..B] to
+// device memory, strided over the threads of one workgroup
+__device__ __forceinline__ void stack_store(const int64_t* C_off, int B, int64_t* __restrict__ len, int64_t* __restrict__ off) {
+  for (int b = threadIdx.x; b <= B; b += blockDim.x) {
+    if (off) off[b] = C_off[b];
+    if (len && b < B) len[b] = C_off[b + 1] - C_off[b];
+  }
 }
 
 // order-preserving float <-> uint mapping (for atomicMin/Max on floats)

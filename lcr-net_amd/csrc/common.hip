@@ -1,5 +1,6 @@
 // common.hip — error plumbing + device-wide scan used by the grid/sort stages.
 #include <atomic>
+#include <climits>
 #include <cstdarg>
 #include <mutex>
 #include <utility>
@@ -18,6 +19,37 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+int stack_from_lengths(const char* who, const int64_t* lengths, int B, Stack* out) {
+  if (B < 1 || B > GRID_MAX_B || !lengths) {
+    set_error("%s: outside the domain (1 <= B <= %d, lengths non-null): B=%d%s", who, GRID_MAX_B, B, lengths ? "" : ", null lengths");
+    return LCR_EARG;
+  }
+  out->B = B;
+  out->off[0] = 0;
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > INT32_MAX) {
+      set_error("%s: cloud %d has a negative or too large length (%lld)", who, b, static_cast<long long>(lengths[b]));
+      return LCR_EARG;
+    }
+    out->off[b + 1] = out->off[b] + lengths[b];
+  }
+  if (out->off[B] > INT32_MAX) {
+    set_error("%s: more than 2^31-1 rows (%lld)", who, static_cast<long long>(out->off[B]));
+    return LCR_EARG;
+  }
+  return LCR_OK;
+}
+
+__global__ void k_stack_store(Stack C, int64_t* __restrict__ len, int64_t* __restrict__ off, int32_t* __restrict__ status) {
+  stack_store(C.off, C.B, len, off);
+  if (status && threadIdx.x == 0) *status = 0;
+}
+
+int stack_to_device(const char* who, const Stack& C, int64_t* len, int64_t* off, int32_t* status, hipStream_t st) {
+  hipLaunchKernelGGL(k_stack_store, dim3(1), dim3(64), 0, st, C, len, off, status);
+  return check_launch(who);
 }
 
 static std::atomic<unsigned> g_turn_next{0}, g_turn_serving{0};

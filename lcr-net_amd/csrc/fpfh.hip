@@ -2,7 +2,7 @@
 // registration_ransac_based_on_feature_matching is documented with) for B stacked clouds in one call, exact in its votes and
 // batch-invariant.  Semantics in include/lcr_hip.h (lcr_fpfh).
 //
-// Per call: k_fpfh_init (cloud lengths to the device), the support grid and the ordered query of radius_search.hip with limit = max_nn
+// Per call: stack_to_device (cloud lengths to the device), the support grid and the ordered query of radius_search.hip with limit = max_nn
 // into an int32 [N, max_nn] table in the workspace (global rows, padded with N), then
 //   k_spfh   one wavefront per row.  Lane l takes ranks l and l + 64 of the row's list, drops the row itself and the padding, computes the
 //            Darboux pair features in fp64 (two divisions, two square roots and one atan2 per pair) and votes into a 33-entry LDS integer
@@ -11,7 +11,7 @@
 //            walks the list serially, acc_j += spfh(nb, j) / d2(nb): each step is one coalesced 264-byte read of a neighbour's SPFH row, the
 //            order of the sum is the list's own, and no cross-lane reduction is needed at all.  Loads are issued four neighbours ahead of
 //            the dependent fp64 division chain.  The three block sums are taken from LDS in ascending bin order.
-// d2 is recomputed with the un-contracted helpers of common.h, so it has the bits the search compared.
+// d2 is recomputed with grid_d2 (grid.h), so it has the bits the search compared.
 #include <climits>
 #include <cmath>
 
@@ -24,24 +24,8 @@ constexpr int FP_WAVES = 4;         // wavefronts (= rows) per workgroup
 constexpr int FP_MAX_NN = 128;      // largest max_nn: two list entries per lane
 constexpr int FP_BINS = 33;
 
-struct FpfhClouds {
-  int     B;
-  int64_t len[GRID_MAX_B];
-};
-
-__device__ __forceinline__ void fp_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ void k_fpfh_init(FpfhClouds C, int64_t* __restrict__ len) {
-  for (int b = threadIdx.x; b < C.B; b += blockDim.x) len[b] = C.len[b];
-}
-
 __device__ __forceinline__ float fp_d2(const float* __restrict__ pts, int64_t i, int64_t j) {
-  const float dx = fsub(pts[3 * i], pts[3 * j]), dy = fsub(pts[3 * i + 1], pts[3 * j + 1]), dz = fsub(pts[3 * i + 2], pts[3 * j + 2]);
-  return fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
+  return grid_d2(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]);
 }
 
 __device__ __forceinline__ int fp_bin(double scaled) {
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(FP_WAVES * 64) void k_spfh(const float* __restrict_
   if (i >= n) return;                                             // wave-uniform
   int* hist = s_hist[w];
   if (lane < FP_BINS) hist[lane] = 0;
-  fp_wave_sync();
+  wave_sync();
   int m = 0;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(FP_WAVES * 64) void k_spfh(const float* __restrict_
     }
     m += __popcll(wave_ballot(valid));
   }
-  fp_wave_sync();
+  wave_sync();
   if (lane < FP_BINS) {
     const double s = m > 0 ? static_cast<double>(hist[lane] * 100) / static_cast<double>(m) : 0.0;
     spfh64[i * FP_BINS + lane] = s;
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(FP_WAVES * 64) void k_fpfh(const float* __restrict_
     }
     k += __popcll(mask);
   }
-  fp_wave_sync();
+  wave_sync();
   const int bin = lane < FP_BINS ? lane : FP_BINS - 1;            // lanes 33..63 shadow bin 32 and write nothing
   double acc = 0.0;
   for (int e0 = 0; e0 < k; e0 += 4) {
@@ -173,7 +157,7 @@ __global__ __launch_bounds__(FP_WAVES * 64) void k_fpfh(const float* __restrict_
       if (e0 + u < k) acc = dadd(acc, v[u] / static_cast<double>(dd[e0 + u]));
   }
   if (lane < FP_BINS) s_acc[w][lane] = acc;
-  fp_wave_sync();
+  wave_sync();
   if (lane < FP_BINS) {
     const int blk = lane / 11;
     double s = 0.0;
@@ -225,28 +209,16 @@ extern "C" int lcr_fpfh_ws_bytes(int B, int64_t n, int max_nn, size_t* bytes) {
 
 extern "C" int lcr_fpfh(const float* points, const float* normals, const int64_t* lengths, int B, float radius, int max_nn, float* features,
                         float* spfh, int32_t* count, void* ws, size_t ws_bytes, void* stream) {
-  if (B < 1 || B > GRID_MAX_B || !(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 2 || max_nn > FP_MAX_NN) {
-    set_error("lcr_fpfh: outside the domain (1 <= B <= %d, radius > 0 with radius*radius finite, 2 <= max_nn <= %d): B=%d radius=%g max_nn=%d",
-              GRID_MAX_B, FP_MAX_NN, B, static_cast<double>(radius), max_nn);
+  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 2 || max_nn > FP_MAX_NN) {
+    set_error("lcr_fpfh: outside the domain (radius > 0 with radius*radius finite, 2 <= max_nn <= %d): radius=%g max_nn=%d", FP_MAX_NN,
+              static_cast<double>(radius), max_nn);
     return LCR_EARG;
   }
-  if (!lengths || !ws) {
-    set_error("lcr_fpfh: null pointer");
-    return LCR_EARG;
-  }
-  FpfhClouds C;
-  C.B = B;
-  int64_t n = 0;
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > INT32_MAX) {
-      set_error("lcr_fpfh: cloud %d has a negative or too large length (%lld)", b, static_cast<long long>(lengths[b]));
-      return LCR_EARG;
-    }
-    C.len[b] = lengths[b];
-    n += lengths[b];
-  }
-  if (n > INT32_MAX || (n > 0 && (!points || !normals || !features))) {
-    set_error("lcr_fpfh: more than 2^31-1 rows, or a null point / normal / feature array (n=%lld)", static_cast<long long>(n));
+  Stack C;
+  if (stack_from_lengths("lcr_fpfh", lengths, B, &C)) return LCR_EARG;
+  const int64_t n = C.off[B];
+  if (!ws || (n > 0 && (!points || !normals || !features))) {
+    set_error("lcr_fpfh: null workspace, or a null point / normal / feature array (n=%lld)", static_cast<long long>(n));
     return LCR_EARG;
   }
   size_t grid_bytes = 0;
@@ -258,8 +230,7 @@ extern "C" int lcr_fpfh(const float* points, const float* normals, const int64_t
   }
   if (n == 0) return LCR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_fpfh_init, dim3(1), dim3(64), 0, st, C, L.len);
-  int rc = check_launch("lcr_fpfh (init)");
+  int rc = stack_to_device("lcr_fpfh (init)", C, L.len, nullptr, nullptr, st);
   if (rc) return rc;
   rc = lcr_support_grid_build(points, L.len, B, n, radius, nullptr, ws, grid_bytes, stream);
   if (rc) return rc;

@@ -2,7 +2,7 @@
 // run it: data/Kitti/generate_kitti_pairs.py:145-147) for S pairs of dense clouds in one call, exact and batch-invariant.  The semantics
 // (correspondence step, update, loop, outputs) are stated in include/lcr_hip.h next to the entry points.
 //
-// Per call: k_icp_init (state from `init`, target lengths to the device), the support grid of radius_search.hip over the targets
+// Per call: k_icp_init (state from `init`, target lengths to the device: stack_store), the support grid of radius_search.hip over the targets
 // (cell >= r, built once), then per iteration two stream-ordered launches:
 //   k_icp_match   the hot path.  One thread per source row (a block = ICP_BLOCK consecutive rows of one pair): fp64 transform to fp32 q,
 //                 arg-min of the (d², target row) key over the nine x-runs of q's 3x3x3 cell neighbourhood (the rule of
@@ -22,8 +22,10 @@
 // Point-to-plane (lcr_icp_point_to_plane) runs the same loop with k_icp_match_plane / k_icp_update_plane: the same nearest-partner search
 // (icp_nearest), a row block of ICP_PLANE_MOM doubles (count, sum d², usable rows, the 21 entries of A = sum J J^T, g = sum J r), and an
 // fp64 LDL^T solve of A x = -g in the update.
+#include <algorithm>
 #include <climits>
 #include <cmath>
+#include <string>
 
 #include "common.h"
 #include "grid.h"
@@ -36,7 +38,7 @@ constexpr int ICP_UNROLL = 4;    // candidate loads in flight per lane
 constexpr int ICP_MOM = 17;      // count, sum d², sum dp[3], sum dr[3], sum dp dr^T [9]  (dp = p - anchor_src, dr = r - anchor_tgt)
 constexpr int ICP_PLANE_MOM = 30;  // count, sum d², usable rows, A = sum J J^T [21, upper triangle row by row], g = sum J r [6]
 
-// pair table, by value in the kernel arguments (S <= GRID_MAX_B): stacked row offsets and the first k_icp_match block of every pair
+// pair table, by value in the kernel arguments (S <= GRID_MAX_B): the first k_icp_match block of every pair and the off[] of the two Stacks
 struct IcpPairs {
   int     S;
   int     blk_off[GRID_MAX_B + 1];
@@ -85,40 +87,24 @@ __device__ __forceinline__ void icp_slab_sum(const double* __restrict__ slab, in
 __device__ __forceinline__ uint64_t icp_nearest(const GridCloud& c, const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
                                                 float r2, float qx, float qy, float qz) {
   uint64_t best = ~0ull;
-  if (c.dim[0] > 0) {
-    // the cells of cell_coord() (clamped to [-2, dim+1]) and their 3x3x3 neighbourhood inside the box, as k_radius_query enumerates them
-    const int cx = cell_coord(qx, c.org[0], c.inv_cell, c.dim[0]);
-    const int cy = cell_coord(qy, c.org[1], c.inv_cell, c.dim[1]);
-    const int cz = cell_coord(qz, c.org[2], c.inv_cell, c.dim[2]);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, c.dim[0] - 1);
-    if (x0 <= x1) {
-      for (int zz = max(cz - 1, 0); zz <= min(cz + 1, c.dim[2] - 1); ++zz)
-        for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.dim[1] - 1); ++yy) {
-          const int crow = c.cell_base + (zz * c.dim[1] + yy) * c.dim[0];
-          const int e = cell_start[crow + x1 + 1];
-          // ICP_UNROLL loads in flight per trip; the tail re-reads the run's last candidate, which cannot change an arg-min
-          for (int k = cell_start[crow + x0]; k < e; k += ICP_UNROLL) {
-            float4 p[ICP_UNROLL];
+  // the candidates are the runs of grid_for_each_run (grid.h), the neighbourhood every client of the grid sees; an empty target has none,
+  // and asking first spares its rows the cell arithmetic
+  if (c.dim[0] > 0) grid_for_each_run(c, cell_start, qx, qy, qz, [&](int k0, int e) {
+    // ICP_UNROLL loads in flight per trip; the tail re-reads the run's last candidate, which cannot change an arg-min
+    for (int k = k0; k < e; k += ICP_UNROLL) {
+      float4 p[ICP_UNROLL];
 #pragma unroll
-            for (int u = 0; u < ICP_UNROLL; ++u) p[u] = sorted[min(k + u, e - 1)];
+      for (int u = 0; u < ICP_UNROLL; ++u) p[u] = sorted[min(k + u, e - 1)];
 #pragma unroll
-            for (int u = 0; u < ICP_UNROLL; ++u) {
-              const float dx = fsub(qx, p[u].x), dy = fsub(qy, p[u].y), dz = fsub(qz, p[u].z);
-              const float d2 = fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
-              const uint64_t key = (static_cast<uint64_t>(__float_as_uint(d2)) << 32) | __float_as_uint(p[u].w);
-              best = (d2 < r2 && key < best) ? key : best;
-            }
-          }
-        }
+      for (int u = 0; u < ICP_UNROLL; ++u) {
+        const float d2 = grid_d2(qx, qy, qz, p[u]);
+        const uint64_t key = grid_key(d2, p[u].w);
+        // &, not &&: `best` is captured by reference, and a short circuit over it stays a branch in the compiled loop
+        best = ((d2 < r2) & (key < best)) ? key : best;
+      }
     }
-  }
+  });
   return best;
-}
-
-__device__ __forceinline__ int icp_pair_of_block(const IcpPairs& P, int blk) {
-  int s = 0;
-  while (s + 1 < P.S && blk >= P.blk_off[s + 1]) ++s;
-  return s;
 }
 
 // the shared head of k_icp_match*: source row i of pair s under the pair's current T.  Tm = rows 0..2 of T, p = the row in fp64; the partner
@@ -144,6 +130,7 @@ __global__ void k_icp_init(IcpPairs P, const double* __restrict__ init, int hist
                            double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ done, int32_t* __restrict__ running,
                            int64_t* __restrict__ tgt_len, double* __restrict__ T_hist, double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
   if (threadIdx.x < 2) running[threadIdx.x] = 0;
+  stack_store(P.tgt_off, P.S, tgt_len, nullptr);
   for (int s = threadIdx.x; s < P.S; s += blockDim.x) {
     const int64_t ns = P.src_off[s + 1] - P.src_off[s], nt = P.tgt_off[s + 1] - P.tgt_off[s];
     for (int k = 0; k < 16; ++k) T[16 * s + k] = init[16 * s + k];
@@ -151,7 +138,6 @@ __global__ void k_icp_init(IcpPairs P, const double* __restrict__ init, int hist
     rmse[s] = 0.0;
     iters[s] = 0;
     done[s] = (ns == 0 || nt == 0) ? 1 : 0;          // empty source or target: init, fitness 0, rmse 0, 0 iterations
-    tgt_len[s] = nt;
     const int64_t h0 = static_cast<int64_t>(s) * hist_rows;
     if (T_hist)
       for (int k = 0; k < 16; ++k) T_hist[16 * h0 + k] = init[16 * s + k];
@@ -169,7 +155,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match(IcpPairs P, const float
                                                          const int32_t* __restrict__ done, double* __restrict__ slab, int32_t* __restrict__ corr) {
   __shared__ double s_red[ICP_BLOCK / 64][ICP_MOM];
   const int blk = blockIdx.x;
-  const int s = icp_pair_of_block(P, blk);
+  const int s = cloud_of(P.blk_off, P.S, blk);
   if (done[s]) return;                                         // workgroup-uniform
   const int64_t a = P.src_off[s], n = P.src_off[s + 1] - a, tb = P.tgt_off[s];
   const int64_t row = static_cast<int64_t>(blk - P.blk_off[s]) * ICP_BLOCK + threadIdx.x;     // pair-local
@@ -300,7 +286,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_match_plane(IcpPairs P, const
                                                                double* __restrict__ slab, int32_t* __restrict__ corr) {
   __shared__ double s_red[ICP_BLOCK / 64][ICP_PLANE_MOM];
   const int blk = blockIdx.x;
-  const int s = icp_pair_of_block(P, blk);
+  const int s = cloud_of(P.blk_off, P.S, blk);
   if (done[s]) return;                                         // workgroup-uniform
   const int64_t a = P.src_off[s], n = P.src_off[s + 1] - a, tb = P.tgt_off[s];
   const int64_t row = static_cast<int64_t>(blk - P.blk_off[s]) * ICP_BLOCK + threadIdx.x;     // pair-local
@@ -470,34 +456,30 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
             double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist, double* rmse_hist,
             int check_every, void* ws, size_t ws_bytes, void* stream) {
   const float r = max_correspondence_distance;
-  if (S < 1 || S > GRID_MAX_B || max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
+  if (max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
       !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0)) {
-    set_error("%s: outside the domain (1 <= S <= %d, 0 <= max_iteration <= %d, r > 0 with r*r finite, relative "
-              "criteria >= 0, check_every >= 0): S=%d max_iteration=%d r=%g check_every=%d", name, GRID_MAX_B, ICP_MAX_ITER, S, max_iteration,
-              static_cast<double>(r), check_every);
+    set_error("%s: outside the domain (0 <= max_iteration <= %d, r > 0 with r*r finite, relative criteria >= 0, check_every >= 0): "
+              "max_iteration=%d r=%g check_every=%d", name, ICP_MAX_ITER, max_iteration, static_cast<double>(r), check_every);
     return LCR_EARG;
   }
-  if (!src_len || !tgt_len || !init || !T || !fitness || !inlier_rmse || !iterations || !ws) {
+  if (!init || !T || !fitness || !inlier_rmse || !iterations || !ws) {
     set_error("%s: null pointer", name);
     return LCR_EARG;
   }
+  Stack sources, targets;
+  const std::string who(name);                                   // the error text says which of the two tables is at fault
+  if (stack_from_lengths((who + ": source lengths").c_str(), src_len, S, &sources) ||
+      stack_from_lengths((who + ": target lengths").c_str(), tgt_len, S, &targets))
+    return LCR_EARG;
   IcpPairs P;
   P.S = S;
+  std::copy(sources.off, sources.off + S + 1, P.src_off);
+  std::copy(targets.off, targets.off + S + 1, P.tgt_off);
   P.blk_off[0] = 0;
-  P.src_off[0] = P.tgt_off[0] = 0;
-  for (int s = 0; s < S; ++s) {
-    if (src_len[s] < 0 || tgt_len[s] < 0 || src_len[s] > INT32_MAX || tgt_len[s] > INT32_MAX) {
-      set_error("%s: pair %d has a negative or too large length (%lld, %lld)", name, s, static_cast<long long>(src_len[s]),
-                static_cast<long long>(tgt_len[s]));
-      return LCR_EARG;
-    }
-    P.src_off[s + 1] = P.src_off[s] + src_len[s];
-    P.tgt_off[s + 1] = P.tgt_off[s] + tgt_len[s];
-    P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
-  }
+  for (int s = 0; s < S; ++s) P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
   const int64_t ns = P.src_off[S], nt = P.tgt_off[S];
-  if (ns > INT32_MAX || nt > INT32_MAX || (ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals)))) {
-    set_error("%s: more than 2^31-1 rows, or a null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
+  if ((ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals)))) {
+    set_error("%s: null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
     return LCR_EARG;
   }
   constexpr int mom = PLANE ? ICP_PLANE_MOM : ICP_MOM;

@@ -126,8 +126,7 @@ __global__ __launch_bounds__(256) void k_inlier_count_seg(const float* __restric
     return;
   }
   if (threadIdx.x == 0) {
-    int sg = 0;
-    while (sg + 1 < S && h >= seg_hyp_start[sg + 1]) ++sg;
+    const int sg = cloud_of(seg_hyp_start, S, h);
     s_lo = seg_row_start[sg];
     s_hi = seg_row_start[sg + 1];
     s_c = 0;
@@ -239,8 +238,7 @@ __global__ __launch_bounds__(256) void k_inlier_weights_seg(const float* __restr
                                                             const float* __restrict__ src, const float* __restrict__ ref,
                                                             const float* __restrict__ score, int n, float radius, float* __restrict__ w_out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    int sg = 0;
-    while (sg + 1 < S && i >= seg_row_start[sg + 1]) ++sg;
+    const int sg = cloud_of(seg_row_start, S, i);
     const float* t = T_seg + 16 * sg;
     w_out[i] = residual(t, src, ref, i) < radius ? score[i] : 0.f;
   }

@@ -186,19 +186,12 @@ __global__ __launch_bounds__(64) void k_nc_overlap(const float* __restrict__ tp,
   }
 }
 
-// ref row r of the stack -> (pair, node)
-__device__ __forceinline__ int nc_pair_of_row(const NcPlan& pl, int r) {
-  int p = 0;
-  while (p + 1 < pl.P && r >= pl.ro[p + 1]) ++p;
-  return p;
-}
-
 __global__ __launch_bounds__(256) void k_nc_rowcount(const float* __restrict__ table, NcPlan pl, int R, int32_t* __restrict__ count) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r > R) return;
   int n = 0;
   if (r < R) {
-    const int p = nc_pair_of_row(pl, r);
+    const int p = cloud_of(pl.ro, pl.P, r);
     const int N = pl.mo[2 * p + 2] - pl.mo[2 * p + 1];
     const float* row = table + pl.to[p] + static_cast<int64_t>(r - pl.ro[p]) * N;
     for (int j0 = 0; j0 < N; j0 += WAVE) n += __popcll(wave_ballot(j0 + lane_id() < N && row[j0 + lane_id()] != 0.f));
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(256) void k_nc_write(const float* __restrict__ tabl
                                                   int32_t* __restrict__ corr, float* __restrict__ overlap) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
-  const int p = nc_pair_of_row(pl, r);
+  const int p = cloud_of(pl.ro, pl.P, r);
   const int N = pl.mo[2 * p + 2] - pl.mo[2 * p + 1], i = r - pl.ro[p];
   const float* row = table + pl.to[p] + static_cast<int64_t>(i) * N;
   int64_t base = scan[r];

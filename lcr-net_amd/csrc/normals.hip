@@ -2,7 +2,7 @@
 // call: utils/utils/open3d.py:53-58) for B stacked clouds in one call, exact and batch-invariant.  Semantics in include/lcr_hip.h
 // (lcr_estimate_normals).
 //
-// Per call: k_normals_init (cloud lengths to the device), the support grid of radius_search.hip (cell >= r, built once), then
+// Per call: stack_to_device (cloud lengths to the device), the support grid of radius_search.hip (cell >= r, built once), then
 //   k_normals_cov     one wavefront per query row.  Its lanes stride over the candidates of the nine x-runs of the row's 3x3x3 cell
 //                     neighbourhood.  Pass 1 counts the hits (d2 < r*r), compacts them into an LDS list while they fit (max_nn slots)
 //                     and histograms the top byte of their (d2, row) keys.  A ball of at most max_nn hits is done after pass 1.  A
@@ -29,54 +29,30 @@ namespace lcr {
 constexpr int NRM_WAVES = 4;        // wavefronts (= query rows) per k_normals_cov workgroup
 constexpr int NRM_MAX_NN = 128;     // largest max_nn: two selected rows per lane
 
-struct NormClouds {
-  int     B;
-  int64_t off[GRID_MAX_B + 1];
-};
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-
-__global__ void k_normals_init(NormClouds C, int64_t* __restrict__ len) {
-  for (int b = threadIdx.x; b < C.B; b += blockDim.x) len[b] = C.off[b + 1] - C.off[b];
-}
-
-// Visit the candidates of row (qx, qy, qz) of cloud c: fn(valid, p) once per lane and per stride of 64, wave-uniform trip counts.
+// Visit the candidates of row (qx, qy, qz) of cloud c, the runs of grid_for_each_run (grid.h): fn(valid, p) once per lane and per stride
+// of 64, wave-uniform trip counts.
 template <typename F>
 __device__ __forceinline__ void nrm_candidates(const GridCloud& c, const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
                                                float qx, float qy, float qz, F&& fn) {
   const int lane = threadIdx.x & 63;
-  const int cx = cell_coord(qx, c.org[0], c.inv_cell, c.dim[0]);
-  const int cy = cell_coord(qy, c.org[1], c.inv_cell, c.dim[1]);
-  const int cz = cell_coord(qz, c.org[2], c.inv_cell, c.dim[2]);
-  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, c.dim[0] - 1);
-  if (x0 > x1) return;
-  for (int zz = max(cz - 1, 0); zz <= min(cz + 1, c.dim[2] - 1); ++zz)
-    for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.dim[1] - 1); ++yy) {
-      const int crow = c.cell_base + (zz * c.dim[1] + yy) * c.dim[0];
-      const int e = cell_start[crow + x1 + 1];
-      for (int k0 = cell_start[crow + x0]; k0 < e; k0 += 64) {
-        const int k = k0 + lane;
-        const bool valid = k < e;
-        const float4 p = sorted[valid ? k : e - 1];
-        fn(valid, p);
-      }
+  grid_for_each_run(c, cell_start, qx, qy, qz, [&](int k0, int e) {
+    for (; k0 < e; k0 += 64) {
+      const int k = k0 + lane;
+      const bool valid = k < e;
+      const float4 p = sorted[valid ? k : e - 1];
+      fn(valid, p);
     }
+  });
 }
 
 __device__ __forceinline__ uint64_t nrm_key(float qx, float qy, float qz, const float4& p, float r2, bool valid, bool& hit) {
-  const float dx = fsub(qx, p.x), dy = fsub(qy, p.y), dz = fsub(qz, p.z);
-  const float d2 = fadd(fadd(fmul(dx, dx), fmul(dy, dy)), fmul(dz, dz));
+  const float d2 = grid_d2(qx, qy, qz, p);
   hit = valid && d2 < r2;
-  return (static_cast<uint64_t>(__float_as_uint(d2)) << 32) | __float_as_uint(p.w);
+  return grid_key(d2, p.w);
 }
 
 // one wavefront per row: the row's neighbourhood (max_nn smallest (d2, row) keys with d2 < r2), covariance about the row -> cov[6], cnt
-__global__ __launch_bounds__(NRM_WAVES * 64) void k_normals_cov(NormClouds C, const float* __restrict__ pts, const GridHeader* __restrict__ h,
+__global__ __launch_bounds__(NRM_WAVES * 64) void k_normals_cov(Stack C, const float* __restrict__ pts, const GridHeader* __restrict__ h,
                                                                const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
                                                                float r2, int max_nn, double* __restrict__ cov, int32_t* __restrict__ cnt_out) {
   __shared__ uint32_t s_hist[NRM_WAVES][256];
@@ -85,8 +61,7 @@ __global__ __launch_bounds__(NRM_WAVES * 64) void k_normals_cov(NormClouds C, co
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * NRM_WAVES + w;
   if (i >= C.off[C.B]) return;                                   // wave-uniform
-  int b = 0;
-  while (b + 1 < C.B && i >= C.off[b + 1]) ++b;
+  const int b = cloud_of(C.off, C.B, i);
   const GridCloud& c = h->cloud[b];
   const float qx = pts[3 * i], qy = pts[3 * i + 1], qz = pts[3 * i + 2];
   uint32_t* hist = s_hist[w];
@@ -232,7 +207,7 @@ __global__ __launch_bounds__(NRM_WAVES * 64) void k_normals_cov(NormClouds C, co
 }
 
 // one thread per row: eigen-solve, degeneracy, orientation toward the viewpoint
-__global__ __launch_bounds__(256) void k_normals_finish(NormClouds C, const float* __restrict__ pts, const float* __restrict__ viewpoint,
+__global__ __launch_bounds__(256) void k_normals_finish(Stack C, const float* __restrict__ pts, const float* __restrict__ viewpoint,
                                                         const double* __restrict__ cov, const int32_t* __restrict__ cnt, float* __restrict__ normals,
                                                         float* __restrict__ curvature, int32_t* __restrict__ count) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -248,8 +223,7 @@ __global__ __launch_bounds__(256) void k_normals_finish(NormClouds C, const floa
     if (!(lam[2] <= 1e-30 || lam[1] <= 1e-12 * lam[2])) {
       const double nr = sqrt(V[0][0] * V[0][0] + V[1][0] * V[1][0] + V[2][0] * V[2][0]);
       for (int r = 0; r < 3; ++r) n[r] = V[r][0] / nr;
-      int b = 0;
-      while (b + 1 < C.B && i >= C.off[b + 1]) ++b;
+      const int b = cloud_of(C.off, C.B, i);
       double v[3] = {0.0, 0.0, 0.0};
       if (viewpoint)
         for (int r = 0; r < 3; ++r) v[r] = viewpoint[3 * b + r];
@@ -302,28 +276,16 @@ extern "C" int lcr_normals_ws_bytes(int B, int64_t n, size_t* bytes) {
 
 extern "C" int lcr_estimate_normals(const float* points, const int64_t* lengths, int B, float radius, int max_nn, const float* viewpoint,
                                     float* normals, float* curvature, int32_t* count, void* ws, size_t ws_bytes, void* stream) {
-  if (B < 1 || B > GRID_MAX_B || !(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 1 || max_nn > NRM_MAX_NN) {
-    set_error("lcr_estimate_normals: outside the domain (1 <= B <= %d, radius > 0 with radius*radius finite, 1 <= max_nn <= %d): B=%d "
-              "radius=%g max_nn=%d", GRID_MAX_B, NRM_MAX_NN, B, static_cast<double>(radius), max_nn);
+  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 1 || max_nn > NRM_MAX_NN) {
+    set_error("lcr_estimate_normals: outside the domain (radius > 0 with radius*radius finite, 1 <= max_nn <= %d): radius=%g max_nn=%d",
+              NRM_MAX_NN, static_cast<double>(radius), max_nn);
     return LCR_EARG;
   }
-  if (!lengths || !ws) {
-    set_error("lcr_estimate_normals: null pointer");
-    return LCR_EARG;
-  }
-  NormClouds C;
-  C.B = B;
-  C.off[0] = 0;
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > INT32_MAX) {
-      set_error("lcr_estimate_normals: cloud %d has a negative or too large length (%lld)", b, static_cast<long long>(lengths[b]));
-      return LCR_EARG;
-    }
-    C.off[b + 1] = C.off[b] + lengths[b];
-  }
+  Stack C;
+  if (stack_from_lengths("lcr_estimate_normals", lengths, B, &C)) return LCR_EARG;
   const int64_t n = C.off[B];
-  if (n > INT32_MAX || (n > 0 && (!points || !normals))) {
-    set_error("lcr_estimate_normals: more than 2^31-1 rows, or a null point / normal array (n=%lld)", static_cast<long long>(n));
+  if (!ws || (n > 0 && (!points || !normals))) {
+    set_error("lcr_estimate_normals: null workspace, or a null point / normal array (n=%lld)", static_cast<long long>(n));
     return LCR_EARG;
   }
   size_t need = 0, grid_bytes = 0;
@@ -340,8 +302,7 @@ extern "C" int lcr_estimate_normals(const float* points, const int64_t* lengths,
   normals_layout(ws, B, n, grid_bytes, &cov, &cnt, &len_dev);
   const GridLayout L = grid_layout(ws, n, B);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_normals_init, dim3(1), dim3(64), 0, st, C, len_dev);
-  int rc = check_launch("lcr_estimate_normals (init)");
+  int rc = stack_to_device("lcr_estimate_normals (init)", C, len_dev, nullptr, nullptr, st);
   if (rc) return rc;
   rc = lcr_support_grid_build(points, len_dev, B, n, radius, nullptr, ws, grid_bytes, stream);
   if (rc) return rc;

@@ -196,8 +196,7 @@ __global__ __launch_bounds__(256) void k_node_topk_stack(const float* __restrict
                                                          uint32_t* __restrict__ status) {
   __shared__ uint64_t s_key[PT_CAP];
   const int m = blockIdx.x;
-  int c = 0;
-  while (c + 1 < sk.C && m >= sk.mo[c + 1]) ++c;            // block-uniform
+  const int c = cloud_of(sk.mo, sk.C, m);                   // block-uniform
   const int64_t p0 = sk.po[c], N = sk.po[c + 1] - p0;
   const float* pts = points + 3 * p0;
   const int a = node_start[m], n_all = node_start[m + 1] - a;

@@ -245,11 +245,6 @@ __device__ __forceinline__ void rq_offsets(const int64_t* __restrict__ qlen, int
   if (lane < B) s_qoff[lane] = inc - len_b;
   if (lane == B - 1) s_qoff[B] = inc;
 }
-__device__ __forceinline__ int rq_cloud_of(const int32_t* off, int B, int i) {
-  int b = 0;
-  while (b + 1 < B && i >= off[b + 1]) ++b;
-  return b;
-}
 
 // One wavefront turn: `nj` (1..4) CONSECUTIVE queries of the processing order starting at position t_blk, set up at once (query j in DPP
 // row j) and then ranked one after the other.  b / off_b / off_b1: the lane's cached cloud lookup, carried from turn to turn.
@@ -275,7 +270,7 @@ __device__ __forceinline__ void rq_turn(const RqSearch& A, int B, const int32_t*
     const int64_t t_me = t_blk + (mine ? row : 0);
     const int64_t qi_me = q_order ? static_cast<int64_t>(q_order[t_me]) : t_me;
     if (qi_me < off_b || qi_me >= off_b1) {      // rare in cell order (a turn seldom straddles two clouds)
-      b = rq_cloud_of(s_qoff, B, static_cast<int>(qi_me));
+      b = cloud_of(s_qoff, B, static_cast<int>(qi_me));
       off_b = s_qoff[b];
       off_b1 = s_qoff[b + 1];
     }

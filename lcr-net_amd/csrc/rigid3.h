@@ -1,5 +1,5 @@
-// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (lgr.hip) and the RANSAC hypotheses (ransac.hip), and the
-// fp64 symmetric 3x3 eigen-solver of the surface normals (normals.hip).
+// rigid3.h — fp64 3x3 rotation fit shared by the weighted Procrustes (lgr.hip), the RANSAC hypotheses (ransac.hip) and the point-to-point
+// ICP update (icp.hip), and the fp64 symmetric 3x3 eigen-solver of the surface normals (normals.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

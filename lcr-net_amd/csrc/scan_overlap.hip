@@ -9,7 +9,7 @@
 //   The row needs asin alone; atan2 (the column) is evaluated for the points of the current band only, so every point pays the transform,
 //   the square root and asin once per band and atan2 once.  A pair therefore writes nothing but its three integers: no scratch image in
 //   HBM, no global atomics (the status word aside), and the counts are plain stores after a fixed tree over the workgroup.
-// The workspace holds the clouds' prefix offsets, written by k_so_init, which also clears the status word.
+// The workspace holds the clouds' prefix offsets, written by stack_to_device (common.h), which also clears the status word.
 #include <climits>
 #include <cmath>
 
@@ -23,27 +23,10 @@ constexpr int SO_MAX_H = 128, SO_MAX_W = 4096;
 constexpr size_t SO_LDS_BYTES = 152 * 1024;      // band image; the rest of the 160 KiB is left to the static reduction arrays
 constexpr uint32_t SO_EMPTY = 0xffffffffu;       // above the bit pattern of every non-negative float
 
-struct SoClouds {
-  int     B;
-  int64_t len[GRID_MAX_B];
-};
-
 struct SoProj {
   int    H, W;
   double afd, fov, max_range, eps;               // |fov_down| and |fov_up| + |fov_down| in radians
 };
-
-__global__ void k_so_init(SoClouds C, int64_t* __restrict__ off, int32_t* __restrict__ status) {
-  if (threadIdx.x == 0) {
-    int64_t s = 0;
-    for (int b = 0; b < C.B; ++b) {
-      off[b] = s;
-      s += C.len[b];
-    }
-    off[C.B] = s;
-    if (status) *status = 0;
-  }
-}
 
 // One point through M (row-major 3x4) onto the H x W grid, as the header states it.  Returns false for a dropped point.  The row comes
 // first; the column (atan2) only where the caller wants the row: rows r0 .. r0 + nr - 1.
@@ -167,14 +150,13 @@ namespace {
 constexpr double SO_PI = 3.14159265358979323846;
 
 // the shared domain checks; fills pr and the band height
-int so_params(const char* who, int B, int H, int W, double fov_up, double fov_down, double max_range, double eps, SoProj* pr, int* band_rows) {
+int so_params(const char* who, int H, int W, double fov_up, double fov_down, double max_range, double eps, SoProj* pr, int* band_rows) {
   const double fu = fov_up * SO_PI / 180.0, fd = fov_down * SO_PI / 180.0;
   const double fov = std::fabs(fu) + std::fabs(fd);
-  if (B < 1 || B > GRID_MAX_B || H < 1 || H > SO_MAX_H || W < 1 || W > SO_MAX_W || !(max_range > 0.0) || !(eps > 0.0) || !(fov > 0.0) ||
+  if (H < 1 || H > SO_MAX_H || W < 1 || W > SO_MAX_W || !(max_range > 0.0) || !(eps > 0.0) || !(fov > 0.0) ||
       !std::isfinite(fov)) {
-    set_error("%s: outside the domain (1 <= B <= %d, 1 <= H <= %d, 1 <= W <= %d, max_range > 0, eps > 0, |fov_up| + |fov_down| > 0 and "
-              "finite): B=%d H=%d W=%d fov_up=%g fov_down=%g max_range=%g eps=%g", who, GRID_MAX_B, SO_MAX_H, SO_MAX_W, B, H, W, fov_up,
-              fov_down, max_range, eps);
+    set_error("%s: outside the domain (1 <= H <= %d, 1 <= W <= %d, max_range > 0, eps > 0, |fov_up| + |fov_down| > 0 and finite): H=%d W=%d "
+              "fov_up=%g fov_down=%g max_range=%g eps=%g", who, SO_MAX_H, SO_MAX_W, H, W, fov_up, fov_down, max_range, eps);
     return LCR_EARG;
   }
   pr->H = H;
@@ -185,24 +167,6 @@ int so_params(const char* who, int B, int H, int W, double fov_up, double fov_do
   pr->eps = eps;
   const int fit = static_cast<int>(SO_LDS_BYTES / (sizeof(uint32_t) * static_cast<size_t>(W)));      // >= 9 at W = 4096
   *band_rows = fit < H ? fit : H;
-  return LCR_OK;
-}
-
-int so_clouds(const char* who, const int64_t* lengths, int B, SoClouds* C, int64_t* n) {
-  C->B = B;
-  *n = 0;
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > INT32_MAX) {
-      set_error("%s: cloud %d has a negative or too large length (%lld)", who, b, static_cast<long long>(lengths[b]));
-      return LCR_EARG;
-    }
-    C->len[b] = lengths[b];
-    *n += lengths[b];
-  }
-  if (*n > INT32_MAX) {
-    set_error("%s: more than 2^31-1 rows (%lld)", who, static_cast<long long>(*n));
-    return LCR_EARG;
-  }
   return LCR_OK;
 }
 
@@ -238,16 +202,16 @@ extern "C" int lcr_range_images(const float* points, const int64_t* lengths, int
                                 float* images, int32_t* valid, void* ws, size_t ws_bytes, void* stream) {
   SoProj pr;
   int band_rows = 0;
-  int rc = so_params("lcr_range_images", B, H, W, fov_up, fov_down, max_range, 1.0, &pr, &band_rows);
+  int rc = so_params("lcr_range_images", H, W, fov_up, fov_down, max_range, 1.0, &pr, &band_rows);
   if (rc) return rc;
-  if (!lengths || !images || !valid || !ws) {
+  if (!images || !valid || !ws) {
     set_error("lcr_range_images: null pointer");
     return LCR_EARG;
   }
-  SoClouds C;
-  int64_t n = 0;
-  rc = so_clouds("lcr_range_images", lengths, B, &C, &n);
+  Stack C;
+  rc = stack_from_lengths("lcr_range_images", lengths, B, &C);
   if (rc) return rc;
+  const int64_t n = C.off[B];
   if (n > 0 && !points) {
     set_error("lcr_range_images: null point array (n=%lld)", static_cast<long long>(n));
     return LCR_EARG;
@@ -258,8 +222,7 @@ extern "C" int lcr_range_images(const float* points, const int64_t* lengths, int
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t* off = static_cast<int64_t*>(ws);
-  hipLaunchKernelGGL(k_so_init, dim3(1), dim3(64), 0, st, C, off, static_cast<int32_t*>(nullptr));
-  rc = check_launch("lcr_range_images (init)");
+  rc = stack_to_device("lcr_range_images (init)", C, nullptr, off, nullptr, st);
   if (rc) return rc;
   return so_launch<false>("lcr_range_images", B, points, off, B, pr, band_rows, images, valid, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                           st);
@@ -285,16 +248,16 @@ extern "C" int lcr_scan_overlap(const float* points, const int64_t* lengths, int
   if (P == 0) return LCR_OK;
   SoProj pr;
   int band_rows = 0;
-  int rc = so_params("lcr_scan_overlap", B, H, W, fov_up, fov_down, max_range, eps, &pr, &band_rows);
+  int rc = so_params("lcr_scan_overlap", H, W, fov_up, fov_down, max_range, eps, &pr, &band_rows);
   if (rc) return rc;
-  if (!lengths || !images || !valid || !pairs || !rel || !counts || !status || !ws) {
+  if (!images || !valid || !pairs || !rel || !counts || !status || !ws) {
     set_error("lcr_scan_overlap: null pointer");
     return LCR_EARG;
   }
-  SoClouds C;
-  int64_t n = 0;
-  rc = so_clouds("lcr_scan_overlap", lengths, B, &C, &n);
+  Stack C;
+  rc = stack_from_lengths("lcr_scan_overlap", lengths, B, &C);
   if (rc) return rc;
+  const int64_t n = C.off[B];
   if (n > 0 && !points) {
     set_error("lcr_scan_overlap: null point array (n=%lld)", static_cast<long long>(n));
     return LCR_EARG;
@@ -305,8 +268,7 @@ extern "C" int lcr_scan_overlap(const float* points, const int64_t* lengths, int
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t* off = static_cast<int64_t*>(ws);
-  hipLaunchKernelGGL(k_so_init, dim3(1), dim3(64), 0, st, C, off, status);
-  rc = check_launch("lcr_scan_overlap (init)");
+  rc = stack_to_device("lcr_scan_overlap (init)", C, nullptr, off, status, st);
   if (rc) return rc;
   return so_launch<true>("lcr_scan_overlap", P, points, off, B, pr, band_rows, nullptr, nullptr, images, valid, pairs, rel, counts, status, st);
 }
