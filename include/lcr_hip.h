@@ -252,7 +252,9 @@ int lcr_gemm_f32(const float* A, const float* B, float* C, int64_t M, int N, int
                  void* stream);
 /* The K-deep contractions on the bf16 matrix cores with fp32-faithful operands: an fp32 number is exactly the sum of three bf16 numbers.
  * lcr_split_bf16x3 writes those terms of an array as planes u16[3][n]; lcr_split_bf16x3_tiles writes them for a constant operand (weights
- * [N,K], K % 32 == 0) in the layout the GEMM stages them in — u16[ceil(N/64)][K/32][3][64][32], i.e. ceil(N/64) * (K/32) * 12288 bytes — once;
+ * [N,K], K % 32 == 0) in the order the GEMM's matrix instructions read them — ceil(N/64) * (K/32) blocks of 12288 bytes, one per (64 columns,
+ * K-step of 32), each [column quarter wn 0..3][plane 0..2][lane 0..63] 16-byte chunks, lane l holding 8 bf16 of column 16 wn + (l & 15),
+ * k 8 (l >> 4) .. + 7; rows beyond N are zero; opaque to callers — once;
  * lcr_gemm_f32_bsplit computes C = A[M,K] . B[N,K]^T with A split on the fly and six of the nine cross products (the dropped ones are
  * <= 2^-24 of a product), fp32 accumulation, same epilogue as lcr_gemm_f32.  Not bit-identical to lcr_gemm_f32 (other rounding points). */
 int lcr_split_bf16x3(const float* w, int64_t n, uint16_t* planes, void* stream);

@@ -256,8 +256,11 @@ def publish_derived(t):
 
 
 def split_bf16x3(w):
-    """The three bf16 terms of a constant fp32 operand [N,K] (K % 32 == 0) in the tiled layout lcr_gemm_f32_bsplit stages them in:
-    int16 [ceil(N/64), K/32, 3, 64, 32] (lcr_split_bf16x3_tiles; made once per weight).  The tensor carries N as `.lcr_n`."""
+    """The three bf16 terms of a constant fp32 operand [N,K] (K % 32 == 0) in the layout lcr_gemm_f32_bsplit reads them in
+    (lcr_split_bf16x3_tiles; made once per weight): int16 [ceil(N/64), K/32, 3, 64, 32], i.e. one opaque 12 KB block per (64 columns,
+    K-step of 32) whose 16-byte chunks (8 bf16 of one plane, column and 8-k group) are ordered as the MFMA's B operand is read:
+    [column quarter wn 0..3][plane 0..2][lane 0..63], lane l holding column 16 wn + (l & 15), k 8 (l >> 4) .. + 7.
+    Rows beyond N are zero.  The tensor carries N as `.lcr_n`."""
     w = w.detach().contiguous()
     N, K = w.shape
     assert K % 32 == 0
@@ -267,15 +270,15 @@ def split_bf16x3(w):
     return tiles
 
 
-def unsplit_bf16x3(tiles):
-    """Inverse view of split_bf16x3 for tests: the three terms as float32 [3, N, K] (un-tiled, un-swizzled)."""
+def unsplit_bf16x3(tiles, padded=False):
+    """Inverse view of split_bf16x3 for tests: the three terms as float32 [3, N, K] (columns and k back in order); padded=True keeps the
+    zero rows of the last 64-column tile ([3, 64 ceil(N/64), K])."""
     CT, KS = tiles.shape[0], tiles.shape[1]
-    t = tiles.view(CT, KS, 3, 64, 4, 8)
-    row = torch.arange(64, device=tiles.device)
-    phys = torch.arange(4, device=tiles.device)[None, :] ^ ((row >> 2) & 3)[:, None]          # [row, logical chunk] -> physical chunk
-    t = torch.gather(t, 4, phys.view(1, 1, 1, 64, 4, 1).expand(CT, KS, 3, 64, 4, 8))
-    t = t.reshape(CT, KS, 3, 64, 32).permute(2, 0, 3, 1, 4).reshape(3, CT * 64, KS * 32)
-    return t[:, :tiles.lcr_n].contiguous().view(torch.bfloat16).float()
+    t = tiles.view(CT, KS, 4, 3, 4, 16, 8)                                         # [ct, ks, wn, plane, lane >> 4, lane & 15, 8 k]
+    t = t.permute(3, 0, 2, 5, 1, 4, 6).reshape(3, CT * 64, KS * 32)                # [plane, (ct, wn, lane & 15), (ks, lane >> 4, 8 k)]
+    if not padded:
+        t = t[:, :tiles.lcr_n]
+    return t.contiguous().view(torch.bfloat16).float()
 
 
 def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0, row_mask=None):
