@@ -64,7 +64,7 @@ static int unary_raw(const LcrUnaryW& u, const float* x, int64_t n, int cin, int
   float* y = ws.take<float>(static_cast<size_t>(n) * cout);
   double* stats = sp.take();
   if (!y || !stats) return LCR_ESPACE;
-  // K-deep Linears (stages 3-4) on the bf16 matrix cores when the caller provides the weight's three bf16 terms (fp32-faithful, gemm_f32.hip)
+  // K-deep Linears (stages 3-4) on the bf16 matrix cores when the caller provides the weight's three bf16 terms (fp32-faithful, gemm_split.hip)
   const bool split = u.w_split && cin >= 288 && cin % 32 == 0 && cout >= 64;
   int rc = split ? TURN(lcr_gemm_f32_bsplit(x, u.w_split, y, n, cout, cin, u.b, nullptr, st.seg, sp.S, sp.groups, stats, s))
                  : TURN(lcr_gemm_f32(x, u.w, y, n, cout, cin, 0, 1, u.b, nullptr, st.seg, sp.S, sp.groups, stats, s));

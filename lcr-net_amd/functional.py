@@ -60,10 +60,6 @@ def set_timer(timer, sample_every=1):
     _lib.lib().lcr_ktimer_enable(1 if timer is not None else 0)
 
 
-def _timed(name, fn, meta=None):
-    return fn()
-
-
 def _seg(seg_len, n, device):
     """GroupNorm segment lengths: None = the reference's behaviour (one segment = the whole stack)."""
     if seg_len is None:
@@ -130,6 +126,18 @@ def _zero_stats(S, groups, device):
     return torch.zeros((GN_REPLICAS, S, groups, 2), dtype=torch.float64, device=device)
 
 
+def _gemm_out(M, N, seg_len, groups, device, always_seg=False):
+    """What every GEMM wrapper allocates: (C [M,N], the segment table to pass or None, S, the zeroed statistics table or None).
+    The table is passed with `groups` only; always_seg: also without (gemm_anorm normalises A by it)."""
+    c = torch.empty((M, N), dtype=torch.float32, device=device)
+    if not (groups or always_seg):
+        return c, None, 0, None
+    if seg_len is None:
+        seg_len = torch.full((1,), int(M), dtype=torch.int64, device=device)      # see _seg
+    S = seg_len.numel()
+    return c, seg_len, S, (_zero_stats(S, groups, device) if groups else None)
+
+
 def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=None, groups=0, row_mask=None):
     """C = A·B (+ fused epilogue).  a: [M,K] ([K,M] if trans_a); b: [K,N] ([N,K] if trans_b, i.e. an nn.Linear weight).
     Returns (C, stats) where stats is the fp64 [GN_REPLICAS,S,groups,2] GroupNorm accumulator (sum the replicas; None if
@@ -142,17 +150,10 @@ def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=Non
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     N = b.shape[0] if trans_b else b.shape[1]
     assert (b.shape[1] if trans_b else b.shape[0]) == K, "inner dimensions differ"
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    stats = None
-    S = 0
-    if groups:
-        seg_len = _seg(seg_len, M, a.device)
-        S = seg_len.numel()
-        stats = _zero_stats(S, groups, a.device)
-    _timed("gemm", lambda: _lib.check(_lib.lib().lcr_gemm_f32(
+    c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
+    _lib.check(_lib.lib().lcr_gemm_f32(
         _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, int(trans_a), int(trans_b), _lib.ptr(bias), _lib.ptr(rowdiv),
-        _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)), "lcr_gemm_f32"),
-        meta=(M, N, K))
+        _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)), "lcr_gemm_f32")
     return c, stats
 
 
@@ -177,19 +178,14 @@ def _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask
     M, K = a.shape
     N = b.shape[0]
     assert b.shape[1] == K, "inner dimensions differ"
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    stats, S = None, 0
-    if groups:
-        seg_len = _seg(seg_len, M, a.device)
-        S = seg_len.numel()
-        stats = _zero_stats(S, groups, a.device)
-    _timed("gemm", lambda: _lib.check(_lib.lib().lcr_gemm_f32_masked(
-        _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv), _lib.ptr(seg_len) if groups else None, S,
-        int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_masked"), meta=(M, N, K))
+    c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
+    _lib.check(_lib.lib().lcr_gemm_f32_masked(
+        _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv), _lib.ptr(seg_len), S,
+        int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_masked")
     return c, stats
 
 
-# ---- split-bf16 form of the K-deep GEMMs (csrc/gemm_f32.hip): fp32 operands as three bf16 terms, six products on the bf16 matrix cores.
+# ---- split-bf16 form of the K-deep GEMMs (csrc/gemm_split.hip): fp32 operands as three bf16 terms, six products on the bf16 matrix cores.
 # DEFAULT since round 5 for the K-deep shapes (K >= 288, K % 32 == 0, N >= 64): every fp32 operand enters as its three bf16 terms (exact), six
 # of the nine cross products are accumulated in fp32 — measured error against fp64 at or below the fp32-MFMA kernel's own, non-finite values
 # propagate to the same outputs (tests/test_gemm_split_gpu.py).  LCR_GEMM_SPLIT=0 selects the true-fp32 MFMA kernel everywhere;
@@ -289,20 +285,15 @@ def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0, row_m
     M, K = a.shape
     N = planes.lcr_n
     assert planes.shape[1] * 32 == K and planes.shape[0] == (N + 63) // 64, "inner dimensions differ"
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    stats, S = None, 0
-    if groups:
-        seg_len = _seg(seg_len, M, a.device)
-        S = seg_len.numel()
-        stats = _zero_stats(S, groups, a.device)
+    c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
     if row_mask is not None:
         block_k = _mask_args(a, row_mask)
         _lib.check(_lib.lib().lcr_gemm_f32_bsplit_masked(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
-                                                         _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats),
+                                                         _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats),
                                                          _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_bsplit_masked")
         return c, stats
     _lib.check(_lib.lib().lcr_gemm_f32_bsplit(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
-                                              _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
+                                              _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
                "lcr_gemm_f32_bsplit")
     return c, stats
 
@@ -324,14 +315,11 @@ def gemm_anorm(a, a_stats, a_gamma, a_beta, a_groups, weight, bias=None, seg_len
     M, K = a.shape
     N = weight.shape[0]
     assert weight.shape[1] == K and gemm_anorm_ok(K, N)
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    seg_len = _seg(seg_len, M, a.device)
-    S = seg_len.numel()
-    stats = _zero_stats(S, groups, a.device) if groups else None
-    _timed("gemm", lambda: _lib.check(_lib.lib().lcr_gemm_f32_anorm(
+    c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device, always_seg=True)
+    _lib.check(_lib.lib().lcr_gemm_f32_anorm(
         _lib.ptr(a), _lib.ptr(weight), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(a_stats), _lib.ptr(a_gamma), _lib.ptr(a_beta),
         int(a_groups), GN_EPS, float(slope), _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
-        "lcr_gemm_f32_anorm"), meta=(M, N, K))
+        "lcr_gemm_f32_anorm")
     return c, stats
 
 
@@ -381,15 +369,15 @@ def kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kernel_points_host
     kp = _kp_host(kernel_points_host)
     if emit_mask:
         mask = torch.empty((M,), dtype=torch.int16, device=s_feats.device)
-        _timed("kpconv_aggregate", lambda: _lib.check(_lib.lib().lcr_kpconv_aggregate_mask(
+        _lib.check(_lib.lib().lcr_kpconv_aggregate_mask(
             _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
             ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(mask), _lib.ptr(order), 0,
-            _lib.stream_ptr(s_feats.device)), "lcr_kpconv_aggregate_mask"), meta=(M, Ns, H, C, idx.element_size()))
+            _lib.stream_ptr(s_feats.device)), "lcr_kpconv_aggregate_mask")
         return A, nn, mask
-    _timed("kpconv_aggregate", lambda: _lib.check(_lib.lib().lcr_kpconv_aggregate(
+    _lib.check(_lib.lib().lcr_kpconv_aggregate(
         _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
         ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(order), _lib.stream_ptr(s_feats.device)),
-        "lcr_kpconv_aggregate"), meta=(M, Ns, H, C, idx.element_size()))
+        "lcr_kpconv_aggregate")
     return A, nn
 
 
@@ -411,11 +399,11 @@ def kpconv_fused(s_feats, s_pos, q_points, s_points, idx, kernel_points_host, si
         S = seg_len.numel()
         stats = _zero_stats(S, groups, s_feats.device)
     kp = _kp_host(kernel_points_host)
-    _timed("kpconv_fused", lambda: _lib.check(_lib.lib().lcr_kpconv_fused(
+    _lib.check(_lib.lib().lcr_kpconv_fused(
         _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
         ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(weights), _lib.ptr(bias), _lib.ptr(out),
         _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.ptr(order), _lib.stream_ptr(s_feats.device)),
-        "lcr_kpconv_fused"), meta=(M, Ns, H, C, idx.element_size()))
+        "lcr_kpconv_fused")
     return out, stats
 
 

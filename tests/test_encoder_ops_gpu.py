@@ -1,5 +1,5 @@
-"""GPU: the encoder's GroupNorm and KPConv operators (csrc/groupnorm.hip, csrc/kpconv.hip, the statistics epilogue and the normalise-on-load
-form of csrc/gemm_f32.hip), each against the fp64 restatement of tests/encoder_ops_restatement.py — an independent reference, where the
+"""GPU: the encoder's GroupNorm and KPConv operators (csrc/groupnorm.hip, csrc/kpconv.hip, the statistics epilogue of csrc/gemm.h and the
+normalise-on-load form of csrc/gemm_f32.hip), each against the fp64 restatement of tests/encoder_ops_restatement.py — an independent reference, where the
 older operator tests compare one HIP form with another.
 
 Inputs, cases and tolerances come from encoder_ops_restatement: TOL[op] = min(1e-4, 4 x the CPU fp32 floor) x max(1, |want|max) for the centred
