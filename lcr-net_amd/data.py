@@ -110,8 +110,7 @@ def _layout_for(n0, B, S, neighbor_limits, upsampling, n_raw):
     if lay is None:
         lay = PrecomputeLayout()
         lim = (ctypes.c_int * S)(*key[3])
-        _lib.check(_lib.lib().lcr_precompute_layout(n0, B, S, ctypes.cast(lim, ctypes.c_void_p), _ups_flag(upsampling), n_raw,
-                                                    ctypes.addressof(lay)), "lcr_precompute_layout")
+        _lib.call.lcr_precompute_layout(n0, B, S, ctypes.cast(lim, ctypes.c_void_p), _ups_flag(upsampling), n_raw, ctypes.addressof(lay))
         if len(_layout_cache) > 64:
             _layout_cache.clear()
         _layout_cache[key] = lay
@@ -164,18 +163,14 @@ def precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neig
     status = ctypes.c_uint32(0)
     if method == 0:
         ws = _workspace(lay.ws_bytes, dev, stream)
-        _lib.check(_lib.lib().lcr_precompute_batch_rows(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
-                                                        float(radius), float(raw_voxel) if raw else 0.0, int(key_bits_hint), _lib.ptr(out),
-                                                        out.numel(), _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host), ctypes.addressof(status),
-                                                        stream), "lcr_precompute_batch")
+        _lib.call.lcr_precompute_batch_rows(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size), float(radius),
+                                            float(raw_voxel) if raw else 0.0, int(key_bits_hint), _lib.ptr(out), out.numel(), _lib.ptr(ws),
+                                            ws.numel(), ctypes.addressof(lens_host), ctypes.addressof(status), stream)
     else:
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(_lib.lib().lcr_precompute_ws_bytes_ex(ctypes.addressof(lay), method, ctypes.byref(nbytes)), "lcr_precompute_ws_bytes_ex")
-        ws = _workspace(nbytes.value, dev, stream)
-        _lib.check(_lib.lib().lcr_precompute_batch_rows_ex(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
-                                                           float(radius), float(raw_voxel) if raw else 0.0, method, int(key_bits_hint), _lib.ptr(out),
-                                                           out.numel(), _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host),
-                                                           ctypes.addressof(status), stream), "lcr_precompute_batch")
+        ws = _workspace(_lib.ws_size("lcr_precompute_ws_bytes_ex", ctypes.addressof(lay), method), dev, stream)
+        _lib.call.lcr_precompute_batch_rows_ex(_lib.ptr(points), row_floats, _lib.ptr(lengths), ctypes.addressof(lay), float(voxel_size),
+                                               float(radius), float(raw_voxel) if raw else 0.0, method, int(key_bits_hint), _lib.ptr(out),
+                                               out.numel(), _lib.ptr(ws), ws.numel(), ctypes.addressof(lens_host), ctypes.addressof(status), stream)
     st = status.value
     if st & STATUS_KEY_OVERFLOW and key_bits_hint:
         return precompute_batch_arena(points, lengths, num_stages, voxel_size, radius, neighbor_limits, upsampling, 0, raw_voxel, capacity,

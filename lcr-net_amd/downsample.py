@@ -3,7 +3,6 @@
 `voxel_downsample` (utils/utils/open3d.py:61-69), through `lcr_voxel_down_sample` (csrc/grid_subsample.hip).  The semantics —
 fp64 origin min - v/2, fp64 in-order averages, libstdc++ unordered_map order over hash_eigen codes — are stated in
 include/lcr_hip.h; this is a different function from the grid subsampling of the model's collate (`modules/ops/grid_subsample.py`)."""
-import ctypes
 
 import numpy as np
 import torch
@@ -32,17 +31,13 @@ def voxel_down_sample_device(rows, lengths, voxel_size, out_cols=3, want_f64=Fal
     B, n = lengths.numel(), rows.shape[0]
     if not 1 <= B <= MAX_CLOUDS:
         raise RuntimeError("voxel_down_sample_device: 1..%d clouds per call" % MAX_CLOUDS)
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_voxel_down_sample_ws_bytes(n, B, ctypes.byref(nbytes)), "lcr_voxel_down_sample_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_voxel_down_sample_ws_bytes", n, B, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     out = torch.empty((max(n, 1), out_cols), dtype=torch.float32, device=dev)
     out64 = torch.empty((max(n, 1), out_cols), dtype=torch.float64, device=dev) if want_f64 else None
     out_len = torch.empty((B,), dtype=torch.int64, device=dev)
-    _lib.check(L.lcr_voxel_down_sample(_lib.ptr(rows), R, int(out_cols), _lib.ptr(lengths), B, n, float(voxel_size), int(key_bits_hint),
-                                       _lib.ptr(out), _lib.ptr(out64), _lib.ptr(out_len), _lib.ptr(status), _lib.ptr(ws), ws.numel(),
-                                       _lib.stream_ptr(dev)), "lcr_voxel_down_sample")
+    _lib.call.lcr_voxel_down_sample(_lib.ptr(rows), R, int(out_cols), _lib.ptr(lengths), B, n, float(voxel_size), int(key_bits_hint), _lib.ptr(out),
+                                    _lib.ptr(out64), _lib.ptr(out_len), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return out, out64, out_len, status
 
 

@@ -151,9 +151,9 @@ def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=Non
     N = b.shape[0] if trans_b else b.shape[1]
     assert (b.shape[1] if trans_b else b.shape[0]) == K, "inner dimensions differ"
     c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
-    _lib.check(_lib.lib().lcr_gemm_f32(
+    _lib.call.lcr_gemm_f32(
         _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, int(trans_a), int(trans_b), _lib.ptr(bias), _lib.ptr(rowdiv),
-        _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)), "lcr_gemm_f32")
+        _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device))
     return c, stats
 
 
@@ -179,9 +179,9 @@ def _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask
     N = b.shape[0]
     assert b.shape[1] == K, "inner dimensions differ"
     c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
-    _lib.check(_lib.lib().lcr_gemm_f32_masked(
+    _lib.call.lcr_gemm_f32_masked(
         _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv), _lib.ptr(seg_len), S,
-        int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_masked")
+        int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device))
     return c, stats
 
 
@@ -261,7 +261,7 @@ def split_bf16x3(w):
     N, K = w.shape
     assert K % 32 == 0
     tiles = torch.empty(((N + 63) // 64, K // 32, 3, 64, 32), dtype=torch.int16, device=w.device)
-    _lib.check(_lib.lib().lcr_split_bf16x3_tiles(_lib.ptr(w), int(N), int(K), _lib.ptr(tiles), _lib.stream_ptr(w.device)), "lcr_split_bf16x3_tiles")
+    _lib.call.lcr_split_bf16x3_tiles(_lib.ptr(w), int(N), int(K), _lib.ptr(tiles), _lib.stream_ptr(w.device))
     tiles.lcr_n = int(N)
     return tiles
 
@@ -288,13 +288,11 @@ def gemm_bsplit(a, planes, bias=None, rowdiv=None, seg_len=None, groups=0, row_m
     c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device)
     if row_mask is not None:
         block_k = _mask_args(a, row_mask)
-        _lib.check(_lib.lib().lcr_gemm_f32_bsplit_masked(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
-                                                         _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats),
-                                                         _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device)), "lcr_gemm_f32_bsplit_masked")
+        _lib.call.lcr_gemm_f32_bsplit_masked(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv), _lib.ptr(seg_len),
+                                             S, int(groups), _lib.ptr(stats), _lib.ptr(row_mask), block_k, _lib.stream_ptr(a.device))
         return c, stats
-    _lib.check(_lib.lib().lcr_gemm_f32_bsplit(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
-                                              _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
-               "lcr_gemm_f32_bsplit")
+    _lib.call.lcr_gemm_f32_bsplit(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(rowdiv),
+                                  _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device))
     return c, stats
 
 
@@ -316,18 +314,17 @@ def gemm_anorm(a, a_stats, a_gamma, a_beta, a_groups, weight, bias=None, seg_len
     N = weight.shape[0]
     assert weight.shape[1] == K and gemm_anorm_ok(K, N)
     c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device, always_seg=True)
-    _lib.check(_lib.lib().lcr_gemm_f32_anorm(
+    _lib.call.lcr_gemm_f32_anorm(
         _lib.ptr(a), _lib.ptr(weight), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(a_stats), _lib.ptr(a_gamma), _lib.ptr(a_beta),
-        int(a_groups), GN_EPS, float(slope), _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device)),
-        "lcr_gemm_f32_anorm")
+        int(a_groups), GN_EPS, float(slope), _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device))
     return c, stats
 
 
 def groupnorm_stats(x, groups, seg_len=None):
     seg_len = _seg(seg_len, x.shape[0], x.device)
     stats = _zero_stats(seg_len.numel(), groups, x.device)
-    _lib.check(_lib.lib().lcr_groupnorm_stats(_lib.ptr(x), x.shape[0], x.shape[1], groups, _lib.ptr(seg_len), seg_len.numel(),
-                                              _lib.ptr(stats), _lib.stream_ptr(x.device)), "lcr_groupnorm_stats")
+    _lib.call.lcr_groupnorm_stats(_lib.ptr(x), x.shape[0], x.shape[1], groups, _lib.ptr(seg_len), seg_len.numel(),
+                                  _lib.ptr(stats), _lib.stream_ptr(x.device))
     return stats
 
 
@@ -337,16 +334,15 @@ def groupnorm_apply(x, stats, gamma, beta, groups, seg_len=None, res=None, res_n
     y = torch.empty_like(x)
     pos = torch.empty((x.shape[0],), dtype=torch.uint8, device=x.device) if want_pos else None
     rs, rg, rb = res_norm if res_norm is not None else (None, None, None)
-    _lib.check(_lib.lib().lcr_groupnorm_apply(_lib.ptr(x), _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(res), _lib.ptr(rs),
-                                              _lib.ptr(rg), _lib.ptr(rb), _lib.ptr(y), x.shape[0], x.shape[1], groups, _lib.ptr(seg_len),
-                                              seg_len.numel(), GN_EPS, float(slope), int(act), _lib.ptr(pos),
-                                              _lib.stream_ptr(x.device)), "lcr_groupnorm_apply")
+    _lib.call.lcr_groupnorm_apply(_lib.ptr(x), _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(res), _lib.ptr(rs), _lib.ptr(rg),
+                                  _lib.ptr(rb), _lib.ptr(y), x.shape[0], x.shape[1], groups, _lib.ptr(seg_len), seg_len.numel(), GN_EPS, float(slope),
+                                  int(act), _lib.ptr(pos), _lib.stream_ptr(x.device))
     return (y, pos) if want_pos else y
 
 
 def row_positive(x):
     pos = torch.empty((x.shape[0],), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().lcr_row_positive(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(pos), _lib.stream_ptr(x.device)), "lcr_row_positive")
+    _lib.call.lcr_row_positive(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(pos), _lib.stream_ptr(x.device))
     return pos
 
 
@@ -369,15 +365,14 @@ def kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kernel_points_host
     kp = _kp_host(kernel_points_host)
     if emit_mask:
         mask = torch.empty((M,), dtype=torch.int16, device=s_feats.device)
-        _lib.check(_lib.lib().lcr_kpconv_aggregate_mask(
+        _lib.call.lcr_kpconv_aggregate_mask(
             _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
             ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(mask), _lib.ptr(order), 0,
-            _lib.stream_ptr(s_feats.device)), "lcr_kpconv_aggregate_mask")
+            _lib.stream_ptr(s_feats.device))
         return A, nn, mask
-    _lib.check(_lib.lib().lcr_kpconv_aggregate(
+    _lib.call.lcr_kpconv_aggregate(
         _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
-        ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(order), _lib.stream_ptr(s_feats.device)),
-        "lcr_kpconv_aggregate")
+        ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(A), _lib.ptr(nn), _lib.ptr(order), _lib.stream_ptr(s_feats.device))
     return A, nn
 
 
@@ -399,11 +394,10 @@ def kpconv_fused(s_feats, s_pos, q_points, s_points, idx, kernel_points_host, si
         S = seg_len.numel()
         stats = _zero_stats(S, groups, s_feats.device)
     kp = _kp_host(kernel_points_host)
-    _lib.check(_lib.lib().lcr_kpconv_fused(
+    _lib.call.lcr_kpconv_fused(
         _lib.ptr(s_feats), _lib.ptr(s_pos), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H, C,
         ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(weights), _lib.ptr(bias), _lib.ptr(out),
-        _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.ptr(order), _lib.stream_ptr(s_feats.device)),
-        "lcr_kpconv_fused")
+        _lib.ptr(seg_len) if groups else None, S, int(groups), _lib.ptr(stats), _lib.ptr(order), _lib.stream_ptr(s_feats.device))
     return out, stats
 
 
@@ -414,17 +408,17 @@ def kpconv_cin1(s_feats, q_points, s_points, idx, kernel_points_host, sigma, wei
     Cout = weights.shape[-1]
     out = torch.empty((M, Cout), dtype=torch.float32, device=s_feats.device)
     kp = _kp_host(kernel_points_host)
-    _lib.check(_lib.lib().lcr_kpconv_cin1(_lib.ptr(s_feats), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H,
-                                          ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(weights), _lib.ptr(bias), Cout,
-                                          _lib.ptr(out), _lib.ptr(order), _lib.stream_ptr(s_feats.device)), "lcr_kpconv_cin1")
+    _lib.call.lcr_kpconv_cin1(_lib.ptr(s_feats), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), M, Ns, H,
+                              ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(weights), _lib.ptr(bias), Cout,
+                              _lib.ptr(out), _lib.ptr(order), _lib.stream_ptr(s_feats.device))
     return out
 
 
 def maxpool(x, idx, order=None):
     M, H = idx.shape
     out = torch.empty((M, x.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().lcr_maxpool(_lib.ptr(x), _lib.ptr(idx), _idx_args(idx), M, x.shape[0], H, x.shape[1], _lib.ptr(out),
-                                      _lib.ptr(order), _lib.stream_ptr(x.device)), "lcr_maxpool")
+    _lib.call.lcr_maxpool(_lib.ptr(x), _lib.ptr(idx), _idx_args(idx), M, x.shape[0], H, x.shape[1], _lib.ptr(out),
+                          _lib.ptr(order), _lib.stream_ptr(x.device))
     return out
 
 
@@ -440,13 +434,10 @@ def netvlad_forward(feats, seg_len_host, weights_struct):
     seg = np.ascontiguousarray(seg_len_host, dtype=np.int64)
     S = int(seg.shape[0])
     assert int(seg.sum()) == feats.shape[0] and feats.shape[1] == 1024 and feats.is_contiguous()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().lcr_netvlad_ws_bytes(feats.shape[0], S, ctypes.byref(nbytes)), "lcr_netvlad_ws_bytes")
-    ws = _lib.workspace(nbytes.value, feats.device)
+    ws = _lib.ws("lcr_netvlad_ws_bytes", feats.shape[0], S, device=feats.device)
     out = torch.empty((S, 256), dtype=torch.float32, device=feats.device)
-    _lib.check(_lib.lib().lcr_netvlad_forward(_lib.ptr(feats), ctypes.c_void_p(seg.ctypes.data), S, ctypes.byref(weights_struct),
-                                              _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(feats.device)),
-               "lcr_netvlad_forward")
+    _lib.call.lcr_netvlad_forward(_lib.ptr(feats), ctypes.c_void_p(seg.ctypes.data), S, ctypes.byref(weights_struct),
+                                  _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(feats.device))
     return out
 
 
@@ -464,9 +455,9 @@ def gemm_batched_ta(a, b, c, M, N, k, a_off, b_off, c_off):
         assert 0 <= ao[i] and ao[i] + max(int(kk[i]), 0) * M <= a.numel(), "A entry out of range"
         assert 0 <= bo[i] and bo[i] + max(int(kk[i]), 0) * N <= b.numel(), "B entry out of range"
         assert 0 <= co[i] and co[i] + M * N <= c.numel(), "C entry out of range"
-    _lib.check(_lib.lib().lcr_gemm_f32_batched_ta(_lib.ptr(a), _lib.ptr(b), _lib.ptr(c), int(M), int(N), count, ctypes.c_void_p(kk.ctypes.data),
-                                                  ctypes.c_void_p(ao.ctypes.data), ctypes.c_void_p(bo.ctypes.data),
-                                                  ctypes.c_void_p(co.ctypes.data), _lib.stream_ptr(a.device)), "lcr_gemm_f32_batched_ta")
+    _lib.call.lcr_gemm_f32_batched_ta(_lib.ptr(a), _lib.ptr(b), _lib.ptr(c), int(M), int(N), count, ctypes.c_void_p(kk.ctypes.data),
+                                      ctypes.c_void_p(ao.ctypes.data), ctypes.c_void_p(bo.ctypes.data),
+                                      ctypes.c_void_p(co.ctypes.data), _lib.stream_ptr(a.device))
     return c
 
 
@@ -474,19 +465,19 @@ def linear(x, weight, bias=None, relu=False):
     """nn.Linear (weight [out,in]) on the MFMA GEMM, optional ReLU."""
     y = gemm(x.contiguous(), weight, trans_b=True, bias=bias)[0]
     if relu:
-        _lib.check(_lib.lib().lcr_relu_inplace(_lib.ptr(y), y.numel(), _lib.stream_ptr(y.device)), "lcr_relu_inplace")
+        _lib.call.lcr_relu_inplace(_lib.ptr(y), y.numel(), _lib.stream_ptr(y.device))
     return y
 
 
 def relu_(x):
-    _lib.check(_lib.lib().lcr_relu_inplace(_lib.ptr(x), x.numel(), _lib.stream_ptr(x.device)), "lcr_relu_inplace")
+    _lib.call.lcr_relu_inplace(_lib.ptr(x), x.numel(), _lib.stream_ptr(x.device))
     return x
 
 
 def rotary_embed_(x, theta, heads):
     """In place rotary position embedding (rpetransformer.py:41-54): x [N, heads*32], theta [N, heads*16]."""
     assert x.is_contiguous() and theta.is_contiguous() and x.shape[1] == heads * 32 and theta.shape[1] == heads * 16
-    _lib.check(_lib.lib().lcr_rotary_embed(_lib.ptr(x), _lib.ptr(theta), x.shape[0], heads, _lib.stream_ptr(x.device)), "lcr_rotary_embed")
+    _lib.call.lcr_rotary_embed(_lib.ptr(x), _lib.ptr(theta), x.shape[0], heads, _lib.stream_ptr(x.device))
     return x
 
 
@@ -499,12 +490,11 @@ def attention(q, k, v, heads, q_lens=None, k_lens=None):
         P = len(q_lens)
         assert len(k_lens) == P and sum(q_lens) == q.shape[0] and sum(k_lens) == k.shape[0]
         ql, kl = (ctypes.c_int64 * P)(*[int(x) for x in q_lens]), (ctypes.c_int64 * P)(*[int(x) for x in k_lens])
-        _lib.check(_lib.lib().lcr_attention_seg_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctypes.cast(ql, ctypes.c_void_p),
-                                                    ctypes.cast(kl, ctypes.c_void_p), P, heads, q.shape[1] // heads, _lib.ptr(out),
-                                                    _lib.stream_ptr(q.device)), "lcr_attention_seg_f32")
+        _lib.call.lcr_attention_seg_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctypes.cast(ql, ctypes.c_void_p), ctypes.cast(kl, ctypes.c_void_p), P,
+                                        heads, q.shape[1] // heads, _lib.ptr(out), _lib.stream_ptr(q.device))
         return out
-    _lib.check(_lib.lib().lcr_attention_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), q.shape[0], k.shape[0], heads, q.shape[1] // heads,
-                                            _lib.ptr(out), _lib.stream_ptr(q.device)), "lcr_attention_f32")
+    _lib.call.lcr_attention_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), q.shape[0], k.shape[0], heads, q.shape[1] // heads,
+                                _lib.ptr(out), _lib.stream_ptr(q.device))
     return out
 
 
@@ -520,32 +510,26 @@ def attention_topk(q, k, v, heads, q_lens, k_lens, kks):
     out = torch.empty_like(q)
     ql, kl = (ctypes.c_int64 * P)(*[int(x) for x in q_lens]), (ctypes.c_int64 * P)(*[int(x) for x in k_lens])
     kk = (ctypes.c_int * P)(*[int(x) for x in kks])
-    _lib.check(_lib.lib().lcr_attention_topk_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctypes.cast(ql, ctypes.c_void_p), ctypes.cast(kl, ctypes.c_void_p),
-                                                 ctypes.cast(kk, ctypes.c_void_p), P, heads, q.shape[1] // heads, _lib.ptr(out), _lib.stream_ptr(q.device)),
-               "lcr_attention_topk_f32")
+    _lib.call.lcr_attention_topk_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ctypes.cast(ql, ctypes.c_void_p), ctypes.cast(kl, ctypes.c_void_p),
+                                     ctypes.cast(kk, ctypes.c_void_p), P, heads, q.shape[1] // heads, _lib.ptr(out), _lib.stream_ptr(q.device))
     return out
 
 
 def add_layernorm(a, b, gamma, beta, eps=1e-5):
     y = torch.empty_like(a)
-    _lib.check(_lib.lib().lcr_add_layernorm(_lib.ptr(a), _lib.ptr(b), _lib.ptr(gamma), _lib.ptr(beta), a.shape[0], a.shape[1], float(eps),
-                                            _lib.ptr(y), _lib.stream_ptr(a.device)), "lcr_add_layernorm")
+    _lib.call.lcr_add_layernorm(_lib.ptr(a), _lib.ptr(b), _lib.ptr(gamma), _lib.ptr(beta), a.shape[0], a.shape[1], float(eps),
+                                _lib.ptr(y), _lib.stream_ptr(a.device))
     return y
 
 
 # ------------------------------------------------------------------------------------------------ pose tail (a-10)
-def _L():
-    return _lib.lib()
-
-
-def _sp(t):
-    return _lib.stream_ptr(t.device)
+_L = _lib.lib     # the raw view under its old name here, for callers outside the package that assert on a return code
 
 
 def vote_shift(xyz, offsets, max_range):
     out = torch.empty_like(xyz)
-    _lib.check(_L().lcr_vote_shift(_lib.ptr(xyz.contiguous()), _lib.ptr(offsets.contiguous()), xyz.shape[0], float(max_range), _lib.ptr(out),
-                                   _sp(xyz)), "lcr_vote_shift")
+    _lib.call.lcr_vote_shift(_lib.ptr(xyz.contiguous()), _lib.ptr(offsets.contiguous()), xyz.shape[0], float(max_range), _lib.ptr(out),
+                             _lib.stream_ptr(xyz.device))
     return out
 
 
@@ -554,18 +538,16 @@ def greedy_nms(points, lengths, radius):
     n, B = points.shape[0], lengths.numel()
     keep = torch.empty((n,), dtype=torch.uint8, device=points.device)
     out_len = torch.empty((B,), dtype=torch.int64, device=points.device)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_greedy_nms_ws_bytes(n, ctypes.byref(nbytes)), "lcr_greedy_nms_ws_bytes")
-    ws = _lib.workspace(nbytes.value, points.device)
-    _lib.check(_L().lcr_greedy_nms(_lib.ptr(points.contiguous()), _lib.ptr(lengths), B, n, float(radius), _lib.ptr(keep), _lib.ptr(out_len),
-                                   _lib.ptr(ws), _sp(points)), "lcr_greedy_nms")
+    ws = _lib.ws("lcr_greedy_nms_ws_bytes", n, device=points.device)
+    _lib.call.lcr_greedy_nms(_lib.ptr(points.contiguous()), _lib.ptr(lengths), B, n, float(radius), _lib.ptr(keep), _lib.ptr(out_len),
+                             _lib.ptr(ws), _lib.stream_ptr(points.device))
     return keep, out_len
 
 
 def neighbor_mean(points, idx, pad):
     out = torch.empty((idx.shape[0], 3), dtype=torch.float32, device=points.device)
-    _lib.check(_L().lcr_neighbor_mean(_lib.ptr(points.contiguous()), _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[0], idx.shape[1], int(pad),
-                                      _lib.ptr(out), _sp(points)), "lcr_neighbor_mean")
+    _lib.call.lcr_neighbor_mean(_lib.ptr(points.contiguous()), _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[0], idx.shape[1], int(pad),
+                                _lib.ptr(out), _lib.stream_ptr(points.device))
     return out
 
 
@@ -573,17 +555,14 @@ def point_to_node_partition(points, nodes, point_limit):
     """(point_to_node i32[N], node_masks bool[M], node_knn_indices i64[M,K], node_knn_masks bool[M,K]) —
     modules/ops/pointcloud_partition.py:60-107."""
     N, M, dev = points.shape[0], nodes.shape[0], points.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_point_to_node_ws_bytes(N, M, ctypes.byref(nbytes)), "lcr_point_to_node_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_point_to_node_ws_bytes", N, M, device=dev)
     p2n = torch.empty((N,), dtype=torch.int32, device=dev)
     knn = torch.empty((M, point_limit), dtype=torch.int64, device=dev)
     km = torch.empty((M, point_limit), dtype=torch.uint8, device=dev)
     nm = torch.empty((M,), dtype=torch.uint8, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_L().lcr_point_to_node_partition(_lib.ptr(points.contiguous()), N, _lib.ptr(nodes.contiguous()), M, int(point_limit), _lib.ptr(p2n),
-                                                _lib.ptr(knn), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _sp(points)),
-               "lcr_point_to_node_partition")
+    _lib.call.lcr_point_to_node_partition(_lib.ptr(points.contiguous()), N, _lib.ptr(nodes.contiguous()), M, int(point_limit), _lib.ptr(p2n),
+                                          _lib.ptr(knn), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     return p2n, nm.bool(), knn, km.bool()
 
 
@@ -599,17 +578,15 @@ def point_to_node_partition_stack(points, point_off, nodes, node_off, point_limi
     N, M = int(point_off[-1] - point_off[0]), int(node_off[-1] - node_off[0])
     po = np.ascontiguousarray(point_off, dtype=np.int64)
     mo = np.ascontiguousarray(node_off, dtype=np.int64)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_point_to_node_ws_bytes(N, M, ctypes.byref(nbytes)), "lcr_point_to_node_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_point_to_node_ws_bytes", N, M, device=dev)
     p2n = torch.empty((N,), dtype=torch.int32, device=dev)
     knn = torch.empty((M, point_limit), dtype=torch.int64, device=dev)
     km = torch.empty((M, point_limit), dtype=torch.uint8, device=dev)
     nm = torch.empty((M,), dtype=torch.uint8, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_L().lcr_point_to_node_partition_stack(_lib.ptr(points.contiguous()), po.ctypes.data, _lib.ptr(nodes.contiguous()), mo.ctypes.data, C,
-                                                      int(point_limit), _lib.ptr(p2n), _lib.ptr(knn), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(status),
-                                                      _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_point_to_node_partition_stack")
+    _lib.call.lcr_point_to_node_partition_stack(_lib.ptr(points.contiguous()), po.ctypes.data, _lib.ptr(nodes.contiguous()), mo.ctypes.data, C,
+                                                int(point_limit), _lib.ptr(p2n), _lib.ptr(knn), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(status),
+                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     return p2n, nm.bool(), knn, km.bool()
 
 
@@ -636,8 +613,8 @@ def log_optimal_transport(raw_scores, row_masks, col_masks, alpha, scale=1.0, it
     dev = raw_scores.device
     rm, cm = row_masks.to(torch.uint8).contiguous(), col_masks.to(torch.uint8).contiguous()
     S = torch.empty((B, M + 1, N + 1), dtype=torch.float32, device=dev)
-    _lib.check(_L().lcr_build_padded_scores(_lib.ptr(raw_scores.contiguous()), _lib.ptr(rm), _lib.ptr(cm), B, M, N, float(scale),
-                                            _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _sp(S)), "lcr_build_padded_scores")
+    _lib.call.lcr_build_padded_scores(_lib.ptr(raw_scores.contiguous()), _lib.ptr(rm), _lib.ptr(cm), B, M, N, float(scale),
+                                      _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _lib.stream_ptr(S.device))
     return _transport_padded(S, rm, cm, iters, inf)
 
 
@@ -658,9 +635,8 @@ def patch_log_optimal_transport(feats_a, idx_a, feats_b, idx_b, mask_a, mask_b, 
     assert ia.dtype == torch.int64 and ib.dtype == torch.int64 and fa.dtype == torch.float32 and fa.shape[1] == fb.shape[1]
     rm, cm = mask_a.to(torch.uint8).contiguous(), mask_b.to(torch.uint8).contiguous()
     S = torch.empty((P, K + 1, K + 1), dtype=torch.float32, device=dev)
-    _lib.check(_L().lcr_patch_scores(_lib.ptr(fa), fa.shape[0], _lib.ptr(fb), fb.shape[0], fa.shape[1], _lib.ptr(ia), _lib.ptr(ib), _lib.ptr(rm),
-                                     _lib.ptr(cm), P, K, float(scale), _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _sp(S)),
-               "lcr_patch_scores")
+    _lib.call.lcr_patch_scores(_lib.ptr(fa), fa.shape[0], _lib.ptr(fb), fb.shape[0], fa.shape[1], _lib.ptr(ia), _lib.ptr(ib), _lib.ptr(rm),
+                               _lib.ptr(cm), P, K, float(scale), _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _lib.stream_ptr(S.device))
     return _transport_padded(S, rm, cm, iters, inf)
 
 
@@ -668,16 +644,14 @@ def _transport_padded(S, rm, cm, iters, inf):
     """Sinkhorn on padded scores S [B,M+1,N+1] in place -> log scores (the second half of LearnableLogOptimalTransport)."""
     B, M, N = S.shape[0], S.shape[1] - 1, S.shape[2] - 1
     dev = S.device
-    nfl = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_log_sinkhorn_ws_floats(B, M, N, ctypes.byref(nfl)), "lcr_log_sinkhorn_ws_floats")
-    uv = torch.empty((nfl.value,), dtype=torch.float32, device=dev)
+    uv = torch.empty((_lib.ws_size("lcr_log_sinkhorn_ws_floats", B, M, N),), dtype=torch.float32, device=dev)
     form = ctypes.c_int(0)
-    _lib.check(_L().lcr_log_sinkhorn_form(B, M, N, ctypes.byref(form)), "lcr_log_sinkhorn_form")
+    _lib.call.lcr_log_sinkhorn_form(B, M, N, ctypes.byref(form))
     persistent = form.value == 2                      # the only form with hand-offs, i.e. the only one that writes a status word
     if persistent:
         uv[-1:].zero_()                               # status word: bit 0 = a hand-off of the persistent form timed out
-    _lib.check(_L().lcr_log_sinkhorn_ex(_lib.ptr(S), _lib.ptr(rm), _lib.ptr(cm), B, M, N, int(iters), float(inf), _lib.ptr(uv), uv.numel(), _sp(S)),
-               "lcr_log_sinkhorn")
+    _lib.call.lcr_log_sinkhorn_ex(_lib.ptr(S), _lib.ptr(rm), _lib.ptr(cm), B, M, N, int(iters), float(inf), _lib.ptr(uv), uv.numel(),
+                                  _lib.stream_ptr(dev))
     if persistent:
         # a stream-ordered 1-element copy (not a view: a view would pin the whole workspace until somebody drains the list)
         items = _pending_ot_status.items
@@ -708,36 +682,34 @@ def top1_matching(log_scores, row_masks=None, col_masks=None, mutual=False, topk
     M, N, dev = M1 - 1, N1 - 1, log_scores.device
     topk = int(topk)
     assert topk >= 1
-    nbytes = ctypes.c_size_t(0)
-    ws_fn = _L().lcr_top1_matching_ws_bytes if (topk == 1 and use_dustbin and global_scores is None) else _L().lcr_topk_matching_ws_bytes
-    _lib.check(ws_fn(B, M, N, ctypes.byref(nbytes)), "lcr_top1_matching_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws_fn = "lcr_top1_matching_ws_bytes" if (topk == 1 and use_dustbin and global_scores is None) else "lcr_topk_matching_ws_bytes"
+    ws = _lib.ws(ws_fn, B, M, N, device=dev)
     rm = row_masks.to(torch.uint8).contiguous() if row_masks is not None else None
     cm = col_masks.to(torch.uint8).contiguous() if col_masks is not None else None
     total = torch.zeros(1, dtype=torch.int64, device=dev)
     if not use_dustbin or global_scores is not None:
         gs = global_scores.float().contiguous() if global_scores is not None else None
         assert gs is None or gs.numel() == B
-        fn, args = _L().lcr_topk_matching_ex, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), topk, int(bool(mutual)),
-                                               int(bool(use_dustbin)), float(confidence_threshold), _lib.ptr(gs))
+        fn, args = _lib.call.lcr_topk_matching_ex, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), topk, int(bool(mutual)),
+                                                    int(bool(use_dustbin)), float(confidence_threshold), _lib.ptr(gs))
     elif topk == 1:
-        fn, args = _L().lcr_top1_matching_ex, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), int(bool(mutual)))
+        fn, args = _lib.call.lcr_top1_matching_ex, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), int(bool(mutual)))
     else:
-        fn, args = _L().lcr_topk_matching, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), topk, int(bool(mutual)))
-    _lib.check(fn(*args, _lib.ptr(total), None, None, _lib.ptr(ws), ws.numel(), _sp(log_scores)), "lcr_top1_matching")
+        fn, args = _lib.call.lcr_topk_matching, (_lib.ptr(log_scores.contiguous()), B, M, N, _lib.ptr(rm), _lib.ptr(cm), topk, int(bool(mutual)))
+    fn(*args, _lib.ptr(total), None, None, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     n = int(total.item())
     check_transport_status()
     bij = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
     sc = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
     if n:
-        _lib.check(fn(*args, _lib.ptr(total), _lib.ptr(bij), _lib.ptr(sc), _lib.ptr(ws), ws.numel(), _sp(log_scores)), "lcr_top1_matching")
+        fn(*args, _lib.ptr(total), _lib.ptr(bij), _lib.ptr(sc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return bij[:n], sc[:n]
 
 
 def upsample_concat(x, idx, skip):
     out = torch.empty((skip.shape[0], x.shape[1] + skip.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(_L().lcr_upsample_concat(_lib.ptr(x.contiguous()), x.shape[0], x.shape[1], _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[1],
-                                        _lib.ptr(skip.contiguous()), skip.shape[1], skip.shape[0], _lib.ptr(out), _sp(x)), "lcr_upsample_concat")
+    _lib.call.lcr_upsample_concat(_lib.ptr(x.contiguous()), x.shape[0], x.shape[1], _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[1],
+                                  _lib.ptr(skip.contiguous()), skip.shape[1], skip.shape[0], _lib.ptr(out), _lib.stream_ptr(x.device))
     return out
 
 
@@ -745,8 +717,7 @@ def gather_rows(src, idx):
     """src[idx] with zero rows where idx == src.shape[0] (index_select on the zero-padded tensor); idx int64 any shape."""
     idx = idx.contiguous()
     out = torch.empty(tuple(idx.shape) + (src.shape[1],), dtype=torch.float32, device=src.device)
-    _lib.check(_L().lcr_gather_rows(_lib.ptr(src.contiguous()), src.shape[0], src.shape[1], _lib.ptr(idx), idx.numel(), _lib.ptr(out), _sp(src)),
-               "lcr_gather_rows")
+    _lib.call.lcr_gather_rows(_lib.ptr(src.contiguous()), src.shape[0], src.shape[1], _lib.ptr(idx), idx.numel(), _lib.ptr(out), _lib.stream_ptr(src.device))
     return out
 
 
@@ -758,8 +729,8 @@ def bmm_nt(a, b):
     a, b = a.contiguous(), b.contiguous()
     for z0 in range(0, P, 65535):
         cnt = min(65535, P - z0)
-        _lib.check(_L().lcr_gemm_f32_strided_batched(_lib.ptr(a[z0:]), _lib.ptr(b[z0:]), _lib.ptr(c[z0:]), M, N, K, 0, 1, M * K, N * K, M * N, cnt,
-                                                     _sp(a)), "lcr_gemm_f32_strided_batched")
+        _lib.call.lcr_gemm_f32_strided_batched(_lib.ptr(a[z0:]), _lib.ptr(b[z0:]), _lib.ptr(c[z0:]), M, N, K, 0, 1, M * K, N * K, M * N, cnt,
+                                               _lib.stream_ptr(a.device))
     return c
 
 
@@ -770,8 +741,8 @@ def procrustes(src, ref, w, start=None):
         start = host_values([0, src.shape[0]], torch.int32, dev)
     P = start.numel() - 1
     T = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
-    _lib.check(_L().lcr_procrustes_batched(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(start), P, 1e-5,
-                                           _lib.ptr(T), _sp(src)), "lcr_procrustes_batched")
+    _lib.call.lcr_procrustes_batched(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(start), P, 1e-5,
+                                     _lib.ptr(T), _lib.stream_ptr(src.device))
     return T
 
 
@@ -779,8 +750,8 @@ def inlier_count(T, src, ref, radius, start=None, min_count=0):
     P, dev = T.shape[0], T.device
     counts = torch.empty((P,), dtype=torch.int32, device=dev)
     best = torch.empty((1,), dtype=torch.int32, device=dev)
-    _lib.check(_L().lcr_inlier_count(_lib.ptr(T), P, _lib.ptr(src), _lib.ptr(ref), src.shape[0], float(radius), _lib.ptr(start), int(min_count),
-                                     _lib.ptr(counts), _lib.ptr(best), _sp(T)), "lcr_inlier_count")
+    _lib.call.lcr_inlier_count(_lib.ptr(T), P, _lib.ptr(src), _lib.ptr(ref), src.shape[0], float(radius), _lib.ptr(start), int(min_count),
+                               _lib.ptr(counts), _lib.ptr(best), _lib.stream_ptr(T.device))
     return counts, best
 
 
@@ -791,25 +762,22 @@ def local_global_registration(src, ref, score, hyp_start, seg_hyp_start, radius,
     correspondence_limit (:152-160): a pair with more correspondences verifies and refits on its highest-scoring `limit` ones only."""
     dev = src.device
     n, H, S = src.shape[0], hyp_start.numel() - 1, seg_hyp_start.numel() - 1
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_lgr_ws_bytes(n, H, S, ctypes.byref(nbytes)), "lcr_lgr_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_lgr_ws_bytes", n, H, S, device=dev)
     T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
     hyp = torch.empty((H, 4, 4), dtype=torch.float32, device=dev) if want_details else None
     counts = torch.empty((H,), dtype=torch.int32, device=dev) if want_details else None
     best = torch.empty((S,), dtype=torch.int32, device=dev) if want_details else None
-    _lib.check(_L().lcr_local_global_registration_ex(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(score.contiguous()), n,
-                                                     _lib.ptr(hyp_start.contiguous()), H, _lib.ptr(seg_hyp_start.contiguous()), S, float(radius),
-                                                     int(min_count), int(steps), int(correspondence_limit or 0), _lib.ptr(T), _lib.ptr(hyp),
-                                                     _lib.ptr(counts), _lib.ptr(best), _lib.ptr(ws), ws.numel(), _sp(src)),
-               "lcr_local_global_registration")
+    _lib.call.lcr_local_global_registration_ex(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(score.contiguous()), n,
+                                               _lib.ptr(hyp_start.contiguous()), H, _lib.ptr(seg_hyp_start.contiguous()), S, float(radius),
+                                               int(min_count), int(steps), int(correspondence_limit or 0), _lib.ptr(T), _lib.ptr(hyp),
+                                               _lib.ptr(counts), _lib.ptr(best), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(src.device))
     return (T, hyp, counts, best) if want_details else T
 
 
 def inlier_weights(T_all, sel, src, ref, score, radius):
     w = torch.empty_like(score)
-    _lib.check(_L().lcr_inlier_weights(_lib.ptr(T_all), _lib.ptr(sel), _lib.ptr(src), _lib.ptr(ref), _lib.ptr(score), src.shape[0], float(radius),
-                                       _lib.ptr(w), _sp(T_all)), "lcr_inlier_weights")
+    _lib.call.lcr_inlier_weights(_lib.ptr(T_all), _lib.ptr(sel), _lib.ptr(src), _lib.ptr(ref), _lib.ptr(score), src.shape[0], float(radius),
+                                 _lib.ptr(w), _lib.stream_ptr(T_all.device))
     return w
 
 
@@ -820,9 +788,7 @@ def ransac_correspondences(src, ref, start, distance_threshold, ransac_n, num_it
     _lib.require_cuda(src, ref, start)
     dev = src.device
     S, iters = start.numel() - 1, int(num_iterations)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_ransac_ws_bytes(S, iters, ctypes.byref(nbytes)), "lcr_ransac_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_ransac_ws_bytes", S, iters, device=dev)
     T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
     inliers = torch.empty((S,), dtype=torch.int32, device=dev)
     rmse = torch.empty((S,), dtype=torch.float32, device=dev)
@@ -830,10 +796,10 @@ def ransac_correspondences(src, ref, start, distance_threshold, ransac_n, num_it
     T_all = torch.empty((S * iters, 4, 4), dtype=torch.float32, device=dev) if want_details else None
     counts = torch.empty((S * iters,), dtype=torch.int32, device=dev) if want_details else None
     sse = torch.empty((S * iters,), dtype=torch.float32, device=dev) if want_details else None
-    _lib.check(_L().lcr_ransac_correspondences(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S,
-                                               float(distance_threshold), int(ransac_n), iters, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(T),
-                                               _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best), _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse),
-                                               _lib.ptr(ws), ws.numel(), _sp(src)), "lcr_ransac_correspondences")
+    _lib.call.lcr_ransac_correspondences(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S,
+                                         float(distance_threshold), int(ransac_n), iters, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(T),
+                                         _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best), _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(src.device))
     if want_details:
         return T, inliers, rmse, best, T_all, counts, sse
     return T, inliers, rmse, best
@@ -858,9 +824,7 @@ def ransac_correspondences_ex(src, ref, start, distance_threshold, ransac_n, num
             raise ValueError("ransac_correspondences_ex: corr must be int32 [n,2] and src_start / ref_start int32 [S+1]")
         corr, src_start, ref_start = corr.contiguous(), src_start.contiguous(), ref_start.contiguous()
         n_corr = corr.shape[0]
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_ransac_ex_ws_bytes(S, iters, n_corr, ctypes.byref(nbytes)), "lcr_ransac_ex_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_ransac_ex_ws_bytes", S, iters, n_corr, device=dev)
     T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
     inliers = torch.empty((S,), dtype=torch.int32, device=dev)
     rmse = torch.empty((S,), dtype=torch.float32, device=dev)
@@ -869,12 +833,11 @@ def ransac_correspondences_ex(src, ref, start, distance_threshold, ransac_n, num
     counts = torch.empty((S * iters,), dtype=torch.int32, device=dev) if want_details else None
     sse = torch.empty((S * iters,), dtype=torch.float32, device=dev) if want_details else None
     reject = torch.empty((S * iters,), dtype=torch.uint8, device=dev) if want_reject else None
-    _lib.check(_L().lcr_ransac_correspondences_ex(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S,
-                                                  _lib.ptr(corr), _lib.ptr(src_start), _lib.ptr(ref_start), n_corr, float(distance_threshold),
-                                                  int(ransac_n), iters, int(seed) & 0xFFFFFFFFFFFFFFFF, float(edge_similarity),
-                                                  float(checker_distance), _lib.ptr(T), _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best),
-                                                  _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse), _lib.ptr(reject), _lib.ptr(ws), ws.numel(),
-                                                  _sp(src)), "lcr_ransac_correspondences_ex")
+    _lib.call.lcr_ransac_correspondences_ex(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S, _lib.ptr(corr),
+                                            _lib.ptr(src_start), _lib.ptr(ref_start), n_corr, float(distance_threshold), int(ransac_n), iters,
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, float(edge_similarity), float(checker_distance), _lib.ptr(T),
+                                            _lib.ptr(inliers), _lib.ptr(rmse), _lib.ptr(best), _lib.ptr(T_all), _lib.ptr(counts), _lib.ptr(sse),
+                                            _lib.ptr(reject), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(src.device))
     out = (T, inliers, rmse, best) + ((T_all, counts, sse) if want_details else ())
     return out + ((reject,) if want_reject else ())
 
@@ -890,14 +853,11 @@ def feature_nn(qf, df, q_start, d_start):
         raise ValueError("feature_nn: q_start and d_start must be int32 [S+1]")
     dev = qf.device
     S, C, nq, nd = q_start.numel() - 1, qf.shape[1], qf.shape[0], df.shape[0]
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_feature_nn_ws_bytes(S, nq, nd, ctypes.byref(nbytes)), "lcr_feature_nn_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_feature_nn_ws_bytes", S, nq, nd, device=dev)
     nn = torch.empty((nq,), dtype=torch.int32, device=dev)
     d2 = torch.empty((nq,), dtype=torch.float32, device=dev)
-    _lib.check(_L().lcr_feature_nn(_lib.ptr(qf.contiguous()), _lib.ptr(df.contiguous()), _lib.ptr(q_start.contiguous()),
-                                   _lib.ptr(d_start.contiguous()), S, C, nq, nd, _lib.ptr(nn), _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _sp(qf)),
-               "lcr_feature_nn")
+    _lib.call.lcr_feature_nn(_lib.ptr(qf.contiguous()), _lib.ptr(df.contiguous()), _lib.ptr(q_start.contiguous()),
+                             _lib.ptr(d_start.contiguous()), S, C, nq, nd, _lib.ptr(nn), _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(qf.device))
     return nn, d2
 
 
@@ -914,26 +874,21 @@ def feature_correspondences(nn_sr, src_start, ref_start, nn_rs=None, min_rows=3)
     S = src_start.numel() - 1
     if ref_start.numel() != S + 1:
         raise ValueError("feature_correspondences: src_start and ref_start must both be int32 [S+1]")
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_feature_correspondences_ws_bytes(S, ctypes.byref(nbytes)), "lcr_feature_correspondences_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_feature_correspondences_ws_bytes", S, device=dev)
     corr = torch.empty((nn_sr.numel(), 2), dtype=torch.int32, device=dev)
     start = torch.empty((S + 1,), dtype=torch.int32, device=dev)
     used = torch.empty((S,), dtype=torch.int32, device=dev)
-    _lib.check(_L().lcr_feature_correspondences(_lib.ptr(nn_sr.contiguous()), _lib.ptr(src_start.contiguous()),
-                                                _lib.ptr(nn_rs.contiguous() if nn_rs is not None else None), _lib.ptr(ref_start.contiguous()), S,
-                                                int(min_rows), _lib.ptr(corr), _lib.ptr(start), _lib.ptr(used), _lib.ptr(ws), ws.numel(),
-                                                _sp(nn_sr)), "lcr_feature_correspondences")
+    _lib.call.lcr_feature_correspondences(_lib.ptr(nn_sr.contiguous()), _lib.ptr(src_start.contiguous()),
+                                          _lib.ptr(nn_rs.contiguous() if nn_rs is not None else None), _lib.ptr(ref_start.contiguous()), S,
+                                          int(min_rows), _lib.ptr(corr), _lib.ptr(start), _lib.ptr(used), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr(nn_sr.device))
     return corr, start, used
 
 
 def node_correspondences_ws_bytes(point_off, node_off, K):
     """Workspace bytes of lcr_node_correspondences for these host offset lists (2P+1 entries each)."""
     po, mo = np.ascontiguousarray(point_off, dtype=np.int64), np.ascontiguousarray(node_off, dtype=np.int64)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_node_correspondences_ws_bytes(po.ctypes.data, mo.ctypes.data, (len(po) - 1) // 2, int(K), ctypes.byref(nbytes)),
-               "lcr_node_correspondences_ws_bytes")
-    return nbytes.value
+    return _lib.ws_size("lcr_node_correspondences_ws_bytes", po.ctypes.data, mo.ctypes.data, (len(po) - 1) // 2, int(K))
 
 
 def node_correspondences_raw(points_f, point_off, nodes, node_off, knn, knn_mask, node_mask, transforms, pos_radius, cap=None, ws=None, corr=None,
@@ -965,10 +920,10 @@ def node_correspondences_raw(points_f, point_off, nodes, node_off, knn, knn_mask
     overlap = torch.empty((max(cap, 1),), dtype=torch.float32, device=dev) if overlap is None else overlap
     start = torch.empty((P + 1,), dtype=torch.int32, device=dev) if start is None else start
     status = torch.empty((1,), dtype=torch.int32, device=dev) if status is None else status
-    _lib.check(_L().lcr_node_correspondences(_lib.ptr(points_f.contiguous()), po.ctypes.data, _lib.ptr(nodes.contiguous()), mo.ctypes.data,
-                                             _lib.ptr(knn.contiguous()), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(transforms.contiguous()), P, K,
-                                             float(pos_radius), int(cap), _lib.ptr(corr), _lib.ptr(overlap), _lib.ptr(start), _lib.ptr(status),
-                                             _lib.ptr(ws), ws.numel(), _sp(points_f)), "lcr_node_correspondences")
+    _lib.call.lcr_node_correspondences(_lib.ptr(points_f.contiguous()), po.ctypes.data, _lib.ptr(nodes.contiguous()), mo.ctypes.data,
+                                       _lib.ptr(knn.contiguous()), _lib.ptr(km), _lib.ptr(nm), _lib.ptr(transforms.contiguous()), P, K,
+                                       float(pos_radius), int(cap), _lib.ptr(corr), _lib.ptr(overlap), _lib.ptr(start), _lib.ptr(status),
+                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points_f.device))
     return corr, overlap, start, status
 
 
@@ -985,8 +940,7 @@ def node_correspondences(points_f, point_off, nodes, node_off, knn, knn_mask, no
 def ransac_sample_host(seed, h0, count, ransac_n, n):
     """The RANSAC sampler on the host (no GPU): int32 [count, ransac_n] row indices of hypotheses h0 .. h0+count-1 for a pair of n rows."""
     out = np.empty((int(count), int(ransac_n)), dtype=np.int32)
-    _lib.check(_L().lcr_ransac_sample_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(h0), int(count), int(ransac_n), int(n), out.ctypes.data),
-               "lcr_ransac_sample_host")
+    _lib.call.lcr_ransac_sample_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(h0), int(count), int(ransac_n), int(n), out.ctypes.data)
     return out
 
 
@@ -1025,10 +979,7 @@ def _icp(name, src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence
     if plane and (tuple(tgt_normals.shape) != tuple(tgt.shape) or tgt_normals.dtype != torch.float32):
         raise ValueError("%s: tgt_normals must be float32 with the shape of tgt" % name)
     src, tgt, init = src.contiguous(), tgt.contiguous(), init.contiguous()
-    nbytes = ctypes.c_size_t(0)
-    ws_fn = "lcr_icp_plane_ws_bytes" if plane else "lcr_icp_ws_bytes"
-    _lib.check(getattr(_L(), ws_fn)(S, src.shape[0], tgt.shape[0], ctypes.byref(nbytes)), ws_fn)
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_icp_plane_ws_bytes" if plane else "lcr_icp_ws_bytes", S, src.shape[0], tgt.shape[0], device=dev)
     f64 = dict(dtype=torch.float64, device=dev)
     out = {"T": torch.empty((S, 4, 4), **f64), "fitness": torch.empty((S,), **f64), "inlier_rmse": torch.empty((S,), **f64),
            "iterations": torch.empty((S,), dtype=torch.int32, device=dev)}
@@ -1037,14 +988,12 @@ def _icp(name, src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence
             torch.full((S, iters + 1), float("nan"), **f64)] if want_history else [None, None, None]
     tail = (float(max_correspondence_distance), iters, float(relative_fitness), float(relative_rmse), _lib.ptr(out["T"]), _lib.ptr(out["fitness"]),
             _lib.ptr(out["inlier_rmse"]), _lib.ptr(out["iterations"]), _lib.ptr(corr), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
-            int(check_every), _lib.ptr(ws), ws.numel(), _sp(src))
+            int(check_every), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(src.device))
     if plane:
         nrm = tgt_normals.contiguous()
-        _lib.check(_L().lcr_icp_point_to_plane(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, _lib.ptr(nrm), S, _lib.ptr(init), *tail),
-                   "lcr_icp_point_to_plane")
+        _lib.call.lcr_icp_point_to_plane(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, _lib.ptr(nrm), S, _lib.ptr(init), *tail)
     else:
-        _lib.check(_L().lcr_icp_point_to_point(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, S, _lib.ptr(init), *tail),
-                   "lcr_icp_point_to_point")
+        _lib.call.lcr_icp_point_to_point(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, S, _lib.ptr(init), *tail)
     if want_corr:
         out["corr"] = corr
     if want_history:
@@ -1074,15 +1023,13 @@ def estimate_normals(points, lengths, radius, max_nn, viewpoint=None, want_curva
         vp = vp.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
         if vp.shape[0] != B:
             raise ValueError("estimate_normals: viewpoint must be [B,3] for the B clouds")
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_normals_ws_bytes(B, points.shape[0], ctypes.byref(nbytes)), "lcr_normals_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_normals_ws_bytes", B, points.shape[0], device=dev)
     n = points.shape[0]
     out = {"normals": torch.empty((n, 3), dtype=torch.float32, device=dev)}
     curv = torch.empty((n,), dtype=torch.float32, device=dev) if want_curvature else None
     cnt = torch.empty((n,), dtype=torch.int32, device=dev) if want_count else None
-    _lib.check(_L().lcr_estimate_normals(_lib.ptr(points), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(vp), _lib.ptr(out["normals"]),
-                                         _lib.ptr(curv), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_estimate_normals")
+    _lib.call.lcr_estimate_normals(_lib.ptr(points), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(vp), _lib.ptr(out["normals"]),
+                                   _lib.ptr(curv), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     if want_curvature:
         out["curvature"] = curv
     if want_count:
@@ -1110,14 +1057,12 @@ def fpfh(points, normals, lengths, radius, max_nn, want_spfh=False, want_count=F
         raise ValueError("fpfh: normals must be float32 with the shape and device of points")
     points, normals = points.contiguous(), normals.contiguous()
     n = points.shape[0]
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_fpfh_ws_bytes(B, n, int(max_nn), ctypes.byref(nbytes)), "lcr_fpfh_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_fpfh_ws_bytes", B, n, int(max_nn), device=dev)
     out = {"features": torch.empty((n, FPFH_BINS), dtype=torch.float32, device=dev)}
     spfh = torch.empty((n, FPFH_BINS), dtype=torch.float32, device=dev) if want_spfh else None
     cnt = torch.empty((n,), dtype=torch.int32, device=dev) if want_count else None
-    _lib.check(_L().lcr_fpfh(_lib.ptr(points), _lib.ptr(normals), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(out["features"]),
-                             _lib.ptr(spfh), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_fpfh")
+    _lib.call.lcr_fpfh(_lib.ptr(points), _lib.ptr(normals), ln.ctypes.data, B, float(radius), int(max_nn), _lib.ptr(out["features"]),
+                       _lib.ptr(spfh), _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     if want_spfh:
         out["spfh"] = spfh
     if want_count:
@@ -1143,13 +1088,11 @@ def range_images(points, lengths, H=64, W=900, fov_up=3.0, fov_down=-25.0, max_r
     current stream."""
     points, ln = _scan_clouds("range_images", points, lengths)
     dev, B = points.device, len(ln)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_range_images_ws_bytes(B, ctypes.byref(nbytes)), "lcr_range_images_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_range_images_ws_bytes", B, device=dev)
     images = torch.empty((B, int(H), int(W)), dtype=torch.float32, device=dev)
     valid = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(_L().lcr_range_images(_lib.ptr(points), ln.ctypes.data, B, int(H), int(W), float(fov_up), float(fov_down), float(max_range),
-                                     _lib.ptr(images), _lib.ptr(valid), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_range_images")
+    _lib.call.lcr_range_images(_lib.ptr(points), ln.ctypes.data, B, int(H), int(W), float(fov_up), float(fov_down), float(max_range),
+                               _lib.ptr(images), _lib.ptr(valid), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     return images, valid
 
 
@@ -1171,12 +1114,10 @@ def scan_overlap(points, lengths, images, valid, pairs, rel, H=64, W=900, fov_up
     images, valid, pairs, rel = images.contiguous(), valid.contiguous(), pairs.contiguous(), rel.contiguous()
     counts = torch.empty((P, 3), dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_scan_overlap_ws_bytes(B, P, ctypes.byref(nbytes)), "lcr_scan_overlap_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
-    _lib.check(_L().lcr_scan_overlap(_lib.ptr(points), ln.ctypes.data, B, _lib.ptr(images), _lib.ptr(valid), _lib.ptr(pairs), _lib.ptr(rel), P,
-                                     int(H), int(W), float(fov_up), float(fov_down), float(max_range), float(eps), _lib.ptr(counts),
-                                     _lib.ptr(status), _lib.ptr(ws), ws.numel(), _sp(points)), "lcr_scan_overlap")
+    ws = _lib.ws("lcr_scan_overlap_ws_bytes", B, P, device=dev)
+    _lib.call.lcr_scan_overlap(_lib.ptr(points), ln.ctypes.data, B, _lib.ptr(images), _lib.ptr(valid), _lib.ptr(pairs), _lib.ptr(rel), P,
+                               int(H), int(W), float(fov_up), float(fov_down), float(max_range), float(eps), _lib.ptr(counts),
+                               _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(points.device))
     return counts, status
 
 
@@ -1258,14 +1199,12 @@ def gap_loss(scores, geom, gamma, pmask, qmask, points=None, overlaps=None, out=
         if name not in out:
             out[name] = torch.empty(shape, dtype=dt, device=dev)
     if ws is None:
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(_L().lcr_gap_loss_ws_bytes(g.rows, g.cols, ctypes.byref(nbytes)), "lcr_gap_loss_ws_bytes")
-        ws = _lib.workspace(nbytes.value, dev)
+        ws = _lib.ws("lcr_gap_loss_ws_bytes", g.rows, g.cols, device=dev)
     P = _lib.ptr
-    _lib.check(_L().lcr_gap_loss(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows, g.cols,
-                                 source, P(pp), P(qp), P(T), float(radius), P(corr), P(ov), P(cstart), C, c_max, float(thr), P(pm), P(qm),
-                                 float(gamma), P(out["terms"]), P(out["kept"]), P(out["labels"]), P(out["line_pos"]), P(out["line_hinge"]),
-                                 P(out["line_count"]), P(out["line_active"]), P(out["status"]), P(ws), ws.numel(), _sp(scores)), "lcr_gap_loss")
+    _lib.call.lcr_gap_loss(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows, g.cols,
+                           source, P(pp), P(qp), P(T), float(radius), P(corr), P(ov), P(cstart), C, c_max, float(thr), P(pm), P(qm),
+                           float(gamma), P(out["terms"]), P(out["kept"]), P(out["labels"]), P(out["line_pos"]), P(out["line_hinge"]),
+                           P(out["line_count"]), P(out["line_active"]), P(out["status"]), P(ws), ws.numel(), _lib.stream_ptr(scores.device))
     return out
 
 
@@ -1279,10 +1218,9 @@ def gap_loss_grad(scores, geom, gamma, saved, upstream, dS=None):
     scores, upstream = scores.contiguous().view(-1), upstream.contiguous()
     dS = torch.empty((g.elems,), dtype=torch.float32, device=scores.device) if dS is None else dS
     P = _lib.ptr
-    _lib.check(_L().lcr_gap_loss_grad(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows,
-                                      g.cols, float(gamma), P(upstream), P(saved["kept"]), P(saved["labels"]), P(saved["line_pos"]),
-                                      P(saved["line_hinge"]), P(saved["line_count"]), P(saved["line_active"]), P(dS), _sp(scores)),
-               "lcr_gap_loss_grad")
+    _lib.call.lcr_gap_loss_grad(P(scores), P(g.soff), P(g.roff), P(g.coff), P(g.seg_start), g.B, g.P, g.n_max, g.m_max, g.elems, g.rows,
+                                g.cols, float(gamma), P(upstream), P(saved["kept"]), P(saved["labels"]), P(saved["line_pos"]),
+                                P(saved["line_hinge"]), P(saved["line_count"]), P(saved["line_active"]), P(dS), _lib.stream_ptr(scores.device))
     return dS
 
 
@@ -1317,8 +1255,8 @@ def min_dist(A, D, a_counts, d_counts, valid=None, starts=None, out=None):
             out[name] = torch.empty(shape, dtype=dt, device=dev)
     out.update({"a_start": starts[0], "d_start": starts[1], "valid": valid})
     P = _lib.ptr
-    _lib.check(_L().lcr_min_dist(P(A), P(starts[0]), A.shape[0], P(D), P(starts[1]), D.shape[0], P(valid), P_, max(a_counts), P(out["dist"]),
-                                 P(out["arg"]), P(out["mean"]), P(out["count"]), _sp(A)), "lcr_min_dist")
+    _lib.call.lcr_min_dist(P(A), P(starts[0]), A.shape[0], P(D), P(starts[1]), D.shape[0], P(valid), P_, max(a_counts), P(out["dist"]),
+                           P(out["arg"]), P(out["mean"]), P(out["count"]), _lib.stream_ptr(A.device))
     return out
 
 
@@ -1331,9 +1269,8 @@ def min_dist_grad(A, D, a_counts, d_counts, saved, upstream, dA=None):
     A, D, upstream = A.contiguous(), D.contiguous(), upstream.contiguous()
     dA = torch.empty_like(A) if dA is None else dA
     P = _lib.ptr
-    _lib.check(_L().lcr_min_dist_grad(P(A), P(saved["a_start"]), A.shape[0], P(D), P(saved["d_start"]), D.shape[0], P(saved["valid"]),
-                                      len(a_counts), max(a_counts), P(saved["arg"]), P(saved["dist"]), P(saved["count"]), P(upstream), P(dA),
-                                      _sp(A)), "lcr_min_dist_grad")
+    _lib.call.lcr_min_dist_grad(P(A), P(saved["a_start"]), A.shape[0], P(D), P(saved["d_start"]), D.shape[0], P(saved["valid"]), len(a_counts),
+                                max(a_counts), P(saved["arg"]), P(saved["dist"]), P(saved["count"]), P(upstream), P(dA), _lib.stream_ptr(A.device))
     return dA
 
 
@@ -1362,9 +1299,7 @@ def adan_table(params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, pre_grads, f
 
 
 def adan_ws_bytes(table):
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_L().lcr_adan_ws_bytes(table.ctypes.data, len(table), ctypes.byref(nbytes)), "lcr_adan_ws_bytes")
-    return nbytes.value
+    return _lib.ws_size("lcr_adan_ws_bytes", table.ctypes.data, len(table))
 
 
 def adan_grad_norm(table, max_grad_norm, eps, device, norm_clip=None, ws=None):
@@ -1374,13 +1309,12 @@ def adan_grad_norm(table, max_grad_norm, eps, device, norm_clip=None, ws=None):
         norm_clip = torch.empty(2, dtype=torch.float32, device=device)
     if ws is None:
         ws = _lib.workspace(adan_ws_bytes(table), device)
-    _lib.check(_L().lcr_adan_grad_norm(table.ctypes.data, len(table), float(max_grad_norm), float(eps), _lib.ptr(norm_clip), _lib.ptr(ws),
-                                       ws.numel() * ws.element_size(), _lib.stream_ptr(device)), "lcr_adan_grad_norm")
+    _lib.call.lcr_adan_grad_norm(table.ctypes.data, len(table), float(max_grad_norm), float(eps), _lib.ptr(norm_clip), _lib.ptr(ws),
+                                 ws.numel() * ws.element_size(), _lib.stream_ptr(device))
     return norm_clip
 
 
 def adan_step(table, hyper, clip, device):
     """lcr_adan_step: one fused pass over the tensors of `table` (adan_table); hyper = AdanHyper, clip = a device float32 tensor of one
     element (the second entry of adan_grad_norm's result) or None.  No host synchronisation."""
-    _lib.check(_L().lcr_adan_step(table.ctypes.data, len(table), ctypes.addressof(hyper), _lib.ptr(clip), _lib.stream_ptr(device)),
-               "lcr_adan_step")
+    _lib.call.lcr_adan_step(table.ctypes.data, len(table), ctypes.addressof(hyper), _lib.ptr(clip), _lib.stream_ptr(device))

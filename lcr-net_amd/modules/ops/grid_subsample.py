@@ -3,7 +3,6 @@
 Reference: ``ext.grid_subsampling(points, lengths, voxel_size) -> (s_points, s_lengths)``
 (utils/extensions/cpu/grid_subsampling/grid_subsampling.cpp:5-62).  Bit-exact, including the output order.
 """
-import ctypes
 
 import torch
 
@@ -28,18 +27,14 @@ def grid_subsample_device(points, lengths, voxel_size, key_bits_hint=0):
     dev = points.device
     lengths = lengths.to(dev, non_blocking=True)
     B, n = lengths.numel(), points.shape[0]
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_grid_subsample_ws_bytes(n, B, ctypes.byref(nbytes)), "lcr_grid_subsample_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_grid_subsample_ws_bytes", n, B, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
     out_len = torch.empty((B,), dtype=torch.int64, device=dev)
     if points.dim() != 2 or points.shape[1] < 3:
         raise RuntimeError("points must be [N, C] with C >= 3 (x, y, z first)")
-    _lib.check(L.lcr_grid_subsample_rows(_lib.ptr(points), int(points.shape[1]), _lib.ptr(lengths), B, n, float(voxel_size), int(key_bits_hint),
-                                         _lib.ptr(out), _lib.ptr(out_len), _lib.ptr(status), _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev)), "lcr_grid_subsample")
+    _lib.call.lcr_grid_subsample_rows(_lib.ptr(points), int(points.shape[1]), _lib.ptr(lengths), B, n, float(voxel_size), int(key_bits_hint),
+                                      _lib.ptr(out), _lib.ptr(out_len), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return out, out_len, status
 
 

@@ -4,7 +4,6 @@ Reference: ``ext.radius_neighbors(q, s, q_lengths, s_lengths, radius)`` then ``[
 non-contiguous view; here the result is always contiguous).  Checks mirror the TORCH_CHECKs of
 utils/extensions/cpu/radius_neighbors/radius_neighbors.cpp:12-23 (dtype / contiguity), with "CUDA" for "CPU".
 """
-import ctypes
 
 import torch
 
@@ -38,17 +37,14 @@ def _call(q_points, s_points, q_lengths, s_lengths, radius, limit, want64, want3
     if B > MAX_CLOUDS:
         return _call_grouped(q_points, s_points, q_lengths, s_lengths, radius, limit, want64, want32, want_cnt)
     nq, ns = q_points.shape[0], s_points.shape[0]
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_radius_search_ws_bytes(nq, ns, B, ctypes.byref(nbytes)), "lcr_radius_search_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_radius_search_ws_bytes", nq, ns, B, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     out64 = torch.empty((nq, limit), dtype=torch.int64, device=dev) if (want64 and limit > 0) else None
     out32 = torch.empty((nq, limit), dtype=torch.int32, device=dev) if (want32 and limit > 0) else None
     cnt = torch.zeros((nq,), dtype=torch.int32, device=dev) if want_cnt else None      # rows beyond sum(q_lengths) are never written
-    _lib.check(L.lcr_radius_search(_lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(q_lengths), _lib.ptr(s_lengths), B,
-                                   nq, ns, float(radius), int(limit), _lib.ptr(out64), _lib.ptr(out32), _lib.ptr(cnt),
-                                   _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "lcr_radius_search")
+    _lib.call.lcr_radius_search(_lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(q_lengths), _lib.ptr(s_lengths), B,
+                                nq, ns, float(radius), int(limit), _lib.ptr(out64), _lib.ptr(out32), _lib.ptr(cnt),
+                                _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return out64, out32, cnt, status
 
 
@@ -148,20 +144,15 @@ class SupportGrid:
         self.s_points, self.s_lengths, self.radius = s_points, s_lengths, float(radius)
         self.B, self.ns_cap = s_lengths.numel(), s_points.shape[0]
         dev = s_points.device
-        L = _lib.lib()
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(L.lcr_support_grid_ws_bytes(self.ns_cap, self.B, ctypes.byref(nbytes)), "lcr_support_grid_ws_bytes")
-        self.ws = _lib.workspace(nbytes.value, dev)
+        self.ws = _lib.ws("lcr_support_grid_ws_bytes", self.ns_cap, self.B, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(L.lcr_support_grid_build(_lib.ptr(s_points), _lib.ptr(s_lengths), self.B, self.ns_cap, self.radius,
-                                            _lib.ptr(self.status), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr(dev)),
-                   "lcr_support_grid_build")
+        _lib.call.lcr_support_grid_build(_lib.ptr(s_points), _lib.ptr(s_lengths), self.B, self.ns_cap, self.radius,
+                                         _lib.ptr(self.status), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr(dev))
 
     def order(self):
         """int32 [ns_cap]: stacked support rows in cell-sorted order (first sum(s_lengths) entries valid)."""
         out = torch.empty((self.ns_cap,), dtype=torch.int32, device=self.s_points.device)
-        _lib.check(_lib.lib().lcr_support_grid_order(_lib.ptr(self.ws), self.ns_cap, self.B, _lib.ptr(out), _lib.stream_ptr(out.device)),
-                   "lcr_support_grid_order")
+        _lib.call.lcr_support_grid_order(_lib.ptr(self.ws), self.ns_cap, self.B, _lib.ptr(out), _lib.stream_ptr(out.device))
         return out
 
     def query(self, q_points, q_lengths, neighbor_limit, dtype=torch.int32, want_counts=False, q_order=None):
@@ -176,7 +167,6 @@ class SupportGrid:
         cnt = torch.empty((nq,), dtype=torch.int32, device=dev) if (want_counts or limit == 0) else None
         o64, o32 = (out, None) if dtype == torch.int64 else (None, out)
         assert q_order is None or (q_order.dtype == torch.int32 and q_order.is_contiguous() and q_order.numel() >= nq)
-        _lib.check(_lib.lib().lcr_radius_query_ordered(_lib.ptr(q_points), _lib.ptr(q_lengths), self.B, nq, _lib.ptr(self.ws), self.ns_cap,
-                                                       self.radius, limit, _lib.ptr(o64), _lib.ptr(o32), _lib.ptr(cnt), _lib.ptr(q_order),
-                                                       _lib.stream_ptr(dev)), "lcr_radius_query")
+        _lib.call.lcr_radius_query_ordered(_lib.ptr(q_points), _lib.ptr(q_lengths), self.B, nq, _lib.ptr(self.ws), self.ns_cap, self.radius, limit,
+                                           _lib.ptr(o64), _lib.ptr(o32), _lib.ptr(cnt), _lib.ptr(q_order), _lib.stream_ptr(dev))
         return (out, cnt) if (want_counts or limit == 0) else out

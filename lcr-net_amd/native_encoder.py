@@ -171,13 +171,10 @@ def forward(enc, feats, data_dict):
     limits = [int(N[i].shape[1]) for i in range(4)]
     for i in range(3):
         assert int(Sub[i].shape[1]) == limits[i] and int(Sub[i].shape[0]) == n[i + 1]
-    L = _lib.lib()
     n_host = (ctypes.c_int64 * 4)(*n)
     min_rows = (ctypes.c_int64 * 4)(*rows)
     lim = (ctypes.c_int * 4)(*limits)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_encoder_ws_bytes(ctypes.byref(tab.w), n_host, nseg, ctypes.byref(nbytes)), "lcr_encoder_ws_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.ws_size("lcr_encoder_ws_bytes", ctypes.byref(tab.w), n_host, nseg), dtype=torch.uint8, device=dev)
     outs = [torch.empty((n[i], tab.out_channels[i]), dtype=torch.float32, device=dev) for i in range(4)]
     vp4 = ctypes.c_void_p * 4
     pts = vp4(*[p.data_ptr() for p in P])
@@ -189,6 +186,6 @@ def forward(enc, feats, data_dict):
     f0 = feats.contiguous()
     # rows known to come from a radius search (our collates mark their dictionaries) may be cut at their first padded chunk
     flags = LISTS_VALID_FIRST if data_dict.get("lists_valid_first") else 0
-    _lib.check(L.lcr_encoder_forward_ex(ctypes.byref(tab.w), _lib.ptr(f0), pts, nb, sb, od, sg, nseg, n_host, min_rows, lim, of, flags, _lib.ptr(ws),
-                                        ws.numel(), _lib.stream_ptr(dev)), "lcr_encoder_forward_ex")
+    _lib.call.lcr_encoder_forward_ex(ctypes.byref(tab.w), _lib.ptr(f0), pts, nb, sb, od, sg, nseg, n_host, min_rows, lim, of, flags, _lib.ptr(ws),
+                                     ws.numel(), _lib.stream_ptr(dev))
     return outs

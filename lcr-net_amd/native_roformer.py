@@ -74,13 +74,10 @@ def forward(tf, points, feats, lens0, lens1):
     P = len(lens0)
     n = int(points.shape[0])
     dev = feats.device
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_roformer_ws_bytes(ctypes.byref(w), n, ctypes.byref(nbytes)), "lcr_roformer_ws_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.ws_size("lcr_roformer_ws_bytes", ctypes.byref(w), n), dtype=torch.uint8, device=dev)
     out = torch.empty((n, w.d_out), dtype=torch.float32, device=dev)
     theta = torch.empty((n, w.d_model // 2), dtype=torch.float32, device=dev)
     l0, l1 = (ctypes.c_int64 * P)(*[int(x) for x in lens0]), (ctypes.c_int64 * P)(*[int(x) for x in lens1])
-    _lib.check(L.lcr_roformer_forward(ctypes.byref(w), _lib.ptr(points.contiguous()), _lib.ptr(feats.contiguous()), l0, l1, P, _lib.ptr(out),
-                                      _lib.ptr(theta), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "lcr_roformer_forward")
+    _lib.call.lcr_roformer_forward(ctypes.byref(w), _lib.ptr(points.contiguous()), _lib.ptr(feats.contiguous()), l0, l1, P, _lib.ptr(out),
+                                   _lib.ptr(theta), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return out, theta

@@ -88,15 +88,14 @@ def _share_queue(a, b, spin_us=400):
     """True if streams a and b are served by the same hardware queue: a short kernel on b behind a long spin on a."""
     import ctypes
     from . import _lib
-    L = _lib.lib()
     best = None
     for _ in range(3):                                                     # the shortest of three trials: a cold launch, a clock
         a.synchronize()                                                    # ramp or another process's kernel can only ADD time
         b.synchronize()
         t0, tb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record(b)                                                       # b's clock starts before a's spin is queued
-        _lib.check(L.lcr_stream_spin(spin_us, ctypes.c_void_p(a.cuda_stream)), "lcr_stream_spin")
-        _lib.check(L.lcr_stream_spin(1, ctypes.c_void_p(b.cuda_stream)), "lcr_stream_spin")
+        _lib.call.lcr_stream_spin(spin_us, ctypes.c_void_p(a.cuda_stream))
+        _lib.call.lcr_stream_spin(1, ctypes.c_void_p(b.cuda_stream))
         tb.record(b)
         a.synchronize()
         b.synchronize()
@@ -122,7 +121,7 @@ def distinct_queue_streams(device, n, priority=0, pool=10):
     import ctypes
     from . import _lib
     for c in cand:                                        # first launch on every candidate (code object load, queue creation)
-        _lib.check(_lib.lib().lcr_stream_spin(1, ctypes.c_void_p(c.cuda_stream)), "lcr_stream_spin")
+        _lib.call.lcr_stream_spin(1, ctypes.c_void_p(c.cuda_stream))
     torch.cuda.synchronize(device)
     chosen = []
     for c in cand:

@@ -6,7 +6,6 @@ IndexIVFFlat(nlist=1) over descriptors [0, i-100), k=50, squared L2 (`eval_one_e
 contiguous range of frames, computes their descriptors, all-gathers the [n_r,256] blocks over RCCL (the only collective
 on the path — it has no counterpart in the reference, which runs retrieval offline on one CPU) and searches its own rows.
 """
-import ctypes
 
 import torch
 
@@ -23,14 +22,11 @@ def retrieval_topk(queries, q0, database, k=K_DEFAULT, exclude=EXCLUDE_DEFAULT):
     Q, D = queries.shape
     C = database.shape[0]
     dev = queries.device
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.lcr_retrieval_ws_bytes(Q, C, ctypes.byref(nbytes)), "lcr_retrieval_ws_bytes")
-    ws = _lib.workspace(nbytes.value, dev)
+    ws = _lib.ws("lcr_retrieval_ws_bytes", Q, C, device=dev)
     idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
     d2 = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    _lib.check(L.lcr_retrieval_topk(_lib.ptr(queries), Q, int(q0), _lib.ptr(database), C, D, int(k), int(exclude), _lib.ptr(idx),
-                                    _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "lcr_retrieval_topk")
+    _lib.call.lcr_retrieval_topk(_lib.ptr(queries), Q, int(q0), _lib.ptr(database), C, D, int(k), int(exclude), _lib.ptr(idx),
+                                 _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return idx, d2
 
 
