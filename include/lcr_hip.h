@@ -518,6 +518,18 @@ int lcr_log_sinkhorn_ws_floats(int64_t B, int M, int N, size_t* floats);
 int lcr_log_sinkhorn_form(int64_t B, int M, int N, int* form);
 int lcr_log_sinkhorn_ex(float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters,
                         float inf_val, float* uv_ws, size_t uv_floats, void* stream);
+/* Reverse pass of the transport (csrc/sinkhorn_grad.hip).  S0: the padded scores BEFORE the transport (what lcr_build_padded_scores /
+ * lcr_patch_scores write), G = dL/d(output) f32[B,M+1,N+1] -> dS f32[B,M+1,N+1] = dL/dS0 (exactly zero on masked rows / columns, whatever G
+ * holds there; all zero for a problem without a valid row or column) and d_alpha_part f32[B] = the per-problem sum of dS over the dustbin
+ * row and column.  The duals of all `iters` iterations are recomputed and recorded by the call itself (no early exit, no truncation).
+ * Deterministic: no floating-point atomics, a problem's result does not depend on its batch.  Form 0 (M+1, N+1 <= 132): one resident
+ * workgroup per problem; form 1: one launch per half-step.  The _ws_bytes and _form queries are host-only; B == 0 is a no-op returning 0;
+ * a short workspace, iters < 1 or a null pointer is refused before any launch.  ws is written in full or in part and holds nothing on
+ * return that a caller should read. */
+int lcr_log_sinkhorn_grad_ws_bytes(int64_t B, int M, int N, int iters, size_t* bytes);
+int lcr_log_sinkhorn_grad_form(int64_t B, int M, int N, int* form);
+int lcr_log_sinkhorn_grad(const float* S0, const float* G, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N,
+                          int iters, float inf_val, float* dS, float* d_alpha_part, void* ws, size_t ws_bytes, void* stream);
 /* Dustbin top-1 matching in the exp domain (superpoint_matching.py:130-162; local_global_registration.py:49-92 with k=1,
  * mutual=False, use_dustbin=True): (b,i,j) kept if it is its row's maximum beating the dustbin column OR its column's
  * maximum beating the dustbin row (and row/col masks, if given).  Phase 1: out_bij == NULL -> *total (device i64);

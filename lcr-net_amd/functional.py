@@ -1,7 +1,8 @@
 """Thin tensor-level wrappers over the C ABI (include/lcr_hip.h).  No arithmetic happens in Python: every function
-allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd), with one exception:
+allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd), with two exceptions:
 gap_loss / min_dist have the gradient launchers gap_loss_grad / min_dist_grad beside them, which losses.py wraps in
-torch.autograd.Functions (gradients to the scores and to the queries only)."""
+torch.autograd.Functions (gradients to the scores and to the queries only); and log_optimal_transport / patch_log_optimal_transport
+are differentiable (_TransportFn over lcr_log_sinkhorn_grad: gradients to the raw scores and to alpha)."""
 import ctypes
 import os
 import threading
@@ -607,8 +608,16 @@ def check_transport_status():
         raise RuntimeError("lcr_log_sinkhorn: a workgroup hand-off of the persistent form timed out (set LCR_SINKHORN_COOP=0)")
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
 def log_optimal_transport(raw_scores, row_masks, col_masks, alpha, scale=1.0, iters=100, inf=1e12):
-    """LearnableLogOptimalTransport on raw products [B,M,N] (scaled by `scale`) -> log scores [B,M+1,N+1]."""
+    """LearnableLogOptimalTransport on raw products [B,M,N] (scaled by `scale`) -> log scores [B,M+1,N+1].  Differentiable in raw_scores and
+    alpha: when either requires grad (and grad mode is on) the result carries a graph whose backward is lcr_log_sinkhorn_grad; its bytes
+    are the no-grad call's."""
+    if _wants_grad(raw_scores, alpha):
+        return _TransportFn.apply(raw_scores, alpha, row_masks, col_masks, float(scale), int(iters), float(inf))
     B, M, N = raw_scores.shape
     dev = raw_scores.device
     rm, cm = row_masks.to(torch.uint8).contiguous(), col_masks.to(torch.uint8).contiguous()
@@ -616,6 +625,50 @@ def log_optimal_transport(raw_scores, row_masks, col_masks, alpha, scale=1.0, it
     _lib.call.lcr_build_padded_scores(_lib.ptr(raw_scores.contiguous()), _lib.ptr(rm), _lib.ptr(cm), B, M, N, float(scale),
                                       _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _lib.stream_ptr(S.device))
     return _transport_padded(S, rm, cm, iters, inf)
+
+
+def log_sinkhorn_grad(S0, G, rm, cm, iters=100, inf=1e12):
+    """(dS [B,M+1,N+1], d_alpha_part [B]) of lcr_log_sinkhorn_grad: S0 the padded scores before the transport, G = dL/d(log scores), rm / cm
+    the uint8 masks.  No host synchronisation."""
+    _lib.require_cuda(S0, G, rm, cm)
+    B, M, N = S0.shape[0], S0.shape[1] - 1, S0.shape[2] - 1
+    assert S0.dtype == torch.float32 and S0.is_contiguous() and G.dtype == torch.float32 and G.is_contiguous() and G.shape == S0.shape
+    assert rm.dtype == torch.uint8 and cm.dtype == torch.uint8 and rm.is_contiguous() and cm.is_contiguous()
+    assert tuple(rm.shape) == (B, M) and tuple(cm.shape) == (B, N)
+    dS = torch.empty_like(S0)
+    part = torch.empty((B,), dtype=torch.float32, device=S0.device)
+    ws = _lib.ws("lcr_log_sinkhorn_grad_ws_bytes", B, M, N, int(iters), device=S0.device)
+    _lib.call.lcr_log_sinkhorn_grad(_lib.ptr(S0), _lib.ptr(G), _lib.ptr(rm), _lib.ptr(cm), B, M, N, int(iters), float(inf), _lib.ptr(dS), _lib.ptr(part),
+                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(S0.device))
+    return dS, part
+
+
+class _TransportFn(torch.autograd.Function):
+    """log_optimal_transport with a backward: the forward pads the scores (S0), keeps them and runs the transport of the no-grad path on a
+    copy; the backward is lcr_log_sinkhorn_grad on S0 (it recomputes the duals itself), d_raw = scale * dS[:, :M, :N] and d_alpha = the sum
+    of the per-problem dustbin sums (in fp64: a long sum with cancellation)."""
+
+    @staticmethod
+    def forward(ctx, raw_scores, alpha, row_masks, col_masks, scale, iters, inf):
+        _lib.require_cuda(raw_scores, row_masks, col_masks, alpha)
+        B, M, N = raw_scores.shape
+        rm, cm = row_masks.to(torch.uint8).contiguous(), col_masks.to(torch.uint8).contiguous()
+        S0 = torch.empty((B, M + 1, N + 1), dtype=torch.float32, device=raw_scores.device)
+        raw, a1 = raw_scores.detach().contiguous(), alpha.detach().reshape(1).float()     # named: copies must outlive the argument list
+        _lib.call.lcr_build_padded_scores(_lib.ptr(raw), _lib.ptr(rm), _lib.ptr(cm), B, M, N, scale, _lib.ptr(a1), inf, _lib.ptr(S0),
+                                          _lib.stream_ptr(S0.device))
+        ctx.save_for_backward(S0, rm, cm)
+        ctx.scale, ctx.iters, ctx.inf, ctx.alpha_shape = scale, iters, inf, alpha.shape
+        return _transport_padded(S0.clone(), rm, cm, iters, inf)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        S0, rm, cm = ctx.saved_tensors
+        dS, part = log_sinkhorn_grad(S0, G.contiguous().float(), rm, cm, ctx.iters, ctx.inf)
+        d_raw = dS[:, :-1, :-1] * ctx.scale if ctx.needs_input_grad[0] else None
+        d_alpha = part.double().sum().float().reshape(ctx.alpha_shape) if ctx.needs_input_grad[1] else None
+        return d_raw, d_alpha, None, None, None, None, None
 
 
 PATCH_SCORES_FUSED = [os.environ.get("LCR_PATCH_SCORES_FUSED", "1") != "0"]      # A/B switch (tests, tools): 0 = gather + batched product + padding
@@ -626,6 +679,12 @@ def patch_log_optimal_transport(feats_a, idx_a, feats_b, idx_b, mask_a, mask_b, 
     rows idx_a[p] of feats_a / idx_b[p] of feats_b (index == number of rows: the zero row of the padded tensor).  The gathers, the batched
     product, the scaling and the dustbin / mask padding are ONE kernel (lcr_patch_scores); LCR_PATCH_SCORES_FUSED=0 runs them apart."""
     P, K = idx_a.shape
+    if _wants_grad(feats_a, feats_b, alpha):
+        # training: the gather (on the zero-row-padded features) and the product are torch's, which differentiates them; the transport
+        # and its reverse pass are the library's
+        fa = torch.cat([feats_a, feats_a.new_zeros(1, feats_a.shape[1])])[idx_a]
+        fb = torch.cat([feats_b, feats_b.new_zeros(1, feats_b.shape[1])])[idx_b]
+        return log_optimal_transport(torch.bmm(fa, fb.transpose(1, 2)), mask_a, mask_b, alpha, scale=scale, iters=iters, inf=inf)
     if not PATCH_SCORES_FUSED[0] or K != 128 or feats_a.shape[1] % 32 != 0 or P == 0:
         fa, fb = gather_rows(feats_a, idx_a.contiguous()), gather_rows(feats_b, idx_b.contiguous())
         return log_optimal_transport(bmm_nt(fa, fb), mask_a, mask_b, alpha, scale=scale, iters=iters, inf=inf)

@@ -6,6 +6,8 @@ The two hot terms run in HIP (csrc/losses.hip, include/lcr_hip.h): the gap loss 
 the points once, both with their gradient kernels behind a torch.autograd.Function (gradient to the scores / to the queries), so
 `loss.backward()` fills the .grad of torch leaf tensors.  The weighted BCE, the rotary regulariser and the triplet loss are a few tiny
 torch ops on the device.  There is no model backward here: the losses are the leaves of a training path, and validate a checkpoint.
+The scores they receive may carry a graph: functional.log_optimal_transport is differentiable, so matching_scores and
+node_matching_scores made with grad mode on lead back to the raw scores and to the two transports' alpha.
 
 Every module also takes the LIST of output dicts `forward_pairs` returns, with data_dict['transform'] stacked (P, 4, 4): one launch set
 for all P pairs, a list of P results.  Patch counts, node counts and patch sizes may differ between the pairs.

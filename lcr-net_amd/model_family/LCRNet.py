@@ -107,6 +107,15 @@ class LearnableLogOptimalTransport(nn.Module):
         self.num_iterations = num_iterations
         self.register_parameter("alpha", nn.Parameter(torch.tensor(1.0)))
 
+    def forward(self, scores, row_masks=None, col_masks=None):
+        """learnable_sinkhorn.py:20-66: scores [B,M,N] -> log scores [B,M+1,N+1]; differentiable in scores and alpha."""
+        B, M, N = scores.shape
+        if row_masks is None:
+            row_masks = torch.ones((B, M), dtype=torch.bool, device=scores.device)
+        if col_masks is None:
+            col_masks = torch.ones((B, N), dtype=torch.bool, device=scores.device)
+        return F.log_optimal_transport(scores, row_masks, col_masks, self.alpha, iters=self.num_iterations)
+
 
 class LCRNet(nn.Module):
     # The reference has three classes with this body: LCRNet (global descriptors + matching), LCRNet_Matching_infer (the same
