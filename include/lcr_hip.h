@@ -432,6 +432,29 @@ int lcr_add_layernorm(const float* a, const float* b, const float* gamma, const 
                       float* y, void* stream);
 int lcr_relu_inplace(float* x, int64_t n, void* stream);
 
+/* Reverse passes of the block above (csrc/attention_grad.hip).  None of them changes what the forward entries compute or keep.
+ *
+ * lcr_attention_seg_grad_f32: q, k, v as the forward consumed them (post-rotary), out = the forward's result, d_out = dL/d(out) ->
+ * dq [sum q_len, heads*32], dk, dv [sum k_len, heads*32].  Same domain as lcr_attention_seg_f32 (P = 1 covers lcr_attention_f32).  The
+ * softmax row statistic is recomputed by the call (L = m + log2 l per query and head, with D = sum_d d_out*out, in ws:
+ * lcr_attention_grad_ws_bytes(sum q_len, heads), host-only); then one kernel over key tiles (dk, dv) and one over query tiles (dq), partial
+ * sums merged in a fixed order: no floating-point atomics, results repeat to the bit and a problem's bytes do not depend on its batch.  A
+ * query whose d_out row is zero gets a zero dq row; with one key dq = dk = 0 and dv = d_out exactly.  A short workspace or a null pointer is
+ * refused before any launch. */
+int lcr_attention_grad_ws_bytes(int64_t n_queries, int heads, size_t* bytes);
+int lcr_attention_seg_grad_f32(const float* q, const float* k, const float* v, const float* out, const float* d_out,
+                               const int64_t* q_len_host, const int64_t* k_len_host, int P, int heads, int head_dim, float* dq, float* dk,
+                               float* dv, void* ws, size_t ws_bytes, void* stream);
+/* From the POST-rotary y [N, heads*32] and dy: dx = R(-theta) dy and dtheta [N, heads*16] = dy0*(-y1) + dy1*y0 per channel pair
+ * (d y / d theta = rot(y): the pre-rotary tensor is not needed). */
+int lcr_rotary_embed_grad(const float* y, const float* dy, const float* theta, int64_t N, int heads, float* dx, float* dtheta, void* stream);
+/* y = LayerNorm(a + b) reversed: dx f32[N,D] = dL/d(a + b) (both addends receive it), dgamma, dbeta f32[D].  Mean and rstd are recomputed
+ * per row; dgamma / dbeta are column sums in two stages with a fixed order (partials in ws: lcr_add_layernorm_grad_ws_bytes(N, D), host-only).
+ * b may be NULL; D <= 1024; N == 0 writes zero dgamma / dbeta. */
+int lcr_add_layernorm_grad_ws_bytes(int64_t N, int D, size_t* bytes);
+int lcr_add_layernorm_grad(const float* a, const float* b, const float* gamma, const float* dy, int64_t N, int D, float eps, float* dx,
+                           float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+
 /* The whole ThDRoFormer.forward (thdroformer_linear.py:60-97: position embedding, in_proj, [self, cross] x num_layers, out_proj) as ONE native
  * call: the host-side sequencer over the entries above (same launches, arguments and order as lcr-net_amd/modules/thdroformer, so the
  * outputs are bit-identical to the module tree).  Dense attention only (cfg.GAT.k = None, the shipped configuration; the top-k form runs

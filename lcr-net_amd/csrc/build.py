@@ -26,7 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # v_accvgpr_read / mov / write per four-neighbour trip (22 % of the loop's VALU instructions, the unit that kernel is short of), and the
 # wider layers hold 120 / 190 registers instead of 75 / 112 (4 -> 6 and 2 -> 4 wavefronts per SIMD).  The attention kernel loses 160
 # accumulator moves (99 vs 102-109 us per launch at 8 pairs per call).
-FILE_FLAGS = {"kpconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+FILE_FLAGS = {"kpconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              "attention_grad.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 if os.environ.get("LCR_BUILD_EXTRA"):       # experiments: "file.hip:-flag -flag;other.hip:-flag"
     for part in os.environ["LCR_BUILD_EXTRA"].split(";"):
         name, _, fl = part.partition(":")

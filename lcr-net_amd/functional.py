@@ -2,7 +2,9 @@
 allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd), with two exceptions:
 gap_loss / min_dist have the gradient launchers gap_loss_grad / min_dist_grad beside them, which losses.py wraps in
 torch.autograd.Functions (gradients to the scores and to the queries only); and log_optimal_transport / patch_log_optimal_transport
-are differentiable (_TransportFn over lcr_log_sinkhorn_grad: gradients to the raw scores and to alpha)."""
+are differentiable (_TransportFn over lcr_log_sinkhorn_grad: gradients to the raw scores and to alpha); and the ops of the 3D-RoFormer —
+linear, rotary_embed, attention, add_layernorm — return a graph when grad mode is on and an input requires grad (backwards in
+csrc/attention_grad.hip and on lcr_gemm_f32), and otherwise make exactly the calls of the inference path."""
 import ctypes
 import os
 import threading
@@ -463,11 +465,66 @@ def gemm_batched_ta(a, b, c, M, N, k, a_off, b_off, c_off):
 
 
 def linear(x, weight, bias=None, relu=False):
-    """nn.Linear (weight [out,in]) on the MFMA GEMM, optional ReLU."""
+    """nn.Linear (weight [out,in]) on the MFMA GEMM, optional ReLU.  Differentiable in x, weight and bias (_LinearFn) when one of them
+    requires grad and grad mode is on; the bytes are the no-grad call's."""
+    if _wants_grad(x, weight, bias):
+        return _LinearFn.apply(x, weight, bias, bool(relu))
     y = gemm(x.contiguous(), weight, trans_b=True, bias=bias)[0]
     if relu:
         _lib.call.lcr_relu_inplace(_lib.ptr(y), y.numel(), _lib.stream_ptr(y.device))
     return y
+
+
+WEIGHT_GRAD_SPLIT_ROWS = 512      # from this many rows on dW = dy^T·x is summed over row chunks (one batched launch)
+
+
+def _weight_grad(dy, x):
+    """dW [out,in] = dy^T·x over the rows.  The output is a handful of 64 x 64 tiles however many rows there are, so one lcr_gemm_f32 call
+    walks all rows in 2 - 32 workgroups, adding them one after the other in fp32: slow at the rows of 16 pairs per call, and at 1023 rows
+    already 4.4 x the error of torch's blocked fp32 sum (tests/test_attention_grad_gpu.py).  From WEIGHT_GRAD_SPLIT_ROWS rows on the rows
+    are cut into equal chunks of at most 256 rows (at most 64 chunks, so longer ones beyond 16 384 rows) whose products are ONE
+    lcr_gemm_f32_batched_ta launch, added in chunk order.  The chunking depends on the shape alone: results repeat to the bit.  That entry
+    wants out and in to be multiples of 4: x is padded with zero columns (the position embedding's in = 3); another `out` takes the plain
+    call."""
+    rows, M, N = dy.shape[0], dy.shape[1], x.shape[1]
+    if rows < WEIGHT_GRAD_SPLIT_ROWS or M % 4:
+        return gemm(dy, x, trans_a=True)[0]
+    if N % 4:
+        return _weight_grad(dy, torch.nn.functional.pad(x, (0, 4 - N % 4)))[:, :N].contiguous()
+    count = min(64, (rows + 255) // 256)
+    per = (rows + count - 1) // count
+    count = (rows + per - 1) // per
+    ks = [min(per, rows - z * per) for z in range(count)]
+    c = torch.empty((count, M, N), dtype=torch.float32, device=dy.device)
+    gemm_batched_ta(dy, x, c, M, N, ks, [z * per * M for z in range(count)], [z * per * N for z in range(count)], [z * M * N for z in range(count)])
+    return c.sum(0)
+
+
+class _LinearFn(torch.autograd.Function):
+    """linear() with a backward on the same GEMM: dx = dy·W, dW = dy^T·x (lcr_gemm_f32 with trans_a), db = the column sum of dy; the ReLU
+    mask is read off the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        xc, w = x.detach().contiguous(), weight.detach().contiguous()
+        y = gemm(xc, w, trans_b=True, bias=None if bias is None else bias.detach())[0]
+        if relu:
+            _lib.call.lcr_relu_inplace(_lib.ptr(y), y.numel(), _lib.stream_ptr(y.device))
+        ctx.save_for_backward(xc, w, y if relu else None)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dy = dy.contiguous().float()
+        if ctx.relu:
+            dy = dy * (y > 0)
+        dx = gemm(dy, w)[0] if ctx.needs_input_grad[0] else None
+        dw = _weight_grad(dy, x) if ctx.needs_input_grad[1] else None
+        db = dy.sum(0) if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None
 
 
 def relu_(x):
@@ -482,9 +539,36 @@ def rotary_embed_(x, theta, heads):
     return x
 
 
-def attention(q, k, v, heads, q_lens=None, k_lens=None):
-    """Fused softmax(q k^T / sqrt(d)) v per head; q [Nq, heads*32], k/v [Nk, heads*32].  With q_lens / k_lens (host sequences of
-    equal length P <= 64, summing to Nq / Nk): P independent problems over the stacked rows in one launch."""
+def rotary_embed(x, theta, heads):
+    """Out-of-place rotary position embedding, differentiable in x and theta (lcr_rotary_embed on a copy; backward lcr_rotary_embed_grad from
+    the rotated tensor).  The bytes are rotary_embed_'s."""
+    if _wants_grad(x, theta):
+        return _RotaryFn.apply(x, theta, int(heads))
+    return rotary_embed_(x.detach().clone(memory_format=torch.contiguous_format), theta.contiguous(), heads)
+
+
+class _RotaryFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, theta, heads):
+        _lib.require_cuda(x, theta)
+        th = theta.detach().contiguous()
+        y = rotary_embed_(x.detach().clone(memory_format=torch.contiguous_format), th, heads)
+        ctx.save_for_backward(y, th)
+        ctx.heads = heads
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y, th = ctx.saved_tensors
+        dy = dy.contiguous().float()
+        dx, dth = torch.empty_like(y), torch.empty_like(th)
+        _lib.call.lcr_rotary_embed_grad(_lib.ptr(y), _lib.ptr(dy), _lib.ptr(th), y.shape[0], ctx.heads, _lib.ptr(dx), _lib.ptr(dth),
+                                        _lib.stream_ptr(y.device))
+        return (dx if ctx.needs_input_grad[0] else None), (dth if ctx.needs_input_grad[1] else None), None
+
+
+def _attention_forward(q, k, v, heads, q_lens, k_lens):
     assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
     out = torch.empty_like(q)
     if q_lens is not None:
@@ -499,12 +583,65 @@ def attention(q, k, v, heads, q_lens=None, k_lens=None):
     return out
 
 
+def attention(q, k, v, heads, q_lens=None, k_lens=None):
+    """Fused softmax(q k^T / sqrt(d)) v per head; q [Nq, heads*32], k/v [Nk, heads*32].  With q_lens / k_lens (host sequences of
+    equal length P <= 64, summing to Nq / Nk): P independent problems over the stacked rows in one launch.  Differentiable in q, k and v
+    (_AttentionFn over lcr_attention_seg_grad_f32) when one of them requires grad and grad mode is on; the bytes are the no-grad call's."""
+    if _wants_grad(q, k, v):
+        return _AttentionFn.apply(q, k, v, int(heads), None if q_lens is None else tuple(int(x) for x in q_lens),
+                                  None if k_lens is None else tuple(int(x) for x in k_lens))
+    return _attention_forward(q, k, v, heads, q_lens, k_lens)
+
+
+def attention_grad(q, k, v, out, d_out, heads, q_lens=None, k_lens=None):
+    """(dq, dk, dv) of lcr_attention_seg_grad_f32 for the problems of `attention`: q, k, v as the forward consumed them, out its result,
+    d_out = dL/d(out).  No host synchronisation."""
+    _lib.require_cuda(q, k, v, out, d_out)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (q, k, v, out, d_out)) and out.shape == q.shape and d_out.shape == q.shape
+    ql = [q.shape[0]] if q_lens is None else [int(x) for x in q_lens]
+    kl = [k.shape[0]] if k_lens is None else [int(x) for x in k_lens]
+    P = len(ql)
+    assert len(kl) == P and sum(ql) == q.shape[0] and sum(kl) == k.shape[0] and k.shape == v.shape
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    ws = _lib.ws("lcr_attention_grad_ws_bytes", q.shape[0], int(heads), device=q.device)
+    qa, ka = (ctypes.c_int64 * P)(*ql), (ctypes.c_int64 * P)(*kl)
+    _lib.call.lcr_attention_seg_grad_f32(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(d_out), ctypes.cast(qa, ctypes.c_void_p),
+                                         ctypes.cast(ka, ctypes.c_void_p), P, int(heads), q.shape[1] // int(heads), _lib.ptr(dq), _lib.ptr(dk),
+                                         _lib.ptr(dv), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(q.device))
+    return dq, dk, dv
+
+
+class _AttentionFn(torch.autograd.Function):
+    """attention() with a backward: keeps q, k, v, the output and the lens; the backward is lcr_attention_seg_grad_f32, which recomputes the
+    softmax row statistic itself (the forward entry and its bytes are unchanged)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, q_lens, k_lens):
+        _lib.require_cuda(q, k, v)
+        qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        out = _attention_forward(qc, kc, vc, heads, q_lens, k_lens)
+        ctx.save_for_backward(qc, kc, vc, out)
+        ctx.heads, ctx.q_lens, ctx.k_lens = heads, q_lens, k_lens
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        q, k, v, out = ctx.saved_tensors
+        dq, dk, dv = attention_grad(q, k, v, out, d_out.contiguous().float(), ctx.heads, ctx.q_lens, ctx.k_lens)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None), (dk if need[1] else None), (dv if need[2] else None), None, None, None
+
+
 ATTENTION_TOPK_MAX_KEYS = 4096     # ATK_MAXK of csrc/attention.hip: one row of scores per (query, head) in LDS
 
 
 def attention_topk(q, k, v, heads, q_lens, k_lens, kks):
     """dynamic_attention with k != None (rpetransformer.py:19-39): per problem p (rows stacked like `attention`), query and head, only the
     kks[p] largest scores are soft-maxed.  kks[p] = int(n_queries_p * fraction) is computed by the caller as the reference does."""
+    if _wants_grad(q, k, v):
+        raise NotImplementedError("top-k attention (cfg.GAT.k) has no backward: train with cfg.GAT.k = None (the shipped configuration), "
+                                  "the dense form")
     assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
     P = len(q_lens)
     assert len(k_lens) == P and len(kks) == P and sum(q_lens) == q.shape[0] and sum(k_lens) == k.shape[0]
@@ -517,10 +654,48 @@ def attention_topk(q, k, v, heads, q_lens, k_lens, kks):
 
 
 def add_layernorm(a, b, gamma, beta, eps=1e-5):
+    """y = LayerNorm(a + b) (b may be None).  Differentiable in a, b, gamma and beta (_AddLayerNormFn over lcr_add_layernorm_grad) when one of
+    them requires grad and grad mode is on; the bytes are the no-grad call's."""
+    if _wants_grad(a, b, gamma, beta):
+        return _AddLayerNormFn.apply(a, b, gamma, beta, float(eps))
     y = torch.empty_like(a)
     _lib.call.lcr_add_layernorm(_lib.ptr(a), _lib.ptr(b), _lib.ptr(gamma), _lib.ptr(beta), a.shape[0], a.shape[1], float(eps),
                                 _lib.ptr(y), _lib.stream_ptr(a.device))
     return y
+
+
+def add_layernorm_grad(a, b, gamma, dy, eps=1e-5):
+    """(d(a + b) [N,D], dgamma [D], dbeta [D]) of lcr_add_layernorm_grad.  No host synchronisation."""
+    _lib.require_cuda(a, b, gamma, dy)
+    assert all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (a, b, gamma, dy)) and dy.shape == a.shape
+    N, D = a.shape
+    dx = torch.empty_like(a)
+    dg, db = torch.empty((D,), dtype=torch.float32, device=a.device), torch.empty((D,), dtype=torch.float32, device=a.device)
+    ws = _lib.ws("lcr_add_layernorm_grad_ws_bytes", N, D, device=a.device)
+    _lib.call.lcr_add_layernorm_grad(_lib.ptr(a), _lib.ptr(b), _lib.ptr(gamma), _lib.ptr(dy), N, D, float(eps), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(a.device))
+    return dx, dg, db
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, gamma, beta, eps):
+        _lib.require_cuda(a, b, gamma, beta)
+        ac, bc, g, be = a.detach().contiguous(), None if b is None else b.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+        y = torch.empty_like(ac)
+        _lib.call.lcr_add_layernorm(_lib.ptr(ac), _lib.ptr(bc), _lib.ptr(g), _lib.ptr(be), ac.shape[0], ac.shape[1], eps, _lib.ptr(y),
+                                    _lib.stream_ptr(ac.device))
+        ctx.save_for_backward(ac, bc, g)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        a, b, g = ctx.saved_tensors
+        dx, dg, db = add_layernorm_grad(a, b, g, dy.contiguous().float(), ctx.eps)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None), (dx if need[1] and b is not None else None), (dg if need[2] else None), (db if need[3] else None), None
 
 
 # ------------------------------------------------------------------------------------------------ pose tail (a-10)

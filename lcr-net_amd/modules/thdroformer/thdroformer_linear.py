@@ -4,7 +4,12 @@
 lcr_rotary_embed, the fused MFMA attention lcr_attention_f32, lcr_add_layernorm).  One pair per call like the reference, or P
 pairs per call (`lens0` / `lens1`): the rows of all first clouds are stacked in one tensor, those of all second clouds in another,
 every Linear / LayerNorm runs once over the stack and the attention kernel takes the P problems in one launch
-(lcr_attention_seg_f32) — per-pair results are those of P separate calls."""
+(lcr_attention_seg_f32) — per-pair results are those of P separate calls.
+
+Differentiable: with grad mode on and an input or a parameter requiring grad, ThDRoFormer.forward takes the module tree, whose ops
+(functional.linear / rotary_embed / attention / add_layernorm) return a graph with HIP backwards (csrc/attention_grad.hip); under no_grad it
+makes the calls it always made.  The forward bytes do not depend on the mode.  Dense attention only: the top-k form (cfg.GAT.k) raises
+NotImplementedError when a gradient is wanted."""
 import torch.nn as nn
 
 from ... import functional as F
@@ -37,8 +42,12 @@ class _MultiHeadAttention(nn.Module):
         k = F.linear(input_k, self.proj_k.weight, self.proj_k.bias)
         v = F.linear(input_v, self.proj_v.weight, self.proj_v.bias)
         if theta_q is not None:                                   # self layers: the SAME theta rotates q and k
-            F.rotary_embed_(q, theta_q, self.num_heads)
-            F.rotary_embed_(k, theta_q, self.num_heads)
+            if F._wants_grad(q, k, theta_q):                      # training: out of place, autograd sums the two dtheta contributions
+                q = F.rotary_embed(q, theta_q, self.num_heads)
+                k = F.rotary_embed(k, theta_q, self.num_heads)
+            else:
+                F.rotary_embed_(q, theta_q, self.num_heads)
+                F.rotary_embed_(k, theta_q, self.num_heads)
         if topk_frac is not None:                                 # dynamic_attention(q, k, v, self.k[layer]): k = int(n * k), n = the cloud's queries
             ql = list(q_lens) if q_lens is not None else [q.shape[0]]
             kl = list(k_lens) if k_lens is not None else [k.shape[0]]
@@ -146,14 +155,21 @@ class ThDRoFormer(nn.Module):
     def forward(self, ref_points, src_points, ref_feats, src_feats, ref_lens=None, src_lens=None, return_pos_emb=False):
         """(N,3), (M,3), (N,C), (M,C)  [a leading batch dim of 1 as in the reference is accepted] -> (N,out), (M,out).
         ref_lens / src_lens (host sequences, one entry per pair): the inputs are the stacks of P pairs' first / second clouds.
-        return_pos_emb: also return the rotary angles theta of both clouds (thdroformer_linear.py:94-95)."""
+        return_pos_emb: also return the rotary angles theta of both clouds (thdroformer_linear.py:94-95).
+        Inference belongs under torch.no_grad(): parameters require grad by default, so a call with grad mode on is taken for training — it
+        runs the module tree instead of the native one-call path, keeps the tensors its ~50 autograd nodes save, and returns outputs that
+        require grad (the same bytes)."""
         squeeze = ref_points.dim() == 3
         if squeeze:
             ref_points, src_points, ref_feats, src_feats = ref_points[0], src_points[0], ref_feats[0], src_feats[0]
         import torch
         n0 = ref_points.shape[0]
         from ... import native_roformer
-        if self.native and native_roformer.eligible(self, ref_feats):
+        # training (grad mode on and an input or a parameter of this module requires grad): the module tree, whose ops carry a graph; its
+        # forward bytes are the native call's
+        wants_grad = torch.is_grad_enabled() and (any(t.requires_grad for t in (ref_points, src_points, ref_feats, src_feats))
+                                                  or any(p.requires_grad for p in self.parameters()))
+        if self.native and not wants_grad and native_roformer.eligible(self, ref_feats):
             lens0 = list(ref_lens) if ref_lens is not None else [n0]
             lens1 = list(src_lens) if src_lens is not None else [src_points.shape[0]]
             f, t = native_roformer.forward(self, torch.cat([ref_points, src_points]), torch.cat([ref_feats, src_feats]), lens0, lens1)
