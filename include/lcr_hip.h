@@ -282,6 +282,16 @@ int lcr_kpconv_mask_ok(int64_t M, int N, int K, int split);
 int lcr_gemm_f32_anorm(const float* A, const float* B, float* C, int64_t M, int N, int K, const float* bias,
                        const double* a_stats, const float* a_gamma, const float* a_beta, int a_groups, float a_eps,
                        float a_slope, const int64_t* seg_len, int S, int groups, double* stats, void* stream);
+/* The same on the split-bf16 form: B given as the tiled planes of lcr_split_bf16x3_tiles, A normalised and THEN split while its tiles are
+ * staged (the normalised operand is bit-equal to lcr_gemm_f32_anorm's).  Needs N >= 64, 32 <= K <= 256, K % 32 == 0, the segment table as
+ * above.  LCR_EARG (with text, no launch) outside that form. */
+int lcr_gemm_f32_bsplit_anorm(const float* A, const uint16_t* Bs_tiles, float* C, int64_t M, int N, int K, const float* bias,
+                              const double* a_stats, const float* a_gamma, const float* a_beta, int a_groups, float a_eps,
+                              float a_slope, const int64_t* seg_len, int S, int groups, double* stats, void* stream);
+/* 1 when a Linear with N outputs and K inputs runs on the split-bf16 form wherever the caller has the weight's planes (the encoder driver's
+ * and the module tree's one dispatch rule, a function of (N, K) alone): N >= 64, K % 32 == 0 and K >= 288, or one of the K <= 256 classes
+ * that measured faster there (environment LCR_GEMM_SPLIT_LIGHT=0: none of those).  0 otherwise. */
+int lcr_gemm_split_ok(int N, int K);
 /* K-deep problems (A [M,K] x B [K,N], K >= 480) whose 64x64 tiles do not divide evenly over the CUs can run as stream-K (opt-in,
  * environment LCR_GEMM_STREAMK; scratch library-owned, one per stream; hook: lcr_gemm_debug_streamk in lcr_hip_debug.h). */
 /* Batched C_z[M,N] = A_z^T · B_z with A_z stored [K_z, M] (per-entry K and element offsets, HOST arrays, count <= 64). */
@@ -352,7 +362,7 @@ int lcr_groupnorm_apply(const float* x, const double* stats, const float* gamma,
 typedef struct LcrUnaryW {
   const float *w, *b;          /* nn.Linear weight [cout,cin], bias [cout] */
   const float *gn_w, *gn_b;    /* GroupNorm affine [cout] */
-  const uint16_t* w_split;     /* optional: lcr_split_bf16x3_tiles of w; used for K-deep shapes (cin >= 288, cin % 32 == 0, cout >= 64) */
+  const uint16_t* w_split;     /* optional: lcr_split_bf16x3_tiles of w; used where lcr_gemm_split_ok(cout, cin) */
 } LcrUnaryW;
 typedef struct LcrBlockW {     /* ResidualBlock (modules.py:148-225) */
   int   cin, cout, strided;

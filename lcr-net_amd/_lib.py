@@ -59,7 +59,7 @@ def build():
 
 
 # int results that are a value, not a code (a record count, a yes / no, the version): never an error, in either view
-_RETURNS_VALUE = {"lcr_version", "lcr_kpconv_mask_ok", "lcr_ktimer_read", "lcr_ktimer_read2"}
+_RETURNS_VALUE = {"lcr_version", "lcr_kpconv_mask_ok", "lcr_gemm_split_ok", "lcr_ktimer_read", "lcr_ktimer_read2"}
 
 
 def __getattr__(name):

@@ -64,8 +64,9 @@ static int unary_raw(const LcrUnaryW& u, const float* x, int64_t n, int cin, int
   float* y = ws.take<float>(static_cast<size_t>(n) * cout);
   double* stats = sp.take();
   if (!y || !stats) return LCR_ESPACE;
-  // K-deep Linears (stages 3-4) on the bf16 matrix cores when the caller provides the weight's three bf16 terms (fp32-faithful, gemm_split.hip)
-  const bool split = u.w_split && cin >= 288 && cin % 32 == 0 && cout >= 64;
+  // on the bf16 matrix cores where the one dispatch rule says so (lcr_gemm_split_ok) and the caller provides the weight's three bf16 terms
+  // (fp32-faithful, gemm_split.hip)
+  const bool split = u.w_split && lcr_gemm_split_ok(cout, cin);
   int rc = split ? TURN(lcr_gemm_f32_bsplit(x, u.w_split, y, n, cout, cin, u.b, nullptr, st.seg, sp.S, sp.groups, stats, s))
                  : TURN(lcr_gemm_f32(x, u.w, y, n, cout, cin, 0, 1, u.b, nullptr, st.seg, sp.S, sp.groups, stats, s));
   *y_out = y;
@@ -139,8 +140,11 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
     y = ws.take<float>(static_cast<size_t>(M) * b.cout);
     sty = sp.take();
     if (!y || !sty) return LCR_ESPACE;
-    if ((rc = TURN(lcr_gemm_f32_anorm(kpo, b.unary2.w, y, M, b.cout, mid, b.unary2.b, stc, b.normconv_w, b.normconv_b, g, ENC_GN_EPS, ENC_SLOPE,
-                                      q.seg, sp.S, g, sty, s))))
+    const bool split2 = b.unary2.w_split && lcr_gemm_split_ok(b.cout, mid);     // the same rule as unary_raw
+    if ((rc = split2 ? TURN(lcr_gemm_f32_bsplit_anorm(kpo, b.unary2.w_split, y, M, b.cout, mid, b.unary2.b, stc, b.normconv_w, b.normconv_b, g,
+                                                      ENC_GN_EPS, ENC_SLOPE, q.seg, sp.S, g, sty, s))
+                     : TURN(lcr_gemm_f32_anorm(kpo, b.unary2.w, y, M, b.cout, mid, b.unary2.b, stc, b.normconv_w, b.normconv_b, g, ENC_GN_EPS,
+                                               ENC_SLOPE, q.seg, sp.S, g, sty, s))))
       return rc;
   } else {
     float* x2 = ws.take<float>(static_cast<size_t>(M) * mid);

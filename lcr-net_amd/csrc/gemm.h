@@ -46,6 +46,59 @@ constexpr int AN_KMAX = 256;   // K of the fused form (the light kernel: K <= 25
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
+// The table of the normalise-on-load forms (k_gemm_f32<.., ANORM>, k_gemm_f32_bsplit_p<.., ANORM>), built once per 256-thread workgroup:
+// s_an[slot][scale | shift][k] (AN_KMAX floats each) for the one or two segments a 64-row block touches (slot 0 = the segment of the block's
+// first row, slot 1 = the next one; the host guarantees that no segment is shorter than the block).  Two calls, so that the loads of the
+// first are in flight under the caller's segment scan:
+//   anorm_load_affine: this thread's (gamma, beta) of table entries e = tid and tid + 256 (2 K <= 512);
+//   anorm_build_table: (mean, rstd) per (slot, group) finalised in fp64 from the producer's statistics replicas exactly as
+//   lcr_groupnorm_apply does, then scale = rstd * gamma, shift = beta - mean * scale.  Ends with a barrier: the table is readable on return.
+__device__ __forceinline__ void anorm_load_affine(const ANorm& an, int K, float (&an_g)[2], float (&an_b)[2]) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int e = threadIdx.x + u * GM_T;
+    an_g[u] = an_b[u] = 0.f;
+    if (e < 2 * K) {
+      const int k = e >= K ? e - K : e;
+      an_g[u] = an.gamma[k];
+      an_b[u] = an.beta[k];
+    }
+  }
+}
+
+__device__ __forceinline__ void anorm_build_table(const ANorm& an, const GemmEpilogue& ep, int K, int blk_first, const float (&an_g)[2],
+                                                  const float (&an_b)[2], float* __restrict__ s_an) {
+  const int gs = K / an.groups;
+  __shared__ float2 s_mr[2 * 64];                        // (mean, rstd) of [slot][group]
+  for (int e = threadIdx.x; e < 2 * an.groups; e += GM_T) {
+    const int slot = e >= an.groups ? 1 : 0, g = e - slot * an.groups;
+    const int sg = min(blk_first + slot, ep.S - 1);
+    const double cnt = static_cast<double>(ep.seg_len[sg]) * gs;
+    double sx = 0.0, sxx = 0.0;
+    for (int rep = 0; rep < GN_REPLICAS; ++rep) {
+      const int64_t o = ((static_cast<int64_t>(rep) * ep.S + sg) * an.groups + g) * 2;
+      sx += an.stats[o];
+      sxx += an.stats[o + 1];
+    }
+    const double mean = sx / cnt;
+    const double var = fmax(sxx / cnt - mean * mean, 0.0);
+    s_mr[e] = make_float2(static_cast<float>(mean), static_cast<float>(1.0 / sqrt(var + static_cast<double>(an.eps))));
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int e = threadIdx.x + u * GM_T;
+    if (e < 2 * K) {
+      const int slot = e >= K ? 1 : 0, k = e - slot * K;
+      const float2 mr = s_mr[slot * an.groups + k / gs];
+      const float sc = mr.y * an_g[u];
+      s_an[slot * 2 * AN_KMAX + k] = sc;
+      s_an[slot * 2 * AN_KMAX + AN_KMAX + k] = fmaf(-mr.x, sc, an_b[u]);
+    }
+  }
+  __syncthreads();
+}
+
 // Epilogue shared by the tile-per-workgroup kernel and the stream-K kernel: C = acc [/ rowdiv] [+ bias], GroupNorm statistics.
 template <int BM, int BN, int WM, int WN, int NT>
 __device__ __forceinline__ void gemm_epilogue(floatx16 (&acc)[NT], float* __restrict__ C, int64_t M, int N, int64_t m0, int n0, int64_t m_tile,

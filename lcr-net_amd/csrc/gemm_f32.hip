@@ -237,17 +237,7 @@ __global__ __launch_bounds__(GM_T, SHORT ? 6 : 2) void k_gemm_f32(const float* _
     bias_v[j] = (ep.bias && col < N) ? ep.bias[col] : 0.f;
   }
   float an_g[2] = {0.f, 0.f}, an_b[2] = {0.f, 0.f};           // normalise-on-load: this thread's (gamma, beta) of table entries
-  if constexpr (ANORM) {                                       // e = tid and tid + 256 (2 K <= 512), requested before the segment scan
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int e = threadIdx.x + u * GM_T;
-      if (e < 2 * K) {
-        const int k = e >= K ? e - K : e;
-        an_g[u] = an.gamma[k];
-        an_b[u] = an.beta[k];
-      }
-    }
-  }
+  if constexpr (ANORM) anorm_load_affine(an, K, an_g, an_b);   // e = tid and tid + 256 (2 K <= 512), requested before the segment scan
   int blk_first = 0;
   int64_t blk_seg_start = 0, blk_seg_end = 0;
   if (want_stats || ANORM) {
@@ -261,38 +251,9 @@ __global__ __launch_bounds__(GM_T, SHORT ? 6 : 2) void k_gemm_f32(const float* _
   __shared__ __attribute__((aligned(16))) float s_an[ANORM ? 4 * AN_KMAX : 4];   // [slot][scale | shift][k]
   int an_split = BM;
   if constexpr (ANORM) {
-    // (scale, shift) per channel for the one or two segments this row block touches (the host guarantees that no segment is
-    // shorter than the block), finalised in fp64 from the producer's statistics replicas exactly as lcr_groupnorm_apply does
+    // (scale, shift) per channel for the one or two segments this row block touches (anorm_build_table, gemm.h)
     an_split = static_cast<int>(min(static_cast<int64_t>(BM), blk_seg_end - m0));
-    const int gs = K / an.groups;
-    __shared__ float2 s_mr[2 * 64];                        // (mean, rstd) of [slot][group]
-    for (int e = threadIdx.x; e < 2 * an.groups; e += GM_T) {
-      const int slot = e >= an.groups ? 1 : 0, g = e - slot * an.groups;
-      const int sg = min(blk_first + slot, ep.S - 1);
-      const double cnt = static_cast<double>(ep.seg_len[sg]) * gs;
-      double sx = 0.0, sxx = 0.0;
-      for (int rep = 0; rep < GN_REPLICAS; ++rep) {
-        const int64_t o = ((static_cast<int64_t>(rep) * ep.S + sg) * an.groups + g) * 2;
-        sx += an.stats[o];
-        sxx += an.stats[o + 1];
-      }
-      const double mean = sx / cnt;
-      const double var = fmax(sxx / cnt - mean * mean, 0.0);
-      s_mr[e] = make_float2(static_cast<float>(mean), static_cast<float>(1.0 / sqrt(var + static_cast<double>(an.eps))));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int e = threadIdx.x + u * GM_T;
-      if (e < 2 * K) {
-        const int slot = e >= K ? 1 : 0, k = e - slot * K;
-        const float2 mr = s_mr[slot * an.groups + k / gs];
-        const float sc = mr.y * an_g[u];
-        s_an[slot * 2 * AN_KMAX + k] = sc;
-        s_an[slot * 2 * AN_KMAX + AN_KMAX + k] = fmaf(-mr.x, sc, an_b[u]);
-      }
-    }
-    __syncthreads();
+    anorm_build_table(an, ep, K, blk_first, an_g, an_b, s_an);
   }
   auto sstore_a0 = [&]() {                                 // the light form's (only) A store
     if constexpr (ANORM) la_t[0].store_norm(As[0], s_an, an_split, an.slope);
@@ -753,6 +714,28 @@ static GemmForm gemm_form(int64_t M, int N, int K, int transA, int transB, bool 
   const bool sk_legal = !transA && !transB && K >= 64 && static_cast<int64_t>(div_up(M, 64)) * div_up(N, 64) <= SK_MAX_TILES;
   if (sk_mode && sk_legal && (sk_mode == 2 || sk_worth(M, N, K))) return GF_STREAMK;
   return GF_TILE;
+}
+
+// Which Linears C[M,N] = A[M,K] · W[N,K]^T run on the split-bf16 form (gemm_split.hip) instead of the form gemm_form picks: the ONE rule, a
+// function of (N, K) alone, that the encoder driver (encoder.hip: unary1, unary2 with or without normalise-on-load, shortcut), the module tree
+// (functional.gemm_split_ok mirrors it; tests/test_gemm_split_light_gpu.py holds the two together) and bench.py's launch classification
+// share.  K >= 288: the K-deep shapes, since round 5.  K <= 256 (the light fp32 form's range): the (N, K) classes where the split kernel
+// measured >= 1.10x the light fp32 kernel in one job (tools/gemm_split_bench.py --light, profiles/r12_light_split.md); the others stay.
+// LCR_GEMM_SPLIT_LIGHT=0: K >= 288 only (A/B).  N < 64 never: those launches stream A at the HBM rate on the fp32 form already.
+// Measured classes (fp32 light us / split us, in the form the encoder launches): (512, 128) 1.21-1.25, (1024, 256) 1.40, (256, 128) 1.29,
+// (512, 256) 1.39, (64, 128) 1.19, (64, 256) 1.30, (128, 256) 1.32 move; (128, 32) 1.05-1.15 and (256, 64) 1.04-1.14 miss the margin on their
+// smaller-M members and stay.  A class that was not measured stays as well.
+static bool gemm_split_light(int N, int K) {
+  switch (K) {
+    case 128: return N == 64 || N == 256 || N == 512;
+    case 256: return N == 64 || N == 128 || N == 512 || N == 1024;
+    default: return false;
+  }
+}
+extern "C" int lcr_gemm_split_ok(int N, int K) {
+  static const bool light = env_int("LCR_GEMM_SPLIT_LIGHT", 1) != 0;
+  if (N < 64 || K < GM_BK || K % GM_BK != 0) return 0;
+  return K >= 288 || (light && K <= AN_KMAX && gemm_split_light(N, K));
 }
 
 // C = leaky(GroupNorm(A)) · B^T (+ bias, + statistics of C): the light GEMM with normalise-on-load (ANorm above).  The caller

@@ -108,10 +108,20 @@ __global__ __launch_bounds__(256) void k_split_bf16x3_tiles(const float* __restr
 // fragment reads, 32 no B fragment loads in the loop.  0 = the product; any other value computes garbage.
 // MASK: row-masked A as in k_gemm_f32_deep.  The A pieces are then buffer loads whose offset is pushed out of the buffer's range for a
 // block that was never stored: the range check returns zeros without a memory access (and without a branch in the K-step).
-template <int ABL, bool MASK = false>
-__global__ __launch_bounds__(256, 3) void k_gemm_f32_bsplit_p(const float* __restrict__ A, const uint16_t* __restrict__ Bs, float* __restrict__ C,
+// ANORM: normalise-on-load as in k_gemm_f32 (ANorm, gemm.h), for the K <= AN_KMAX Linears that follow a KPConv (unary2): a piece of A becomes
+// y = leaky(fmaf(x, scale[k], shift[k])) with the (scale, shift) of its row's segment slot BEFORE it is split, on its way from registers to
+// LDS — the same operations in the same order as LoaderT::store_norm, so both GEMM forms see bit-equal normalised operands, and the table
+// is the one anorm_build_table (gemm.h) makes for both.  Per thread and K-step: 4 more LDS reads (16 B) and 16 more VALU under the MFMAs;
+// +5 KB of LDS (table + (mean, rstd)): 31 KB.  Left to itself the form takes 132 VGPRs (three workgroups per CU); bounded to four per SIMD it
+// takes 128 and spills five registers (20 bytes) that live only outside the K loop — stored before it, reloaded after it.  Measured
+// (tools/gemm_split_bench.py --light, profiles/r12_light_split.md): 1.21-1.40x lcr_gemm_f32_anorm at K = 128 / 256.  The prologue (tiles 0
+// and 1 requested, tile 0 parked, tile 2 requested) clamps every tile index to nk - 1, so nk = 1 and 2 (K = 32, 64) re-request the last tile
+// (cache hits, parked into the idle LDS stage, never read): correct for every nk >= 1, and the table index is clamped the same way.
+template <int ABL, bool MASK = false, bool ANORM = false>
+__global__ __launch_bounds__(256, ANORM ? 4 : 3) void k_gemm_f32_bsplit_p(const float* __restrict__ A, const uint16_t* __restrict__ Bs, float* __restrict__ C,
                                                            int64_t M, int N, int K, GemmEpilogue ep, const uint16_t* __restrict__ amask,
-                                                           int kshift) {
+                                                           int kshift, ANorm an) {
+  static_assert(!(ANORM && MASK), "normalise-on-load reads a dense A");
   // LDS plane tile of A: 64 rows x 64 B (32 bf16), no padding; the four 16-B chunks of row r are XOR-ed with (r >> 2) & 3.  A ds_read_b128 is
   // serviced in groups of 16 lanes over 64 banks (16 different rows, one logical chunk: rows r, r+4, r+8, r+12 share a 64-B bank quadrant
   // and get four different chunks).
@@ -179,12 +189,23 @@ __global__ __launch_bounds__(256, 3) void k_gemm_f32_bsplit_p(const float* __res
 #pragma unroll
     for (int p = 0; p < 3; ++p) rb[st][p] = *reinterpret_cast<const u32x4_t*>(bp + static_cast<int64_t>(tt) * 12288 + p * 1024);
   };
-  auto park = [&](auto st_c, int lds_stage) {                  // A register stage -> split -> LDS stage
+  __shared__ __attribute__((aligned(16))) float s_an[ANORM ? 4 * AN_KMAX : 4];   // [slot][scale | shift][k]
+  int toff[2] = {0, 0};                                        // ANORM: this thread's piece j in the table of its row's slot, at k = 0
+  auto park = [&](auto st_c, int lds_stage, int t) {           // A register stage (tile t) -> [normalise] -> split -> LDS stage
     constexpr int st = decltype(st_c)::value;
     char* da = sA + lds_stage * STGA;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       uint32_t h1, h2, h3, g1, g2, g3;
+      if constexpr (ANORM) {
+        const float* tb = s_an + toff[j] + (t < nk ? t : nk - 1) * GM_BK;        // the tile fetch_a loaded
+        const float4 sc = *reinterpret_cast<const float4*>(tb), sh = *reinterpret_cast<const float4*>(tb + AN_KMAX);
+        f32x4_t v = ra[st][j];
+        v.x = fmaf(v.x, sc.x, sh.x), v.y = fmaf(v.y, sc.y, sh.y), v.z = fmaf(v.z, sc.z, sh.z), v.w = fmaf(v.w, sc.w, sh.w);
+        v.x = v.x > 0.f ? v.x : v.x * an.slope, v.y = v.y > 0.f ? v.y : v.y * an.slope;
+        v.z = v.z > 0.f ? v.z : v.z * an.slope, v.w = v.w > 0.f ? v.w : v.w * an.slope;
+        ra[st][j] = v;
+      }
       if constexpr (ABL & 2) {
         h1 = __float_as_uint(ra[st][j].x), h2 = __float_as_uint(ra[st][j].y), h3 = h1, g1 = __float_as_uint(ra[st][j].z), g2 = __float_as_uint(ra[st][j].w), g3 = g1;
       } else {
@@ -212,9 +233,11 @@ __global__ __launch_bounds__(256, 3) void k_gemm_f32_bsplit_p(const float* __res
   fetch_a(I0{}, 0);
   fetch_a(I1{}, 1);
   fetch_b(I0{}, 0);
+  float an_g[2], an_b[2];
+  if constexpr (ANORM) anorm_load_affine(an, K, an_g, an_b);
   int blk_first = 0;
   int64_t blk_seg_start = 0, blk_seg_end = 0;
-  if (ep.stats != nullptr) {
+  if (ep.stats != nullptr || ANORM) {
     blk_seg_end = ep.seg_len[0];
     while (blk_first + 1 < ep.S && m0 >= blk_seg_end) {
       ++blk_first;
@@ -222,7 +245,13 @@ __global__ __launch_bounds__(256, 3) void k_gemm_f32_bsplit_p(const float* __res
       blk_seg_end += ep.seg_len[blk_first];
     }
   }
-  park(I0{}, 0);
+  if constexpr (ANORM) {
+    const int an_split = static_cast<int>(min(static_cast<int64_t>(BM), blk_seg_end - m0));   // rows >= an_split: the next segment (slot 1)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) toff[j] = (srow + j * (T / 8) >= an_split ? 2 * AN_KMAX : 0) + spc * 4;
+    anorm_build_table(an, ep, K, blk_first, an_g, an_b, s_an);
+  }
+  park(I0{}, 0, 0);
   fetch_a(I0{}, 2);
   fetch_b(I1{}, 1);
   __syncthreads();
@@ -264,7 +293,7 @@ __global__ __launch_bounds__(256, 3) void k_gemm_f32_bsplit_p(const float* __res
       mm(a[b][0], b0, acc2[b]);
     };
     six(0), six(1);
-    park(NX{}, P ^ 1);                                         // tile t+1 -> the other LDS stage (its last readers passed the barrier of step t-1)
+    park(NX{}, P ^ 1, t + 1);                                       // tile t+1 -> the other LDS stage (its last readers passed the barrier of step t-1)
     six(2), six(3);
     if constexpr (!(ABL & 8)) fetch_a(NX{}, t + 3);
     if constexpr (!(ABL & (8 | 32))) fetch_b(lds_c, t + 2);
@@ -333,19 +362,19 @@ static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, 
   static const int abl = env_int("LCR_SPLIT_ABL", 0);      // timing ablations only (garbage results)
   const dim3 grid(gemm_grid(M, N, 64, 64)), block(256);
   if (amask) {
-    LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, true>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift);
+    LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, true>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{});
     return check_launch("lcr_gemm_f32_bsplit_masked");
   }
   switch (abl) {
-    case 1: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<1>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 2: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 4: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<4>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 8: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<8>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 16: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<16>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 23: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<23>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 30: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<30>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    case 32: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<32>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
-    default: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift); break;
+    case 1: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<1>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 2: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<2>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 4: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<4>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 8: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<8>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 16: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<16>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 23: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<23>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 30: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<30>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    case 32: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<32>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
+    default: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
   }
   return check_launch("lcr_gemm_f32_bsplit");
 }
@@ -353,6 +382,27 @@ static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, 
 extern "C" int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
                                    const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
   return bsplit_impl(A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, nullptr, 0, stream);
+}
+
+// C = leaky(GroupNorm(A)) · B^T (+ bias, + statistics of C) on the split form: lcr_gemm_f32_anorm's arguments with the tiled planes in place of
+// the weight, and its domain (K <= 256, every segment >= 64 rows by the caller's guarantee) narrowed to the split kernel's K % 32 == 0, N >= 64.
+extern "C" int lcr_gemm_f32_bsplit_anorm(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias,
+                                         const double* a_stats, const float* a_gamma, const float* a_beta, int a_groups, float a_eps,
+                                         float a_slope, const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
+  if (!A || !Bs || !C || M < 0 || N < 64 || K < GM_BK || K > AN_KMAX || K % GM_BK != 0 || !a_stats || !a_gamma || !a_beta || a_groups < 1 ||
+      K % a_groups != 0 || a_groups > 64 || !seg_len || S < 1 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(Bs) % 16 != 0) {
+    set_error("lcr_gemm_f32_bsplit_anorm: needs N >= 64, K <= 256, K %% 32 == 0, a_groups (<= 64) dividing K, a segment table and 16-byte aligned operands");
+    return LCR_EARG;
+  }
+  if (!gemm_stats_ok("lcr_gemm_f32_bsplit_anorm", stats, seg_len, S, groups, N)) return LCR_EARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KernelTimerScope timed(KT_GEMM, st, M, N, K);
+  if (M == 0) return LCR_OK;
+  GemmEpilogue ep{bias, nullptr, seg_len, S, groups, stats};
+  ANorm an{a_stats, a_gamma, a_beta, a_groups, a_eps, a_slope};
+  LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, false, true>), dim3(gemm_grid(M, N, 64, 64)), dim3(256), 0, st, A, Bs, C, M, N, K, ep,
+                   static_cast<const uint16_t*>(nullptr), 0, an);
+  return check_launch("lcr_gemm_f32_bsplit_anorm");
 }
 
 extern "C" int lcr_gemm_f32_bsplit_masked(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias,

@@ -191,7 +191,8 @@ def _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask
 # ---- split-bf16 form of the K-deep GEMMs (csrc/gemm_split.hip): fp32 operands as three bf16 terms, six products on the bf16 matrix cores.
 # DEFAULT since round 5 for the K-deep shapes (K >= 288, K % 32 == 0, N >= 64): every fp32 operand enters as its three bf16 terms (exact), six
 # of the nine cross products are accumulated in fp32 — measured error against fp64 at or below the fp32-MFMA kernel's own, non-finite values
-# propagate to the same outputs (tests/test_gemm_split_gpu.py).  LCR_GEMM_SPLIT=0 selects the true-fp32 MFMA kernel everywhere;
+# propagate to the same outputs (tests/test_gemm_split_gpu.py).  Since R12.1 also for the K = 128 / 256 Linears where it measured >= 1.10x the
+# light fp32 kernel (gemm_split_ok below; LCR_GEMM_SPLIT_LIGHT=0: K >= 288 only).  LCR_GEMM_SPLIT=0 selects the true-fp32 MFMA kernel everywhere;
 # `set_gemm_split` is the run-time switch (tests, bench A/B).  Domain of the split form: |x| <= 3.3895e38 (the largest bf16), beyond which
 # the first term rounds to infinity.
 _GEMM_SPLIT = [os.environ.get("LCR_GEMM_SPLIT", "1") not in ("", "0")]
@@ -205,8 +206,22 @@ def set_gemm_split(on):
     _GEMM_SPLIT[0] = bool(on)
 
 
+_GEMM_SPLIT_LIGHT = os.environ.get("LCR_GEMM_SPLIT_LIGHT", "1") not in ("", "0")
+
+
+_GEMM_SPLIT_LIGHT_CLASSES = {(64, 128), (256, 128), (512, 128), (64, 256), (128, 256), (512, 256), (1024, 256)}     # (N, K), profiles/r12_light_split.md
+
+
+def _gemm_split_light(N, K):
+    return (N, K) in _GEMM_SPLIT_LIGHT_CLASSES
+
+
 def gemm_split_ok(N, K):
-    return K >= 288 and K % 32 == 0 and N >= 64
+    """The one dispatch rule for the Linears, a function of (N, K) alone: the mirror of lcr_gemm_split_ok (csrc/gemm_f32.hip, where the
+    K <= 256 classes and their measurement are described; tests/test_gemm_split_light_gpu.py compares the two on every encoder shape)."""
+    if N < 64 or K < 32 or K % 32 != 0:
+        return False
+    return K >= 288 or (_GEMM_SPLIT_LIGHT and K <= ANORM_MAX_K and _gemm_split_light(N, K))
 
 
 # Derived weight tensors (transposed KPConv weights, bf16 planes, the native encoder's table) are built lazily by whichever host thread gets
@@ -319,6 +334,21 @@ def gemm_anorm(a, a_stats, a_gamma, a_beta, a_groups, weight, bias=None, seg_len
     c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device, always_seg=True)
     _lib.call.lcr_gemm_f32_anorm(
         _lib.ptr(a), _lib.ptr(weight), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(a_stats), _lib.ptr(a_gamma), _lib.ptr(a_beta),
+        int(a_groups), GN_EPS, float(slope), _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device))
+    return c, stats
+
+
+def gemm_bsplit_anorm(a, a_stats, a_gamma, a_beta, a_groups, planes, bias=None, seg_len=None, groups=0, slope=0.1):
+    """gemm_anorm on the split-bf16 form: `planes` = split_bf16x3(weight) in place of the weight (lcr_gemm_f32_bsplit_anorm; N >= 64,
+    K <= 256, K % 32 == 0).  The normalised operand is bit-equal to gemm_anorm's; the product has the split form's rounding points."""
+    _lib.require_cuda(a, planes)
+    assert a.dtype == torch.float32 and a.is_contiguous() and planes.dtype == torch.int16 and planes.is_contiguous() and planes.dim() == 5
+    M, K = a.shape
+    N = planes.lcr_n
+    assert planes.shape[1] * 32 == K and planes.shape[0] == (N + 63) // 64, "inner dimensions differ"
+    c, seg_len, S, stats = _gemm_out(M, N, seg_len, groups, a.device, always_seg=True)
+    _lib.call.lcr_gemm_f32_bsplit_anorm(
+        _lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, _lib.ptr(bias), _lib.ptr(a_stats), _lib.ptr(a_gamma), _lib.ptr(a_beta),
         int(a_groups), GN_EPS, float(slope), _lib.ptr(seg_len), S, int(groups), _lib.ptr(stats), _lib.stream_ptr(a.device))
     return c, stats
 
@@ -793,6 +823,7 @@ def log_optimal_transport(raw_scores, row_masks, col_masks, alpha, scale=1.0, it
     are the no-grad call's."""
     if _wants_grad(raw_scores, alpha):
         return _TransportFn.apply(raw_scores, alpha, row_masks, col_masks, float(scale), int(iters), float(inf))
+    _lib.require_cuda(raw_scores, row_masks, col_masks, alpha)      # as _TransportFn.forward: a host pointer must never reach a launch
     B, M, N = raw_scores.shape
     dev = raw_scores.device
     rm, cm = row_masks.to(torch.uint8).contiguous(), col_masks.to(torch.uint8).contiguous()

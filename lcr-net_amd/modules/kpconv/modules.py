@@ -151,8 +151,12 @@ class ResidualBlock(nn.Module):
                                            order=q_ctx.order)
         if q_ctx.norm_on_load(x.shape[1], self.out_channels, x.shape[0]):
             # norm_conv + LeakyReLU applied while unary2's GEMM stages its A tiles: no stand-alone GroupNorm pass over x
-            y, ystats = F.gemm_anorm(x, stats, self.norm_conv.norm.weight, self.norm_conv.norm.bias, g, self.unary2.mlp.weight,
-                                     bias=self.unary2.mlp.bias, seg_len=q_ctx.seg_len, groups=g)
+            if F.gemm_split_enabled() and F.gemm_split_ok(self.out_channels, x.shape[1]):      # the same rule as UnaryBlock.raw
+                y, ystats = F.gemm_bsplit_anorm(x, stats, self.norm_conv.norm.weight, self.norm_conv.norm.bias, g, self.unary2.weight_split(),
+                                                bias=self.unary2.mlp.bias, seg_len=q_ctx.seg_len, groups=g)
+            else:
+                y, ystats = F.gemm_anorm(x, stats, self.norm_conv.norm.weight, self.norm_conv.norm.bias, g, self.unary2.mlp.weight,
+                                         bias=self.unary2.mlp.bias, seg_len=q_ctx.seg_len, groups=g)
         else:
             x = F.groupnorm_apply(x, stats, self.norm_conv.norm.weight, self.norm_conv.norm.bias, g, q_ctx.seg_len, act=True)
             y, ystats = self.unary2.raw(x, q_ctx)                                      # normalised below, fused with the shortcut

@@ -1,7 +1,8 @@
 """fp32-MFMA K-deep GEMM (lcr_gemm_f32, pre-transposed B) vs the split-bf16 form (lcr_gemm_f32_bsplit: fp32 operands as three bf16 terms, six
 cross products on the bf16 matrix cores) on the encoder's deep shapes: kernel begin-to-end times (interleaved rounds) and the error of BOTH
 against an fp64 product of the same fp32 inputs — max |c - ref| / max |ref| and the rms ratio.  One JSON line per shape + a summary
-(--table: one short text row per shape instead)."""
+(--table: one short text row per shape instead; --light: the encoder's K <= 256 Linears instead, light fp32 kernel against the split
+kernel with and without normalise-on-load, as a markdown table)."""
 import ctypes
 import json
 import os
@@ -25,7 +26,70 @@ if "--splitk-proxy" in sys.argv:       # the same work as a split-K of the stage
               ("4_x unary1", 6479, 256, 1024, 0), ("4_x K/2", 12958, 256, 512, 0), ("3_1", 19061, 64, 960, 1), ("3_1 K/2", 38122, 64, 480, 1)]
 
 
+# --light: the encoder's K <= 256 Linears that are bound by the fp32 matrix instruction — the ten unary2 (plain and with normalise-on-load),
+# the two shortcuts and the four unary1 — light fp32 kernel against the split kernel, back to back in one job.  A markdown table: one row per
+# (shape, form) with the median of the rounds and their range; `class` is the (N, K) the dispatch rule sees.
+LIGHT = [("1_2 unary2", 127812, 128, 32, 1), ("2_1 unary2", 51547, 128, 32, 1), ("2_2 unary2", 51547, 256, 64, 1), ("2_3 unary2", 51547, 256, 64, 1),
+         ("3_1 unary2", 19061, 256, 64, 1), ("3_2 unary2", 19061, 512, 128, 1), ("3_3 unary2", 19061, 512, 128, 1), ("4_1 unary2", 6479, 512, 128, 1),
+         ("4_2 unary2", 6479, 1024, 256, 1), ("4_3 unary2", 6479, 1024, 256, 1), ("2_2 shortcut", 51547, 256, 128, 0),
+         ("3_2 shortcut", 19061, 512, 256, 0), ("2_2 unary1", 51547, 64, 128, 0), ("2_3 unary1", 51547, 64, 256, 0), ("3_1 unary1", 51547, 64, 256, 0),
+         ("3_2 unary1", 19061, 128, 256, 0)]
+
+
+def light():
+    dev = torch.device("cuda")
+    rounds, reps = 7, 4
+    items = []
+    for i, (tag, M, N, K, unary2) in enumerate(LIGHT):
+        g = torch.Generator(device=dev).manual_seed(100 + i)
+        a = torch.randn(M, K, device=dev, generator=g) * 2.0 + 0.7
+        w = torch.randn(N, K, device=dev, generator=g) / K ** 0.5
+        bias = torch.randn(N, device=dev, generator=g)
+        gamma, beta = torch.rand(K, device=dev, generator=g) + 0.5, torch.randn(K, device=dev, generator=g)
+        seg = torch.tensor([M // 8 - 3] * 7 + [M - 7 * (M // 8 - 3)], dtype=torch.int64, device=dev)     # eight scans per step
+        planes = F.split_bf16x3(w)
+        a_stats = F.groupnorm_stats(a, 32, seg)
+        kw = dict(bias=bias, seg_len=seg, groups=32)
+        forms = [("plain", lambda a=a, w=w, kw=kw: F.gemm(a, w, trans_b=True, **kw), lambda a=a, planes=planes, kw=kw: F.gemm_bsplit(a, planes, **kw))]
+        if unary2:
+            forms.append(("anorm", lambda a=a, s=a_stats, ga=gamma, be=beta, w=w, kw=kw: F.gemm_anorm(a, s, ga, be, 32, w, **kw),
+                          lambda a=a, s=a_stats, ga=gamma, be=beta, planes=planes, kw=kw: F.gemm_bsplit_anorm(a, s, ga, be, 32, planes, **kw)))
+        for form, run0, run1 in forms:
+            c0, c1 = run0()[0], run1()[0]
+            torch.cuda.synchronize()
+            diff = ((c0 - c1).abs().max() / c0.abs().max()).item()
+            items.append((tag, M, N, K, form, run0, run1, diff))
+    times = {(j, m): [] for j in range(len(items)) for m in (0, 1)}
+    for rnd in range(rounds):
+        for mode in (0, 1):
+            timer = F.KernelTimer({"gemm"})
+            F.set_timer(timer)
+            with F.stats_arena(dev, entries=1 << 22):                 # no fill launch between the timed launches
+                for it in items:
+                    for _ in range(reps):
+                        it[5 + mode]()
+            torch.cuda.synchronize()
+            F.set_timer(None)
+            own = [kk for _, kk, _ in timer.records()["gemm"]]
+            assert len(own) == reps * len(items)
+            for j in range(len(items)):
+                times[(j, mode)].append(min(own[reps * j + 1:reps * (j + 1)]) * 1e6)
+    print("| layer | M | class (N, K) | form | fp32 light us (min-max) | split us (min-max) | fp32 / split | max diff |")
+    print("|---|---|---|---|---|---|---|---|")
+    tot = [0.0, 0.0]
+    for j, (tag, M, N, K, form, _, _, diff) in enumerate(items):
+        t0, t1 = sorted(times[(j, 0)]), sorted(times[(j, 1)])
+        m0, m1 = t0[rounds // 2], t1[rounds // 2]
+        tot[0] += m0
+        tot[1] += m1
+        print("| %s | %d | (%d, %d) | %s | %.1f (%.1f-%.1f) | %.1f (%.1f-%.1f) | %.2f | %.1e |" % (tag, M, N, K, form, m0, t0[0], t0[-1], m1, t1[0], t1[-1],
+                                                                                               m0 / m1, diff))
+    print("| sum | | | | %.1f | %.1f | %.2f | |" % (tot[0], tot[1], tot[0] / tot[1]))
+
+
 def main():
+    if "--light" in sys.argv:
+        return light()
     dev = torch.device("cuda")
     L = _lib.lib()
     sp = lambda t: _lib.stream_ptr(t.device)
