@@ -346,6 +346,47 @@ int lcr_groupnorm_apply(const float* x, const double* stats, const float* gamma,
                         const double* res_stats, const float* res_gamma, const float* res_beta, float* y, int64_t N, int C,
                         int groups, const int64_t* seg_len, int S, float eps, float slope, int act, uint8_t* pos, void* stream);
 
+/* Reverse passes of the encoder block above (csrc/kpconv_grad.hip, csrc/groupnorm_grad.hip).  None of them changes what the forward entries
+ * compute.  They are gathers over an INVERTED neighbour list and two-stage sums with a fixed order: no floating-point atomics, results
+ * repeat to the bit, and a cloud's rows get the same bytes alone and inside a stack.  Index lists: int32 or int64 (idx_is_64), padding =
+ * any index outside [0, Ns); H <= 128 and M * H < 2^30.  A call outside the domain returns LCR_EARG with text and launches nothing.
+ *
+ * lcr_neighbor_transpose: idx [M,H] -> row_start i32[Ns + 1], edges u32[row_start[Ns]] (capacity M * H).  The edges of support row n,
+ * edges[row_start[n] : row_start[n + 1]], are the flat positions m * H + h with idx[m,h] == n in ascending order (the stable radix sort of
+ * csrc/radix_sort.h on (support index, flat position)); padding entries appear nowhere.  ws: lcr_neighbor_transpose_ws_bytes(M, H), host-only. */
+int lcr_neighbor_transpose_ws_bytes(int64_t M, int H, size_t* bytes);
+int lcr_neighbor_transpose(const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int32_t* row_start, uint32_t* edges,
+                           void* ws, size_t ws_bytes, void* stream);
+/* Reverse of lcr_kpconv_aggregate to s_feats: d_s_feats[n][c] = sum over the edges (m,h) of n, sum_k w(m,h,k) dA[m][k*C + c], with the
+ * forward's influence w = max(0, 1 - |s_n - q_m - kp_k| / sigma) evaluated operation for operation as the forward does.  dA [M,15*C];
+ * C in {32, 64, 128, 256}.  Only the kernel-point blocks of dA with a non-zero influence are read.  A support nobody lists gets zeros. */
+int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, const float* s_pts, const int32_t* row_start, const uint32_t* edges,
+                              int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma, float* d_s_feats,
+                              void* stream);
+/* Reverse of lcr_kpconv_cin1: dW [15,Cout] and dbias [Cout] (may be NULL) from d_out [M,Cout], per-workgroup partials added in ascending
+ * order.  nn: the forward's neighbour count per query, or NULL (recounted from s_feats > 0; at least 1 either way).  d_s_feats [Ns] is
+ * optional (NULL: skipped, row_start / edges may then be NULL too).  ws: lcr_kpconv_cin1_grad_ws_bytes(M, Cout, d_s_feats != NULL). */
+int lcr_kpconv_cin1_grad_ws_bytes(int64_t M, int Cout, int want_feats, size_t* bytes);
+int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, const float* q_pts, const float* s_pts, const void* idx, int idx_is_64,
+                         const float* nn, const int32_t* row_start, const uint32_t* edges, int64_t M, int64_t Ns, int H,
+                         const float* kernel_points_host, float sigma, const float* W, int Cout, float* dW, float* dbias,
+                         float* d_s_feats, void* ws, size_t ws_bytes, void* stream);
+/* Reverse of lcr_maxpool: d_x[n][c] = sum of d_out[m][c] over the edges (m,h) of n for which h is the FIRST real entry of row m with
+ * x[idx[m,h]][c] == pooled[m][c] (pooled = the forward's output); a maximum owned by the zero shadow row sends its gradient nowhere.
+ * winners u8[M,C] is written by a first pass (the winning column, 255 = none) and may be discarded afterwards. */
+int lcr_maxpool_grad(const float* d_out, const float* x, const float* pooled, const void* idx, int idx_is_64, const int32_t* row_start,
+                     const uint32_t* edges, int64_t M, int64_t Ns, int H, int C, uint8_t* winners, float* d_x, void* stream);
+/* Reverse of lcr_groupnorm_apply, including the path through the statistics.  x: the raw input, stats: the forward's own table, y: the
+ * forward's output (read for the LeakyReLU mask only; may be NULL when act == 0), dy [N,C].  With dz = dy * (y > 0 ? 1 : slope) (act) or dy,
+ * x^ = (x - mean) * rstd and g = dz * gamma: dbeta[c] = sum_n dz, dgamma[c] = sum_n dz x^, dx = rstd * (g - mean_sg(g) - x^ mean_sg(g x^)), the
+ * means over the elements of one (segment, group); mean and rstd are derived from the table exactly as the forward derives them.  dz
+ * (optional) is the gradient of a plain residual; for a normalised residual call again on dz with act = 0 and the residual's table.
+ * dgamma / dbeta may be NULL.  C % 4 == 0, C % groups == 0, C <= 2048, S <= 256.  ws: lcr_groupnorm_apply_grad_ws_bytes(N, C, groups, S). */
+int lcr_groupnorm_apply_grad_ws_bytes(int64_t N, int C, int groups, int S, size_t* bytes);
+int lcr_groupnorm_apply_grad(const float* x, const double* stats, const float* gamma, const float* y, const float* dy, int64_t N, int C,
+                             int groups, const int64_t* seg_len, int S, float eps, float slope, int act, float* dx, float* dgamma,
+                             float* dbeta, float* dz, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * a-6  the whole KPEncoder.forward (experiments/lcrnet/backbone4.py:60-89: encoder1_1 ... encoder4_3) as ONE native call: the
  *      host-side sequencer over the building blocks above (same launches, arguments and order as the module tree of

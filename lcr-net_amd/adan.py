@@ -215,6 +215,8 @@ class Adan(Optimizer):
             c = clip if clip is None or clip.device == dev else clip.to(dev)
             if fused:
                 F.adan_step(F.adan_table(*tensors, fresh), F.AdanHyper(**hyper), c, dev)
+                for p in tensors[0]:            # the pass wrote the parameters through raw pointers: tell torch, so that caches keyed on the
+                    torch.autograd.graph.increment_version(p)      # version counter (functional.WeightStamp: transposed / split weights) are rebuilt
             else:
                 _torch_step(*tensors, fresh, hyper, c, group["foreach"])
         return loss

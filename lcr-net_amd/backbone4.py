@@ -1,6 +1,7 @@
 """KPEncoder — experiments/lcrnet/backbone4.py:11-89 (4 stages / 11 blocks), same attribute names => same checkpoint keys."""
 import os
 
+import torch
 import torch.nn as nn
 
 from . import functional as F
@@ -57,6 +58,7 @@ class KPEncoder(nn.Module):
         d["_native_table"] = None
         return d
 
+    @F.eval_without_graph
     def forward(self, feats, data_dict):
         """data_dict: 'points'[4], 'neighbors'[4], 'subsampling'[3] (+ optional 'segment_lengths'[4]: per-stage device
         int64 GroupNorm segment lengths; absent => one segment = whole stack, the reference's semantics)."""
@@ -67,11 +69,18 @@ class KPEncoder(nn.Module):
         # (tests/test_encoder_gpu.py), ~30 % less host time per pass and no interpreter lock held while the pass is issued.  In the
         # descriptor pipeline both drivers measure the same rate today (2 413 vs 2 421 scans/s, LABNOTES.md §4.2; round 1's 10 % deficit
         # went away with the launch-turn gate and the prioritised pre-processing stream), so the native one is the default.
-        if self.native and native_encoder.eligible(feats, data_dict):
+        # With a gradient wanted (training mode, grad mode on and feats or a parameter requiring grad; eval mode never builds a graph) the module tree is taken: its blocks carry the graph
+        # (functional._KPConvFn, _GroupNormApplyFn, _LinearStatsFn, _MaxPoolFn) and equal the tree with LCR_NO_NORM_ON_LOAD set, bit for bit.
+        # The seven index lists are inverted once per pass, on first use in the backward (functional.inverted_lists).
+        wants = torch.is_grad_enabled() and F._wants_grad(feats, *self.parameters())      # grad mode first: no walk over the parameters without it
+        if not wants and self.native and native_encoder.eligible(feats, data_dict):
             return native_encoder.forward(self, feats, data_dict)
         rows = segment_min_rows(data_dict)
         ctx = [StageContext(None if seg is None else seg[i], None if order is None else order[i], rows[i]) for i in range(4)]
         with F.stats_arena(feats.device):
+            if wants:
+                with F.inverted_lists():
+                    return self._forward(feats, P, N, S, ctx)
             return self._forward(feats, P, N, S, ctx)
 
     def _forward(self, feats, P, N, S, ctx):

@@ -362,7 +362,18 @@ def groupnorm_stats(x, groups, seg_len=None):
 
 
 def groupnorm_apply(x, stats, gamma, beta, groups, seg_len=None, res=None, res_norm=None, slope=0.1, act=True, want_pos=False):
-    """y = act(GN(x) [+ res | + GN(res)]); res_norm = (stats, gamma, beta) of the residual branch or None."""
+    """y = act(GN(x) [+ res | + GN(res)]); res_norm = (stats, gamma, beta) of the residual branch or None.  Differentiable in x, gamma,
+    beta, res and the residual's gamma / beta (_GroupNormApplyFn: the full GroupNorm reverse pass, the terms through `stats` included,
+    wherever the table was produced) when one of them requires grad and grad mode is on; the bytes are the no-grad call's.  The row flags
+    of want_pos carry no gradient."""
+    rs, rg, rb = res_norm if res_norm is not None else (None, None, None)
+    if _wants_grad(x, gamma, beta, res, rg, rb):
+        out = _GroupNormApplyFn.apply(x, gamma, beta, res, rg, rb, stats, rs, int(groups), seg_len, float(slope), bool(act), bool(want_pos))
+        return out if want_pos else out[0]
+    return _groupnorm_apply(x, stats, gamma, beta, groups, seg_len, res, res_norm, slope, act, want_pos)
+
+
+def _groupnorm_apply(x, stats, gamma, beta, groups, seg_len=None, res=None, res_norm=None, slope=0.1, act=True, want_pos=False):
     seg_len = _seg(seg_len, x.shape[0], x.device)
     y = torch.empty_like(x)
     pos = torch.empty((x.shape[0],), dtype=torch.uint8, device=x.device) if want_pos else None
@@ -448,11 +459,297 @@ def kpconv_cin1(s_feats, q_points, s_points, idx, kernel_points_host, sigma, wei
 
 
 def maxpool(x, idx, order=None):
+    """Max over the neighbours with a zero shadow row.  Differentiable in x (_MaxPoolFn: the gradient goes to the FIRST real entry of the row
+    that holds the maximum, nowhere when the shadow row owns it) when x requires grad and grad mode is on."""
+    if _wants_grad(x):
+        return _MaxPoolFn.apply(x, idx, order)
+    return _maxpool(x, idx, order)
+
+
+def _maxpool(x, idx, order=None):
     M, H = idx.shape
     out = torch.empty((M, x.shape[1]), dtype=torch.float32, device=x.device)
     _lib.call.lcr_maxpool(_lib.ptr(x), _lib.ptr(idx), _idx_args(idx), M, x.shape[0], H, x.shape[1], _lib.ptr(out),
                           _lib.ptr(order), _lib.stream_ptr(x.device))
     return out
+
+
+# ---- reverse passes of the encoder (csrc/kpconv_grad.hip, csrc/groupnorm_grad.hip) -------------------------------------------------------
+class InvertedList:
+    """The inverted form of a neighbour list idx [M,H] over Ns supports, built on first use (lcr_neighbor_transpose) and then kept: every
+    block of a pass that gathers over the same list shares one object (inverted())."""
+
+    def __init__(self, idx, Ns):
+        self.idx, self.Ns, self._built = idx, int(Ns), None
+
+    def get(self):
+        if self._built is None:
+            self._built = neighbor_transpose(self.idx, self.Ns)
+        return self._built
+
+
+class _InvertedCache(threading.local):
+    lists = None
+
+
+_INVERTED = _InvertedCache()
+
+
+class inverted_lists:
+    """Context manager: inside, inverted() hands out ONE InvertedList per index tensor (keyed on its storage, shape and support count), so
+    the seven lists of an encoder pass are inverted once per pass, not once per block.  Per host thread; nests by replacement.  The objects
+    outlive the context in the graph that refers to them."""
+
+    def __enter__(self):
+        self.prev = _INVERTED.lists
+        _INVERTED.lists = {}
+        return self
+
+    def __exit__(self, *exc):
+        _INVERTED.lists = self.prev
+        return False
+
+
+def inverted(idx, Ns):
+    cache = _INVERTED.lists
+    if cache is None:
+        return InvertedList(idx, Ns)
+    key = (idx.data_ptr(), tuple(idx.shape), idx.dtype, int(Ns))
+    inv = cache.get(key)
+    if inv is None:
+        inv = cache[key] = InvertedList(idx, Ns)        # holds idx: the address cannot be reused while the cache lives
+    return inv
+
+
+def neighbor_transpose(idx, Ns):
+    """(row_start int32 [Ns + 1], edges int32 [M * H]) of lcr_neighbor_transpose: the edges of support n, edges[row_start[n]:row_start[n + 1]],
+    are the flat positions m * H + h with idx[m, h] == n, ascending; padding (an index outside [0, Ns)) appears nowhere, and the entries of
+    `edges` from row_start[Ns] on are unspecified.  No host synchronisation."""
+    _lib.require_cuda(idx)
+    assert idx.dim() == 2 and idx.is_contiguous()
+    M, H = idx.shape
+    row_start = torch.empty((int(Ns) + 1,), dtype=torch.int32, device=idx.device)
+    edges = torch.empty((max(M * H, 1),), dtype=torch.int32, device=idx.device)
+    ws = _lib.ws("lcr_neighbor_transpose_ws_bytes", M, H, device=idx.device)
+    _lib.call.lcr_neighbor_transpose(_lib.ptr(idx), _idx_args(idx), M, int(Ns), H, _lib.ptr(row_start), _lib.ptr(edges), _lib.ptr(ws), ws.numel(),
+                                     _lib.stream_ptr(idx.device))
+    return row_start, edges
+
+
+def _inv_args(inv, M, H, Ns):
+    row_start, edges = inv.get() if isinstance(inv, InvertedList) else inv
+    _lib.require_cuda(row_start, edges)
+    assert row_start.dtype == torch.int32 and edges.dtype == torch.int32 and row_start.is_contiguous() and edges.is_contiguous()
+    assert row_start.numel() == Ns + 1 and edges.numel() >= M * H, "the inverted list belongs to another index list"
+    return row_start, edges
+
+
+def kpconv_aggregate_grad(dA, q_points, s_points, inv, H, kernel_points_host, sigma):
+    """d_s_feats [Ns, C] of lcr_kpconv_aggregate_grad from dA [M, 15 C]; inv: the InvertedList (or (row_start, edges)) of the forward's
+    index list [M, H]."""
+    _lib.require_cuda(dA, q_points, s_points)
+    M, Ns = q_points.shape[0], s_points.shape[0]
+    C = dA.shape[1] // 15
+    assert dA.dtype == torch.float32 and dA.is_contiguous() and tuple(dA.shape) == (M, 15 * C)
+    assert q_points.is_contiguous() and s_points.is_contiguous() and q_points.dtype == torch.float32 and s_points.dtype == torch.float32
+    row_start, edges = _inv_args(inv, M, H, Ns)
+    out = torch.empty((Ns, C), dtype=torch.float32, device=dA.device)
+    kp = _kp_host(kernel_points_host)
+    _lib.call.lcr_kpconv_aggregate_grad(_lib.ptr(dA), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(row_start), _lib.ptr(edges), M, Ns, int(H), C,
+                                        ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(out), _lib.stream_ptr(dA.device))
+    return out
+
+
+def kpconv_cin1_grad(d_out, s_feats, q_points, s_points, idx, kernel_points_host, sigma, weights, inv=None, want_feats=False, nn=None):
+    """(dW [15, 1, Cout], dbias [Cout], d_s_feats [Ns] or None) of lcr_kpconv_cin1_grad.  want_feats needs the inverted list."""
+    _lib.require_cuda(d_out, s_feats, q_points, s_points, idx, weights)
+    M, H = idx.shape
+    Ns, Cout = s_feats.shape[0], weights.shape[-1]
+    assert d_out.dtype == torch.float32 and d_out.is_contiguous() and tuple(d_out.shape) == (M, Cout)
+    assert idx.is_contiguous() and s_feats.is_contiguous() and q_points.is_contiguous() and s_points.is_contiguous() and weights.is_contiguous()
+    assert s_feats.numel() == Ns and weights.numel() == 15 * Cout
+    row_start, edges = _inv_args(inv, M, H, Ns) if want_feats else (None, None)
+    dW = torch.empty((15, 1, Cout), dtype=torch.float32, device=d_out.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=d_out.device)
+    df = torch.empty((Ns,), dtype=torch.float32, device=d_out.device) if want_feats else None
+    ws = _lib.ws("lcr_kpconv_cin1_grad_ws_bytes", M, Cout, int(bool(want_feats)), device=d_out.device)
+    kp = _kp_host(kernel_points_host)
+    _lib.call.lcr_kpconv_cin1_grad(_lib.ptr(d_out), _lib.ptr(s_feats), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx), _lib.ptr(nn),
+                                   _lib.ptr(row_start), _lib.ptr(edges), M, Ns, H, ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(weights), Cout,
+                                   _lib.ptr(dW), _lib.ptr(db), _lib.ptr(df), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(d_out.device))
+    return dW, db, df
+
+
+def maxpool_grad(d_out, x, pooled, idx, inv):
+    """d_x [Ns, C] of lcr_maxpool_grad; pooled = maxpool(x, idx)."""
+    _lib.require_cuda(d_out, x, pooled, idx)
+    M, H = idx.shape
+    Ns, C = x.shape
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (d_out, x, pooled)) and idx.is_contiguous()
+    assert tuple(d_out.shape) == (M, C) and tuple(pooled.shape) == (M, C)
+    row_start, edges = _inv_args(inv, M, H, Ns)
+    winners = torch.empty((max(M * C, 1),), dtype=torch.uint8, device=x.device)
+    dx = torch.empty((Ns, C), dtype=torch.float32, device=x.device)
+    _lib.call.lcr_maxpool_grad(_lib.ptr(d_out), _lib.ptr(x), _lib.ptr(pooled), _lib.ptr(idx), _idx_args(idx), _lib.ptr(row_start), _lib.ptr(edges), M, Ns, H,
+                               C, _lib.ptr(winners), _lib.ptr(dx), _lib.stream_ptr(x.device))
+    return dx
+
+
+def groupnorm_apply_grad(x, stats, gamma, y, dy, groups, seg_len=None, slope=0.1, act=True, want_dz=False):
+    """(dx, dgamma, dbeta, dz or None) of lcr_groupnorm_apply_grad: x the raw input of groupnorm_apply, stats its table, y its output (the
+    LeakyReLU mask; None with act=False), dy the gradient of y.  dz is the gradient of a plain residual."""
+    _lib.require_cuda(x, stats, gamma, y, dy)
+    N, C = x.shape
+    assert all(t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (N, C)) for t in (x, y, dy))
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and gamma.is_contiguous() and gamma.numel() == C and (y is not None or not act)
+    seg_len = _seg(seg_len, N, x.device)
+    S = seg_len.numel()
+    assert stats.numel() == GN_REPLICAS * S * groups * 2
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
+    dbeta = torch.empty((C,), dtype=torch.float32, device=x.device)
+    dz = torch.empty_like(x) if want_dz else None
+    ws = _lib.ws("lcr_groupnorm_apply_grad_ws_bytes", N, C, int(groups), S, device=x.device)
+    _lib.call.lcr_groupnorm_apply_grad(_lib.ptr(x), _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(y), _lib.ptr(dy), N, C, int(groups), _lib.ptr(seg_len), S, GN_EPS,
+                                       float(slope), int(bool(act)), _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dz), _lib.ptr(ws), ws.numel(),
+                                       _lib.stream_ptr(x.device))
+    return dx, dgamma, dbeta, dz
+
+
+def _det(t):
+    return None if t is None else t.detach().contiguous()
+
+
+class _GroupNormApplyFn(torch.autograd.Function):
+    """groupnorm_apply with the full GroupNorm reverse pass (lcr_groupnorm_apply_grad).  The statistics tables are inputs without a gradient of
+    their own: they are functions of x (of res), and the backward carries their terms."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, res, rgamma, rbeta, stats, rstats, groups, seg_len, slope, act, want_pos):
+        x, gamma, beta, res, rgamma, rbeta = (_det(t) for t in (x, gamma, beta, res, rgamma, rbeta))
+        res_norm = None if rstats is None else (rstats, rgamma, rbeta)
+        out = _groupnorm_apply(x, stats, gamma, beta, groups, seg_len, res, res_norm, slope, act, want_pos)
+        y, pos = out if want_pos else (out, None)
+        ctx.save_for_backward(x, gamma, y if act else None, res if rstats is not None else None, rgamma, stats, rstats, seg_len)
+        ctx.groups, ctx.slope, ctx.act, ctx.has_res = groups, slope, act, res is not None
+        if pos is None:
+            pos = torch.empty(0, dtype=torch.uint8, device=x.device)
+        ctx.mark_non_differentiable(pos)
+        return y, pos
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dpos):
+        x, gamma, y, res, rgamma, stats, rstats, seg_len = ctx.saved_tensors
+        dy = dy.contiguous().float()
+        dx, dgamma, dbeta, dz = groupnorm_apply_grad(x, stats, gamma, y, dy, ctx.groups, seg_len, ctx.slope, ctx.act, want_dz=ctx.has_res)
+        dres = drg = drb = None
+        if ctx.has_res:
+            if rstats is None:
+                dres = dz
+            else:
+                dres, drg, drb, _ = groupnorm_apply_grad(res, rstats, rgamma, None, dz, ctx.groups, seg_len, ctx.slope, False)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, dres if need[3] else None,
+                drg if need[4] else None, drb if need[5] else None, None, None, None, None, None, None, None)
+
+
+class _MaxPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, idx, order):
+        x = x.detach().contiguous()
+        out = _maxpool(x, idx, order)
+        ctx.save_for_backward(x, out, idx)
+        ctx.inv = inverted(idx, x.shape[0])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        x, out, idx = ctx.saved_tensors
+        return maxpool_grad(d_out.contiguous().float(), x, out, idx, ctx.inv), None, None
+
+
+def linear_stats(x, weight, bias, planes=None, seg_len=None, groups=0):
+    """(y, stats) = the Linear with GroupNorm sums fused (gemm / gemm_bsplit with `planes`, a callable that returns split_bf16x3(weight)), with
+    a graph when x, weight or bias requires grad: dx = dy W and dW = dy^T x on the same GEMMs as _LinearFn (the row-chunked _weight_grad
+    included), db the column sum.  stats carries no gradient: groupnorm_apply's backward holds the terms through it."""
+    if _wants_grad(x, weight, bias):
+        return _LinearStatsFn.apply(x, weight, bias, planes, seg_len, int(groups))
+    return _linear_stats(x.contiguous(), weight, bias, planes, seg_len, groups)
+
+
+def _linear_stats(x, weight, bias, planes, seg_len, groups):
+    if planes is not None:
+        return gemm_bsplit(x, planes(), bias=bias, seg_len=seg_len, groups=groups)
+    return gemm(x, weight, trans_b=True, bias=bias, seg_len=seg_len, groups=groups)
+
+
+class _LinearStatsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, planes, seg_len, groups):
+        xc, w = x.detach().contiguous(), weight.detach().contiguous()
+        y, stats = _linear_stats(xc, w, _det(bias), planes, seg_len, groups)
+        ctx.save_for_backward(xc, w)
+        if stats is None:
+            stats = torch.empty(0, dtype=torch.float64, device=y.device)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dstats):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous().float()
+        dx = gemm(dy, w)[0] if ctx.needs_input_grad[0] else None
+        dw = _weight_grad(dy, x) if ctx.needs_input_grad[1] else None
+        db = dy.sum(0) if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None, None
+
+
+class _KPConvFn(torch.autograd.Function):
+    """KPConv.forward_raw with a backward.  Forward: the module's own no-grad path (masked aggregate, split-bf16 contraction; C_in = 1: the fused
+    kernel).  Backward, with dOut' = dOut / nn: dbias = the column sum of dOut, A recomputed by the unmasked kpconv_aggregate (15 x the
+    activation: never kept), dW = dOut'^T A on _weight_grad, dA = dOut' W^T on the GEMM, d_s_feats = lcr_kpconv_aggregate_grad over the inverted
+    list.  The neighbour count is an integer and carries no gradient (as in the reference's autograd); points and kernel points get none."""
+
+    @staticmethod
+    def forward(ctx, s_feats, weights, bias, module, q_points, s_points, idx, s_pos, seg_len, groups, order):
+        s_feats = s_feats.detach().contiguous()
+        if module.in_channels != 1 and s_pos is None:
+            s_pos = row_positive(s_feats)
+        out, stats, nn = module.run_raw(s_feats, q_points, s_points, idx, s_pos, seg_len, groups, order, want_nn=True)
+        ctx.save_for_backward(s_feats, q_points, s_points, idx, s_pos, nn)
+        ctx.module, ctx.order = module, order
+        ctx.inv = inverted(idx, s_feats.shape[0]) if (ctx.needs_input_grad[0] and module.in_channels != 1) else None
+        if stats is None:
+            stats = torch.empty(0, dtype=torch.float64, device=out.device)
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, _dstats):
+        s_feats, q_points, s_points, idx, s_pos, nn = ctx.saved_tensors
+        mod, need = ctx.module, ctx.needs_input_grad
+        d_out = d_out.contiguous().float()
+        kp = mod.kernel_points_host()
+        if mod.in_channels == 1:
+            want = need[0]
+            inv = inverted(idx, s_feats.shape[0]) if want else None
+            dW, db, df = kpconv_cin1_grad(d_out, s_feats.view(-1), q_points, s_points, idx, kp, mod.sigma, mod.weights.detach(), inv, want_feats=want)
+            return (df.view(-1, 1) if want else None, dW if need[1] else None, db if need[2] else None) + (None,) * 8
+        db = d_out.sum(0) if need[2] else None
+        g = d_out / nn[:, None]
+        dW = df = None
+        if need[1]:
+            A, _ = kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kp, mod.sigma, order=ctx.order)
+            dW = _weight_grad(g, A).t().reshape(mod.kernel_size, mod.in_channels, mod.out_channels)
+            del A
+        if need[0]:
+            dA = gemm(g, mod.weights_t())[0]
+            df = kpconv_aggregate_grad(dA, q_points, s_points, ctx.inv, idx.shape[1], kp, mod.sigma)
+        return (df, dW, db) + (None,) * 8
 
 
 class NetvladWeights(ctypes.Structure):
@@ -815,6 +1112,21 @@ def check_transport_status():
 
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def eval_without_graph(forward):
+    """Decorator for the forward of the encoder's modules: in eval mode the forward runs with grad mode off, i.e. it makes the calls and returns
+    the plain tensors it always did, whatever requires grad (models are evaluated with `.eval()` and not always under torch.no_grad()).  A
+    graph is built in training mode only."""
+    import functools
+
+    @functools.wraps(forward)
+    def wrapped(self, *args, **kwargs):
+        if not self.training and torch.is_grad_enabled():
+            with torch.no_grad():
+                return forward(self, *args, **kwargs)
+        return forward(self, *args, **kwargs)
+    return wrapped
 
 
 def log_optimal_transport(raw_scores, row_masks, col_masks, alpha, scale=1.0, iters=100, inf=1e12):

@@ -77,17 +77,31 @@ class KPConv(nn.Module):
         F.drop_derived(self, "_kp_cache", "_wt_cache", "_wts_cache")      # .to() / .cuda() / .cpu(): new tensors, possibly at the old addresses
         return super()._apply(fn, *args, **kwargs)
 
+    @F.eval_without_graph
     def forward_raw(self, s_feats, q_points, s_points, neighbor_indices, s_pos=None, seg_len=None, groups=0, order=None):
-        """Returns (q_feats (M,Cout), stats) — stats = GroupNorm sums of the output when groups > 0."""
+        """Returns (q_feats (M,Cout), stats) — stats = GroupNorm sums of the output when groups > 0.  With a graph (functional._KPConvFn) when
+        the module is in training mode, grad mode is on and the features, the weights or the bias require grad: same launches, except that
+        LCR_KPCONV_FUSED is not taken."""
+        if F._wants_grad(s_feats, self.weights, self.bias):
+            out, stats = F._KPConvFn.apply(s_feats, self.weights, self.bias, self, q_points, s_points, neighbor_indices, s_pos, seg_len, groups, order)
+            return out, (stats if groups else None)
+        return self.run_raw(s_feats, q_points, s_points, neighbor_indices, s_pos, seg_len, groups, order)
+
+    def run_raw(self, s_feats, q_points, s_points, neighbor_indices, s_pos=None, seg_len=None, groups=0, order=None, want_nn=False):
+        """The launches of forward_raw.  want_nn (the autograd path): (q_feats, stats, neighbour count or None), never the fused form."""
+        if want_nn:
+            weights, bias = self.weights.detach(), None if self.bias is None else self.bias.detach()
+        else:
+            weights, bias = self.weights, self.bias
         kp = self.kernel_points_host()
         if self.in_channels == 1:
             out = F.kpconv_cin1(s_feats.contiguous().view(-1), q_points, s_points, neighbor_indices, kp, self.sigma,
-                                self.weights, self.bias, order=order)
+                                weights, bias, order=order)
             stats = F.groupnorm_stats(out, groups, seg_len) if groups else None
-            return out, stats
+            return (out, stats, None) if want_nn else (out, stats)
         if s_pos is None:
             s_pos = F.row_positive(s_feats)
-        if (_FUSED and self.in_channels == self.out_channels == F.KPCONV_FUSED_C and neighbor_indices.shape[1] <= 128
+        if (_FUSED and not want_nn and self.in_channels == self.out_channels == F.KPCONV_FUSED_C and neighbor_indices.shape[1] <= 128
                 and (seg_len is None or seg_len.numel() <= 64)):
             # aggregate + contraction in one launch: the (M, 480) intermediate never reaches memory
             return F.kpconv_fused(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, self.weights, self.bias,
@@ -101,8 +115,10 @@ class KPConv(nn.Module):
         else:
             (A, nn_cnt), mask = F.kpconv_aggregate(s_feats, s_pos, q_points, s_points, neighbor_indices, kp, self.sigma, order=order), None
         if split:
-            return F.gemm_bsplit(A, self.weights_t_split(), bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
-        return F.gemm(A, wt, trans_b=True, bias=self.bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
+            out = F.gemm_bsplit(A, self.weights_t_split(), bias=bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
+        else:
+            out = F.gemm(A, wt, trans_b=True, bias=bias, rowdiv=nn_cnt, seg_len=seg_len, groups=groups, row_mask=mask)
+        return out + (nn_cnt,) if want_nn else out
 
     def forward(self, s_feats, q_points, s_points, neighbor_indices):
         return self.forward_raw(s_feats, q_points, s_points, neighbor_indices)[0]

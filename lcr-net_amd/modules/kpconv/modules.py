@@ -47,6 +47,7 @@ class GroupNorm(nn.Module):
         self.num_groups, self.num_channels = num_groups, num_channels
         self.norm = nn.GroupNorm(num_groups, num_channels)     # holds weight / bias under the reference key `norm.norm.*`
 
+    @F.eval_without_graph
     def forward(self, x, ctx=_WHOLE, act=False, slope=0.1):
         stats = F.groupnorm_stats(x.contiguous(), self.num_groups, ctx.seg_len)
         return F.groupnorm_apply(x.contiguous(), stats, self.norm.weight, self.norm.bias, self.num_groups, ctx.seg_len, act=act, slope=slope)
@@ -75,12 +76,13 @@ class UnaryBlock(nn.Module):
         F.drop_derived(self, "_ws_cache")
         return super()._apply(fn, *args, **kwargs)
 
+    @F.eval_without_graph
     def raw(self, x, ctx):
-        """Linear + GroupNorm sums (no normalisation yet)."""
-        if F.gemm_split_enabled() and F.gemm_split_ok(self.out_channels, self.in_channels):
-            return F.gemm_bsplit(x.contiguous(), self.weight_split(), bias=self.mlp.bias, seg_len=ctx.seg_len, groups=self.group_norm)
-        return F.gemm(x.contiguous(), self.mlp.weight, trans_b=True, bias=self.mlp.bias, seg_len=ctx.seg_len, groups=self.group_norm)
+        """Linear + GroupNorm sums (no normalisation yet); with a graph when a gradient is wanted (functional.linear_stats)."""
+        split = F.gemm_split_enabled() and F.gemm_split_ok(self.out_channels, self.in_channels)
+        return F.linear_stats(x, self.mlp.weight, self.mlp.bias, self.weight_split if split else None, ctx.seg_len, self.group_norm)
 
+    @F.eval_without_graph
     def forward(self, x, ctx=_WHOLE, want_pos=False):
         y, stats = self.raw(x, ctx)
         return F.groupnorm_apply(y, stats, self.norm.norm.weight, self.norm.norm.bias, self.group_norm, ctx.seg_len,
@@ -92,17 +94,21 @@ class LastUnaryBlock(nn.Module):
         super().__init__()
         self.mlp = nn.Linear(in_channels, out_channels, bias=bias)
 
+    def weight_split(self):
+        w = self.mlp.weight
+        c = getattr(self, "_ws_cache", None)
+        if c is None or not c[0].same(w):
+            with F.derived_lock:
+                c = getattr(self, "_ws_cache", None)
+                if c is None or not c[0].same(w):
+                    c = self._ws_cache = (F.WeightStamp(w), F.publish_derived(F.split_bf16x3(w)))
+        return c[1]
+
+    @F.eval_without_graph
     def forward(self, x):
         w = self.mlp.weight
-        if F.gemm_split_enabled() and F.gemm_split_ok(w.shape[0], w.shape[1]):
-            c = getattr(self, "_ws_cache", None)
-            if c is None or not c[0].same(w):
-                with F.derived_lock:
-                    c = getattr(self, "_ws_cache", None)
-                    if c is None or not c[0].same(w):
-                        c = self._ws_cache = (F.WeightStamp(w), F.publish_derived(F.split_bf16x3(w)))
-            return F.gemm_bsplit(x.contiguous(), c[1], bias=self.mlp.bias)[0]
-        return F.gemm(x.contiguous(), w, trans_b=True, bias=self.mlp.bias)[0]
+        split = F.gemm_split_enabled() and F.gemm_split_ok(w.shape[0], w.shape[1])
+        return F.linear_stats(x, w, self.mlp.bias, self.weight_split if split else None)[0]
 
     def _apply(self, fn, *args, **kwargs):
         F.drop_derived(self, "_ws_cache")
@@ -119,6 +125,7 @@ class ConvBlock(nn.Module):
         self.leaky_relu = nn.LeakyReLU(negative_slope=negative_slope)
         self.negative_slope = negative_slope
 
+    @F.eval_without_graph
     def forward(self, s_feats, q_points, s_points, neighbor_indices, q_ctx=_WHOLE, s_ctx=_WHOLE):
         x, stats = self.KPConv.forward_raw(s_feats, q_points, s_points, neighbor_indices, seg_len=q_ctx.seg_len, groups=self.group_norm,
                                            order=q_ctx.order)
@@ -140,6 +147,7 @@ class ResidualBlock(nn.Module):
                                if in_channels != out_channels else nn.Identity())
         self.leaky_relu = nn.LeakyReLU(0.1)
 
+    @F.eval_without_graph
     def forward(self, s_feats, q_points, s_points, neighbor_indices, q_ctx=_WHOLE, s_ctx=_WHOLE):
         g = self.group_norm
         s_feats = s_feats.contiguous()
@@ -149,7 +157,8 @@ class ResidualBlock(nn.Module):
             x, pos = self.unary1(s_feats, s_ctx, want_pos=True)                       # Linear+GN+LeakyReLU, pos flags for the count
         x, stats = self.KPConv.forward_raw(x, q_points, s_points, neighbor_indices, s_pos=pos, seg_len=q_ctx.seg_len, groups=g,
                                            order=q_ctx.order)
-        if q_ctx.norm_on_load(x.shape[1], self.out_channels, x.shape[0]):
+        # with a gradient wanted the stand-alone groupnorm_apply is taken: the normalise-on-load GEMM has no reverse form
+        if not (torch.is_grad_enabled() and F._wants_grad(x, *self.parameters())) and q_ctx.norm_on_load(x.shape[1], self.out_channels, x.shape[0]):
             # norm_conv + LeakyReLU applied while unary2's GEMM stages its A tiles: no stand-alone GroupNorm pass over x
             if F.gemm_split_enabled() and F.gemm_split_ok(self.out_channels, x.shape[1]):      # the same rule as UnaryBlock.raw
                 y, ystats = F.gemm_bsplit_anorm(x, stats, self.norm_conv.norm.weight, self.norm_conv.norm.bias, g, self.unary2.weight_split(),
