@@ -457,6 +457,35 @@ typedef struct LcrNetvladWeights {   /* device pointers; reference parameter nam
 int lcr_netvlad_ws_bytes(int64_t n_rows, int S, size_t* bytes);
 int lcr_netvlad_forward(const float* feats /*[sum(seg_len),1024]*/, const int64_t* seg_len_host, int S,
                         const LcrNetvladWeights* weights_host, float* out /*[S,256]*/, void* ws, size_t ws_bytes, void* stream);
+/* The head in TRAINING mode (GlobalDescritionHEAD's training branch, LCRNet_GlobalDescrition.py:40-57): every cloud stands for its cyclic
+ * padding to Lmax = max(seg_len) rows — local row i of a cloud of L rows counts c = (Lmax-1-i)/L + 1 times in bn1's batch statistics (taken
+ * over S*Lmax rows) and carries the assignment softmax + (c-1)/64 (padding rows are uniform) — and bn2 / context_gating.bn1 use the
+ * statistics of the S descriptors.  The running_mean / running_var members of `weights_host` are not read.
+ * batch_stats[1152] receives mean and BIASED variance: bn1 mean[64], var[64], bn2 mean[256], var[256], context_gating.bn1 mean[256], var[256].
+ * `saved` (lcr_netvlad_train_saved_bytes) keeps what lcr_netvlad_backward reads: x.Wc and the softmax [N,64], each row's multiplicity and cloud,
+ * v [S,65536] with its raw norms, the column sums of the assignment and the [S,256] tensors of the tail; the unit rows are formed again there.
+ * Domain: 1 < S <= 128, every seg_len >= 1; LCR_EARG with text and no launch outside it.  Every sum has a fixed order (no atomics): the same
+ * call gives the same bytes. */
+typedef struct LcrNetvladGrads {     /* device pointers, shapes of the parameters; NULL = that gradient is not formed */
+  float* cluster_weights;
+  float* cluster_weights2;
+  float* hidden1_weights;
+  float *bn1_w, *bn1_b;
+  float *bn2_w, *bn2_b;
+  float* gating_weights;
+  float *gbn_w, *gbn_b;
+} LcrNetvladGrads;
+int lcr_netvlad_train_ws_bytes(int64_t n_rows, int S, size_t* bytes);
+int lcr_netvlad_train_saved_bytes(int64_t n_rows, int S, size_t* bytes);
+int lcr_netvlad_train_forward(const float* feats /*[sum(seg_len),1024]*/, const int64_t* seg_len_host, int S,
+                              const LcrNetvladWeights* weights_host, float* out /*[S,256]*/, float* batch_stats /*[1152]*/, void* saved,
+                              size_t saved_bytes, void* ws, size_t ws_bytes, void* stream);
+/* d_out [S,256] -> d_feats [N,1024] (NULL: skipped) and the gradients named in `grads_host`; feats, seg_len_host, weights and `saved` as in the
+ * forward call.  The hidden projection's reverse is one sweep over the rows of hidden1_weights that forms dv = dh.H^T and dH = v^T.dh together. */
+int lcr_netvlad_backward_ws_bytes(int64_t n_rows, int S, size_t* bytes);
+int lcr_netvlad_backward(const float* d_out, const float* feats, const int64_t* seg_len_host, int S, const LcrNetvladWeights* weights_host,
+                         const void* saved, size_t saved_bytes, float* d_feats, const LcrNetvladGrads* grads_host, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a-8  3D-RoFormer attention block (fp32) — RPEMultiHeadAttention / MultiHeadAttention of

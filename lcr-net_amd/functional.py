@@ -771,6 +771,85 @@ def netvlad_forward(feats, seg_len_host, weights_struct):
     return out
 
 
+NETVLAD_GRAD_NAMES = ("cluster_weights", "cluster_weights2", "hidden1_weights", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "gating_weights", "gbn_w", "gbn_b")
+_NETVLAD_GRAD_SHAPES = {"cluster_weights": (1024, 64), "cluster_weights2": (1, 1024, 64), "hidden1_weights": (65536, 256), "bn1_w": (64,), "bn1_b": (64,),
+                        "bn2_w": (256,), "bn2_b": (256,), "gating_weights": (256, 256), "gbn_w": (256,), "gbn_b": (256,)}
+NETVLAD_STAT_FLOATS = 2 * 64 + 4 * 256
+
+
+class NetvladGrads(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in NETVLAD_GRAD_NAMES]
+
+
+def _netvlad_seg(feats, seg_len_host):
+    _lib.require_cuda(feats)
+    seg = np.ascontiguousarray(seg_len_host, dtype=np.int64)
+    assert seg.ndim == 1 and feats.dim() == 2 and feats.shape[1] == 1024 and feats.dtype == torch.float32 and feats.is_contiguous()
+    assert int(seg.sum()) == feats.shape[0], "seg_len does not add up to the rows of feats"
+    return seg, int(seg.shape[0])
+
+
+def netvlad_train(feats, seg_len_host, weights_struct):
+    """The head in training mode (lcr_netvlad_train_forward: cyclic padding by multiplicities, batch statistics, uniform assignment on the
+    padding rows): feats [sum(seg_len),1024] -> (out [S,256], batch_stats [1152] = mean and biased variance of bn1, bn2 and
+    context_gating.bn1, saved = the opaque buffer netvlad_backward reads).  No host synchronisation.  One cloud has no batch statistics:
+    ValueError, as nn.BatchNorm1d raises for one value per channel."""
+    seg, S = _netvlad_seg(feats, seg_len_host)
+    if S == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got one cloud (batch statistics of bn2)")
+    dev = feats.device
+    out = torch.empty((S, 256), dtype=torch.float32, device=dev)
+    stats = torch.empty((NETVLAD_STAT_FLOATS,), dtype=torch.float32, device=dev)
+    saved = _lib.ws("lcr_netvlad_train_saved_bytes", feats.shape[0], S, device=dev)
+    ws = _lib.ws("lcr_netvlad_train_ws_bytes", feats.shape[0], S, device=dev)
+    _lib.call.lcr_netvlad_train_forward(_lib.ptr(feats), ctypes.c_void_p(seg.ctypes.data), S, ctypes.byref(weights_struct), _lib.ptr(out), _lib.ptr(stats),
+                                        _lib.ptr(saved), saved.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return out, stats, saved
+
+
+def netvlad_backward(d_out, feats, seg_len_host, weights_struct, saved, want=NETVLAD_GRAD_NAMES, want_feats=True):
+    """lcr_netvlad_backward: d_out [S,256] -> (d_feats [N,1024] or None, {name: gradient} for the names of `want`).  feats, seg_len_host, the
+    weights and `saved` are those of the netvlad_train call.  No host synchronisation."""
+    seg, S = _netvlad_seg(feats, seg_len_host)
+    _lib.require_cuda(d_out, saved)
+    assert d_out.dtype == torch.float32 and d_out.is_contiguous() and tuple(d_out.shape) == (S, 256)
+    dev = feats.device
+    grads = {n: torch.empty(_NETVLAD_GRAD_SHAPES[n], dtype=torch.float32, device=dev) for n in want}
+    table = NetvladGrads()
+    for n, t in grads.items():
+        setattr(table, n, t.data_ptr())
+    d_feats = torch.empty_like(feats) if want_feats else None
+    ws = _lib.ws("lcr_netvlad_backward_ws_bytes", feats.shape[0], S, device=dev)
+    _lib.call.lcr_netvlad_backward(_lib.ptr(d_out), _lib.ptr(feats), ctypes.c_void_p(seg.ctypes.data), S, ctypes.byref(weights_struct), _lib.ptr(saved),
+                                   saved.numel(), _lib.ptr(d_feats), ctypes.byref(table), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return d_feats, grads
+
+
+class _NetvladTrainFn(torch.autograd.Function):
+    """netvlad_train with lcr_netvlad_backward behind it.  `module` is the NetVLADLoupe2 (its _weights() gives the pointer table); the ten
+    parameters follow in NETVLAD_GRAD_NAMES order so that autograd routes their gradients.  Returns (out, batch_stats)."""
+
+    @staticmethod
+    def forward(ctx, feats, module, seg, *params):
+        x = feats.detach().contiguous()
+        out, stats, saved = netvlad_train(x, seg, module._weights())
+        ctx.save_for_backward(x, saved)
+        ctx.module, ctx.seg = module, seg
+        ctx.versions = [p._version for p in params]
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, _dstats):
+        x, saved = ctx.saved_tensors
+        if [p._version for p in ctx.module._grad_params()] != ctx.versions:
+            raise RuntimeError("a NetVLAD parameter was modified in place between the training forward and its backward")
+        want = [n for i, n in enumerate(NETVLAD_GRAD_NAMES) if ctx.needs_input_grad[3 + i]]
+        d_feats, grads = netvlad_backward(d_out.contiguous().float(), x, ctx.seg, ctx.module._weights(), saved, want, ctx.needs_input_grad[0])
+        return (d_feats, None, None) + tuple(grads.get(n) for n in NETVLAD_GRAD_NAMES)
+
+
 def gemm_batched_ta(a, b, c, M, N, k, a_off, b_off, c_off):
     """c[c_off[z] : c_off[z] + M*N] <- A_z^T · B_z for every entry z, in place, where A_z = a[a_off[z]:] read as [k[z], M] and
     B_z = b[b_off[z]:] as [k[z], N] (lcr_gemm_f32_batched_ta: a, b, c flat fp32 device buffers; k and the ELEMENT offsets are host sequences,

@@ -1,6 +1,7 @@
 """NetVLADLoupe2 + GatingContext — parameters as in experiments/lcrnet/modules/netvlad/NetVlad.py:12-47, 165-186
 (cluster_weights, cluster_weights2, hidden1_weights, bn1, bn2, context_gating.{gating_weights,bn1}); eval forward on the
-HIP path (lcr_netvlad_forward), batched over scans.  BatchNorm1d runs in eval mode only (running statistics)."""
+HIP path (lcr_netvlad_forward), batched over scans; training forward and backward on lcr_netvlad_train_forward / lcr_netvlad_backward
+(batch statistics, the reference's cyclic padding restated as row multiplicities)."""
 import math
 
 import numpy as np
@@ -45,9 +46,45 @@ class NetVLADLoupe2(nn.Module):
             setattr(w, name, t.data_ptr())
         return w
 
+    def _grad_params(self):
+        """the ten trainable tensors in functional.NETVLAD_GRAD_NAMES order"""
+        g = self.context_gating
+        return (self.cluster_weights, self.cluster_weights2, self.hidden1_weights, self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias,
+                g.gating_weights, g.bn1.weight, g.bn1.bias)
+
+    def _track(self, stats, rows):
+        """nn.BatchNorm1d's running statistics from the batch statistics of one training call (mean, biased variance; `rows` values per
+        channel for bn1, S for the other two): momentum 0.1, unbiased variance, device ops only."""
+        S = rows[1]
+        o = 0
+        with torch.no_grad():
+            for bn, n in ((self.bn1, rows[0]), (self.bn2, S), (self.context_gating.bn1, S)):
+                c = bn.num_features
+                mean, var = stats[o:o + c], stats[o + c:o + 2 * c]
+                o += 2 * c
+                if not bn.track_running_stats or bn.running_mean is None:
+                    continue
+                assert bn.momentum is not None, "cumulative-average BatchNorm would read the counter on the host"
+                bn.num_batches_tracked += 1
+                m = bn.momentum
+                bn.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+                bn.running_var.mul_(1.0 - m).add_(var, alpha=m * n / (n - 1.0))
+
     def describe(self, feats, lengths_host):
         """Stacked coarse features [sum(len),1024] of S scans -> [S,256] L2-normalised descriptors
-        (= GlobalDescritionHEAD per scan: F.normalize -> netvlad -> F.normalize)."""
-        if self.training:
-            raise RuntimeError("lcr-net_amd implements inference only (BatchNorm running statistics)")
-        return F.netvlad_forward(feats.contiguous(), np.asarray(lengths_host, dtype=np.int64), self._weights())
+        (= GlobalDescritionHEAD per scan: F.normalize -> netvlad -> F.normalize).
+
+        Eval mode: running statistics, one lcr_netvlad_forward call, never a graph.  Training mode: the reference's training branch
+        (LCRNet_GlobalDescrition.py:40-57 — cyclic padding to the longest cloud, batch statistics in all three BatchNorm1d, uniform assignment
+        on the padding rows) through lcr_netvlad_train_forward; the running buffers are updated as nn.BatchNorm1d does; with grad mode on and an
+        input or parameter requiring grad the result carries a graph whose backward is lcr_netvlad_backward."""
+        if not self.training:
+            return F.netvlad_forward(feats.contiguous(), np.asarray(lengths_host, dtype=np.int64), self._weights())
+        seg = np.asarray(lengths_host, dtype=np.int64)
+        params = self._grad_params()
+        if F._wants_grad(feats, *params):
+            out, stats = F._NetvladTrainFn.apply(feats, self, seg, *params)
+        else:
+            out, stats, _ = F.netvlad_train(feats.detach().contiguous(), seg, self._weights())
+        self._track(stats, (float(len(seg)) * float(seg.max()), float(len(seg))))
+        return out
