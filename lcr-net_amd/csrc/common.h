@@ -279,6 +279,24 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
+// Sum over a workgroup of WAVES wavefronts through lds[WAVES], returned to every thread; lds may be reused on return.  The tree is
+// fixed: four wavefronts as (l0 + l1) + (l2 + l3), any other count in ascending order.
+template <int WAVES>
+__device__ __forceinline__ float block_sum(float v, float* lds) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t;
+  if constexpr (WAVES == 4) {
+    t = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+  } else {
+    t = 0.f;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) t += lds[i];
+  }
+  __syncthreads();
+  return t;
+}
 #endif  // __HIPCC__
 
 // FIFO gate for the native drivers' launch sequences.  Two host threads that issue launches back to back contend for the

@@ -1,68 +1,16 @@
-// netvlad_grad.hip — row p: the global-descriptor head in TRAINING mode (forward with batch statistics) and its reverse pass, fp32.
+// netvlad_grad.hip — row p: the reverse pass of the global-descriptor head in training mode (lcr_netvlad_backward), fp32.
 //
-// Reference: GlobalDescritionHEAD's training branch (model_family/LCRNet_GlobalDescrition.py:40-57) around NetVLADLoupe2.forward with a mask
-// (modules/netvlad/NetVlad.py:49-87) and GatingContext (:165-201), all three BatchNorm1d on batch statistics.  The reference pads every
-// cloud to Lmax rows by repeating its rows cyclically, takes bn1's statistics over all S*Lmax rows and gives the padding rows the uniform
-// assignment 1/64.  No padded tensor exists here: local row i of a cloud of L rows stands for c = (Lmax-1-i)/L + 1 padded rows, one real and
-// p = c-1 padding copies, so
-//     bn1 statistics  = sums weighted by c over the real rows, divided by S*Lmax
-//     assignment      w = softmax(bn1(a)) + p/64
-// and everything behind w is the eval head's arithmetic (csrc/netvlad.hip, whose kernels and bytes this file leaves alone).
-//
-// Saved for the reverse pass (lcr_netvlad_train_saved_bytes): a = x^.Wc and softmax [N,64], the multiplicity and cloud of every row, v [S,65536]
-// with both raw norms, the column sums of w, and the [S,256] tensors of the tail.  x^ (4 KB a row) is NOT kept: the reverse pass
-// normalises the rows again.  Every sum has one order: wavefront / workgroup trees of fixed shape, cross-workgroup partials added in
-// ascending order by one thread per column, batch statistics in fp64.  No floating-point atomics.
+// The forward it reverses is lcr_netvlad_train_forward (csrc/netvlad.hip, which also says how the reference's cyclic padding becomes the
+// row multiplicities c = p + 1).  It reads what that forward saved (nv::Saved in netvlad.h); x^ (4 KB a row) is NOT among it: the rows are
+// normalised again here, by the forward's own kernel.  Every sum has one order: wavefront / workgroup trees of fixed shape,
+// cross-workgroup partials added in ascending order by one thread per column, batch statistics in fp64.  No floating-point atomics.
 #include <algorithm>
-#include <vector>
 
-#include "common.h"
-
-extern "C" int lcr_gemm_f32(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const float* bias,
-                            const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, void* stream);
-extern "C" int lcr_gemm_f32_batched_ta(const float* A, const float* B, float* C, int64_t M, int N, int count, const int* k_host,
-                                       const int64_t* a_off_host, const int64_t* b_off_host, const int64_t* c_off_host, void* stream);
+#include "netvlad.h"
 
 namespace lcr {
 namespace {
-
-constexpr int F = 1024;          // feature size
-constexpr int K = 64;            // clusters
-constexpr int D = 256;           // output dim
-constexpr int FK = F * K;        // 65536 rows of hidden1_weights
-constexpr int SPLIT = 256;       // K-slices of the forward hidden projection
-constexpr int S_MAX = 128;       // clouds per call
-constexpr int STAT_G = 128;      // workgroups of the bn1 column sums
-constexpr float BN_EPS = 1e-5f;
-
-struct Seg {                     // row offsets of the S clouds (+ total), by value in kernel arguments
-  int S, Lmax;
-  int64_t off[S_MAX + 1];
-};
-
-// ------------------------------------------------------------------------------------------------ rows
-__global__ __launch_bounds__(256) void k_rows_of(Seg seg, int64_t N, int32_t* __restrict__ cmul, int32_t* __restrict__ rseg) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (n >= N) return;
-  const int s = cloud_of(seg.off, seg.S, n);
-  const int64_t i = n - seg.off[s], L = seg.off[s + 1] - seg.off[s];
-  cmul[n] = static_cast<int32_t>((seg.Lmax - 1 - i) / L + 1);
-  rseg[n] = s;
-}
-
-__global__ __launch_bounds__(256) void k_row_unit(const float* __restrict__ x, int64_t N, float* __restrict__ y) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int64_t n = static_cast<int64_t>(blockIdx.x) * 4 + w; n < N; n += static_cast<int64_t>(gridDim.x) * 4) {
-    float ss = 0.f;
-    for (int c = lane; c < F; c += 64) {
-      const float v = x[n * F + c];
-      ss = fmaf(v, v, ss);
-    }
-    ss = wave_sum(ss);
-    const float d = fmaxf(sqrtf(ss), 1e-12f);
-    for (int c = lane; c < F; c += 64) y[n * F + c] = x[n * F + c] / d;
-  }
-}
+using namespace nv;
 
 // dx = dx^/d - [n >= eps] (dx^ . x^) x^ / n with x^ = x/d, d = max(n, 1e-12): F.normalize's backward, a zero row included (dx = dx^/1e-12)
 __global__ __launch_bounds__(256) void k_row_unit_grad(const float* __restrict__ x, const float* __restrict__ g, int64_t N, float* __restrict__ dx) {
@@ -89,48 +37,25 @@ __global__ __launch_bounds__(256) void k_row_unit_grad(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ bn1 column sums (fp64, fixed order)
-// MODE 0: (sum c a, sum c a^2) of a[N,64];  MODE 1: (sum g, sum g a^) of g[N,64] with a^ = (a - mu) r.   part[g][2][64]
-template <int MODE>
-__global__ __launch_bounds__(256) void k_col64_partial(const float* __restrict__ a, const float* __restrict__ g, const int32_t* __restrict__ cmul,
-                                                        const float* __restrict__ mu, const float* __restrict__ r, int64_t N,
-                                                        double* __restrict__ part) {
+// (sum g, sum g a^) of g[N,64] with a^ = (a - mu) r, partitioned as the forward's k_bn1_moments.   part[g][2][64]
+__global__ __launch_bounds__(256) void k_bn1_grad_partial(const float* __restrict__ a, const float* __restrict__ g, const float* __restrict__ mu,
+                                                           const float* __restrict__ r, int64_t N, double* __restrict__ part) {
   __shared__ double s_p[4][2][K];
   const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int64_t chunk = (N + gridDim.x - 1) / gridDim.x;
   const int64_t lo = static_cast<int64_t>(blockIdx.x) * chunk, hi = std::min<int64_t>(lo + chunk, N);
   double t0 = 0.0, t1 = 0.0;
-  const float m = MODE == 1 ? mu[k] : 0.f, rr = MODE == 1 ? r[k] : 0.f;
+  const float m = mu[k], rr = r[k];
   for (int64_t n = lo + q; n < hi; n += 4) {
     const float av = a[n * K + k];
-    if (MODE == 0) {
-      const double c = static_cast<double>(cmul[n]);
-      t0 += c * av;
-      t1 += c * (static_cast<double>(av) * av);
-    } else {
-      const float gv = g[n * K + k];
-      t0 += gv;
-      t1 += static_cast<double>(gv) * ((av - m) * rr);
-    }
+    const float gv = g[n * K + k];
+    t0 += gv;
+    t1 += static_cast<double>(gv) * ((av - m) * rr);
   }
   s_p[q][0][k] = t0;
   s_p[q][1][k] = t1;
   __syncthreads();
   if (q < 2) part[(static_cast<int64_t>(blockIdx.x) * 2 + q) * K + k] = (s_p[0][q][k] + s_p[1][q][k]) + (s_p[2][q][k] + s_p[3][q][k]);
-}
-
-__global__ __launch_bounds__(K) void k_bn1_stats(const double* __restrict__ part, int G, double count, float* __restrict__ stat_mean,
-                                                  float* __restrict__ stat_var, float* __restrict__ mu, float* __restrict__ r) {
-  const int k = threadIdx.x;
-  double t0 = 0.0, t1 = 0.0;
-  for (int g = 0; g < G; ++g) {
-    t0 += part[(g * 2 + 0) * K + k];
-    t1 += part[(g * 2 + 1) * K + k];
-  }
-  const double mean = t0 / count, var = fmax(t1 / count - mean * mean, 0.0);
-  stat_mean[k] = static_cast<float>(mean);
-  stat_var[k] = static_cast<float>(var);
-  mu[k] = static_cast<float>(mean);
-  r[k] = static_cast<float>(1.0 / sqrt(var + static_cast<double>(BN_EPS)));
 }
 
 // d gamma1 = sum g a^, d beta1 = sum g; sums[0][k] = gamma sum g, sums[1][k] = gamma sum g a^ (the two means of the bn1 backward, times S Lmax)
@@ -148,180 +73,7 @@ __global__ __launch_bounds__(K) void k_bn1_grad_sums(const double* __restrict__ 
   sums[K + k] = static_cast<float>(t1 * gamma[k]);
 }
 
-// sm = softmax_k(gamma (a - mu) r + beta) kept; w = sm + p/64 (the real copy and its p padding copies, which the reference sets to -1e12
-// before the softmax: uniform 1/64 each)
-__global__ __launch_bounds__(256) void k_bn_softmax_train(const float* __restrict__ a, const int32_t* __restrict__ cmul, const float* __restrict__ mu,
-                                                           const float* __restrict__ r, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           int64_t N, float* __restrict__ sm, float* __restrict__ wgt) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const float m = mu[lane], rr = r[lane], ga = gamma[lane], be = beta[lane];
-  for (int64_t n = static_cast<int64_t>(blockIdx.x) * 4 + w; n < N; n += static_cast<int64_t>(gridDim.x) * 4) {
-    const float v = (a[n * K + lane] - m) * rr * ga + be;
-    float mx = v;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    const float e = expf(v - mx);
-    const float p = e / wave_sum(e);
-    sm[n * K + lane] = p;
-    if (wgt) wgt[n * K + lane] = p + static_cast<float>(cmul[n] - 1) * (1.f / 64.f);
-  }
-}
-
-// asum[s][k] = sum of w over the rows of cloud s = blockIdx.x (fixed 16-way row partition, fixed combine order)
-__global__ __launch_bounds__(1024) void k_colsum_seg(const float* __restrict__ w, Seg seg, float* __restrict__ out) {
-  __shared__ float part[16][K];
-  const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int64_t row0 = seg.off[blockIdx.x], rows = seg.off[blockIdx.x + 1] - row0;
-  float s = 0.f;
-  for (int64_t n = q; n < rows; n += 16) s += w[(row0 + n) * K + k];
-  part[q][k] = s;
-  __syncthreads();
-  if (q == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += part[i][k];
-    out[blockIdx.x * K + k] = t;
-  }
-}
-
-// V[c][k] of cloud blockIdx.x: subtract asum * W2, normalise each column (eps 1e-6), then the whole vector (eps 1e-6); the raw norms are kept
-__global__ __launch_bounds__(1024) void k_vlad_finalize_train(float* __restrict__ V, const float* __restrict__ asum, const float* __restrict__ W2,
-                                                               float* __restrict__ n1raw, float* __restrict__ n2raw) {
-  __shared__ float s_col[16][K];
-  __shared__ float s_inv[K];
-  __shared__ float s_tot;
-  float* v = V + static_cast<int64_t>(blockIdx.x) * FK;
-  const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const float ak = asum[blockIdx.x * K + k];
-  float ss = 0.f;
-  for (int c = q; c < F; c += 16) {
-    const float t = v[c * K + k] - ak * W2[c * K + k];
-    v[c * K + k] = t;
-    ss = fmaf(t, t, ss);
-  }
-  s_col[q][k] = ss;
-  __syncthreads();
-  if (q == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += s_col[i][k];
-    const float nrm = sqrtf(t);
-    const float inv = 1.f / fmaxf(nrm, 1e-6f);
-    s_inv[k] = inv;
-    n1raw[blockIdx.x * K + k] = nrm;
-    const float u = nrm * inv;
-    const float tot = wave_sum(u * u);
-    if (k == 0) s_tot = tot;
-  }
-  __syncthreads();
-  const float n2 = sqrtf(s_tot);
-  if (threadIdx.x == 0) n2raw[blockIdx.x] = n2;
-  const float f = s_inv[k] * (1.f / fmaxf(n2, 1e-6f));
-  for (int c = q; c < F; c += 16) v[c * K + k] *= f;
-}
-
-// ------------------------------------------------------------------------------------------------ the hidden projection, forward
-// partial[slice][s][j] = sum_{i in slice} v[s][i] H[i][j] for up to SMAX clouds from s0: H is streamed once per SMAX clouds
-template <int SMAX>
-__global__ __launch_bounds__(D) void k_hidden_fwd(const float* __restrict__ V, const float* __restrict__ H, int S, int s0, float* __restrict__ partial) {
-  constexpr int ROWS = FK / SPLIT, CH = 128, HB = 8;
-  __shared__ float s_v[SMAX][CH];
-  const int j = threadIdx.x;
-  const int i0 = blockIdx.x * ROWS;
-  const int ns = min(SMAX, S - s0);
-  float acc[SMAX];
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s) acc[s] = 0.f;
-  for (int c0 = 0; c0 < ROWS; c0 += CH) {
-    __syncthreads();
-    for (int t = j; t < SMAX * CH; t += D) {
-      const int s = t / CH, i = t % CH;
-      s_v[s][i] = s < ns ? V[static_cast<int64_t>(s0 + s) * FK + i0 + c0 + i] : 0.f;
-    }
-    __syncthreads();
-    const float* hp = H + static_cast<int64_t>(i0 + c0) * D + j;
-    for (int i = 0; i < CH; i += HB) {
-      float h[HB];
-#pragma unroll
-      for (int u = 0; u < HB; ++u) h[u] = hp[static_cast<int64_t>(i + u) * D];
-#pragma unroll
-      for (int u = 0; u < HB; ++u)
-#pragma unroll
-        for (int s = 0; s < SMAX; ++s) acc[s] = fmaf(s_v[s][i + u], h[u], acc[s]);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s)
-    if (s < ns) partial[(static_cast<int64_t>(blockIdx.x) * S + s0 + s) * D + j] = acc[s];
-}
-
-__global__ __launch_bounds__(D) void k_hidden_reduce(const float* __restrict__ partial, int S, float* __restrict__ h) {
-  const int s = blockIdx.x, j = threadIdx.x;
-  float o = 0.f;
-  constexpr int TB = 16;
-  for (int b = 0; b < SPLIT; b += TB) {
-    float p[TB];
-#pragma unroll
-    for (int u = 0; u < TB; ++u) p[u] = partial[(static_cast<int64_t>(b + u) * S + s) * D + j];
-#pragma unroll
-    for (int u = 0; u < TB; ++u) o += p[u];
-  }
-  h[s * D + j] = o;
-}
-
 // ------------------------------------------------------------------------------------------------ the tail ([S,256]; thread = column)
-// BatchNorm over the S descriptors of x[S,256] on batch statistics (fp64 sums in ascending s): xh = (x - mean) r, y = gamma xh + beta
-__global__ __launch_bounds__(D) void k_bn_batch(const float* __restrict__ x, int S, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                 float* __restrict__ stat_mean, float* __restrict__ stat_var, float* __restrict__ r_out,
-                                                 float* __restrict__ xh, float* __restrict__ y) {
-  const int j = threadIdx.x;
-  double t = 0.0;
-  for (int s = 0; s < S; ++s) t += x[s * D + j];
-  const double mean = t / S;
-  double q = 0.0;
-  for (int s = 0; s < S; ++s) {
-    const double d = x[s * D + j] - mean;
-    q += d * d;
-  }
-  const double var = q / S;
-  const float r = static_cast<float>(1.0 / sqrt(var + static_cast<double>(BN_EPS)));
-  stat_mean[j] = static_cast<float>(mean);
-  stat_var[j] = static_cast<float>(var);
-  r_out[j] = r;
-  const float mf = static_cast<float>(mean), ga = gamma[j], be = beta[j];
-  for (int s = 0; s < S; ++s) {
-    const float n = (x[s * D + j] - mf) * r;
-    xh[s * D + j] = n;
-    if (y) y[s * D + j] = n * ga + be;
-  }
-}
-
-__device__ __forceinline__ float block256_sum(float v, float* lds) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float t = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-  __syncthreads();
-  return t;
-}
-
-// cloud blockIdx.x: g = sigmoid(gamma gh + beta), t = h' g, out = t / max(|t|, 1e-12)
-__global__ __launch_bounds__(D) void k_gate_out(const float* __restrict__ hp, const float* __restrict__ gh, const float* __restrict__ gamma,
-                                                 const float* __restrict__ beta, float* __restrict__ g, float* __restrict__ tn, float* __restrict__ out_keep,
-                                                 float* __restrict__ out) {
-  __shared__ float s_red[4];
-  const int s = blockIdx.x, j = threadIdx.x;
-  const float pre = gh[s * D + j] * gamma[j] + beta[j];
-  const float gv = 1.f / (1.f + expf(-pre));
-  const float t = hp[s * D + j] * gv;
-  const float nrm = sqrtf(block256_sum(t * t, s_red));
-  const float o = t / fmaxf(nrm, 1e-12f);
-  g[s * D + j] = gv;
-  out[s * D + j] = o;
-  out_keep[s * D + j] = o;
-  if (j == 0) tn[s] = nrm;
-}
-
 // cloud blockIdx.x: through the last normalise, the product and the sigmoid: dhp1 = dt g, dpre = dt h' g (1 - g)
 __global__ __launch_bounds__(D) void k_gate_out_grad(const float* __restrict__ d_out, const float* __restrict__ out, const float* __restrict__ tn,
                                                       const float* __restrict__ g, const float* __restrict__ hp, float* __restrict__ dhp1,
@@ -329,7 +81,7 @@ __global__ __launch_bounds__(D) void k_gate_out_grad(const float* __restrict__ d
   __shared__ float s_red[4];
   const int s = blockIdx.x, j = threadIdx.x;
   const float dy = d_out[s * D + j], o = out[s * D + j];
-  const float dot = block256_sum(dy * o, s_red);
+  const float dot = block_sum<4>(dy * o, s_red);
   const float nrm = tn[s], d = fmaxf(nrm, 1e-12f);
   const float dt = dy / d - (nrm >= 1e-12f ? dot * o / nrm : 0.f);
   const float gv = g[s * D + j];
@@ -421,17 +173,6 @@ __global__ __launch_bounds__(SW_THREADS) void k_hidden_sweep(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ both normalisations of V, reverse
-__device__ __forceinline__ float block1024_sum(float v, float* lds16) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) lds16[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) t += lds16[i];
-  __syncthreads();
-  return t;
-}
-
 // cloud blockIdx.x, in place on g = dv -> dV0:
 //   dV1 = dv/n2 - [n2raw >= eps] (dv . v) v / n2raw;  per column: dV0 = dV1/n1 - [n1raw >= eps] (dV1 . V1) V1 / n1raw with V1 = v n2
 // and dasum[k] = -sum_c dV0[c][k] W2[c][k]
@@ -445,7 +186,7 @@ __global__ __launch_bounds__(1024) void k_vlad_finalize_grad(float* __restrict__
   const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
   float t = 0.f;
   for (int c = q; c < F; c += 16) t = fmaf(g[c * K + k], v[c * K + k], t);
-  const float dot2 = block1024_sum(t, s_red);
+  const float dot2 = block_sum<16>(t, s_red);
   const float r2 = n2raw[blockIdx.x], n2 = fmaxf(r2, 1e-6f);
   const float back2 = r2 >= 1e-6f ? dot2 / r2 : 0.f;
   float dd = 0.f;
@@ -638,60 +379,9 @@ __global__ __launch_bounds__(256) void k_sum_chunks(const float* __restrict__ pa
 }  // namespace lcr
 
 using namespace lcr;
+using namespace lcr::nv;
 
 namespace {
-
-constexpr int STAT_FLOATS = 2 * K + 4 * D;   // mean, biased variance of bn1 [64], bn2 [256], context_gating.bn1 [256]
-
-struct Saved {
-  float *a, *sm, *v, *n1raw, *n2raw, *asum, *hh, *hp, *gh, *g, *out, *tn, *mu1, *r1, *r2, *rg;
-  int32_t *cmul, *rseg;
-  size_t bytes;
-};
-Saved saved_layout(void* p, int64_t n_rows, int S) {
-  Saved L;
-  Carver c(p, ~size_t(0));
-  const size_t rows = static_cast<size_t>(std::max<int64_t>(n_rows, 1)), s = static_cast<size_t>(S);
-  L.a = c.take<float>(rows * K);
-  L.sm = c.take<float>(rows * K);
-  L.cmul = c.take<int32_t>(rows);
-  L.rseg = c.take<int32_t>(rows);
-  L.v = c.take<float>(s * FK);
-  L.n1raw = c.take<float>(s * K);
-  L.n2raw = c.take<float>(s);
-  L.asum = c.take<float>(s * K);
-  L.hh = c.take<float>(s * D);
-  L.hp = c.take<float>(s * D);
-  L.gh = c.take<float>(s * D);
-  L.g = c.take<float>(s * D);
-  L.out = c.take<float>(s * D);
-  L.tn = c.take<float>(s);
-  L.mu1 = c.take<float>(K);
-  L.r1 = c.take<float>(K);
-  L.r2 = c.take<float>(D);
-  L.rg = c.take<float>(D);
-  L.bytes = c.off;
-  return L;
-}
-
-struct FwdWs {
-  float *xn, *w, *partial, *h, *g0;
-  double* part;
-  size_t bytes;
-};
-FwdWs fwd_layout(void* p, int64_t n_rows, int S) {
-  FwdWs L;
-  Carver c(p, ~size_t(0));
-  const size_t rows = static_cast<size_t>(std::max<int64_t>(n_rows, 1)), s = static_cast<size_t>(S);
-  L.xn = c.take<float>(rows * F);
-  L.w = c.take<float>(rows * K);
-  L.partial = c.take<float>(static_cast<size_t>(SPLIT) * s * D);
-  L.h = c.take<float>(s * D);
-  L.g0 = c.take<float>(s * D);
-  L.part = c.take<double>(static_cast<size_t>(STAT_G) * 2 * K);
-  L.bytes = c.off;
-  return L;
-}
 
 int chunk_count(int64_t n_rows) { return static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, (n_rows + 255) / 256))); }
 
@@ -722,117 +412,12 @@ BwdWs bwd_layout(void* p, int64_t n_rows, int S) {
   return L;
 }
 
-// the domain of both entries: 1 < S <= 128, every length >= 1 (and the total below 2^31)
-int seg_table(const char* who, const int64_t* seg_len_host, int S, Seg* seg, int64_t* n_rows) {
-  if (!seg_len_host || S < 2 || S > S_MAX) {
-    set_error("%s: S = %d outside 2 .. %d (batch statistics need more than one cloud)", who, S, S_MAX);
-    return LCR_EARG;
-  }
-  int64_t N = 0, Lmax = 0;
-  for (int s = 0; s < S; ++s) {
-    if (seg_len_host[s] < 1 || seg_len_host[s] > 2147483647LL - N) {
-      set_error("%s: segment %d has length %lld", who, s, static_cast<long long>(seg_len_host[s]));
-      return LCR_EARG;
-    }
-    seg->off[s] = N;
-    N += seg_len_host[s];
-    Lmax = std::max(Lmax, seg_len_host[s]);
-  }
-  seg->off[S] = N;
-  seg->S = S;
-  seg->Lmax = static_cast<int>(Lmax);
-  *n_rows = N;
-  return LCR_OK;
-}
-
-int row_blocks(int64_t N) { return static_cast<int>(std::min<int64_t>((N + 3) / 4, 256 * 16)); }
-int stat_blocks(int64_t N) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(STAT_G, (N + 63) / 64))); }
-
-template <int SMAX>
-void launch_hidden(const float* V, const float* H, int S, float* partial, hipStream_t st) {
-  for (int s0 = 0; s0 < S; s0 += SMAX) hipLaunchKernelGGL((k_hidden_fwd<SMAX>), dim3(SPLIT), dim3(D), 0, st, V, H, S, s0, partial);
-}
-
 }  // namespace
-
-extern "C" int lcr_netvlad_train_saved_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
-  *bytes = saved_layout(nullptr, n_rows, S).bytes;
-  return LCR_OK;
-}
-
-extern "C" int lcr_netvlad_train_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
-  *bytes = fwd_layout(nullptr, n_rows, S).bytes;
-  return LCR_OK;
-}
 
 extern "C" int lcr_netvlad_backward_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
   if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
   *bytes = bwd_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
-}
-
-extern "C" int lcr_netvlad_train_forward(const float* feats, const int64_t* seg_len_host, int S, const LcrNetvladWeights* wt, float* out,
-                                         float* batch_stats, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "lcr_netvlad_train_forward";
-  if (!feats || !wt || !out || !batch_stats || !saved || !ws) {
-    set_error("%s: bad argument", who);
-    return LCR_EARG;
-  }
-  Seg seg;
-  int64_t N = 0;
-  int rc = seg_table(who, seg_len_host, S, &seg, &N);
-  if (rc) return rc;
-  const Saved sv = saved_layout(saved, N, S);
-  const FwdWs L = fwd_layout(ws, N, S);
-  if (sv.bytes > saved_bytes || L.bytes > ws_bytes) {
-    set_error("%s: buffer too small (saved %zu < %zu or workspace %zu < %zu)", who, saved_bytes, sv.bytes, ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
-  hipStream_t st = ST(stream);
-  float* st_mean1 = batch_stats;
-  float* st_var1 = batch_stats + K;
-  float* st_mean2 = batch_stats + 2 * K;
-  float* st_var2 = st_mean2 + D;
-  float* st_meang = st_var2 + D;
-  float* st_varg = st_meang + D;
-  const int nblk = row_blocks(N);
-  hipLaunchKernelGGL(k_rows_of, dim3(div_up(N, 256)), dim3(256), 0, st, seg, N, sv.cmul, sv.rseg);
-  hipLaunchKernelGGL(k_row_unit, dim3(nblk), dim3(256), 0, st, feats, N, L.xn);
-  rc = lcr_gemm_f32(L.xn, wt->cluster_weights, sv.a, N, K, F, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
-  if (rc) return rc;
-  const int G = stat_blocks(N);
-  hipLaunchKernelGGL((k_col64_partial<0>), dim3(G), dim3(256), 0, st, sv.a, static_cast<const float*>(nullptr), sv.cmul, static_cast<const float*>(nullptr),
-                     static_cast<const float*>(nullptr), N, L.part);
-  hipLaunchKernelGGL(k_bn1_stats, dim3(1), dim3(K), 0, st, L.part, G, static_cast<double>(S) * seg.Lmax, st_mean1, st_var1, sv.mu1, sv.r1);
-  hipLaunchKernelGGL(k_bn_softmax_train, dim3(nblk), dim3(256), 0, st, sv.a, sv.cmul, sv.mu1, sv.r1, wt->bn1_w, wt->bn1_b, N, sv.sm, L.w);
-  for (int s0 = 0; s0 < S; s0 += 64) {
-    const int cnt = std::min(64, S - s0);
-    int kk[64];
-    int64_t ao[64], bo[64], co[64];
-    for (int i = 0; i < cnt; ++i) {
-      kk[i] = static_cast<int>(seg.off[s0 + i + 1] - seg.off[s0 + i]);
-      ao[i] = seg.off[s0 + i] * F;
-      bo[i] = seg.off[s0 + i] * K;
-      co[i] = static_cast<int64_t>(s0 + i) * FK;
-    }
-    rc = lcr_gemm_f32_batched_ta(L.xn, L.w, sv.v, F, K, cnt, kk, ao, bo, co, stream);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(k_colsum_seg, dim3(S), dim3(1024), 0, st, L.w, seg, sv.asum);
-  hipLaunchKernelGGL(k_vlad_finalize_train, dim3(S), dim3(1024), 0, st, sv.v, sv.asum, wt->cluster_weights2, sv.n1raw, sv.n2raw);
-  // H is streamed once up to 64 clouds, twice up to 128
-  if (S <= 8) launch_hidden<8>(sv.v, wt->hidden1_weights, S, L.partial, st);
-  else if (S <= 32) launch_hidden<32>(sv.v, wt->hidden1_weights, S, L.partial, st);
-  else launch_hidden<64>(sv.v, wt->hidden1_weights, S, L.partial, st);
-  hipLaunchKernelGGL(k_hidden_reduce, dim3(S), dim3(D), 0, st, L.partial, S, L.h);
-  hipLaunchKernelGGL(k_bn_batch, dim3(1), dim3(D), 0, st, L.h, S, wt->bn2_w, wt->bn2_b, st_mean2, st_var2, sv.r2, sv.hh, sv.hp);
-  rc = lcr_gemm_f32(sv.hp, wt->gating_weights, L.g0, S, D, D, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_bn_batch, dim3(1), dim3(D), 0, st, L.g0, S, wt->gbn_w, wt->gbn_b, st_meang, st_varg, sv.rg, sv.gh, static_cast<float*>(nullptr));
-  hipLaunchKernelGGL(k_gate_out, dim3(S), dim3(D), 0, st, sv.hp, sv.gh, wt->gbn_w, wt->gbn_b, sv.g, sv.tn, sv.out, out);
-  return check_launch(who);
 }
 
 extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, const int64_t* seg_len_host, int S, const LcrNetvladWeights* wt,
@@ -843,10 +428,12 @@ extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, cons
     set_error("%s: bad argument", who);
     return LCR_EARG;
   }
-  Seg seg;
-  int64_t N = 0;
-  int rc = seg_table(who, seg_len_host, S, &seg, &N);
+  std::vector<int64_t> off;
+  int Lmax = 0;
+  int rc = seg_offsets(who, seg_len_host, S, 2, S_MAX, &off, &Lmax);   // the training forward's domain
   if (rc) return rc;
+  const Seg seg = seg_window(off, 0, S, Lmax);
+  const int64_t N = off[S];
   const Saved sv = saved_layout(const_cast<void*>(saved), N, S);
   const BwdWs L = bwd_layout(ws, N, S);
   if (sv.bytes > saved_bytes || L.bytes > ws_bytes) {
@@ -887,11 +474,11 @@ extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, cons
   if (!(d_feats || g.cluster_weights || g.bn1_w || g.bn1_b)) return check_launch(who);
   // dw = x^ . dV0 per cloud, softmax and bn1 on the real rows
   const int nblk = row_blocks(N);
-  hipLaunchKernelGGL(k_row_unit, dim3(nblk), dim3(256), 0, st, feats, N, L.xn);
+  launch_row_l2norm(feats, N, L.xn, st);
   hipLaunchKernelGGL(k_assign_grad, dim3(div_up(seg.Lmax, 64), S), dim3(256), 0, st, L.xn, L.dv, seg, L.dw);
   hipLaunchKernelGGL(k_softmax_grad, dim3(nblk), dim3(256), 0, st, L.dw, sv.sm, L.dasum, sv.rseg, sv.cmul, N, L.w);
   const int G = stat_blocks(N);
-  hipLaunchKernelGGL((k_col64_partial<1>), dim3(G), dim3(256), 0, st, sv.a, L.dw, sv.cmul, sv.mu1, sv.r1, N, L.part);
+  hipLaunchKernelGGL(k_bn1_grad_partial, dim3(G), dim3(256), 0, st, sv.a, L.dw, sv.mu1, sv.r1, N, L.part);
   hipLaunchKernelGGL(k_bn1_grad_sums, dim3(1), dim3(K), 0, st, L.part, G, wt->bn1_w, g.bn1_w, g.bn1_b, L.sums);
   if (!(d_feats || g.cluster_weights)) return check_launch(who);
   hipLaunchKernelGGL(k_bn1_grad, dim3(div_up(N * K, 256)), dim3(256), 0, st, L.dw, sv.a, sv.cmul, sv.mu1, sv.r1, wt->bn1_w, L.sums,

@@ -758,12 +758,17 @@ class NetvladWeights(ctypes.Structure):
         "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "gating_weights", "gbn_w", "gbn_b", "gbn_mean", "gbn_var")]
 
 
-def netvlad_forward(feats, seg_len_host, weights_struct):
-    """feats [sum(seg_len),1024] stacked coarse features -> [S,256] unit-norm descriptors."""
+def _netvlad_seg(feats, seg_len_host):
     _lib.require_cuda(feats)
     seg = np.ascontiguousarray(seg_len_host, dtype=np.int64)
-    S = int(seg.shape[0])
-    assert int(seg.sum()) == feats.shape[0] and feats.shape[1] == 1024 and feats.is_contiguous()
+    assert seg.ndim == 1 and feats.dim() == 2 and feats.shape[1] == 1024 and feats.dtype == torch.float32 and feats.is_contiguous()
+    assert int(seg.sum()) == feats.shape[0], "seg_len does not add up to the rows of feats"
+    return seg, int(seg.shape[0])
+
+
+def netvlad_forward(feats, seg_len_host, weights_struct):
+    """feats [sum(seg_len),1024] stacked coarse features -> [S,256] unit-norm descriptors."""
+    seg, S = _netvlad_seg(feats, seg_len_host)
     ws = _lib.ws("lcr_netvlad_ws_bytes", feats.shape[0], S, device=feats.device)
     out = torch.empty((S, 256), dtype=torch.float32, device=feats.device)
     _lib.call.lcr_netvlad_forward(_lib.ptr(feats), ctypes.c_void_p(seg.ctypes.data), S, ctypes.byref(weights_struct),
@@ -779,14 +784,6 @@ NETVLAD_STAT_FLOATS = 2 * 64 + 4 * 256
 
 class NetvladGrads(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in NETVLAD_GRAD_NAMES]
-
-
-def _netvlad_seg(feats, seg_len_host):
-    _lib.require_cuda(feats)
-    seg = np.ascontiguousarray(seg_len_host, dtype=np.int64)
-    assert seg.ndim == 1 and feats.dim() == 2 and feats.shape[1] == 1024 and feats.dtype == torch.float32 and feats.is_contiguous()
-    assert int(seg.sum()) == feats.shape[0], "seg_len does not add up to the rows of feats"
-    return seg, int(seg.shape[0])
 
 
 def netvlad_train(feats, seg_len_host, weights_struct):

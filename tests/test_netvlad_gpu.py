@@ -196,8 +196,10 @@ def test_refusals_leave_the_output_alone():
     x = nv.netvlad_features(seg_lens, seed)
     empty = list(seg_lens)
     empty[1] = 0
+    huge = list(seg_lens)
+    huge[1] = 2 ** 31                                      # a length no int holds: refused as an argument, before the workspace is sized
     for what, kwargs, lens, rc in (("empty segment", {}, empty, EARG), ("S = 0", {"S": 0}, seg_lens, EARG),
-                                   ("workspace one byte short", {"ws_short": 1}, seg_lens, ESPACE)):
+                                   ("segment of 2^31 rows", {}, huge, EARG), ("workspace one byte short", {"ws_short": 1}, seg_lens, ESPACE)):
         run = Owned("seeded", x, lens, **kwargs)
         assert run.rc == rc, (what, run.rc)
         assert _lib.lib().lcr_last_error(), what

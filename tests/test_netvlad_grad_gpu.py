@@ -1,4 +1,4 @@
-"""GPU: the descriptor head in training mode and its reverse pass (csrc/netvlad_grad.hip behind lcrnet_amd.functional.netvlad_train /
+"""GPU: the descriptor head in training mode and its reverse pass (csrc/netvlad.hip, csrc/netvlad_grad.hip behind lcrnet_amd.functional.netvlad_train /
 netvlad_backward, NetVLADLoupe2.describe and LCRNet_GlobalDescrition.forward) against the fp64 restatement of
 tests/netvlad_grad_restatement.py, the reference's own numbers (tests/golden/netvlad_grad_golden.npz) and a CPU training run.
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The descriptor head's training forward and backward (csrc/netvlad_grad.hip) against its eval forward at the same shape, against torch autograd
+"""The descriptor head's training forward and backward (csrc/netvlad.hip, csrc/netvlad_grad.hip) against its eval forward at the same shape, against torch autograd
 through the dense padded reference formula on the same card, and the sweep over hidden1_weights against its traffic floor.
 
     python tools/netvlad_grad_bench.py [--clouds 8 78] [--rows 800] [--steps 7] [--warmup 2] [--out FILE]
