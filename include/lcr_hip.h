@@ -376,6 +376,18 @@ int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, const float* 
  * winners u8[M,C] is written by a first pass (the winning column, 255 = none) and may be discarded afterwards. */
 int lcr_maxpool_grad(const float* d_out, const float* x, const float* pooled, const void* idx, int idx_is_64, const int32_t* row_start,
                      const uint32_t* edges, int64_t M, int64_t Ns, int H, int C, uint8_t* winners, float* d_x, void* stream);
+/* Reverse of lcr_kpconv_aggregate to the POINTS (csrc/kpconv_grad.hip).  dA [M,15*C] as above, s_feats [Ns,C], idx the forward's list.  With
+ * e = s_n - q_m - kp_k, r = |e|, t(m,h,k) = sum_c dA[m][k*C + c] s_feats[idx[m,h]][c] and v(m,h) = sum over the k with 0 < r < sigma of
+ * t e / (sigma r):  d_q[m] = sum_h v(m,h) in column order, d_s[n] = -(sum of v over the edges of n, in inverted-list order).  Either output
+ * may be NULL; d_s needs row_start / edges (lcr_neighbor_transpose), d_q alone does not.  Whether an edge is live (w > 0) is decided by the
+ * forward's own arithmetic; a term with r == 0 is DEFINED as zero (the self edge of a cloud convolved with itself does not move
+ * with the point), a term with w == 0 and a padding entry contribute exactly 0.  q_pts and s_pts may be the same tensor: the caller adds
+ * d_q and d_s.  C in {32, 64, 128, 256}.  M == 0 or Ns == 0: a no-op apart from zero-filling the output that has rows.
+ * ws: lcr_kpconv_points_grad_ws_bytes(M, H) (v [M,H,3]; host-only query). */
+int lcr_kpconv_points_grad_ws_bytes(int64_t M, int H, size_t* bytes);
+int lcr_kpconv_points_grad(const float* dA, const float* s_feats, const float* q_pts, const float* s_pts, const void* idx, int idx_is_64,
+                           const int32_t* row_start, const uint32_t* edges, int64_t M, int64_t Ns, int H, int C,
+                           const float* kernel_points_host, float sigma, float* d_q, float* d_s, void* ws, size_t ws_bytes, void* stream);
 /* Reverse of lcr_groupnorm_apply, including the path through the statistics.  x: the raw input, stats: the forward's own table, y: the
  * forward's output (read for the LeakyReLU mask only; may be NULL when act == 0), dy [N,C].  With dz = dy * (y > 0 ? 1 : slope) (act) or dy,
  * x^ = (x - mean) * rstd and g = dz * gamma: dbeta[c] = sum_n dz, dgamma[c] = sum_n dz x^, dx = rstd * (g - mean_sg(g) - x^ mean_sg(g x^)), the
@@ -669,6 +681,23 @@ int lcr_topk_matching_ex(const float* logS, int64_t B, int M, int N, const uint8
 /* out[n] = [ x[idx[n,0]] (zeros for the shadow index), skip[n] ]  (nearest_upsample + cat, backbone4.py:355-367) */
 int lcr_upsample_concat(const float* x, int64_t Nx, int C1, const void* idx, int idx_is_64, int H, const float* skip, int C2,
                         int64_t N, float* out, void* stream);
+/* Reverse passes of lcr_vote_shift, lcr_neighbor_mean and lcr_upsample_concat (csrc/pose_tail.hip), in the manner of the encoder's: gathers
+ * over an inverted list (lcr_neighbor_transpose), every sum in one fixed order, no floating-point atomics, results repeat to the bit and
+ * a cloud's rows get the same bytes alone and inside a stack.  LCR_EARG with text and no launch outside the domain; no rows: a no-op.
+ *
+ * lcr_vote_shift_grad: d_off [N,3] from g = d_out [N,3] (d_xyz = g needs no kernel).  |o| <= R: d_off = g; else, with a = R / |o| and
+ * o^ = o / |o|, d_off = a (g - o^ (o^ . g)).  The branch is the forward's comparison (|o| > R) on the forward's own |o|.
+ * lcr_neighbor_mean_grad: d_pts[j] = sum of d_out[m] / c_m over the edges (m,h) of j, c_m = the number of valid entries of row m counted
+ * as the forward counts them; (row_start, edges) = the inverted form of idx [M,H] over `pad` points.  H <= 128, M * H < 2^30.
+ * lcr_upsample_concat_grad: d_out [N, C1 + C2] -> d_x [Nx, C1] with d_x[j] = sum of d_out[n][:C1] over the rows n with idx[n,0] == j in
+ * ascending n — (row_start, edges) = the inverted form of COLUMN 0 of idx as an [N,1] list over Nx rows; the shadow index sends its
+ * gradient nowhere and a row nobody lists gets zeros — and d_skip [N, C2] = d_out[:, C1:].  Either output may be NULL (d_skip alone
+ * needs no list).  N < 2^30. */
+int lcr_vote_shift_grad(const float* offsets, const float* d_out, int64_t N, float max_range, float* d_off, void* stream);
+int lcr_neighbor_mean_grad(const float* d_out, const void* idx, int idx_is_64, const int32_t* row_start, const uint32_t* edges, int64_t M,
+                           int H, int64_t pad, float* d_pts, void* stream);
+int lcr_upsample_concat_grad(const float* d_out, const int32_t* row_start, const uint32_t* edges, int64_t N, int64_t Nx, int C1, int C2,
+                             float* d_x, float* d_skip, void* stream);
 /* out[r] = src[idx[r]] (zeros where idx == pad): index_select on a zero-padded tensor */
 int lcr_gather_rows(const float* src, int64_t pad, int C, const int64_t* idx, int64_t R, float* out, void* stream);
 /* weighted_procrustes (modules/registration/procrustes.py:6-73), batched: problem p = correspondences [start[p],start[p+1]);

@@ -1,7 +1,7 @@
 // kpconv_grad.hip — reverse passes of the encoder's gather kernels (kpconv.hip): the inverted neighbour list, the KPConv aggregate's
-// gradient to the support features, the C_in = 1 KPConv's gradient to weights and bias, the max-pool's gradient.
+// gradient to the support features and to the points, the C_in = 1 KPConv's gradient to weights and bias, the max-pool's gradient.
 //
-// All of them are GATHERS over the inverted list: the support row n owns the flat positions e = m*H + h of the forward list with
+// All sums per support row are GATHERS over the inverted list: the support row n owns the flat positions e = m*H + h of the forward list with
 // idx[m,h] == n, in ascending order (lcr_neighbor_transpose: a stable radix sort of (support index, flat position)), and one wavefront
 // sums what its edges send, in list order.  No floating-point atomics: a row's sum has one order, results repeat to the bit, and a
 // cloud's rows get the same bytes alone and inside a stack (its edges keep their relative order).
@@ -219,6 +219,139 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const f
     } else {
       out[n * C + ch] = acc[0];
     }
+  }
+}
+
+// ---- gradient of the aggregate to the points ----------------------------------------------------------------------------------------
+// A[m][k*C + c] = sum_h w(m,h,k) f[idx[m,h]][c] with w = max(0, 1 - r / sigma), r = |e|, e = s_n - q_m - kp_k.  Where 0 < r < sigma,
+// dw/dq = e / (sigma r) = -dw/ds, so with t(m,h,k) = sum_c dA[m][k*C + c] f[n][c] the edge (m,h) sends v(m,h) = sum_k t e / (sigma r) to q_m
+// and -v to s_n.  r == 0 is defined as no term (the self edge of a cloud convolved with itself: e does not move with the point).
+//
+// "Store each contribution once, then sum per destination through an inverted index": k_kpconv_points_grad, one wavefront per query row,
+// keeps dA[m] in registers (15 V values per lane, V = C / 64 channels), walks the row's columns in order, and per real neighbour reads the
+// feature row once (V consecutive channels per lane: 16 bytes at C = 256).  Lane k < 15 evaluates kernel point k with the forward's
+// arithmetic; a ballot names the live kernel points and only those are contracted.  A lane folds its partial dots into three sums with
+// the (wave-uniform) coefficients e / (sigma r) before the wavefront is reduced: three reductions per edge, not one per kernel point.
+// v goes to the [M,H,3] workspace, d_q[m] is the sum of the row's v in column order.  k_kpconv_points_grad_s, one wavefront per support
+// row, then sums -v over the row's inverted list: lane l takes the list positions l, l + 64, ... in order and the lanes are folded once.
+// C = 32: the upper half of the wavefront holds zeros.
+__device__ __forceinline__ void kg_edge(float dx, float dy, float dz, float kx, float ky, float kz, float inv_sigma, float& ex, float& ey, float& ez,
+                                        float& r, float& w) {
+  ex = dx - kx, ey = dy - ky, ez = dz - kz;                // the operations of kg_influence, with e and r kept
+  r = __builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
+  w = fmaxf(fmaf(-r, inv_sigma, 1.f), 0.f);
+}
+
+template <int C, typename IdxT>
+__global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const float* __restrict__ dA, const float* __restrict__ s_feats,
+                                                                      const float* __restrict__ q_pts, const float* __restrict__ s_pts,
+                                                                      const IdxT* __restrict__ idx, int64_t M, int64_t Ns, int H, KGPoints kp,
+                                                                      float sigma, float* __restrict__ v_ws, float* __restrict__ d_q) {
+  constexpr int V = C >= 64 ? C / 64 : 1;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 15;
+  const bool has = C >= 64 || lane < 32;
+  const int ch = C >= 64 ? lane * V : (lane & 31);
+  const float inv_sigma = 1.f / sigma;
+  float kx = 0.f, ky = 0.f, kz = 0.f;
+#pragma unroll
+  for (int k = 0; k < KG_K; ++k)
+    if (col == k) {
+      kx = kp.p[k][0];
+      ky = kp.p[k][1];
+      kz = kp.p[k][2];
+    }
+  auto load_row = [&](const float* row, float (&dst)[V]) {
+    if (V == 4) {
+      const float4 t = *reinterpret_cast<const float4*>(row);
+      dst[0] = t.x, dst[1 % V] = t.y, dst[2 % V] = t.z, dst[3 % V] = t.w;
+    } else if (V == 2) {
+      const float2 t = *reinterpret_cast<const float2*>(row);
+      dst[0] = t.x, dst[1 % V] = t.y;
+    } else {
+      dst[0] = *row;
+    }
+  };
+  const KGBand band = kg_band(M, w, KG_WAVES);
+  for (int64_t m = band.begin; m < band.end; m += band.stride) {
+    float g[KG_K][V];
+#pragma unroll
+    for (int k = 0; k < KG_K; ++k) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) g[k][v] = 0.f;
+      if (has) load_row(dA + (m * KG_K + k) * C + ch, g[k]);
+    }
+    int jrow[2];                                           // the row's indices, column lane + 64 i; -1 = padding
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int h = lane + 64 * i;
+      const int64_t j = h < H ? static_cast<int64_t>(idx[m * H + h]) : -1;
+      jrow[i] = (j >= 0 && j < Ns) ? static_cast<int>(j) : -1;
+    }
+    const float qx = q_pts[3 * m], qy = q_pts[3 * m + 1], qz = q_pts[3 * m + 2];
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    for (int h = 0; h < H; ++h) {
+      const int j = h < 64 ? rdlane(jrow[0], h) : rdlane(jrow[1], h - 64);      // wave-uniform
+      float vx = 0.f, vy = 0.f, vz = 0.f;
+      if (j >= 0) {
+        const int64_t n = j;
+        float ex, ey, ez, r, wv;
+        kg_edge(s_pts[3 * n] - qx, s_pts[3 * n + 1] - qy, s_pts[3 * n + 2] - qz, kx, ky, kz, inv_sigma, ex, ey, ez, r, wv);
+        const uint64_t mask = wave_ballot(lane < KG_K && wv > 0.f && r > 0.f);
+        if (mask) {                                        // wave-uniform
+          const float cs = 1.f / (sigma * r);              // lanes outside the mask are never read
+          const float cx = ex * cs, cy = ey * cs, cz = ez * cs;
+          float f[V];
+#pragma unroll
+          for (int v = 0; v < V; ++v) f[v] = 0.f;
+          if (has) load_row(s_feats + n * C + ch, f);
+          float px = 0.f, py = 0.f, pz = 0.f;
+#pragma unroll
+          for (int k = 0; k < KG_K; ++k)
+            if ((mask >> k) & 1) {
+              float p = 0.f;
+#pragma unroll
+              for (int v = 0; v < V; ++v) p = fmaf(g[k][v], f[v], p);
+              px = fmaf(p, rdlane(cx, k), px);
+              py = fmaf(p, rdlane(cy, k), py);
+              pz = fmaf(p, rdlane(cz, k), pz);
+            }
+          vx = wave_sum(px);
+          vy = wave_sum(py);
+          vz = wave_sum(pz);
+        }
+      }
+      if (v_ws && lane < 3) v_ws[(m * H + h) * 3 + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
+      tx += vx;
+      ty += vy;
+      tz += vz;
+    }
+    if (d_q && lane < 3) d_q[3 * m + lane] = lane == 0 ? tx : (lane == 1 ? ty : tz);
+  }
+}
+
+__global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad_s(const float* __restrict__ v_ws, const int32_t* __restrict__ row_start,
+                                                                        const uint32_t* __restrict__ edges, int64_t M, int64_t Ns, int H,
+                                                                        float* __restrict__ d_s) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t MH = static_cast<uint32_t>(M * H);
+  const KGBand band = kg_band(Ns, w, KG_WAVES);
+  for (int64_t n = band.begin; n < band.end; n += band.stride) {
+    int b = row_start[n], e = row_start[n + 1];
+    b = max(0, min(b, static_cast<int>(MH)));
+    e = max(b, min(e, static_cast<int>(MH)));
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    for (int p = b + lane; p < e; p += 64) {
+      const uint32_t ed = edges[p];
+      if (ed >= MH) continue;                              // a list entry outside the forward list is skipped, never dereferenced
+      tx += v_ws[3 * static_cast<int64_t>(ed)];
+      ty += v_ws[3 * static_cast<int64_t>(ed) + 1];
+      tz += v_ws[3 * static_cast<int64_t>(ed) + 2];
+    }
+    tx = wave_sum(tx);
+    ty = wave_sum(ty);
+    tz = wave_sum(tz);
+    if (lane < 3) d_s[3 * n + lane] = -(lane == 0 ? tx : (lane == 1 ? ty : tz));
   }
 }
 
@@ -460,6 +593,59 @@ extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, co
   }
 #undef LCR_AGG_GRAD
   return check_launch("lcr_kpconv_aggregate_grad");
+}
+
+static size_t points_grad_bytes(int64_t M, int H) { return align_up(static_cast<size_t>(std::max<int64_t>(M * H, 1)) * 3 * sizeof(float)); }
+
+extern "C" int lcr_kpconv_points_grad_ws_bytes(int64_t M, int H, size_t* bytes) {
+  if (!bytes || M < 0 || H < 1 || H > KG_HMAX || M * H >= (int64_t(1) << 30)) {
+    set_error("lcr_kpconv_points_grad_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KG_HMAX);
+    return LCR_EARG;
+  }
+  *bytes = points_grad_bytes(M, H);
+  return LCR_OK;
+}
+
+extern "C" int lcr_kpconv_points_grad(const float* dA, const float* s_feats, const float* q_pts, const float* s_pts, const void* idx, int idx_is_64,
+                                      const int32_t* row_start, const uint32_t* edges, int64_t M, int64_t Ns, int H, int C,
+                                      const float* kernel_points_host, float sigma, float* d_q, float* d_s, void* ws, size_t ws_bytes, void* stream) {
+  if (!list_args_ok(M, Ns, H) || !kernel_points_host || !(sigma > 0.f) || (M > 0 && (!dA || !q_pts || !idx)) || (Ns > 0 && (!s_feats || !s_pts)) ||
+      (d_s && (!row_start || !edges || !ws))) {
+    set_error("lcr_kpconv_points_grad: bad argument (H in [1,%d], M * H < 2^30; d_s needs the inverted list and the workspace)", KG_HMAX);
+    return LCR_EARG;
+  }
+  if (C != 32 && C != 64 && C != 128 && C != 256) {
+    set_error("lcr_kpconv_points_grad: C must be 32, 64, 128 or 256 (got %d)", C);
+    return LCR_EARG;
+  }
+  if (d_s && ws_bytes < points_grad_bytes(M, H)) {
+    set_error("lcr_kpconv_points_grad: workspace of %zu bytes, %zu needed", ws_bytes, points_grad_bytes(M, H));
+    return LCR_EARG;
+  }
+  if ((!d_q && !d_s) || (M == 0 && (Ns == 0 || !d_s))) return LCR_OK;
+  const KGPoints kp = kg_load_kp(kernel_points_host);
+  hipStream_t st = ST(stream);
+  float* v_ws = d_s ? static_cast<float*>(ws) : nullptr;
+  if (M > 0) {
+    dim3 grid(kg_grid_xcd(M, KG_WAVES)), block(KG_WAVES * 64);
+#define LCR_PTS_GRAD(CC)                                                                                                                                   \
+  do {                                                                                                                                                     \
+    if (idx_is_64) hipLaunchKernelGGL((k_kpconv_points_grad<CC, int64_t>), grid, block, 0, st, dA, s_feats, q_pts, s_pts, static_cast<const int64_t*>(idx), \
+                                      M, Ns, H, kp, sigma, v_ws, d_q);                                                                                     \
+    else hipLaunchKernelGGL((k_kpconv_points_grad<CC, int32_t>), grid, block, 0, st, dA, s_feats, q_pts, s_pts, static_cast<const int32_t*>(idx), M, Ns, H, \
+                            kp, sigma, v_ws, d_q);                                                                                                         \
+  } while (0)
+    switch (C) {
+      case 32: LCR_PTS_GRAD(32); break;
+      case 64: LCR_PTS_GRAD(64); break;
+      case 128: LCR_PTS_GRAD(128); break;
+      default: LCR_PTS_GRAD(256); break;
+    }
+#undef LCR_PTS_GRAD
+  }
+  if (d_s && Ns > 0)                                       // M == 0: every list is empty and the rows are zeroed
+    hipLaunchKernelGGL(k_kpconv_points_grad_s, dim3(kg_grid_xcd(Ns, KG_WAVES)), dim3(KG_WAVES * 64), 0, st, v_ws, row_start, edges, M, Ns, H, d_s);
+  return check_launch("lcr_kpconv_points_grad");
 }
 
 static size_t cin1_grad_bytes(int64_t M, int Cout, bool feats) {

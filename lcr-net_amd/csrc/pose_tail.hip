@@ -30,6 +30,26 @@ __global__ __launch_bounds__(256) void k_vote_shift(const float* __restrict__ xy
   }
 }
 
+// reverse: with a = R / |o| and o^ = o / |o|, d_off = a (g - o^ (o^ . g)) where the forward clipped (the same |o| and the same comparison), else g
+__global__ __launch_bounds__(256) void k_vote_shift_grad(const float* __restrict__ off, const float* __restrict__ g, int64_t N, float max_range,
+                                                         float* __restrict__ d_off) {
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < N; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const float ox = off[3 * i], oy = off[3 * i + 1], oz = off[3 * i + 2];
+    float gx = g[3 * i], gy = g[3 * i + 1], gz = g[3 * i + 2];
+    const float d = sqrtf(ox * ox + oy * oy + oz * oz);
+    if (d > max_range) {
+      const float a = max_range / d, ux = ox / d, uy = oy / d, uz = oz / d;
+      const float dot = ux * gx + uy * gy + uz * gz;
+      gx = a * (gx - ux * dot);
+      gy = a * (gy - uy * dot);
+      gz = a * (gz - uz * dot);
+    }
+    d_off[3 * i + 0] = gx;
+    d_off[3 * i + 1] = gy;
+    d_off[3 * i + 2] = gz;
+  }
+}
+
 // ---- greedy NMS: exact parallel replay of the sequential rule ------------------------------------------------------------
 // keep[i] <=> no kept j < i with ||p_i - p_j + 1e-6|| <= radius (nn.PairwiseDistance semantics, vote.py:48-54).  Each round,
 // an undecided node is dropped if a kept lower node is in range, kept if no lower node in range is still undecided.  Every
@@ -125,6 +145,40 @@ __global__ __launch_bounds__(256) void k_neighbor_mean(const float* __restrict__
     out[3 * m] = sx / d;
     out[3 * m + 1] = sy / d;
     out[3 * m + 2] = sz / d;
+  }
+}
+
+// reverse: d_pts[j] = sum of d_out[m] / c_m over the edges (m,h) of j.  One wavefront per point; lane l takes the positions l, l + 64, ... of
+// the point's inverted list in order, recounts c_m over row m exactly as the forward does, and the lanes are folded once.
+template <typename IdxT>
+__global__ __launch_bounds__(256) void k_neighbor_mean_grad(const float* __restrict__ d_out, const IdxT* __restrict__ idx, const int32_t* __restrict__ row_start,
+                                                            const uint32_t* __restrict__ edges, int64_t M, int H, int64_t pad, float* __restrict__ d_pts) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t MH = static_cast<uint32_t>(M * H);          // host-checked: M * H < 2^30
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6), nwaves = static_cast<int64_t>(gridDim.x) * 4;
+  for (int64_t j = wave; j < pad; j += nwaves) {
+    int b = row_start[j], e = row_start[j + 1];
+    b = max(0, min(b, static_cast<int>(MH)));
+    e = max(b, min(e, static_cast<int>(MH)));
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    for (int p = b + lane; p < e; p += 64) {
+      const uint32_t ed = edges[p];
+      if (ed >= MH) continue;                                // a list entry outside the forward list is skipped, never dereferenced
+      const int64_t m = ed / static_cast<uint32_t>(H);
+      int c = 0;
+      for (int h = 0; h < H; ++h) {
+        const int64_t q = static_cast<int64_t>(idx[m * H + h]);
+        c += (q >= 0 && q < pad) ? 1 : 0;
+      }
+      const float d = static_cast<float>(c);
+      tx += d_out[3 * m] / d;
+      ty += d_out[3 * m + 1] / d;
+      tz += d_out[3 * m + 2] / d;
+    }
+    tx = wave_sum(tx);
+    ty = wave_sum(ty);
+    tz = wave_sum(tz);
+    if (lane < 3) d_pts[3 * j + lane] = lane == 0 ? tx : (lane == 1 ? ty : tz);
   }
 }
 
@@ -300,9 +354,98 @@ __global__ __launch_bounds__(256) void k_gather_rows_vec(const float* __restrict
   }
 }
 
+// reverse of the decoder's gather: d_x[j][:] = sum of d_out[n][:C1] over the rows n that list j in column 0, in ascending n (the inverted
+// form of column 0: an [N,1] list, so an edge IS its row n).  One wavefront per x row, lanes over the channels (T = float4 when the widths
+// and bases allow 16-byte accesses, else float); a row nobody lists gets zeros.  q1 / q: C1 / (C1 + C2) in units of T.
+__device__ __forceinline__ void acc_zero(float& a) { a = 0.f; }
+__device__ __forceinline__ void acc_zero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void acc_add(float& a, float b) { a += b; }
+__device__ __forceinline__ void acc_add(float4& a, const float4& b) {
+  a.x += b.x;
+  a.y += b.y;
+  a.z += b.z;
+  a.w += b.w;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_upsample_concat_grad_x(const T* __restrict__ d_out, const int32_t* __restrict__ row_start,
+                                                                const uint32_t* __restrict__ edges, int64_t N, int64_t Nx, int q1, int q, T* __restrict__ d_x) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6), nwaves = static_cast<int64_t>(gridDim.x) * 4;
+  const int n_max = static_cast<int>(N);                     // host-checked: N < 2^30
+  for (int64_t j = wave; j < Nx; j += nwaves) {
+    int b = row_start[j], e = row_start[j + 1];
+    b = max(0, min(b, n_max));
+    e = max(b, min(e, n_max));
+    for (int c = lane; c < q1; c += 64) {
+      T t;
+      acc_zero(t);
+      for (int p = b; p < e; ++p) {
+        const uint32_t n = edges[p];                         // wave-uniform
+        if (n >= static_cast<uint32_t>(n_max)) continue;     // a list entry outside the forward list is skipped, never dereferenced
+        acc_add(t, d_out[static_cast<int64_t>(n) * q + c]);
+      }
+      d_x[j * q1 + c] = t;
+    }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_upsample_concat_grad_skip(const T* __restrict__ d_out, int64_t N, int q1, int q, T* __restrict__ d_skip) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6), nwaves = static_cast<int64_t>(gridDim.x) * 4;
+  for (int64_t n = wave; n < N; n += nwaves)
+    for (int c = lane; c < q - q1; c += 64) d_skip[n * (q - q1) + c] = d_out[n * q + q1 + c];
+}
+
 }  // namespace lcr
 
 using namespace lcr;
+
+extern "C" int lcr_vote_shift_grad(const float* offsets, const float* d_out, int64_t N, float max_range, float* d_off, void* stream) {
+  if (N == 0) return LCR_OK;
+  if (!offsets || !d_out || !d_off || N < 0) {
+    set_error("lcr_vote_shift_grad: bad argument (null pointer or N < 0)");
+    return LCR_EARG;
+  }
+  hipLaunchKernelGGL(k_vote_shift_grad, dim3(blocks_for(N)), dim3(256), 0, ST(stream), offsets, d_out, N, max_range, d_off);
+  return check_launch("lcr_vote_shift_grad");
+}
+
+extern "C" int lcr_neighbor_mean_grad(const float* d_out, const void* idx, int idx_is_64, const int32_t* row_start, const uint32_t* edges, int64_t M,
+                                      int H, int64_t pad, float* d_pts, void* stream) {
+  if (M < 0 || pad < 0 || pad >= (int64_t(1) << 31) - 1 || H < 1 || H > 128 || M * H >= (int64_t(1) << 30) || (pad > 0 && (!row_start || !edges || !d_pts)) ||
+      (M > 0 && (!d_out || !idx))) {
+    set_error("lcr_neighbor_mean_grad: bad argument (H in [1,128], M * H < 2^30, pad < 2^31 - 1, no null pointer)");
+    return LCR_EARG;
+  }
+  if (pad == 0) return LCR_OK;                               // no points: nothing to write
+  const int nb = blocks_for(pad, 4, 8192);                   // one wavefront per point
+  if (idx_is_64) hipLaunchKernelGGL((k_neighbor_mean_grad<int64_t>), dim3(nb), dim3(256), 0, ST(stream), d_out, static_cast<const int64_t*>(idx), row_start, edges, M, H, pad, d_pts);
+  else hipLaunchKernelGGL((k_neighbor_mean_grad<int32_t>), dim3(nb), dim3(256), 0, ST(stream), d_out, static_cast<const int32_t*>(idx), row_start, edges, M, H, pad, d_pts);
+  return check_launch("lcr_neighbor_mean_grad");
+}
+
+extern "C" int lcr_upsample_concat_grad(const float* d_out, const int32_t* row_start, const uint32_t* edges, int64_t N, int64_t Nx, int C1, int C2,
+                                        float* d_x, float* d_skip, void* stream) {
+  if (N < 0 || N >= (int64_t(1) << 30) || Nx < 0 || Nx >= (int64_t(1) << 31) - 1 || C1 < 1 || C2 < 1 || (N > 0 && !d_out) ||
+      (d_x && Nx > 0 && (!row_start || !edges))) {
+    set_error("lcr_upsample_concat_grad: bad argument (N < 2^30, C1, C2 >= 1; d_x needs the inverted list of column 0)");
+    return LCR_EARG;
+  }
+  hipStream_t st = ST(stream);
+  const bool vec = C1 % 4 == 0 && C2 % 4 == 0 &&
+                   ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_skip)) & 15) == 0;
+  if (d_x && Nx > 0) {                                       // N == 0: every list is empty and the rows are zeroed
+    const int nb = blocks_for(Nx, 4, 8192);
+    if (vec) hipLaunchKernelGGL((k_upsample_concat_grad_x<float4>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const float4*>(d_out), row_start, edges, N, Nx, C1 / 4, (C1 + C2) / 4, reinterpret_cast<float4*>(d_x));
+    else hipLaunchKernelGGL((k_upsample_concat_grad_x<float>), dim3(nb), dim3(256), 0, st, d_out, row_start, edges, N, Nx, C1, C1 + C2, d_x);
+  }
+  if (d_skip && N > 0) {
+    const int nb = blocks_for(N, 4, 8192);
+    if (vec) hipLaunchKernelGGL((k_upsample_concat_grad_skip<float4>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const float4*>(d_out), N, C1 / 4, (C1 + C2) / 4, reinterpret_cast<float4*>(d_skip));
+    else hipLaunchKernelGGL((k_upsample_concat_grad_skip<float>), dim3(nb), dim3(256), 0, st, d_out, N, C1, C1 + C2, d_skip);
+  }
+  return check_launch("lcr_upsample_concat_grad");
+}
 
 extern "C" int lcr_vote_shift(const float* xyz, const float* offsets, int64_t N, float max_range, float* out, void* stream) {
   if (N == 0) return LCR_OK;                               // no points: nothing to read or write, null pointers allowed

@@ -560,6 +560,26 @@ def kpconv_aggregate_grad(dA, q_points, s_points, inv, H, kernel_points_host, si
     return out
 
 
+def kpconv_points_grad(dA, s_feats, q_points, s_points, idx, kernel_points_host, sigma, inv=None, want_q=True, want_s=True):
+    """(d_q_points [M, 3] or None, d_s_points [Ns, 3] or None) of lcr_kpconv_points_grad from dA [M, 15 C]: the gradient of the KPConv aggregate
+    through its influence weights.  A zero-length edge contributes nothing.  want_s needs the inverted list of idx."""
+    _lib.require_cuda(dA, s_feats, q_points, s_points, idx)
+    M, H = idx.shape
+    Ns, C = s_feats.shape
+    assert dA.dtype == torch.float32 and dA.is_contiguous() and tuple(dA.shape) == (M, 15 * C)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (s_feats, q_points, s_points)) and idx.is_contiguous()
+    assert tuple(q_points.shape) == (M, 3) and tuple(s_points.shape) == (Ns, 3)
+    row_start, edges = _inv_args(inv, M, H, Ns) if want_s else (None, None)
+    dq = torch.empty((M, 3), dtype=torch.float32, device=dA.device) if want_q else None
+    ds = torch.empty((Ns, 3), dtype=torch.float32, device=dA.device) if want_s else None
+    ws = _lib.ws("lcr_kpconv_points_grad_ws_bytes", M, H, device=dA.device) if want_s else None
+    kp = _kp_host(kernel_points_host)
+    _lib.call.lcr_kpconv_points_grad(_lib.ptr(dA), _lib.ptr(s_feats), _lib.ptr(q_points), _lib.ptr(s_points), _lib.ptr(idx), _idx_args(idx),
+                                     _lib.ptr(row_start), _lib.ptr(edges), M, Ns, H, C, ctypes.c_void_p(kp.ctypes.data), float(sigma), _lib.ptr(dq),
+                                     _lib.ptr(ds), _lib.ptr(ws), ws.numel() if want_s else 0, _lib.stream_ptr(dA.device))
+    return dq, ds
+
+
 def kpconv_cin1_grad(d_out, s_feats, q_points, s_points, idx, kernel_points_host, sigma, weights, inv=None, want_feats=False, nn=None):
     """(dW [15, 1, Cout], dbias [Cout], d_s_feats [Ns] or None) of lcr_kpconv_cin1_grad.  want_feats needs the inverted list."""
     _lib.require_cuda(d_out, s_feats, q_points, s_points, idx, weights)
@@ -711,17 +731,22 @@ class _KPConvFn(torch.autograd.Function):
     """KPConv.forward_raw with a backward.  Forward: the module's own no-grad path (masked aggregate, split-bf16 contraction; C_in = 1: the fused
     kernel).  Backward, with dOut' = dOut / nn: dbias = the column sum of dOut, A recomputed by the unmasked kpconv_aggregate (15 x the
     activation: never kept), dW = dOut'^T A on _weight_grad, dA = dOut' W^T on the GEMM, d_s_feats = lcr_kpconv_aggregate_grad over the inverted
-    list.  The neighbour count is an integer and carries no gradient (as in the reference's autograd); points and kernel points get none."""
+    list.  The neighbour count is an integer and carries no gradient (as in the reference's autograd); kernel points get none.  q_points /
+    s_points, when they require grad (the vote encoder's node centres), get lcr_kpconv_points_grad from the same dA — one tensor passed as both
+    receives the sum of the two from autograd.  A zero-length edge sends nothing; C_in = 1 has no such form and refuses."""
 
     @staticmethod
     def forward(ctx, s_feats, weights, bias, module, q_points, s_points, idx, s_pos, seg_len, groups, order):
-        s_feats = s_feats.detach().contiguous()
+        need = ctx.needs_input_grad
+        if module.in_channels == 1 and (need[4] or need[5]):
+            raise NotImplementedError("KPConv with in_channels == 1 has no gradient to the points (no model of this package needs one)")
+        s_feats, q_points, s_points = s_feats.detach().contiguous(), q_points.detach().contiguous(), s_points.detach().contiguous()
         if module.in_channels != 1 and s_pos is None:
             s_pos = row_positive(s_feats)
         out, stats, nn = module.run_raw(s_feats, q_points, s_points, idx, s_pos, seg_len, groups, order, want_nn=True)
         ctx.save_for_backward(s_feats, q_points, s_points, idx, s_pos, nn)
         ctx.module, ctx.order = module, order
-        ctx.inv = inverted(idx, s_feats.shape[0]) if (ctx.needs_input_grad[0] and module.in_channels != 1) else None
+        ctx.inv = inverted(idx, s_feats.shape[0]) if ((need[0] or need[5]) and module.in_channels != 1) else None
         if stats is None:
             stats = torch.empty(0, dtype=torch.float64, device=out.device)
         ctx.mark_non_differentiable(stats)
@@ -746,10 +771,14 @@ class _KPConvFn(torch.autograd.Function):
             A, _ = kpconv_aggregate(s_feats, s_pos, q_points, s_points, idx, kp, mod.sigma, order=ctx.order)
             dW = _weight_grad(g, A).t().reshape(mod.kernel_size, mod.in_channels, mod.out_channels)
             del A
-        if need[0]:
+        dq = ds = None
+        if need[0] or need[4] or need[5]:
             dA = gemm(g, mod.weights_t())[0]
-            df = kpconv_aggregate_grad(dA, q_points, s_points, ctx.inv, idx.shape[1], kp, mod.sigma)
-        return (df, dW, db) + (None,) * 8
+            if need[0]:
+                df = kpconv_aggregate_grad(dA, q_points, s_points, ctx.inv, idx.shape[1], kp, mod.sigma)
+            if need[4] or need[5]:
+                dq, ds = kpconv_points_grad(dA, s_feats, q_points, s_points, idx, kp, mod.sigma, ctx.inv, want_q=need[4], want_s=need[5])
+        return (df, dW, db, None, dq, ds) + (None,) * 5
 
 
 class NetvladWeights(ctypes.Structure):
@@ -1106,10 +1135,44 @@ _L = _lib.lib     # the raw view under its old name here, for callers outside th
 
 
 def vote_shift(xyz, offsets, max_range):
+    """xyz + offsets clipped to max_range; differentiable in both (_VoteShiftFn) when one requires grad and grad mode is on."""
+    _lib.require_cuda(xyz, offsets)
+    if _wants_grad(xyz, offsets):
+        return _VoteShiftFn.apply(xyz, offsets, float(max_range))
+    return _vote_shift(xyz, offsets, max_range)
+
+
+def _vote_shift(xyz, offsets, max_range):
     out = torch.empty_like(xyz)
     _lib.call.lcr_vote_shift(_lib.ptr(xyz.contiguous()), _lib.ptr(offsets.contiguous()), xyz.shape[0], float(max_range), _lib.ptr(out),
                              _lib.stream_ptr(xyz.device))
     return out
+
+
+def vote_shift_grad(offsets, d_out, max_range):
+    """d_offsets [N, 3] of lcr_vote_shift_grad (d_xyz is d_out itself)."""
+    _lib.require_cuda(offsets, d_out)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3 for t in (offsets, d_out)) and offsets.shape == d_out.shape
+    d_off = torch.empty_like(offsets)
+    _lib.call.lcr_vote_shift_grad(_lib.ptr(offsets), _lib.ptr(d_out), offsets.shape[0], float(max_range), _lib.ptr(d_off), _lib.stream_ptr(offsets.device))
+    return d_off
+
+
+class _VoteShiftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, offsets, max_range):
+        offsets = offsets.detach().contiguous().float()
+        ctx.save_for_backward(offsets)
+        ctx.max_range = max_range
+        return _vote_shift(xyz.detach().contiguous(), offsets, max_range)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        offsets, = ctx.saved_tensors
+        d_out = d_out.contiguous().float()
+        d_off = vote_shift_grad(offsets, d_out, ctx.max_range) if ctx.needs_input_grad[1] else None
+        return (d_out if ctx.needs_input_grad[0] else None), d_off, None
 
 
 def greedy_nms(points, lengths, radius):
@@ -1124,10 +1187,51 @@ def greedy_nms(points, lengths, radius):
 
 
 def neighbor_mean(points, idx, pad):
+    """Mean of points[idx[m, h]] over the valid (0 <= idx < pad) entries of every row; differentiable in points (_NeighborMeanFn) when they
+    require grad and grad mode is on."""
+    _lib.require_cuda(points, idx)
+    if _wants_grad(points):
+        return _NeighborMeanFn.apply(points, idx, int(pad))
+    return _neighbor_mean(points, idx, pad)
+
+
+def _neighbor_mean(points, idx, pad):
     out = torch.empty((idx.shape[0], 3), dtype=torch.float32, device=points.device)
     _lib.call.lcr_neighbor_mean(_lib.ptr(points.contiguous()), _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[0], idx.shape[1], int(pad),
                                 _lib.ptr(out), _lib.stream_ptr(points.device))
     return out
+
+
+def neighbor_mean_grad(d_out, idx, pad, inv):
+    """d_points [pad, 3] of lcr_neighbor_mean_grad; inv: the InvertedList (or (row_start, edges)) of idx [M, H] over `pad` points."""
+    _lib.require_cuda(d_out, idx)
+    M, H = idx.shape
+    assert d_out.dtype == torch.float32 and d_out.is_contiguous() and tuple(d_out.shape) == (M, 3) and idx.is_contiguous()
+    row_start, edges = _inv_args(inv, M, H, int(pad))
+    d_pts = torch.empty((int(pad), 3), dtype=torch.float32, device=d_out.device)
+    _lib.call.lcr_neighbor_mean_grad(_lib.ptr(d_out), _lib.ptr(idx), _idx_args(idx), _lib.ptr(row_start), _lib.ptr(edges), M, H, int(pad), _lib.ptr(d_pts),
+                                     _lib.stream_ptr(d_out.device))
+    return d_pts
+
+
+class _NeighborMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, idx, pad):
+        idx = idx.contiguous()
+        assert pad <= points.shape[0]
+        ctx.save_for_backward(idx)
+        ctx.pad, ctx.rows = pad, points.shape[0]
+        ctx.inv = inverted(idx, pad)
+        return _neighbor_mean(points.detach(), idx, pad)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        idx, = ctx.saved_tensors
+        d = neighbor_mean_grad(d_out.contiguous().float(), idx, ctx.pad, ctx.inv)
+        if ctx.rows != ctx.pad:                               # rows behind `pad` are never read
+            d = torch.cat([d, d.new_zeros((ctx.rows - ctx.pad, 3))])
+        return d, None, None
 
 
 def point_to_node_partition(points, nodes, point_limit):
@@ -1360,6 +1464,52 @@ def top1_matching(log_scores, row_masks=None, col_masks=None, mutual=False, topk
 
 
 def upsample_concat(x, idx, skip):
+    """[x[idx[:, 0]] (zeros for the shadow index), skip]; differentiable in x and skip (_UpsampleConcatFn) when one requires grad and grad
+    mode is on."""
+    _lib.require_cuda(x, idx, skip)
+    if _wants_grad(x, skip):
+        return _UpsampleConcatFn.apply(x, idx, skip)
+    return _upsample_concat(x, idx, skip)
+
+
+def upsample_concat_grad(d_out, idx, Nx, C1, inv=None, want_x=True, want_skip=True):
+    """(d_x [Nx, C1] or None, d_skip [N, C - C1] or None) of lcr_upsample_concat_grad from d_out [N, C]; inv: the InvertedList (or
+    (row_start, edges)) of COLUMN 0 of idx as an [N, 1] list over Nx rows (built here when None)."""
+    _lib.require_cuda(d_out, idx)
+    N, C = d_out.shape
+    C1, C2 = int(C1), C - int(C1)
+    assert d_out.dtype == torch.float32 and d_out.is_contiguous() and idx.shape[0] == N and 0 < C1 < C
+    row_start = edges = None
+    if want_x:
+        if inv is None:
+            inv = inverted(idx[:, :1].contiguous(), Nx)
+        row_start, edges = _inv_args(inv, N, 1, int(Nx))
+    dx = torch.empty((int(Nx), C1), dtype=torch.float32, device=d_out.device) if want_x else None
+    ds = torch.empty((N, C2), dtype=torch.float32, device=d_out.device) if want_skip else None
+    _lib.call.lcr_upsample_concat_grad(_lib.ptr(d_out), _lib.ptr(row_start), _lib.ptr(edges), N, int(Nx), C1, C2, _lib.ptr(dx), _lib.ptr(ds),
+                                       _lib.stream_ptr(d_out.device))
+    return dx, ds
+
+
+class _UpsampleConcatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, idx, skip):
+        ctx.Nx, ctx.C1 = x.shape[0], x.shape[1]
+        col0 = idx[:, :1].contiguous()
+        ctx.save_for_backward(col0)
+        ctx.inv = inverted(col0, x.shape[0]) if ctx.needs_input_grad[0] else None
+        return _upsample_concat(x.detach(), idx, skip.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        col0, = ctx.saved_tensors
+        dx, ds = upsample_concat_grad(d_out.contiguous().float(), col0, ctx.Nx, ctx.C1, ctx.inv, want_x=ctx.needs_input_grad[0],
+                                      want_skip=ctx.needs_input_grad[2])
+        return dx, None, ds
+
+
+def _upsample_concat(x, idx, skip):
     out = torch.empty((skip.shape[0], x.shape[1] + skip.shape[1]), dtype=torch.float32, device=x.device)
     _lib.call.lcr_upsample_concat(_lib.ptr(x.contiguous()), x.shape[0], x.shape[1], _lib.ptr(idx.contiguous()), _idx_args(idx), idx.shape[1],
                                   _lib.ptr(skip.contiguous()), skip.shape[1], skip.shape[0], _lib.ptr(out), _lib.stream_ptr(x.device))

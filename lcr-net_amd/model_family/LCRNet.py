@@ -31,11 +31,16 @@ class Vote_layer(nn.Module):
         self.ctr_reg = nn.Linear(c, 3)
         self.max_translate_range = max_translate_range
 
+    @F.eval_without_graph
     def forward(self, xyz, features):
+        """Training mode with a gradient wanted: a graph to the features and to every parameter (linear, add_layernorm and vote_shift carry HIP
+        backwards).  The ReLU is then applied out of place: relu_ writes through a raw pointer, behind autograd's back, and the LayerNorm's
+        backward would silently see the rectified values."""
         x = features
         for i in (0, 3):
             lin, ln = self.mlp_modules[i], self.mlp_modules[i + 1]
-            x = F.relu_(F.add_layernorm(F.linear(x, lin.weight, lin.bias), None, ln.weight, ln.bias, ln.eps))
+            x = F.add_layernorm(F.linear(x, lin.weight, lin.bias), None, ln.weight, ln.bias, ln.eps)
+            x = torch.relu(x) if F._wants_grad(x) else F.relu_(x)
         off = F.linear(x, self.ctr_reg.weight, self.ctr_reg.bias)
         return F.vote_shift(xyz, off, self.max_translate_range)
 
@@ -56,27 +61,36 @@ class Vote_Encoder(nn.Module):
         self.init_radius = init_radius
         self.neighbor_limits = list(neighbor_limits)
 
+    @F.eval_without_graph
     def forward(self, feats, data_dict, neighbor_limit=None, pairs=1):
         """pairs > 1: the stack holds `pairs` registration pairs; GroupNorm statistics are taken per pair (the reference's
-        statistics over its one-pair stack), everything else is per cloud anyway."""
+        statistics over its one-pair stack), everything else is per cloud anyway.
+
+        Training mode with a gradient wanted: the same launches with a graph.  The node centres carry a gradient as in the reference
+        (backbone4.py:121-220) — through the mean of the votes, the clipped offsets and the vote MLP — and receive one from the three blocks
+        through KPConv's influence weights (q_points of encoder6_1, q_points and s_points of encoder6_2/3).  The NMS mask, the three radius
+        searches and the node count are index computations without a gradient, as in the reference."""
         limits = list(neighbor_limit) if neighbor_limit is not None else self.neighbor_limits
         lens_c = data_dict["lengths"][-1]
         points_c = data_dict["points"][-1].contiguous()
         shifted = self.vote(points_c, feats)
-        keep, length = F.greedy_nms(shifted, lens_c, self.NMS_radius)
-        nms_pts = shifted[keep.bool()].contiguous()                       # compaction (host sync: output size is data dependent)
+        votes = shifted.detach()
+        keep, length = F.greedy_nms(votes, lens_c, self.NMS_radius)
+        nms_pts = votes[keep.bool()].contiguous()                         # compaction (host sync: output size is data dependent)
         pad = shifted.shape[0]
-        knn = radius_search(nms_pts, shifted, length, lens_c, 2.4, limits[-1], check=False)                    # backbone4.py:149-156 (literal 2.4)
+        knn = radius_search(nms_pts, votes, length, lens_c, 2.4, limits[-1], check=False)                      # backbone4.py:149-156 (literal 2.4)
         centers = F.neighbor_mean(shifted, knn, pad)
-        sub = radius_search(centers, points_c, length, lens_c, self.init_radius * 8, limits[-2], check=False)
-        nb = radius_search(centers, centers, length, length, self.init_radius * 16, limits[-1], check=False)
+        nodes = centers.detach()
+        sub = radius_search(nodes, points_c, length, lens_c, self.init_radius * 8, limits[-2], check=False)
+        nb = radius_search(nodes, nodes, length, length, self.init_radius * 16, limits[-1], check=False)
         if pairs > 1:                                                  # min_rows unknown on the host here (node counts live on the device):
             q_ctx, s_ctx = StageContext(length.view(pairs, 2).sum(1)), StageContext(lens_c.view(pairs, 2).sum(1))   # plain GroupNorm pass
         else:
             q_ctx = s_ctx = StageContext(None)
-        f = self.encoder6_1(feats, centers, points_c, sub, q_ctx, s_ctx)
-        f = self.encoder6_2(f, centers, centers, nb, q_ctx, q_ctx)
-        f = self.encoder6_3(f, centers, centers, nb, q_ctx, q_ctx)
+        with F.inverted_lists():                                       # encoder6_2 / 6_3 share one inverted form of `nb` in the backward
+            f = self.encoder6_1(feats, centers, points_c, sub, q_ctx, s_ctx)
+            f = self.encoder6_2(f, centers, centers, nb, q_ctx, q_ctx)
+            f = self.encoder6_3(f, centers, centers, nb, q_ctx, q_ctx)
         return {"shifted_points_c": shifted, "nms_mask": keep, "length": length, "points_c": centers, "feats_c": f}
 
 
@@ -89,7 +103,10 @@ class KPDecoder(nn.Module):
         self.decoder2 = UnaryBlock(init_dim * 12, init_dim * 4, group_norm)
         self.decoder1 = LastUnaryBlock(init_dim * 6, init_dim * 2)
 
+    @F.eval_without_graph
     def forward(self, feats, data_dict, pairs=1):
+        """Training mode with a gradient wanted: a graph to the four feature inputs and to every parameter (upsample_concat gathers its
+        gradient over the inverted list of column 0; the unary blocks carry theirs)."""
         f1, f2, f3, f4 = feats
         U = data_dict["upsampling"]
         L = data_dict["lengths"]

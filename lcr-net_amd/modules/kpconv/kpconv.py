@@ -80,9 +80,10 @@ class KPConv(nn.Module):
     @F.eval_without_graph
     def forward_raw(self, s_feats, q_points, s_points, neighbor_indices, s_pos=None, seg_len=None, groups=0, order=None):
         """Returns (q_feats (M,Cout), stats) — stats = GroupNorm sums of the output when groups > 0.  With a graph (functional._KPConvFn) when
-        the module is in training mode, grad mode is on and the features, the weights or the bias require grad: same launches, except that
-        LCR_KPCONV_FUSED is not taken."""
-        if F._wants_grad(s_feats, self.weights, self.bias):
+        the module is in training mode, grad mode is on and the features, the weights, the bias or one of the two point tensors require grad:
+        same launches, except that LCR_KPCONV_FUSED is not taken.  Points that require grad (the vote encoder's node centres) receive the
+        gradient through the influence weights; in_channels == 1 refuses them (NotImplementedError)."""
+        if F._wants_grad(s_feats, self.weights, self.bias, q_points, s_points):
             out, stats = F._KPConvFn.apply(s_feats, self.weights, self.bias, self, q_points, s_points, neighbor_indices, s_pos, seg_len, groups, order)
             return out, (stats if groups else None)
         return self.run_raw(s_feats, q_points, s_points, neighbor_indices, s_pos, seg_len, groups, order)
