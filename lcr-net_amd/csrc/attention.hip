@@ -18,14 +18,9 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "attention.h"
 
 namespace lcr {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int AT_D = 32;    // head dim (d_model 128 / 4 heads)
-constexpr int AT_LD = 33;   // LDS row stride: conflict-free ds_read_b32 for both "row = lane" operand patterns
 
 // x [N, H*32] in place; theta [N, H*16]
 __global__ __launch_bounds__(256) void k_rotary(float* __restrict__ x, const float* __restrict__ theta, int64_t N, int heads) {
@@ -67,29 +62,11 @@ __device__ __forceinline__ void regs_to_lds(const float4 (&reg)[4], float* __res
   }
 }
 
-__device__ __forceinline__ void load_tile(const float* __restrict__ src, int64_t rows, int64_t r0, int ld_src, int col0, float* __restrict__ dst) {
-  // 32 x 32 tile (rows r0.., columns col0..col0+31) of a row-major matrix -> dst[32][AT_LD]; rows beyond `rows` -> 0
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int f = lane + 64 * i;          // 256 float4 pieces
-    const int r = f >> 3, c4 = f & 7;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r0 + r < rows) v = *reinterpret_cast<const float4*>(src + (r0 + r) * ld_src + col0 + c4 * 4);
-    float* d = dst + r * AT_LD + c4 * 4;
-    d[0] = v.x;
-    d[1] = v.y;
-    d[2] = v.z;
-    d[3] = v.w;
-  }
-}
-
 // one (head, 32-query tile) of one attention problem: q [Nq, H*32], k/v [Nk, H*32] -> out [Nq, H*32]; 64 threads
 // Key split: the AT_SPLIT wavefronts of a workgroup share the query tile and take the 32-key blocks w, w + AT_SPLIT, ... each with its
 // own running (max, sum, O^T); the partial states are merged through LDS at the end (O = sum_w O_w e^{m_w - m} / sum_w l_w e^{m_w - m}).
 // One wavefront per tile walked all ~26 key blocks of a cloud one after the other, every block a dependent chain (S^T MFMAs -> softmax
 // -> P·V MFMAs), and a pair's layer was 108 wavefronts on 1 024 SIMDs: the launch took as long as that one chain (68-90 us).
-constexpr int AT_SPLIT = 4;
 struct AttnMerge {
   float m[AT_SPLIT][32], l[AT_SPLIT][32];
   float o[AT_SPLIT][16][64];
@@ -120,13 +97,10 @@ __device__ __forceinline__ void attention_tile(const float* __restrict__ q, cons
     tile_to_regs(v, Nk, kb0, ld, head * AT_D, vreg);
   }
   for (int64_t k0 = kb0; k0 < Nk; k0 += kstep) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                      // everyone is done reading the previous tile
+    wave_sync();                                          // everyone is done reading the previous tile
     regs_to_lds(kreg, s_k);
     regs_to_lds(vreg, s_v);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     if (k0 + kstep < Nk) {                                // next tile's loads fly while this tile's 32 MFMAs run
       tile_to_regs(k, Nk, k0 + kstep, ld, head * AT_D, kreg);
       tile_to_regs(v, Nk, k0 + kstep, ld, head * AT_D, vreg);
@@ -165,9 +139,7 @@ __device__ __forceinline__ void attention_tile(const float* __restrict__ q, cons
     // O^T[d][query] += sum_key V[key][d] * P[key][query]:  A[i=d][kk] = V[key][d],  B[kk][j=query] = P[key][query]
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) {
-      // the key this lane must supply is 2*kk + half; it lives in half hp = (kk>>1)&1, register 2*(kk&1) + (key&1) + 4*(kk>>2)
-      constexpr int dummy = 0;
-      (void)dummy;
+      // attention.h's acc_as_b(s, kk, half), written out: through the call this kernel comes out with 174 instead of 154 registers
       const int hp = (kk >> 1) & 1;
       const int rbase = 2 * (kk & 1) + 4 * (kk >> 2);
       const float own = (half == 0) ? s[rbase + 0] : s[rbase + 1];       // value for a requester in my own half
@@ -223,7 +195,6 @@ __global__ __launch_bounds__(64 * AT_SPLIT) void k_attention(const float* __rest
 // Several independent attention problems in ONE launch (registration pairs batched per call: the self layers of 2P clouds, the
 // cross layers of P pairs): problem p attends queries [q_off[p], q_off[p+1]) to keys [k_off[p], k_off[p+1]) of the stacked
 // tensors.  One pair alone is 27 query tiles x 4 heads = 108 wavefronts on 256 CUs; P pairs fill the chip.
-constexpr int AT_MAX_P = 64;
 struct AttnSeg {
   int P;
   int q_off[AT_MAX_P + 1], k_off[AT_MAX_P + 1], tile_off[AT_MAX_P + 1];   // row offsets; first query tile of every problem
@@ -301,9 +272,7 @@ __global__ __launch_bounds__(256) void k_attention_topk(const float* __restrict_
     mx = fmaxf(mx, sdot);
   }
   mx = wave_max_f(mx);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_sync();
   // kk-th largest score: radix select over the order-preserving 32-bit keys, most significant byte first
   uint32_t prefix = 0u, mask = 0u;
   int remaining = kk;                                           // how many of the keys matching `prefix` are still to be taken from the top
@@ -311,16 +280,12 @@ __global__ __launch_bounds__(256) void k_attention_topk(const float* __restrict_
     for (int pass = 3; pass >= 0; --pass) {
       const int sh = 8 * pass;
       for (int i = lane; i < 256; i += 64) hist[i] = 0;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       for (int j = lane; j < m; j += 64) {
         const uint32_t u = f2ord(sc[j]);
         if ((u & mask) == prefix) atomicAdd(&hist[(u >> sh) & 255u], 1);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       // lane L owns bins 255-4L .. 252-4L (descending), so an inclusive scan over the lanes counts the keys in HIGHER bins
       const int d0 = 255 - 4 * lane;
       const int c0 = hist[d0], c1 = hist[d0 - 1], c2 = hist[d0 - 2], c3 = hist[d0 - 3];
@@ -381,9 +346,7 @@ __global__ __launch_bounds__(256) void k_attention_topk(const float* __restrict_
     const float t = wave_sum(acc[d]);
     if (lane == 0) s_o[w][d] = t / sum;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_sync();
   if (lane < AT_D) op[lane] = s_o[w][lane];
 }
 

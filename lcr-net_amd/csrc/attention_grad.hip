@@ -9,8 +9,8 @@
 //                S = Q·K^T, P = exp2(S - L), dV^T += dO^T·P, dP = dO·V^T, dS = P∘(dP - D), dK^T += Q^T·dS;
 //   k_ag_dq    : one workgroup per (problem, head, 32-query tile), a lane owns one QUERY; its wavefronts take the key tiles round-robin:
 //                S^T = K·Q^T, P^T, dP^T = V·dO^T, dS^T, dQ^T += K^T·dS^T.
-// As in the forward the 32x32 result of one MFMA group feeds the next one as its B operand straight from the accumulator registers (one
-// cross-half swap per step).  The four partial sums of a workgroup are added in LDS in wavefront order: no floating-point atomics, a
+// As in the forward the 32x32 result of one MFMA group feeds the next one as its B operand straight from the accumulator registers
+// (attention.h's acc_as_b), and tiles reach LDS through the forward's load_tile.  The four partial sums of a workgroup are added in LDS in wavefront order: no floating-point atomics, a
 // problem's bytes do not depend on its batch.
 //   k_rotary_grad     : dx = R(-theta)·dy, dtheta = dy0·(-y1) + dy1·y0 from the POST-rotary y (d y / d theta = rot(y));
 //   k_ln_grad / k_ln_grad_reduce : LayerNorm(a + b) reverse; mean and rstd recomputed per row as the forward computes them, dgamma / dbeta
@@ -18,97 +18,49 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "attention.h"
 
 namespace lcr {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int AG_D = 32;      // head dim
-constexpr int AG_LD = 33;     // LDS row stride (attention.hip)
-constexpr int AG_SPLIT = 4;   // wavefronts per workgroup
-constexpr int AG_MAX_P = 64;
-constexpr int AG_TILE = 32 * AG_LD;
-
 struct AgSeg {
   int P;
-  int q_off[AG_MAX_P + 1], k_off[AG_MAX_P + 1];        // row offsets
-  int qt_off[AG_MAX_P + 1], kt_off[AG_MAX_P + 1];      // first 32-query tile / first 32-key tile of every problem
+  int q_off[AT_MAX_P + 1], k_off[AT_MAX_P + 1];        // row offsets
+  int qt_off[AT_MAX_P + 1], kt_off[AT_MAX_P + 1];      // first 32-query tile / first 32-key tile of every problem
 };
-
-// 32 x 32 tile (rows r0.., columns col0..col0+31) of a row-major matrix -> dst[32][AG_LD]; rows beyond `rows` -> 0.  One wavefront.
-__device__ __forceinline__ void ag_load_tile(const float* __restrict__ src, int64_t rows, int64_t r0, int ld_src, int col0, float* __restrict__ dst) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int f = lane + 64 * i;
-    const int r = f >> 3, c4 = f & 7;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r0 + r < rows) v = *reinterpret_cast<const float4*>(src + (r0 + r) * ld_src + col0 + c4 * 4);
-    float* d = dst + r * AG_LD + c4 * 4;
-    d[0] = v.x;
-    d[1] = v.y;
-    d[2] = v.z;
-    d[3] = v.w;
-  }
-}
-
-__device__ __forceinline__ void ag_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // row of accumulator register r in this lane's half
 __device__ __forceinline__ int ag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-// A 32x32 MFMA result (this lane: column `col`, rows ag_row(r, half)) as the B operand of the next product: at step kk this lane must supply
-// row 2 kk + half, which sits in half (kk >> 1) & 1 at register 2 (kk & 1) + 4 (kk >> 2) + (row & 1).  kk is a compile-time constant.
-__device__ __forceinline__ float ag_acc_as_b(const floatx16& s, int kk, int half) {
-  const int hp = (kk >> 1) & 1;
-  const int rbase = 2 * (kk & 1) + 4 * (kk >> 2);
-  const float own = (half == 0) ? s[rbase + 0] : s[rbase + 1];
-  const float other = (half == 0) ? s[rbase + 1] : s[rbase + 0];
-  const float recv = __shfl_xor(other, 32);
-  return (half == hp) ? own : recv;
-}
-
-__device__ __forceinline__ int ag_problem(const int* tile_off, int P, int tile) {
-  int p = 0;
-  while (p + 1 < P && tile >= tile_off[p + 1]) ++p;       // block-uniform, scalar; empty problems (equal offsets) are stepped over
-  return p;
-}
-
 // grid (query tiles of all problems, heads).  Lq / Dq: [heads][total queries]
-__global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_stats(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ out,
+__global__ __launch_bounds__(64 * AT_SPLIT) void k_ag_stats(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ out,
                                                             const float* __restrict__ d_out, AgSeg seg, int heads, float scale,
                                                             float* __restrict__ Lq, float* __restrict__ Dq) {
-  __shared__ __attribute__((aligned(16))) float s_q[AG_TILE], s_k[AG_SPLIT][AG_TILE], s_do[AG_TILE], s_o[AG_TILE];
-  __shared__ float s_m[AG_SPLIT][32], s_l[AG_SPLIT][32];
+  __shared__ __attribute__((aligned(16))) float s_q[AT_TILE], s_k[AT_SPLIT][AT_TILE], s_do[AT_TILE], s_o[AT_TILE];
+  __shared__ float s_m[AT_SPLIT][32], s_l[AT_SPLIT][32];
   const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
   const int wsp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int p = ag_problem(seg.qt_off, seg.P, static_cast<int>(blockIdx.x));
-  const int head = blockIdx.y, ld = heads * AG_D;
+  const int p = cloud_of(seg.qt_off, seg.P, static_cast<int>(blockIdx.x));
+  const int head = blockIdx.y, ld = heads * AT_D;
   const int64_t qo = seg.q_off[p], ko = seg.k_off[p];
   const int64_t Nq = seg.q_off[p + 1] - qo, Nk = seg.k_off[p + 1] - ko, Ntot = seg.q_off[seg.P];
   const int64_t q0 = static_cast<int64_t>(static_cast<int>(blockIdx.x) - seg.qt_off[p]) * 32;
-  if (wsp == 0) ag_load_tile(q + qo * ld, Nq, q0, ld, head * AG_D, s_q);
+  if (wsp == 0) load_tile(q + qo * ld, Nq, q0, ld, head * AT_D, s_q);
   __syncthreads();
   float qf[16];
   const float scale2 = scale * 1.44269504088896341f;
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) qf[kk] = s_q[col * AG_LD + 2 * kk + half] * scale2;
+  for (int kk = 0; kk < 16; ++kk) qf[kk] = s_q[col * AT_LD + 2 * kk + half] * scale2;
   float m = -INFINITY, l = 0.f;
   float* sk = s_k[wsp];
-  for (int64_t k0 = 32 * static_cast<int64_t>(wsp); k0 < Nk; k0 += 32 * AG_SPLIT) {
-    ag_wave_sync();
-    ag_load_tile(k + ko * ld, Nk, k0, ld, head * AG_D, sk);
-    ag_wave_sync();
+  for (int64_t k0 = 32 * static_cast<int64_t>(wsp); k0 < Nk; k0 += 32 * AT_SPLIT) {
+    wave_sync();
+    load_tile(k + ko * ld, Nk, k0, ld, head * AT_D, sk);
+    wave_sync();
     floatx16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[col * AG_LD + 2 * kk + half], qf[kk], s, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[col * AT_LD + 2 * kk + half], qf[kk], s, 0, 0, 0);
     float tmax = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -132,21 +84,21 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_stats(const float* __restr
   if (wsp == 0) {
     float mm = -INFINITY;
 #pragma unroll
-    for (int u = 0; u < AG_SPLIT; ++u) mm = fmaxf(mm, s_m[u][col]);
+    for (int u = 0; u < AT_SPLIT; ++u) mm = fmaxf(mm, s_m[u][col]);
     float lsum = 0.f;
 #pragma unroll
-    for (int u = 0; u < AG_SPLIT; ++u) lsum += s_l[u][col] * __builtin_amdgcn_exp2f(s_m[u][col] - mm);
+    for (int u = 0; u < AT_SPLIT; ++u) lsum += s_l[u][col] * __builtin_amdgcn_exp2f(s_m[u][col] - mm);
     if (half == 0 && q0 + col < Nq) Lq[head * Ntot + qo + q0 + col] = mm + __builtin_amdgcn_logf(lsum);     // v_log_f32: base 2
   } else if (wsp == 1) {
-    ag_load_tile(d_out + qo * ld, Nq, q0, ld, head * AG_D, s_do);
-    ag_load_tile(out + qo * ld, Nq, q0, ld, head * AG_D, s_o);
-    ag_wave_sync();
+    load_tile(d_out + qo * ld, Nq, q0, ld, head * AT_D, s_do);
+    load_tile(out + qo * ld, Nq, q0, ld, head * AT_D, s_o);
+    wave_sync();
     floatx16 acc;      // acc[query i][query j] = sum_d dO[i][d] O[j][d]; wanted: the diagonal
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(s_do[col * AG_LD + 2 * kk + half], s_o[col * AG_LD + 2 * kk + half], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(s_do[col * AT_LD + 2 * kk + half], s_o[col * AT_LD + 2 * kk + half], acc, 0, 0, 0);
     float dsum = 0.f;
     bool mine = false;
 #pragma unroll
@@ -157,53 +109,53 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_stats(const float* __restr
 }
 
 // grid (key tiles of all problems, heads)
-__global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dkdv(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+__global__ __launch_bounds__(64 * AT_SPLIT) void k_ag_dkdv(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                            const float* __restrict__ d_out, const float* __restrict__ Lq, const float* __restrict__ Dq,
                                                            AgSeg seg, int heads, float scale, float* __restrict__ dk, float* __restrict__ dv) {
-  __shared__ __attribute__((aligned(16))) float s_k[AG_TILE], s_v[AG_TILE];
-  __shared__ __attribute__((aligned(16))) float s_buf[2 * AG_SPLIT * AG_TILE];      // per wavefront a Q and a dO tile; afterwards the merge buffer
-  __shared__ float s_L[AG_SPLIT][32], s_D[AG_SPLIT][32];
-  static_assert(2 * AG_SPLIT * AG_TILE >= AG_SPLIT * 2 * 16 * 64, "merge buffer");
+  __shared__ __attribute__((aligned(16))) float s_k[AT_TILE], s_v[AT_TILE];
+  __shared__ __attribute__((aligned(16))) float s_buf[2 * AT_SPLIT * AT_TILE];      // per wavefront a Q and a dO tile; afterwards the merge buffer
+  __shared__ float s_L[AT_SPLIT][32], s_D[AT_SPLIT][32];
+  static_assert(2 * AT_SPLIT * AT_TILE >= AT_SPLIT * 2 * 16 * 64, "merge buffer");
   const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
   const int wsp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int p = ag_problem(seg.kt_off, seg.P, static_cast<int>(blockIdx.x));
-  const int head = blockIdx.y, ld = heads * AG_D;
+  const int p = cloud_of(seg.kt_off, seg.P, static_cast<int>(blockIdx.x));
+  const int head = blockIdx.y, ld = heads * AT_D;
   const int64_t qo = seg.q_off[p], ko = seg.k_off[p];
   const int64_t Nq = seg.q_off[p + 1] - qo, Nk = seg.k_off[p + 1] - ko, Ntot = seg.q_off[seg.P];
   const int64_t k0 = static_cast<int64_t>(static_cast<int>(blockIdx.x) - seg.kt_off[p]) * 32;
-  if (wsp == 0) ag_load_tile(k + ko * ld, Nk, k0, ld, head * AG_D, s_k);
-  if (wsp == 1) ag_load_tile(v + ko * ld, Nk, k0, ld, head * AG_D, s_v);
+  if (wsp == 0) load_tile(k + ko * ld, Nk, k0, ld, head * AT_D, s_k);
+  if (wsp == 1) load_tile(v + ko * ld, Nk, k0, ld, head * AT_D, s_v);
   __syncthreads();
   float kf[16], vf[16];
   const float scale2 = scale * 1.44269504088896341f;
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) {
-    kf[kk] = s_k[col * AG_LD + 2 * kk + half];               // B[kd][j = key] of S = Q·K^T
-    vf[kk] = s_v[col * AG_LD + 2 * kk + half];               // B[kd][j = key] of dP = dO·V^T
+    kf[kk] = s_k[col * AT_LD + 2 * kk + half];               // B[kd][j = key] of S = Q·K^T
+    vf[kk] = s_v[col * AT_LD + 2 * kk + half];               // B[kd][j = key] of dP = dO·V^T
   }
   const bool key_ok = k0 + col < Nk;
-  float* sq = s_buf + (2 * wsp) * AG_TILE;
-  float* sdo = s_buf + (2 * wsp + 1) * AG_TILE;
+  float* sq = s_buf + (2 * wsp) * AT_TILE;
+  float* sdo = s_buf + (2 * wsp + 1) * AT_TILE;
   floatx16 adv, adk;     // dV^T[d][key], dK^T[d][key]
 #pragma unroll
   for (int r = 0; r < 16; ++r) adv[r] = 0.f, adk[r] = 0.f;
-  for (int64_t q0 = 32 * static_cast<int64_t>(wsp); q0 < Nq; q0 += 32 * AG_SPLIT) {
-    ag_wave_sync();
-    ag_load_tile(q + qo * ld, Nq, q0, ld, head * AG_D, sq);
-    ag_load_tile(d_out + qo * ld, Nq, q0, ld, head * AG_D, sdo);
+  for (int64_t q0 = 32 * static_cast<int64_t>(wsp); q0 < Nq; q0 += 32 * AT_SPLIT) {
+    wave_sync();
+    load_tile(q + qo * ld, Nq, q0, ld, head * AT_D, sq);
+    load_tile(d_out + qo * ld, Nq, q0, ld, head * AT_D, sdo);
     if (lane < 32) {
       const bool ok = q0 + lane < Nq;
       s_L[wsp][lane] = ok ? Lq[head * Ntot + qo + q0 + lane] : 0.f;
       s_D[wsp][lane] = ok ? Dq[head * Ntot + qo + q0 + lane] : 0.f;
     }
-    ag_wave_sync();
+    wave_sync();
     floatx16 s, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f, dp[r] = 0.f;
     // S[query][key] = sum_d Q[query][d] K[key][d]; q is scaled as in k_ag_stats ((q scale2) k, not q (k scale2)): the products, and with
     // them S - L, carry the bits L was formed from (one key: P = exp2(0) = 1 exactly)
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sq[col * AG_LD + 2 * kk + half] * scale2, kf[kk], s, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sq[col * AT_LD + 2 * kk + half] * scale2, kf[kk], s, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = ag_row(r, half);
@@ -211,15 +163,15 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dkdv(const float* __restri
     }
     // dV^T[d][key] += sum_query dO[query][d] P[query][key]
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) adv = __builtin_amdgcn_mfma_f32_32x32x2f32(sdo[(2 * kk + half) * AG_LD + col], ag_acc_as_b(s, kk, half), adv, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) adv = __builtin_amdgcn_mfma_f32_32x32x2f32(sdo[(2 * kk + half) * AT_LD + col], acc_as_b(s, kk, half), adv, 0, 0, 0);
     // dP[query][key] = sum_d dO[query][d] V[key][d]
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sdo[col * AG_LD + 2 * kk + half], vf[kk], dp, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sdo[col * AT_LD + 2 * kk + half], vf[kk], dp, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = s[r] * (dp[r] - s_D[wsp][ag_row(r, half)]);      // dS
     // dK^T[d][key] += sum_query Q[query][d] dS[query][key]
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) adk = __builtin_amdgcn_mfma_f32_32x32x2f32(sq[(2 * kk + half) * AG_LD + col], ag_acc_as_b(s, kk, half), adk, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) adk = __builtin_amdgcn_mfma_f32_32x32x2f32(sq[(2 * kk + half) * AT_LD + col], acc_as_b(s, kk, half), adk, 0, 0, 0);
   }
   __syncthreads();                                             // every wavefront is done with its tiles: s_buf becomes the merge buffer
   float* mg = s_buf;                                           // [wavefront][dv | dk][16][64]
@@ -231,15 +183,15 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dkdv(const float* __restri
   __syncthreads();
   if (key_ok) {
 #pragma unroll
-    for (int rr = 0; rr < 16 / AG_SPLIT; ++rr) {
-      const int r = wsp * (16 / AG_SPLIT) + rr;
+    for (int rr = 0; rr < 16 / AT_SPLIT; ++rr) {
+      const int r = wsp * (16 / AT_SPLIT) + rr;
       float sv = 0.f, sk2 = 0.f;
 #pragma unroll
-      for (int u = 0; u < AG_SPLIT; ++u) {                      // fixed order
+      for (int u = 0; u < AT_SPLIT; ++u) {                      // fixed order
         sv += mg[((u * 2 + 0) * 16 + r) * 64 + lane];
         sk2 += mg[((u * 2 + 1) * 16 + r) * 64 + lane];
       }
-      const int64_t at = (ko + k0 + col) * ld + head * AG_D + ag_row(r, half);
+      const int64_t at = (ko + k0 + col) * ld + head * AT_D + ag_row(r, half);
       dv[at] = sv;
       dk[at] = sk2 * scale;
     }
@@ -247,48 +199,48 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dkdv(const float* __restri
 }
 
 // grid (query tiles of all problems, heads)
-__global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dq(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+__global__ __launch_bounds__(64 * AT_SPLIT) void k_ag_dq(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                          const float* __restrict__ d_out, const float* __restrict__ Lq, const float* __restrict__ Dq,
                                                          AgSeg seg, int heads, float scale, float* __restrict__ dq) {
-  __shared__ __attribute__((aligned(16))) float s_q[AG_TILE], s_do[AG_TILE];
-  __shared__ __attribute__((aligned(16))) float s_buf[2 * AG_SPLIT * AG_TILE];      // per wavefront a K and a V tile; afterwards the merge buffer
+  __shared__ __attribute__((aligned(16))) float s_q[AT_TILE], s_do[AT_TILE];
+  __shared__ __attribute__((aligned(16))) float s_buf[2 * AT_SPLIT * AT_TILE];      // per wavefront a K and a V tile; afterwards the merge buffer
   const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
   const int wsp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int p = ag_problem(seg.qt_off, seg.P, static_cast<int>(blockIdx.x));
-  const int head = blockIdx.y, ld = heads * AG_D;
+  const int p = cloud_of(seg.qt_off, seg.P, static_cast<int>(blockIdx.x));
+  const int head = blockIdx.y, ld = heads * AT_D;
   const int64_t qo = seg.q_off[p], ko = seg.k_off[p];
   const int64_t Nq = seg.q_off[p + 1] - qo, Nk = seg.k_off[p + 1] - ko, Ntot = seg.q_off[seg.P];
   const int64_t q0 = static_cast<int64_t>(static_cast<int>(blockIdx.x) - seg.qt_off[p]) * 32;
-  if (wsp == 0) ag_load_tile(q + qo * ld, Nq, q0, ld, head * AG_D, s_q);
-  if (wsp == 1) ag_load_tile(d_out + qo * ld, Nq, q0, ld, head * AG_D, s_do);
+  if (wsp == 0) load_tile(q + qo * ld, Nq, q0, ld, head * AT_D, s_q);
+  if (wsp == 1) load_tile(d_out + qo * ld, Nq, q0, ld, head * AT_D, s_do);
   __syncthreads();
   float qf[16], dof[16];
   const float scale2 = scale * 1.44269504088896341f;
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) {
-    qf[kk] = s_q[col * AG_LD + 2 * kk + half] * scale2;      // B[kd][j = query] of S^T = K·Q^T
-    dof[kk] = s_do[col * AG_LD + 2 * kk + half];             // B[kd][j = query] of dP^T = V·dO^T
+    qf[kk] = s_q[col * AT_LD + 2 * kk + half] * scale2;      // B[kd][j = query] of S^T = K·Q^T
+    dof[kk] = s_do[col * AT_LD + 2 * kk + half];             // B[kd][j = query] of dP^T = V·dO^T
   }
   const bool q_ok = q0 + col < Nq;
   const float Lr = q_ok ? Lq[head * Ntot + qo + q0 + col] : 0.f;
   const float Dr = q_ok ? Dq[head * Ntot + qo + q0 + col] : 0.f;
-  float* sk = s_buf + (2 * wsp) * AG_TILE;
-  float* sv = s_buf + (2 * wsp + 1) * AG_TILE;
+  float* sk = s_buf + (2 * wsp) * AT_TILE;
+  float* sv = s_buf + (2 * wsp + 1) * AT_TILE;
   floatx16 adq;     // dQ^T[d][query]
 #pragma unroll
   for (int r = 0; r < 16; ++r) adq[r] = 0.f;
-  for (int64_t k0 = 32 * static_cast<int64_t>(wsp); k0 < Nk; k0 += 32 * AG_SPLIT) {
-    ag_wave_sync();
-    ag_load_tile(k + ko * ld, Nk, k0, ld, head * AG_D, sk);
-    ag_load_tile(v + ko * ld, Nk, k0, ld, head * AG_D, sv);
-    ag_wave_sync();
+  for (int64_t k0 = 32 * static_cast<int64_t>(wsp); k0 < Nk; k0 += 32 * AT_SPLIT) {
+    wave_sync();
+    load_tile(k + ko * ld, Nk, k0, ld, head * AT_D, sk);
+    load_tile(v + ko * ld, Nk, k0, ld, head * AT_D, sv);
+    wave_sync();
     floatx16 s, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f, dp[r] = 0.f;
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[col * AG_LD + 2 * kk + half], qf[kk], s, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[col * AT_LD + 2 * kk + half], qf[kk], s, 0, 0, 0);
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[col * AG_LD + 2 * kk + half], dof[kk], dp, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[col * AT_LD + 2 * kk + half], dof[kk], dp, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float pr = (q_ok && k0 + ag_row(r, half) < Nk) ? __builtin_amdgcn_exp2f(s[r] - Lr) : 0.f;
@@ -296,7 +248,7 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dq(const float* __restrict
     }
     // dQ^T[d][query] += sum_key K[key][d] dS^T[key][query]
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) adq = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[(2 * kk + half) * AG_LD + col], ag_acc_as_b(s, kk, half), adq, 0, 0, 0);
+    for (int kk = 0; kk < 16; ++kk) adq = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[(2 * kk + half) * AT_LD + col], acc_as_b(s, kk, half), adq, 0, 0, 0);
   }
   __syncthreads();
   float* mg = s_buf;                                           // [wavefront][16][64]
@@ -305,12 +257,12 @@ __global__ __launch_bounds__(64 * AG_SPLIT) void k_ag_dq(const float* __restrict
   __syncthreads();
   if (q_ok) {
 #pragma unroll
-    for (int rr = 0; rr < 16 / AG_SPLIT; ++rr) {
-      const int r = wsp * (16 / AG_SPLIT) + rr;
+    for (int rr = 0; rr < 16 / AT_SPLIT; ++rr) {
+      const int r = wsp * (16 / AT_SPLIT) + rr;
       float sum = 0.f;
 #pragma unroll
-      for (int u = 0; u < AG_SPLIT; ++u) sum += mg[(u * 16 + r) * 64 + lane];      // fixed order
-      dq[(qo + q0 + col) * ld + head * AG_D + ag_row(r, half)] = sum * scale;
+      for (int u = 0; u < AT_SPLIT; ++u) sum += mg[(u * 16 + r) * 64 + lane];      // fixed order
+      dq[(qo + q0 + col) * ld + head * AT_D + ag_row(r, half)] = sum * scale;
     }
   }
 }
@@ -434,9 +386,9 @@ extern "C" int lcr_attention_grad_ws_bytes(int64_t n_queries, int heads, size_t*
 extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const float* v, const float* out, const float* d_out,
                                           const int64_t* q_len_host, const int64_t* k_len_host, int P, int heads, int head_dim, float* dq, float* dk,
                                           float* dv, void* ws, size_t ws_bytes, void* stream) {
-  if (!q || !k || !v || !out || !d_out || !dq || !dk || !dv || !q_len_host || !k_len_host || P < 1 || P > AG_MAX_P || heads < 1 || heads > 65535 ||
-      head_dim != AG_D) {
-    set_error("lcr_attention_seg_grad_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AG_D, AG_MAX_P);
+  if (!q || !k || !v || !out || !d_out || !dq || !dk || !dv || !q_len_host || !k_len_host || P < 1 || P > AT_MAX_P || heads < 1 || heads > 65535 ||
+      head_dim != AT_D) {
+    set_error("lcr_attention_seg_grad_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
     return LCR_EARG;
   }
   AgSeg seg;
@@ -475,9 +427,9 @@ extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const 
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* Lq = static_cast<float*>(ws);
   float* Dq = Lq + static_cast<size_t>(heads) * static_cast<size_t>(qo);
-  if (qt > 0) hipLaunchKernelGGL(k_ag_stats, dim3(static_cast<int>(qt), heads), dim3(64 * AG_SPLIT), 0, st, q, k, out, d_out, seg, heads, scale, Lq, Dq);
-  hipLaunchKernelGGL(k_ag_dkdv, dim3(static_cast<int>(kt), heads), dim3(64 * AG_SPLIT), 0, st, q, k, v, d_out, Lq, Dq, seg, heads, scale, dk, dv);
-  if (qt > 0) hipLaunchKernelGGL(k_ag_dq, dim3(static_cast<int>(qt), heads), dim3(64 * AG_SPLIT), 0, st, q, k, v, d_out, Lq, Dq, seg, heads, scale, dq);
+  if (qt > 0) hipLaunchKernelGGL(k_ag_stats, dim3(static_cast<int>(qt), heads), dim3(64 * AT_SPLIT), 0, st, q, k, out, d_out, seg, heads, scale, Lq, Dq);
+  hipLaunchKernelGGL(k_ag_dkdv, dim3(static_cast<int>(kt), heads), dim3(64 * AT_SPLIT), 0, st, q, k, v, d_out, Lq, Dq, seg, heads, scale, dk, dv);
+  if (qt > 0) hipLaunchKernelGGL(k_ag_dq, dim3(static_cast<int>(qt), heads), dim3(64 * AT_SPLIT), 0, st, q, k, v, d_out, Lq, Dq, seg, heads, scale, dq);
   return check_launch("lcr_attention_seg_grad_f32");
 }
 

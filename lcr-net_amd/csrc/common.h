@@ -16,9 +16,12 @@ namespace lcr {
 
 constexpr int WAVE = 64;
 
+typedef float floatx16 __attribute__((ext_vector_type(16)));   // a lane's share of a 32x32 MFMA accumulator
+
 // GroupNorm statistics are accumulated into GN_REPLICAS copies of the [S, groups, 2] fp64 table (copy = workgroup % R) so that
 // same-address fp64 atomics — which serialise in the memory-side atomic unit — are spread out; consumers sum the copies.
 constexpr int GN_REPLICAS = 8;
+constexpr int GN_MAX_SEG = 256;  // segments per GroupNorm call
 
 void set_error(const char* fmt, ...);
 
@@ -136,6 +139,28 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// GroupNorm's (mean, rstd) of one (segment, group) from its fp64 sums over cnt elements: m = sx / cnt, var = max(sxx / cnt - m^2, 0), the
+// mean carried as two floats (mean_lo: what it lost when it was rounded to fp32), rstd rounded once.  What the reverse pass and the
+// normalise-on-load GEMMs call; k_gn_apply (groupnorm.hip) writes the same lines out.
+__device__ __forceinline__ void gn_finalise(double sx, double sxx, double cnt, float eps, float* mean_hi, float* mean_lo, float* rstd) {
+  const double m = sx / cnt;
+  const double var = fmax(sxx / cnt - m * m, 0.0);
+  *mean_hi = static_cast<float>(m);
+  *mean_lo = static_cast<float>(m - static_cast<double>(static_cast<float>(m)));
+  *rstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
+}
+// the same for (segment sg, group g) of the [GN_REPLICAS, S, groups, 2] table: the replicas folded in order (deterministic given the sums)
+__device__ __forceinline__ void gn_mean_rstd(const double* __restrict__ stats, int S, int groups, int sg, int g, double cnt, float eps, float* mean_hi,
+                                             float* mean_lo, float* rstd) {
+  double sx = 0.0, sxx = 0.0;
+  for (int rep = 0; rep < GN_REPLICAS; ++rep) {
+    const int64_t o = ((static_cast<int64_t>(rep) * S + sg) * groups + g) * 2;
+    sx += stats[o];
+    sxx += stats[o + 1];
+  }
+  gn_finalise(sx, sxx, cnt, eps, mean_hi, mean_lo, rstd);
 }
 
 // cloud that owns stacked row i, given exclusive prefix offsets off[0..B] (off[B] = total); the comparison is made in the common type

@@ -8,8 +8,6 @@
 
 namespace lcr {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int GM_BK = 32;
 constexpr int GM_T = 256;
 
@@ -51,7 +49,7 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 // first row, slot 1 = the next one; the host guarantees that no segment is shorter than the block).  Two calls, so that the loads of the
 // first are in flight under the caller's segment scan:
 //   anorm_load_affine: this thread's (gamma, beta) of table entries e = tid and tid + 256 (2 K <= 512);
-//   anorm_build_table: (mean, rstd) per (slot, group) finalised in fp64 from the producer's statistics replicas exactly as
+//   anorm_build_table: (mean, rstd) per (slot, group) finalised in fp64 from the producer's statistics replicas by gn_finalise, as
 //   lcr_groupnorm_apply does, then scale = rstd * gamma, shift = beta - mean * scale.  Ends with a barrier: the table is readable on return.
 __device__ __forceinline__ void anorm_load_affine(const ANorm& an, int K, float (&an_g)[2], float (&an_b)[2]) {
 #pragma unroll
@@ -74,15 +72,15 @@ __device__ __forceinline__ void anorm_build_table(const ANorm& an, const GemmEpi
     const int slot = e >= an.groups ? 1 : 0, g = e - slot * an.groups;
     const int sg = min(blk_first + slot, ep.S - 1);
     const double cnt = static_cast<double>(ep.seg_len[sg]) * gs;
-    double sx = 0.0, sxx = 0.0;
-    for (int rep = 0; rep < GN_REPLICAS; ++rep) {
+    double sx = 0.0, sxx = 0.0;                          // gn_mean_rstd's fold, written out: through the call one k_gemm_f32 form peels
+    for (int rep = 0; rep < GN_REPLICAS; ++rep) {        // the first replica instead of the last
       const int64_t o = ((static_cast<int64_t>(rep) * ep.S + sg) * an.groups + g) * 2;
       sx += an.stats[o];
       sxx += an.stats[o + 1];
     }
-    const double mean = sx / cnt;
-    const double var = fmax(sxx / cnt - mean * mean, 0.0);
-    s_mr[e] = make_float2(static_cast<float>(mean), static_cast<float>(1.0 / sqrt(var + static_cast<double>(an.eps))));
+    float mean, mean_lo, rstd;                           // mean_lo is not carried: the table is in scale / shift form
+    gn_finalise(sx, sxx, cnt, an.eps, &mean, &mean_lo, &rstd);
+    s_mr[e] = make_float2(mean, rstd);
   }
   __syncthreads();
 #pragma unroll

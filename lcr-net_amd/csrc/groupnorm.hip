@@ -38,7 +38,6 @@ __device__ __forceinline__ int seg_of(const int64_t* __restrict__ seg_len, int S
 // Flat float4 mapping: thread t handles 4 consecutive channels of one row (C % 4 == 0), so loads/stores are 16-B vectors and
 // all 64 lanes are busy for every C.  Row flags (pos) are reduced across the C/4 lanes of a row (C <= 256).
 constexpr int GN_TABLE = 2048;   // (segment, group) pairs whose mean / rstd fit the LDS table
-constexpr int GN_MAX_SEG = 256;  // segments per call
 
 // RM: residual mode, compile-time (0 none, 1 plain residual, 2 GroupNorm-ed residual): no per-element branches on it
 template <bool POS, int RM>
@@ -78,6 +77,8 @@ __global__ __launch_bounds__(256) void k_gn_apply(const float* __restrict__ x, G
   for (int i = threadIdx.x; i < nseg * groups; i += blockDim.x) {
     const int sg = seg_lo + i / groups, g = i - (i / groups) * groups;
     const double cnt = static_cast<double>(seg_len[sg]) * gs;
+    // common.h's gn_mean_rstd for both sides, written out: the two folds share one loop, and the (mean, rstd) pair is stored before the
+    // mean's low part is formed — through calls the kernel comes out with another instruction order
     double sx = 0.0, sxx = 0.0, rx = 0.0, rxx = 0.0;
     for (int rep = 0; rep < GN_REPLICAS; ++rep) {     // fold the statistics replicas (fixed order: deterministic given the sums)
       const int64_t o = ((static_cast<int64_t>(rep) * S + sg) * groups + g) * 2;

@@ -2,8 +2,8 @@
 //
 // With z = GN(x) [+ residual], y = act(z), dz = dy * (y > 0 ? 1 : slope) (act) or dy, x^ = (x - mean) * rstd and g = dz * gamma:
 //     dbeta[c] = sum_n dz,   dgamma[c] = sum_n dz x^,   dx = rstd * (g - mean_sg(g) - x^ * mean_sg(g x^)),
-// the means over the elements of one (segment, group).  mean and rstd come from the forward's own fp64 table exactly as k_gn_apply
-// derives them: replicas folded in order, m = sx / cnt, var = max(sxx / cnt - m^2, 0), the mean carried as two floats, rstd rounded once.
+// the means over the elements of one (segment, group).  mean and rstd come from the forward's own fp64 table through gn_mean_rstd, the
+// function k_gn_apply finalises them with.
 //
 // Two passes, no floating-point atomics:
 //   1. reduce — a segment is cut into pieces of GG_ROWS rows counted from ITS first row; a workgroup owns one piece and writes, per channel,
@@ -19,7 +19,6 @@
 namespace lcr {
 
 constexpr int GG_ROWS = 128;       // rows per piece
-constexpr int GG_MAX_SEG = 256;    // segments per call (the forward's limit)
 constexpr int GG_MAX_C = 2048;     // channels (the per-segment fold keeps 2 doubles per channel in LDS)
 
 struct GgRow {                     // finalised per (segment, group)
@@ -27,21 +26,6 @@ struct GgRow {                     // finalised per (segment, group)
   float m1, m2;                    // mean(g), mean(g x^)
   float pad2[2];
 };
-
-__device__ __forceinline__ void gg_mean_rstd(const double* __restrict__ stats, int S, int groups, int sg, int g, double cnt, float eps, float* mean_hi,
-                                             float* mean_lo, float* rstd) {
-  double sx = 0.0, sxx = 0.0;
-  for (int rep = 0; rep < GN_REPLICAS; ++rep) {
-    const int64_t o = ((static_cast<int64_t>(rep) * S + sg) * groups + g) * 2;
-    sx += stats[o];
-    sxx += stats[o + 1];
-  }
-  const double m = sx / cnt;
-  const double var = fmax(sxx / cnt - m * m, 0.0);
-  *mean_hi = static_cast<float>(m);
-  *mean_lo = static_cast<float>(m - static_cast<double>(static_cast<float>(m)));
-  *rstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
-}
 
 __device__ __forceinline__ float gg_xhat(float x, float mean_hi, float mean_lo, float rstd) { return fmaf(x - mean_hi, rstd, -(mean_lo * rstd)); }
 __device__ __forceinline__ float gg_dz(float dy, float y, int act, float slope) { return act ? (y > 0.f ? dy : dy * slope) : dy; }
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(256) void k_gg_reduce(const float* __restrict__ x, 
     if (seg == S - 1) slen = N - start;
   }
   const double cnt = static_cast<double>(slen) * gs;
-  for (int g = threadIdx.x; g < groups; g += blockDim.x) gg_mean_rstd(stats, S, groups, seg, g, cnt, eps, &s_mh[g], &s_ml[g], &s_rs[g]);
+  for (int g = threadIdx.x; g < groups; g += blockDim.x) gn_mean_rstd(stats, S, groups, seg, g, cnt, eps, &s_mh[g], &s_ml[g], &s_rs[g]);
   __syncthreads();
   const int Cl = C < 256 ? C : 256;      // channels per slab
   const int RS = 256 / Cl;               // rows side by side
@@ -162,7 +146,7 @@ __global__ __launch_bounds__(256) void k_gg_fold_seg(const float* __restrict__ p
     r.rstd = 0.f;
     r.m1 = r.m2 = 0.f;
     if (slen > 0) {
-      gg_mean_rstd(stats, S, groups, seg, g, cnt, eps, &r.mean_hi, &r.mean_lo, &r.rstd);
+      gn_mean_rstd(stats, S, groups, seg, g, cnt, eps, &r.mean_hi, &r.mean_lo, &r.rstd);
       r.m1 = static_cast<float>(a1 / cnt);
       r.m2 = static_cast<float>(a2 / cnt);
     }
@@ -185,7 +169,7 @@ __global__ __launch_bounds__(256) void k_gg_fold_chan(const double* __restrict__
 __global__ __launch_bounds__(256) void k_gg_apply(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ y,
                                                   const float* __restrict__ dy, int64_t N, int C, int groups, const int64_t* __restrict__ seg_len, int S,
                                                   float slope, int act, const GgRow* __restrict__ table, float* __restrict__ dx, float* __restrict__ dz_out) {
-  __shared__ int64_t s_start[GG_MAX_SEG + 1];
+  __shared__ int64_t s_start[GN_MAX_SEG + 1];
   if (threadIdx.x == 0) {
     int64_t o = 0;
     for (int i = 0; i < S; ++i) {
@@ -246,7 +230,7 @@ static GgLayout gg_layout(void* ws, int64_t N, int C, int groups, int S) {
   return L;
 }
 static bool gg_domain(int64_t N, int C, int groups, int S) {
-  return N >= 0 && C >= 4 && C % 4 == 0 && C <= GG_MAX_C && groups >= 1 && C % groups == 0 && S >= 1 && S <= GG_MAX_SEG && N * (C / 4) < (int64_t(1) << 40);
+  return N >= 0 && C >= 4 && C % 4 == 0 && C <= GG_MAX_C && groups >= 1 && C % groups == 0 && S >= 1 && S <= GN_MAX_SEG && N * (C / 4) < (int64_t(1) << 40);
 }
 
 }  // namespace lcr
@@ -255,7 +239,7 @@ using namespace lcr;
 
 extern "C" int lcr_groupnorm_apply_grad_ws_bytes(int64_t N, int C, int groups, int S, size_t* bytes) {
   if (!bytes || !gg_domain(N, C, groups, S)) {
-    set_error("lcr_groupnorm_apply_grad_ws_bytes: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GG_MAX_SEG);
+    set_error("lcr_groupnorm_apply_grad_ws_bytes: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
     return LCR_EARG;
   }
   *bytes = gg_layout(nullptr, N, C, groups, S).bytes;
@@ -270,7 +254,7 @@ extern "C" int lcr_groupnorm_apply_grad(const float* x, const double* stats, con
     return LCR_EARG;
   }
   if (!gg_domain(N, C, groups, S)) {
-    set_error("lcr_groupnorm_apply_grad: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GG_MAX_SEG);
+    set_error("lcr_groupnorm_apply_grad: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
     return LCR_EARG;
   }
   const GgLayout L = gg_layout(ws, N, C, groups, S);

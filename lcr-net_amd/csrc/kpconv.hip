@@ -16,42 +16,11 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "kpconv.h"
 
 namespace lcr {
 
-constexpr int KP_K = 15;       // kernel points (cfg.backbone.kernel_size)
-constexpr int KP_HMAX = 128;   // neighbour columns supported per query
-constexpr int KP_WAVES = 4;
-
-struct KPoints {
-  float p[KP_K][3];
-};
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-// Query -> workgroup mapping of the gather kernels.  Workgroups go round-robin to the 8 XCDs (id % 8), each with its own,
-// non-coherent L2.  With a plain grid-stride walk all XCDs sweep the (spatially ordered) query list side by side, so every XCD
-// pulls the SAME support rows into its own L2 — the gathered table crosses the fabric up to eight times (PMC: max-pool fetched
-// 445 MB for a 65 MB table).  Here XCD x walks the x-th CONTIGUOUS eighth of the list: its L2 only ever holds that region's rows.
-struct XcdBand {
-  int64_t begin, end, stride;   // this wavefront's first query, the end of its band, the step
-};
-__device__ __forceinline__ XcdBand xcd_band(int64_t M, int wave_in_block, int waves_per_block) {
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;      // the grid is a multiple of 8
-  const int64_t per = (M + 7) / 8;
-  XcdBand b;
-  b.begin = xcd * per + static_cast<int64_t>(slot) * waves_per_block + wave_in_block;
-  b.end = min(M, (xcd + 1) * per);
-  b.stride = static_cast<int64_t>(nslots) * waves_per_block;
-  return b;
-}
 
 // The aggregation kernel.  A lane fetches V = 4 (C >= 64)
 // or 2 (C = 32) CONSECUTIVE channels of its neighbour's row with one 16-B / 8-B load, so a 4-neighbour step of C = 64 is one
@@ -88,14 +57,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const fl
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave index in an SGPR
   const int sub = lane >> 4, col = lane & 15;
   const float inv_sigma = 1.f / sigma;
-  float kx = 0.f, ky = 0.f, kz = 0.f;
-#pragma unroll
-  for (int k = 0; k < KP_K; ++k)
-    if (col == k) {
-      kx = kp.p[k][0];
-      ky = kp.p[k][1];
-      kz = kp.p[k][2];
-    }
+  LCR_KP_SELECT(kp, col, kx, ky, kz);
   const XcdBand band = xcd_band(M, w, KP_WAVES);
   for (int64_t t = band.begin; t < band.end; t += band.stride) {
     const int64_t m = order ? order[t] : t;
@@ -141,7 +103,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const fl
     // 4-neighbour step in a kernel that is VALU-issue-bound for C <= 64.  (Lane column 15 is no kernel point: its influence is
     // garbage, accumulates into row 15 of D and is never stored.)
     if (lane < PAD) s_rel[w][n + lane] = make_float4(1e6f, 1e6f, 1e6f, __uint_as_float(0u));
-    wave_lds_sync();
+    wave_sync();
 
     floatx4 acc[NL][V];
 #pragma unroll
@@ -169,8 +131,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const fl
     // the compiler waited for vmcnt(0) — the load it had just issued — before every MFMA group.
     if (n > 0) {
       auto compute = [&](int s, const float4& pp, const VecT (&ff)[NL]) {
-        const float ex = pp.x - kx, ey = pp.y - ky, ez = pp.z - kz;
-        const float wv = fmaxf(fmaf(-__builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex))), inv_sigma, 1.f), 0.f);
+        const float wv = kp_influence(pp.x, pp.y, pp.z, kx, ky, kz, inv_sigma);
 #pragma unroll
         for (int q = 0; q < NL; ++q)
 #pragma unroll
@@ -224,7 +185,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_vec(const fl
       }
     }
     if (lane == 0) nn[m] = static_cast<float>(cnt > 1 ? cnt : 1);
-    wave_lds_sync();
+    wave_sync();
   }
 }
 
@@ -259,14 +220,7 @@ __global__ __launch_bounds__(KP_WAVES * 64, 3) void k_kpconv_fused32(const float
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 4, col = lane & 15;
   const float inv_sigma = 1.f / sigma;
-  float kx = 0.f, ky = 0.f, kz = 0.f;
-#pragma unroll
-  for (int k = 0; k < KP_K; ++k)
-    if (col == k) {
-      kx = kp.p[k][0];
-      ky = kp.p[k][1];
-      kz = kp.p[k][2];
-    }
+  LCR_KP_SELECT(kp, col, kx, ky, kz);
   const bool real_k = col < KP_K;
   if (threadIdx.x == 0) {
     int64_t o = 0;
@@ -333,7 +287,7 @@ __global__ __launch_bounds__(KP_WAVES * 64, 3) void k_kpconv_fused32(const float
         n += __popcll(mk);
         cnt += __popcll(wave_ballot(positive));
       }
-      wave_lds_sync();
+      wave_sync();
       floatx4 acc[V];
 #pragma unroll
       for (int v = 0; v < V; ++v) acc[v] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -347,8 +301,7 @@ __global__ __launch_bounds__(KP_WAVES * 64, 3) void k_kpconv_fused32(const float
       };
       if (n > 0) {
         auto compute = [&](int st, const float4& pp, const float2& ff) {
-          const float ex = pp.x - kx, ey = pp.y - ky, ez = pp.z - kz;
-          float wv = fmaxf(fmaf(-__builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex))), inv_sigma, 1.f), 0.f);
+          float wv = kp_influence(pp.x, pp.y, pp.z, kx, ky, kz, inv_sigma);
           wv = (real_k && 4 * st + sub < n) ? wv : 0.f;
           acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, ff.x, acc[0], 0, 0, 0);
           acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, ff.y, acc[1], 0, 0, 0);
@@ -380,7 +333,7 @@ __global__ __launch_bounds__(KP_WAVES * 64, 3) void k_kpconv_fused32(const float
         s_nn[ql] = static_cast<float>(cnt > 1 ? cnt : 1);
         s_seg[ql] = sg;
       }
-      wave_lds_sync();
+      wave_sync();
     }
     __syncthreads();
     // ---- 2. contraction of the tile with this wavefront's 120 weight rows
@@ -541,10 +494,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_cin1(const float* __re
       a[15] += f > 0.f ? 1.f : 0.f;              // neighbour count rides along as the 16th value (exact: small integers)
       const float dx = px - qx, dy = py - qy, dz = pz - qz;
 #pragma unroll
-      for (int k = 0; k < KP_K; ++k) {
-        const float ex = dx - kp.p[k][0], ey = dy - kp.p[k][1], ez = dz - kp.p[k][2];
-        a[k] = fmaf(fmaxf(fmaf(-__builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex))), inv_sigma, 1.f), 0.f), f, a[k]);
-      }
+      for (int k = 0; k < KP_K; ++k) a[k] = fmaf(kp_influence(dx, dy, dz, kp.p[k][0], kp.p[k][1], kp.p[k][2], inv_sigma), f, a[k]);
     };
     if (r0.j >= 0 && r0.j < Ns) add(n0.f, n0.x, n0.y, n0.z);
     for (int h = lane + 64; h < H; h += 64) {      // neighbour columns beyond 64: not prefetched
@@ -568,7 +518,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_cin1(const float* __re
       b1 += __shfl_xor(b1, 1);
       if ((lane & 3) == 0) s_a[w][(u5 ? 8 : 0) + (u4 ? 4 : 0) + (u3 ? 2 : 0) + (u2 ? 1 : 0)] = b1;
     }
-    wave_lds_sync();
+    wave_sync();
     const float cntf = s_a[w][15];
     const float div = cntf > 1.f ? cntf : 1.f;
     float av[KP_K];
@@ -586,7 +536,7 @@ __global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_cin1(const float* __re
         out[m * Cout + o] = v;
       }
     }
-    wave_lds_sync();
+    wave_sync();
     r0 = r1;
     n0 = n1;
     r1 = r2;
@@ -614,7 +564,7 @@ __global__ __launch_bounds__(256) void k_maxpool(const float* __restrict__ x, co
       any_shadow |= (wave_ballot(h < H && !ok) != 0ull);
       n += __popcll(mk);
     }
-    wave_lds_sync();
+    wave_sync();
     const float init = any_shadow ? 0.f : -INFINITY;
     if ((C & 255) == 0) {
       // a lane owns 4 consecutive channels per 256-channel slab: one 16-B load per gathered row instead of four 4-B ones
@@ -664,7 +614,7 @@ __global__ __launch_bounds__(256) void k_maxpool(const float* __restrict__ x, co
         out[m * C + c] = v;
       }
     }
-    wave_lds_sync();
+    wave_sync();
   }
 }
 
@@ -679,19 +629,7 @@ __global__ __launch_bounds__(256) void k_row_pos(const float* __restrict__ x, in
   }
 }
 
-static KPoints load_kp(const float* kp_host) {
-  KPoints k;
-  for (int i = 0; i < KP_K; ++i)
-    for (int d = 0; d < 3; ++d) k.p[i][d] = kp_host[3 * i + d];
-  return k;
-}
-
 static int grid_for(int64_t rows, int per_block) { return static_cast<int>(std::min<int64_t>((rows + per_block - 1) / per_block, 256 * 16)); }
-// gather kernels (xcd_band): a multiple of 8 workgroups, enough for every XCD's eighth of the rows
-static int grid_for_xcd(int64_t rows, int per_block) {
-  const int64_t per_xcd = ((rows + 7) / 8 + per_block - 1) / per_block;
-  return 8 * static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(per_xcd, 256 * 2)));
-}
 
 static int g_agg_force_off64 = 0;          // tests: run the 64-bit-offset form of the aggregation (tensors of 2^30 elements and more)
 

@@ -6,52 +6,14 @@
 // sums what its edges send, in list order.  No floating-point atomics: a row's sum has one order, results repeat to the bit, and a
 // cloud's rows get the same bytes alone and inside a stack (its edges keep their relative order).
 //
-// The influence w(m,h,k) = max(0, 1 - |s_n - q_m - kp_k| / sigma) is evaluated operation for operation as k_kpconv_aggregate_vec and
-// k_kpconv_cin1 do: (s - q) - kp per component, fma(ez, ez, fma(ey, ey, ex * ex)), v_sqrt_f32, fma(-d, 1/sigma, 1), max with 0.
+// The influence w(m,h,k) = max(0, 1 - |s_n - q_m - kp_k| / sigma) is kpconv.h's kp_influence / kp_edge, the functions the forward's
+// k_kpconv_aggregate_vec, k_kpconv_fused32 and k_kpconv_cin1 call; the rows are walked in the forward's xcd_band.
 #include <algorithm>
 
-#include "common.h"
+#include "kpconv.h"
 #include "radix_sort.h"
 
 namespace lcr {
-
-constexpr int KG_K = 15;        // kernel points
-constexpr int KG_HMAX = 128;    // neighbour columns per query (the forward's domain)
-constexpr int KG_WAVES = 4;
-
-struct KGPoints {
-  float p[KG_K][3];
-};
-static KGPoints kg_load_kp(const float* kp_host) {
-  KGPoints k;
-  for (int i = 0; i < KG_K; ++i)
-    for (int d = 0; d < 3; ++d) k.p[i][d] = kp_host[3 * i + d];
-  return k;
-}
-
-// Row -> workgroup mapping, the same as kpconv.hip's xcd_band: XCD x (workgroup id % 8) walks the x-th contiguous eighth of the rows,
-// so a region's dA rows are pulled into one L2 only.
-struct KGBand {
-  int64_t begin, end, stride;
-};
-__device__ __forceinline__ KGBand kg_band(int64_t rows, int wave_in_block, int waves_per_block) {
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;      // the grid is a multiple of 8
-  const int64_t per = (rows + 7) / 8;
-  KGBand b;
-  b.begin = xcd * per + static_cast<int64_t>(slot) * waves_per_block + wave_in_block;
-  b.end = min(rows, (xcd + 1) * per);
-  b.stride = static_cast<int64_t>(nslots) * waves_per_block;
-  return b;
-}
-static int kg_grid_xcd(int64_t rows, int per_block) {
-  const int64_t per_xcd = ((rows + 7) / 8 + per_block - 1) / per_block;
-  return 8 * static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(per_xcd, 256 * 2)));
-}
-
-__device__ __forceinline__ float kg_influence(float dx, float dy, float dz, float kx, float ky, float kz, float inv_sigma) {
-  const float ex = dx - kx, ey = dy - ky, ez = dz - kz;
-  return fmaxf(fmaf(-__builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex))), inv_sigma, 1.f), 0.f);
-}
 
 // ---- inverted neighbour list ---------------------------------------------------------------------------------------------------
 template <typename IdxT>
@@ -114,10 +76,10 @@ static NtLayout nt_layout(void* ws, int64_t E) {
 // a ballot names the non-zero ones and only their dA blocks are read: up to 4 G block loads are issued before the first is used.  The
 // next trip's edge numbers and query points are fetched before this trip's blocks.
 template <int C>
-__global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const float* __restrict__ dA, const float* __restrict__ q_pts,
+__global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_aggregate_grad(const float* __restrict__ dA, const float* __restrict__ q_pts,
                                                                          const float* __restrict__ s_pts, const int32_t* __restrict__ row_start,
                                                                          const uint32_t* __restrict__ edges, int64_t M, int64_t Ns, int H,
-                                                                         KGPoints kp, float sigma, float* __restrict__ out) {
+                                                                         KPoints kp, float sigma, float* __restrict__ out) {
   constexpr int V = C >= 64 ? C / 64 : 1;
   constexpr int G = C >= 64 ? 1 : 2;           // terms taken side by side
   constexpr int U = 4;                          // block loads in flight per lane
@@ -126,16 +88,9 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const f
   const int grp = G == 1 ? 0 : lane >> 5;
   const int ch = G == 1 ? lane * V : (lane & 31);
   const float inv_sigma = 1.f / sigma;
-  float kx = 0.f, ky = 0.f, kz = 0.f;
-#pragma unroll
-  for (int k = 0; k < KG_K; ++k)
-    if (col == k) {
-      kx = kp.p[k][0];
-      ky = kp.p[k][1];
-      kz = kp.p[k][2];
-    }
+  LCR_KP_SELECT(kp, col, kx, ky, kz);
   const uint32_t MH = static_cast<uint32_t>(M * H);        // host-checked: M * H < 2^30
-  const KGBand band = kg_band(Ns, w, KG_WAVES);
+  const XcdBand band = xcd_band(Ns, w, KP_WAVES);
   for (int64_t n = band.begin; n < band.end; n += band.stride) {
     int b = row_start[n], e = row_start[n + 1];
     b = max(0, min(b, static_cast<int>(MH)));
@@ -163,7 +118,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const f
     if (b < e) header(b, cur);
     for (int p = b; p < e; p += 4) {
       if (p + 4 < e) header(p + 4, nxt);
-      float wv = kg_influence(sx - cur.qx, sy - cur.qy, sz - cur.qz, kx, ky, kz, inv_sigma);
+      float wv = kp_influence(sx - cur.qx, sy - cur.qy, sz - cur.qz, kx, ky, kz, inv_sigma);
       if (!cur.ok || col == 15) wv = 0.f;
       uint64_t mask = wave_ballot(wv > 0.f);
       while (mask) {                                       // wave-uniform
@@ -189,7 +144,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const f
             mm = __shfl(cur.m, src);
           }
           wu[u] = mine < 0 ? 0.f : ww;
-          const float* row = dA + (static_cast<int64_t>(mm) * KG_K + (src & 15)) * C + ch;
+          const float* row = dA + (static_cast<int64_t>(mm) * KP_K + (src & 15)) * C + ch;
           if (V == 4) {
             const float4 t = *reinterpret_cast<const float4*>(row);
             val[u][0] = t.x, val[u][1 % V] = t.y, val[u][2 % V] = t.z, val[u][3 % V] = t.w;
@@ -235,17 +190,10 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_aggregate_grad(const f
 // v goes to the [M,H,3] workspace, d_q[m] is the sum of the row's v in column order.  k_kpconv_points_grad_s, one wavefront per support
 // row, then sums -v over the row's inverted list: lane l takes the list positions l, l + 64, ... in order and the lanes are folded once.
 // C = 32: the upper half of the wavefront holds zeros.
-__device__ __forceinline__ void kg_edge(float dx, float dy, float dz, float kx, float ky, float kz, float inv_sigma, float& ex, float& ey, float& ez,
-                                        float& r, float& w) {
-  ex = dx - kx, ey = dy - ky, ez = dz - kz;                // the operations of kg_influence, with e and r kept
-  r = __builtin_amdgcn_sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-  w = fmaxf(fmaf(-r, inv_sigma, 1.f), 0.f);
-}
-
 template <int C, typename IdxT>
-__global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const float* __restrict__ dA, const float* __restrict__ s_feats,
+__global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_points_grad(const float* __restrict__ dA, const float* __restrict__ s_feats,
                                                                       const float* __restrict__ q_pts, const float* __restrict__ s_pts,
-                                                                      const IdxT* __restrict__ idx, int64_t M, int64_t Ns, int H, KGPoints kp,
+                                                                      const IdxT* __restrict__ idx, int64_t M, int64_t Ns, int H, KPoints kp,
                                                                       float sigma, float* __restrict__ v_ws, float* __restrict__ d_q) {
   constexpr int V = C >= 64 ? C / 64 : 1;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -253,14 +201,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const floa
   const bool has = C >= 64 || lane < 32;
   const int ch = C >= 64 ? lane * V : (lane & 31);
   const float inv_sigma = 1.f / sigma;
-  float kx = 0.f, ky = 0.f, kz = 0.f;
-#pragma unroll
-  for (int k = 0; k < KG_K; ++k)
-    if (col == k) {
-      kx = kp.p[k][0];
-      ky = kp.p[k][1];
-      kz = kp.p[k][2];
-    }
+  LCR_KP_SELECT(kp, col, kx, ky, kz);
   auto load_row = [&](const float* row, float (&dst)[V]) {
     if (V == 4) {
       const float4 t = *reinterpret_cast<const float4*>(row);
@@ -272,14 +213,14 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const floa
       dst[0] = *row;
     }
   };
-  const KGBand band = kg_band(M, w, KG_WAVES);
+  const XcdBand band = xcd_band(M, w, KP_WAVES);
   for (int64_t m = band.begin; m < band.end; m += band.stride) {
-    float g[KG_K][V];
+    float g[KP_K][V];
 #pragma unroll
-    for (int k = 0; k < KG_K; ++k) {
+    for (int k = 0; k < KP_K; ++k) {
 #pragma unroll
       for (int v = 0; v < V; ++v) g[k][v] = 0.f;
-      if (has) load_row(dA + (m * KG_K + k) * C + ch, g[k]);
+      if (has) load_row(dA + (m * KP_K + k) * C + ch, g[k]);
     }
     int jrow[2];                                           // the row's indices, column lane + 64 i; -1 = padding
 #pragma unroll
@@ -296,8 +237,8 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const floa
       if (j >= 0) {
         const int64_t n = j;
         float ex, ey, ez, r, wv;
-        kg_edge(s_pts[3 * n] - qx, s_pts[3 * n + 1] - qy, s_pts[3 * n + 2] - qz, kx, ky, kz, inv_sigma, ex, ey, ez, r, wv);
-        const uint64_t mask = wave_ballot(lane < KG_K && wv > 0.f && r > 0.f);
+        kp_edge(s_pts[3 * n] - qx, s_pts[3 * n + 1] - qy, s_pts[3 * n + 2] - qz, kx, ky, kz, inv_sigma, ex, ey, ez, r, wv);
+        const uint64_t mask = wave_ballot(lane < KP_K && wv > 0.f && r > 0.f);
         if (mask) {                                        // wave-uniform
           const float cs = 1.f / (sigma * r);              // lanes outside the mask are never read
           const float cx = ex * cs, cy = ey * cs, cz = ez * cs;
@@ -307,7 +248,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const floa
           if (has) load_row(s_feats + n * C + ch, f);
           float px = 0.f, py = 0.f, pz = 0.f;
 #pragma unroll
-          for (int k = 0; k < KG_K; ++k)
+          for (int k = 0; k < KP_K; ++k)
             if ((mask >> k) & 1) {
               float p = 0.f;
 #pragma unroll
@@ -330,12 +271,12 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad(const floa
   }
 }
 
-__global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad_s(const float* __restrict__ v_ws, const int32_t* __restrict__ row_start,
+__global__ __launch_bounds__(KP_WAVES * 64) void k_kpconv_points_grad_s(const float* __restrict__ v_ws, const int32_t* __restrict__ row_start,
                                                                         const uint32_t* __restrict__ edges, int64_t M, int64_t Ns, int H,
                                                                         float* __restrict__ d_s) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t MH = static_cast<uint32_t>(M * H);
-  const KGBand band = kg_band(Ns, w, KG_WAVES);
+  const XcdBand band = xcd_band(Ns, w, KP_WAVES);
   for (int64_t n = band.begin; n < band.end; n += band.stride) {
     int b = row_start[n], e = row_start[n + 1];
     b = max(0, min(b, static_cast<int>(MH)));
@@ -363,10 +304,10 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_kpconv_points_grad_s(const fl
 constexpr int CG_ROWS = 256;
 
 template <typename IdxT, int MAXO>
-__global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_partial(const float* __restrict__ d_out, const float* __restrict__ s_feats,
+__global__ __launch_bounds__(KP_WAVES * 64) void k_cin1_grad_partial(const float* __restrict__ d_out, const float* __restrict__ s_feats,
                                                                      const float* __restrict__ q_pts, const float* __restrict__ s_pts,
                                                                      const IdxT* __restrict__ idx, const float* __restrict__ nn_saved, int64_t M, int64_t Ns,
-                                                                     int H, KGPoints kp, float sigma, const float* __restrict__ W, int Cout,
+                                                                     int H, KPoints kp, float sigma, const float* __restrict__ W, int Cout,
                                                                      float* __restrict__ part, float* __restrict__ gk) {
   __shared__ float s_fold[16][64 * MAXO];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -377,7 +318,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_partial(const float
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[q][k] = 0.f;
   const int64_t m_lo = static_cast<int64_t>(blockIdx.x) * CG_ROWS, m_hi = min(M, m_lo + CG_ROWS);
-  for (int64_t m = m_lo + w; m < m_hi; m += KG_WAVES) {
+  for (int64_t m = m_lo + w; m < m_hi; m += KP_WAVES) {
     const float qx = q_pts[3 * m], qy = q_pts[3 * m + 1], qz = q_pts[3 * m + 2];
     float a[16];
 #pragma unroll
@@ -389,38 +330,38 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_partial(const float
         a[15] += f > 0.f ? 1.f : 0.f;
         const float dx = s_pts[3 * j] - qx, dy = s_pts[3 * j + 1] - qy, dz = s_pts[3 * j + 2] - qz;
 #pragma unroll
-        for (int k = 0; k < KG_K; ++k) a[k] = fmaf(kg_influence(dx, dy, dz, kp.p[k][0], kp.p[k][1], kp.p[k][2], inv_sigma), f, a[k]);
+        for (int k = 0; k < KP_K; ++k) a[k] = fmaf(kp_influence(dx, dy, dz, kp.p[k][0], kp.p[k][1], kp.p[k][2], inv_sigma), f, a[k]);
       }
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = wave_sum(a[k]);
     const float cnt = nn_saved ? nn_saved[m] : a[15];
     const float div = cnt > 1.f ? cnt : 1.f;
-    float gsum[KG_K];
+    float gsum[KP_K];
 #pragma unroll
-    for (int k = 0; k < KG_K; ++k) gsum[k] = 0.f;
+    for (int k = 0; k < KP_K; ++k) gsum[k] = 0.f;
 #pragma unroll
     for (int q = 0; q < MAXO; ++q) {
       const int o = lane + 64 * q;
       const float g = o < Cout ? d_out[m * Cout + o] : 0.f;
       const float gd = g / div;
 #pragma unroll
-      for (int k = 0; k < KG_K; ++k) acc[q][k] = fmaf(a[k], gd, acc[q][k]);
+      for (int k = 0; k < KP_K; ++k) acc[q][k] = fmaf(a[k], gd, acc[q][k]);
       acc[q][15] += g;
       if (gk) {
 #pragma unroll
-        for (int k = 0; k < KG_K; ++k) gsum[k] = fmaf(o < Cout ? W[k * Cout + o] : 0.f, gd, gsum[k]);
+        for (int k = 0; k < KP_K; ++k) gsum[k] = fmaf(o < Cout ? W[k * Cout + o] : 0.f, gd, gsum[k]);
       }
     }
     if (gk) {                                            // gk[m][k] = sum_o W[k][o] dOut[m][o] / div: what d_s_feats gathers
 #pragma unroll
-      for (int k = 0; k < KG_K; ++k) {
+      for (int k = 0; k < KP_K; ++k) {
         const float t = wave_sum(gsum[k]);
         if (lane == 0) gk[m * 16 + k] = t;
       }
     }
   }
-  for (int ww = 0; ww < KG_WAVES; ++ww) {                  // the wavefronts add their sums one after the other, wavefront 0 first
+  for (int ww = 0; ww < KP_WAVES; ++ww) {                  // the wavefronts add their sums one after the other, wavefront 0 first
     if (w == ww) {
 #pragma unroll
       for (int q = 0; q < MAXO; ++q)
@@ -442,19 +383,19 @@ __global__ __launch_bounds__(256) void k_cin1_grad_fold(const float* __restrict_
   double t = 0.0;
   for (int b = 0; b < nblk; ++b) t += static_cast<double>(part[static_cast<int64_t>(b) * 16 * Cout + i]);
   const int k = i / Cout, o = i - k * Cout;
-  if (k < KG_K) dW[k * Cout + o] = static_cast<float>(t);
+  if (k < KP_K) dW[k * Cout + o] = static_cast<float>(t);
   else if (dbias) dbias[o] = static_cast<float>(t);
 }
 
 // d_s_feats[n] = sum over the edges (m,h) of n, sum_k w(m,h,k) gk[m][k]: one wavefront per support, lanes = edges, folded once per row
-__global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_feats(const float* __restrict__ gk, const float* __restrict__ q_pts,
+__global__ __launch_bounds__(KP_WAVES * 64) void k_cin1_grad_feats(const float* __restrict__ gk, const float* __restrict__ q_pts,
                                                                    const float* __restrict__ s_pts, const int32_t* __restrict__ row_start,
-                                                                   const uint32_t* __restrict__ edges, int64_t M, int64_t Ns, int H, KGPoints kp,
+                                                                   const uint32_t* __restrict__ edges, int64_t M, int64_t Ns, int H, KPoints kp,
                                                                    float sigma, float* __restrict__ out) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const float inv_sigma = 1.f / sigma;
   const uint32_t MH = static_cast<uint32_t>(M * H);
-  const KGBand band = kg_band(Ns, w, KG_WAVES);
+  const XcdBand band = xcd_band(Ns, w, KP_WAVES);
   for (int64_t n = band.begin; n < band.end; n += band.stride) {
     int b = row_start[n], e = row_start[n + 1];
     b = max(0, min(b, static_cast<int>(MH)));
@@ -467,7 +408,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_feats(const float* 
       const int64_t m = ed / static_cast<uint32_t>(H);
       const float dx = sx - q_pts[3 * m], dy = sy - q_pts[3 * m + 1], dz = sz - q_pts[3 * m + 2];
 #pragma unroll
-      for (int k = 0; k < KG_K; ++k) t = fmaf(kg_influence(dx, dy, dz, kp.p[k][0], kp.p[k][1], kp.p[k][2], inv_sigma), gk[m * 16 + k], t);
+      for (int k = 0; k < KP_K; ++k) t = fmaf(kp_influence(dx, dy, dz, kp.p[k][0], kp.p[k][1], kp.p[k][2], inv_sigma), gk[m * 16 + k], t);
     }
     t = wave_sum(t);
     if (lane == 0) out[n] = t;
@@ -480,7 +421,7 @@ __global__ __launch_bounds__(KG_WAVES * 64) void k_cin1_grad_feats(const float* 
 template <typename IdxT>
 __global__ __launch_bounds__(256) void k_maxpool_winners(const float* __restrict__ x, const IdxT* __restrict__ idx, const float* __restrict__ pooled,
                                                          int64_t M, int64_t Ns, int H, int C, uint8_t* __restrict__ winners) {
-  __shared__ int32_t s_idx[4][KG_HMAX];
+  __shared__ int32_t s_idx[4][KP_HMAX];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   for (int64_t m = static_cast<int64_t>(blockIdx.x) * 4 + w; m < M; m += static_cast<int64_t>(gridDim.x) * 4) {
     for (int h = lane; h < H; h += 64) {
@@ -506,7 +447,7 @@ __global__ __launch_bounds__(256) void k_maxpool_grad(const float* __restrict__ 
                                                       int H, int C, float* __restrict__ dx) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t MH = static_cast<uint32_t>(M * H);
-  const KGBand band = kg_band(Ns, w, 4);
+  const XcdBand band = xcd_band(Ns, w, 4);
   for (int64_t n = band.begin; n < band.end; n += band.stride) {
     int b = row_start[n], e = row_start[n + 1];
     b = max(0, min(b, static_cast<int>(MH)));
@@ -525,7 +466,7 @@ __global__ __launch_bounds__(256) void k_maxpool_grad(const float* __restrict__ 
 }
 
 static bool list_args_ok(int64_t M, int64_t Ns, int H) {
-  return M >= 0 && Ns >= 0 && Ns < (int64_t(1) << 31) - 1 && H >= 1 && H <= KG_HMAX && M * H < (int64_t(1) << 30);
+  return M >= 0 && Ns >= 0 && Ns < (int64_t(1) << 31) - 1 && H >= 1 && H <= KP_HMAX && M * H < (int64_t(1) << 30);
 }
 
 }  // namespace lcr
@@ -533,8 +474,8 @@ static bool list_args_ok(int64_t M, int64_t Ns, int H) {
 using namespace lcr;
 
 extern "C" int lcr_neighbor_transpose_ws_bytes(int64_t M, int H, size_t* bytes) {
-  if (!bytes || M < 0 || H < 1 || H > KG_HMAX || M * H >= (int64_t(1) << 30)) {
-    set_error("lcr_neighbor_transpose_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KG_HMAX);
+  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30)) {
+    set_error("lcr_neighbor_transpose_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
     return LCR_EARG;
   }
   *bytes = nt_layout(nullptr, M * H).bytes;
@@ -544,7 +485,7 @@ extern "C" int lcr_neighbor_transpose_ws_bytes(int64_t M, int H, size_t* bytes) 
 extern "C" int lcr_neighbor_transpose(const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int32_t* row_start, uint32_t* edges,
                                       void* ws, size_t ws_bytes, void* stream) {
   if (!idx || !row_start || !edges || !ws || !list_args_ok(M, Ns, H)) {
-    set_error("lcr_neighbor_transpose: bad argument (H in [1,%d], M * H < 2^30, Ns < 2^31 - 1)", KG_HMAX);
+    set_error("lcr_neighbor_transpose: bad argument (H in [1,%d], M * H < 2^30, Ns < 2^31 - 1)", KP_HMAX);
     return LCR_EARG;
   }
   const int64_t E = M * H;
@@ -572,7 +513,7 @@ extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, co
                                          int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma, float* d_s_feats,
                                          void* stream) {
   if (!dA || !q_pts || !s_pts || !row_start || !edges || !kernel_points_host || !d_s_feats || !list_args_ok(M, Ns, H) || !(sigma > 0.f)) {
-    set_error("lcr_kpconv_aggregate_grad: bad argument (H in [1,%d], M * H < 2^30)", KG_HMAX);
+    set_error("lcr_kpconv_aggregate_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
     return LCR_EARG;
   }
   if (C != 32 && C != 64 && C != 128 && C != 256) {
@@ -580,9 +521,9 @@ extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, co
     return LCR_EARG;
   }
   if (Ns == 0) return LCR_OK;
-  const KGPoints kp = kg_load_kp(kernel_points_host);
+  const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
-  dim3 grid(kg_grid_xcd(Ns, KG_WAVES)), block(KG_WAVES * 64);
+  dim3 grid(grid_for_xcd(Ns, KP_WAVES)), block(KP_WAVES * 64);
 #define LCR_AGG_GRAD(CC) \
   hipLaunchKernelGGL((k_kpconv_aggregate_grad<CC>), grid, block, 0, st, dA, q_pts, s_pts, row_start, edges, M, Ns, H, kp, sigma, d_s_feats)
   switch (C) {
@@ -598,8 +539,8 @@ extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, co
 static size_t points_grad_bytes(int64_t M, int H) { return align_up(static_cast<size_t>(std::max<int64_t>(M * H, 1)) * 3 * sizeof(float)); }
 
 extern "C" int lcr_kpconv_points_grad_ws_bytes(int64_t M, int H, size_t* bytes) {
-  if (!bytes || M < 0 || H < 1 || H > KG_HMAX || M * H >= (int64_t(1) << 30)) {
-    set_error("lcr_kpconv_points_grad_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KG_HMAX);
+  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30)) {
+    set_error("lcr_kpconv_points_grad_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
     return LCR_EARG;
   }
   *bytes = points_grad_bytes(M, H);
@@ -611,7 +552,7 @@ extern "C" int lcr_kpconv_points_grad(const float* dA, const float* s_feats, con
                                       const float* kernel_points_host, float sigma, float* d_q, float* d_s, void* ws, size_t ws_bytes, void* stream) {
   if (!list_args_ok(M, Ns, H) || !kernel_points_host || !(sigma > 0.f) || (M > 0 && (!dA || !q_pts || !idx)) || (Ns > 0 && (!s_feats || !s_pts)) ||
       (d_s && (!row_start || !edges || !ws))) {
-    set_error("lcr_kpconv_points_grad: bad argument (H in [1,%d], M * H < 2^30; d_s needs the inverted list and the workspace)", KG_HMAX);
+    set_error("lcr_kpconv_points_grad: bad argument (H in [1,%d], M * H < 2^30; d_s needs the inverted list and the workspace)", KP_HMAX);
     return LCR_EARG;
   }
   if (C != 32 && C != 64 && C != 128 && C != 256) {
@@ -623,11 +564,11 @@ extern "C" int lcr_kpconv_points_grad(const float* dA, const float* s_feats, con
     return LCR_EARG;
   }
   if ((!d_q && !d_s) || (M == 0 && (Ns == 0 || !d_s))) return LCR_OK;
-  const KGPoints kp = kg_load_kp(kernel_points_host);
+  const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
   float* v_ws = d_s ? static_cast<float*>(ws) : nullptr;
   if (M > 0) {
-    dim3 grid(kg_grid_xcd(M, KG_WAVES)), block(KG_WAVES * 64);
+    dim3 grid(grid_for_xcd(M, KP_WAVES)), block(KP_WAVES * 64);
 #define LCR_PTS_GRAD(CC)                                                                                                                                   \
   do {                                                                                                                                                     \
     if (idx_is_64) hipLaunchKernelGGL((k_kpconv_points_grad<CC, int64_t>), grid, block, 0, st, dA, s_feats, q_pts, s_pts, static_cast<const int64_t*>(idx), \
@@ -644,7 +585,7 @@ extern "C" int lcr_kpconv_points_grad(const float* dA, const float* s_feats, con
 #undef LCR_PTS_GRAD
   }
   if (d_s && Ns > 0)                                       // M == 0: every list is empty and the rows are zeroed
-    hipLaunchKernelGGL(k_kpconv_points_grad_s, dim3(kg_grid_xcd(Ns, KG_WAVES)), dim3(KG_WAVES * 64), 0, st, v_ws, row_start, edges, M, Ns, H, d_s);
+    hipLaunchKernelGGL(k_kpconv_points_grad_s, dim3(grid_for_xcd(Ns, KP_WAVES)), dim3(KP_WAVES * 64), 0, st, v_ws, row_start, edges, M, Ns, H, d_s);
   return check_launch("lcr_kpconv_points_grad");
 }
 
@@ -668,20 +609,20 @@ extern "C" int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, co
                                     float* d_s_feats, void* ws, size_t ws_bytes, void* stream) {
   if (!d_out || !s_feats || !q_pts || !s_pts || !idx || !kernel_points_host || !W || !dW || !ws || !list_args_ok(M, Ns, H) || Cout < 1 ||
       Cout > 256 || !(sigma > 0.f) || (d_s_feats && (!row_start || !edges))) {
-    set_error("lcr_kpconv_cin1_grad: bad argument (Cout in [1,256], H in [1,%d]; d_s_feats needs the inverted list)", KG_HMAX);
+    set_error("lcr_kpconv_cin1_grad: bad argument (Cout in [1,256], H in [1,%d]; d_s_feats needs the inverted list)", KP_HMAX);
     return LCR_EARG;
   }
   if (ws_bytes < cin1_grad_bytes(M, Cout, d_s_feats != nullptr)) {
     set_error("lcr_kpconv_cin1_grad: workspace of %zu bytes, %zu needed", ws_bytes, cin1_grad_bytes(M, Cout, d_s_feats != nullptr));
     return LCR_EARG;
   }
-  const KGPoints kp = kg_load_kp(kernel_points_host);
+  const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
   const int nblk = static_cast<int>(std::max<int64_t>(1, (M + CG_ROWS - 1) / CG_ROWS));
   float* part = static_cast<float*>(ws);
   float* gk = d_s_feats ? reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(static_cast<size_t>(nblk) * 16 * Cout * sizeof(float))) : nullptr;
 #define LCR_CIN1_GRAD(IDX, MAXO)                                                                                                                  \
-  hipLaunchKernelGGL((k_cin1_grad_partial<IDX, MAXO>), dim3(nblk), dim3(KG_WAVES * 64), 0, st, d_out, s_feats, q_pts, s_pts, static_cast<const IDX*>(idx), nn, \
+  hipLaunchKernelGGL((k_cin1_grad_partial<IDX, MAXO>), dim3(nblk), dim3(KP_WAVES * 64), 0, st, d_out, s_feats, q_pts, s_pts, static_cast<const IDX*>(idx), nn, \
                      M, Ns, H, kp, sigma, W, Cout, part, gk)
   if (idx_is_64) {
     if (Cout <= 64) LCR_CIN1_GRAD(int64_t, 1);
@@ -693,7 +634,7 @@ extern "C" int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, co
 #undef LCR_CIN1_GRAD
   hipLaunchKernelGGL(k_cin1_grad_fold, dim3((16 * Cout + 255) / 256), dim3(256), 0, st, part, nblk, Cout, dW, dbias);
   if (d_s_feats && Ns > 0)
-    hipLaunchKernelGGL(k_cin1_grad_feats, dim3(kg_grid_xcd(Ns, KG_WAVES)), dim3(KG_WAVES * 64), 0, st, gk, q_pts, s_pts, row_start, edges, M, Ns, H, kp, sigma,
+    hipLaunchKernelGGL(k_cin1_grad_feats, dim3(grid_for_xcd(Ns, KP_WAVES)), dim3(KP_WAVES * 64), 0, st, gk, q_pts, s_pts, row_start, edges, M, Ns, H, kp, sigma,
                        d_s_feats);
   return check_launch("lcr_kpconv_cin1_grad");
 }
@@ -701,7 +642,7 @@ extern "C" int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, co
 extern "C" int lcr_maxpool_grad(const float* d_out, const float* x, const float* pooled, const void* idx, int idx_is_64, const int32_t* row_start,
                                 const uint32_t* edges, int64_t M, int64_t Ns, int H, int C, uint8_t* winners, float* d_x, void* stream) {
   if (!d_out || !x || !pooled || !idx || !row_start || !edges || !winners || !d_x || !list_args_ok(M, Ns, H) || C < 1) {
-    set_error("lcr_maxpool_grad: bad argument (H in [1,%d], M * H < 2^30)", KG_HMAX);
+    set_error("lcr_maxpool_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
     return LCR_EARG;
   }
   hipStream_t st = ST(stream);
@@ -710,6 +651,6 @@ extern "C" int lcr_maxpool_grad(const float* d_out, const float* x, const float*
     if (idx_is_64) hipLaunchKernelGGL((k_maxpool_winners<int64_t>), dim3(grid), dim3(256), 0, st, x, static_cast<const int64_t*>(idx), pooled, M, Ns, H, C, winners);
     else hipLaunchKernelGGL((k_maxpool_winners<int32_t>), dim3(grid), dim3(256), 0, st, x, static_cast<const int32_t*>(idx), pooled, M, Ns, H, C, winners);
   }
-  if (Ns > 0) hipLaunchKernelGGL(k_maxpool_grad, dim3(kg_grid_xcd(Ns, 4)), dim3(256), 0, st, d_out, winners, row_start, edges, M, Ns, H, C, d_x);
+  if (Ns > 0) hipLaunchKernelGGL(k_maxpool_grad, dim3(grid_for_xcd(Ns, 4)), dim3(256), 0, st, d_out, winners, row_start, edges, M, Ns, H, C, d_x);
   return check_launch("lcr_maxpool_grad");
 }

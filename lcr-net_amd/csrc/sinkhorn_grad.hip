@@ -13,29 +13,14 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "sinkhorn.h"
 
 namespace lcr {
 namespace skg {
 
-constexpr float LOG2E = 1.44269504088896341f;
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }     // v_exp_f32
-__device__ __forceinline__ float log2_hw(float x) { return __builtin_amdgcn_logf(x); }      // v_log_f32
-__device__ __forceinline__ float quad_max(float x) {
-  x = fmaxf(x, dpp0<DPP_QUAD_1032>(x));
-  return fmaxf(x, dpp0<DPP_QUAD_2301>(x));
-}
-__device__ __forceinline__ float quad_sum(float x) {
-  x += dpp0<DPP_QUAD_1032>(x);
-  return x + dpp0<DPP_QUAD_2301>(x);
-}
-
 // ---- resident form: M + 1, N + 1 <= 132 (the 129 x 129 patch problems), one workgroup per problem ------------------------------------
-// The forward's register layout (k_log_sinkhorn_reg): four threads per line, thread (line, part) holds entries 8k + part and 8k + 4 + part
-// of its row in R AND of its column in C, in base-2 logarithms.  A reverse half-step needs one sum along the line that its softmax is NOT
-// normalised over — du_i -= sum_j Pc_ij dv_j runs along row i, dv_j = -sum_i Pr_ij du_i along column j — so the v-step terms are formed
+// The forward's register layout (sinkhorn.h; the duals are recomputed with its skr_lse2), R for the row and C for the column of a
+// thread.  A reverse half-step needs one sum along the line that its softmax is NOT normalised over — du_i -= sum_j Pc_ij dv_j runs along row i, dv_j = -sum_i Pr_ij du_i along column j — so the v-step terms are formed
 // and accumulated in the row layout (dSr) and the u-step terms in the column layout (dSc): both sums are quad folds, nothing is transposed
 // per step, and the two accumulators meet once at the end (dS = G - dSr - dSc^T, the column part through the output buffer).  Per entry and
 // half-step: three LDS reads (the recorded dual, and {log marginal, dv or du} as one 8-byte pair), three adds, one exponential, one
@@ -44,38 +29,17 @@ __device__ __forceinline__ float quad_sum(float x) {
 // (T <= 140; 109 KB at T = 100): the four accumulator copies already hold the kernel at 3 wavefronts per SIMD, i.e. one workgroup per CU, so
 // the LDS costs no occupancy, and every half-step reads 33 duals per thread that would otherwise be dependent L2 loads.  Longer iteration
 // counts record into the caller's workspace instead (same code, HIST_LDS = false).
-constexpr int GR_E = 33;                  // entries per thread
-constexpr int GR_LINES = 4 * GR_E;        // 132 rows / columns at most
-constexpr int GR_T = 576;                 // 9 wavefronts >= 4 * 132 threads
-constexpr int GR_P = (GR_E + 1) / 2;      // entry pairs per thread
 constexpr int GR_LS = 136;                // floats per recorded line: pair reads reach index 8 * 16 + 3 + 4 = 135
 constexpr size_t GR_LDS_ROOM = 150 * 1024;
 
-__device__ __forceinline__ float gr_lse2(const float2v (&x)[GR_P], bool live) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < GR_P; ++k) mx = fmaxf(fmaxf(mx, x[k].x), x[k].y);
-  mx = quad_max(mx);
-  const float m0 = live ? mx : 0.f;
-  const float2v neg = {-m0, -m0};
-  float2v acc = {0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < GR_P; ++k) {
-    const float2v y = x[k] + neg;
-    const float2v e = {exp2_hw(y.x), exp2_hw(y.y)};
-    acc += e;
-  }
-  return mx + log2_hw(quad_sum(acc.x + acc.y));
-}
-
 template <bool HIST_LDS>
-__global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restrict__ S0, const float* G,
+__global__ __launch_bounds__(SKR_T) void k_sinkhorn_grad_res(const float* __restrict__ S0, const float* G,
                                                             const uint8_t* __restrict__ row_mask, const uint8_t* __restrict__ col_mask, int M,
                                                             int N, int iters, float* dS, float* __restrict__ d_alpha_part, float* hist_ws) {
   extern __shared__ __attribute__((aligned(16))) float s_hist[];
   __shared__ float2 s_mu[GR_LS], s_nu[GR_LS];      // {base-2 log marginal, du} per row, {.., dv} per column
   __shared__ float s_pr[GR_LS], s_pc[GR_LS];       // 0 on a valid line, -inf on a masked one and beyond the matrix
-  __shared__ float s_red[GR_T];
+  __shared__ float s_red[SKR_T];
   __shared__ int s_nr, s_nc;
   const int64_t b = blockIdx.x;
   const int M1 = M + 1, N1 = N + 1, tid = threadIdx.x;
@@ -93,41 +57,41 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   __syncthreads();
   {
     int cr = 0, cc = 0;
-    for (int i = tid; i < M; i += GR_T) cr += row_mask[b * M + i] ? 1 : 0;
-    for (int j = tid; j < N; j += GR_T) cc += col_mask[b * N + j] ? 1 : 0;
+    for (int i = tid; i < M; i += SKR_T) cr += row_mask[b * M + i] ? 1 : 0;
+    for (int j = tid; j < N; j += SKR_T) cc += col_mask[b * N + j] ? 1 : 0;
     if (cr) atomicAdd(&s_nr, cr);
     if (cc) atomicAdd(&s_nc, cc);
   }
   __syncthreads();
   const int nr = s_nr, nc = s_nc;
   if (nr == 0 || nc == 0) {                         // block-uniform: no transport to differentiate
-    for (int t = tid; t < M1 * N1; t += GR_T) dg[t] = 0.f;
+    for (int t = tid; t < M1 * N1; t += SKR_T) dg[t] = 0.f;
     if (tid == 0) d_alpha_part[b] = 0.f;
     return;
   }
   {
     const float norm = -logf(static_cast<float>(nr + nc));
-    for (int t = tid; t < GR_LS; t += GR_T) {
+    for (int t = tid; t < GR_LS; t += SKR_T) {
       const bool rv = t < M ? row_mask[b * M + t] != 0 : t == M;
       const bool cv = t < N ? col_mask[b * N + t] != 0 : t == N;
       s_pr[t] = rv ? 0.f : -INFINITY;
       s_pc[t] = cv ? 0.f : -INFINITY;
-      s_mu[t] = make_float2(rv ? (t < M ? norm : logf(static_cast<float>(nc)) + norm) * LOG2E : 0.f, 0.f);
-      s_nu[t] = make_float2(cv ? (t < N ? norm : logf(static_cast<float>(nr)) + norm) * LOG2E : 0.f, 0.f);
+      s_mu[t] = make_float2(rv ? (t < M ? norm : logf(static_cast<float>(nc)) + norm) * SKR_LOG2E : 0.f, 0.f);
+      s_nu[t] = make_float2(cv ? (t < N ? norm : logf(static_cast<float>(nr)) + norm) * SKR_LOG2E : 0.f, 0.f);
     }
-    for (size_t t = tid; t < hist_floats; t += GR_T) hist[t] = 0.f;      // v_0 = 0; masked lines and the padding of a line stay 0
+    for (size_t t = tid; t < hist_floats; t += SKR_T) hist[t] = 0.f;      // v_0 = 0; masked lines and the padding of a line stay 0
   }
   __syncthreads();
   const int part = tid & 3, line = tid >> 2, lc = min(line, GR_LS - 1);
   const bool row_live = s_pr[lc] == 0.f, col_live = s_pc[lc] == 0.f;
-  float2v R[GR_P], C[GR_P];                         // base-2 scores; -inf on masked lines and beyond the matrix
+  float2v R[SKR_P], C[SKR_P];                         // base-2 scores; -inf on masked lines and beyond the matrix
 #pragma unroll
-  for (int k = 0; k < GR_P; ++k) {
+  for (int k = 0; k < SKR_P; ++k) {
     const int j0 = 8 * k + part, j1 = j0 + 4;
-    R[k].x = ((line < M1 && j0 < N1) ? sg[line * N1 + j0] * LOG2E : 0.f) + (s_pr[lc] + s_pc[j0]);
-    R[k].y = ((line < M1 && j1 < N1) ? sg[line * N1 + j1] * LOG2E : 0.f) + (s_pr[lc] + s_pc[j1]);
-    C[k].x = ((line < N1 && j0 < M1) ? sg[j0 * N1 + line] * LOG2E : 0.f) + (s_pc[lc] + s_pr[j0]);
-    C[k].y = ((line < N1 && j1 < M1) ? sg[j1 * N1 + line] * LOG2E : 0.f) + (s_pc[lc] + s_pr[j1]);
+    R[k].x = ((line < M1 && j0 < N1) ? sg[line * N1 + j0] * SKR_LOG2E : 0.f) + (s_pr[lc] + s_pc[j0]);
+    R[k].y = ((line < M1 && j1 < N1) ? sg[line * N1 + j1] * SKR_LOG2E : 0.f) + (s_pr[lc] + s_pc[j1]);
+    C[k].x = ((line < N1 && j0 < M1) ? sg[j0 * N1 + line] * SKR_LOG2E : 0.f) + (s_pc[lc] + s_pr[j0]);
+    C[k].y = ((line < N1 && j1 < M1) ? sg[j1 * N1 + line] * SKR_LOG2E : 0.f) + (s_pc[lc] + s_pr[j1]);
   }
   // ---- the forward iteration again, every dual recorded ----
   // When a whole iteration leaves every u AND every v bit-identical, all later iterations repeat it (k_log_sinkhorn_reg's exact early exit):
@@ -137,13 +101,13 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
     int changed = 0;
     {
       const float* vp = hv + static_cast<size_t>(t - 1) * GR_LS;
-      float2v x[GR_P];
+      float2v x[SKR_P];
 #pragma unroll
-      for (int k = 0; k < GR_P; ++k) {
+      for (int k = 0; k < SKR_P; ++k) {
         const float2v d = {vp[8 * k + part], vp[8 * k + part + 4]};
         x[k] = R[k] + d;
       }
-      const float lse = gr_lse2(x, row_live);
+      const float lse = skr_lse2(x, row_live);
       if (row_live && part == 0) {
         const float un = s_mu[line].x - lse;
         changed |= t == 1 || __float_as_uint(un) != __float_as_uint(hu[static_cast<size_t>(max(t - 2, 0)) * GR_LS + line]);
@@ -153,13 +117,13 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
     __syncthreads();
     {
       const float* up = hu + static_cast<size_t>(t - 1) * GR_LS;
-      float2v x[GR_P];
+      float2v x[SKR_P];
 #pragma unroll
-      for (int k = 0; k < GR_P; ++k) {
+      for (int k = 0; k < SKR_P; ++k) {
         const float2v d = {up[8 * k + part], up[8 * k + part + 4]};
         x[k] = C[k] + d;
       }
-      const float lse = gr_lse2(x, col_live);
+      const float lse = skr_lse2(x, col_live);
       if (col_live && part == 0) {
         const float vn = s_nu[line].x - lse;
         changed |= __float_as_uint(vn) != __float_as_uint(hv[static_cast<size_t>(t - 1) * GR_LS + line]);
@@ -176,7 +140,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   {
     float ar = 0.f, ac = 0.f;
 #pragma unroll
-    for (int k = 0; k < GR_P; ++k) {
+    for (int k = 0; k < SKR_P; ++k) {
       const int j0 = 8 * k + part, j1 = j0 + 4;
       ar += R[k].x > -INFINITY ? gg[line * N1 + j0] : 0.f;
       ar += R[k].y > -INFINITY ? gg[line * N1 + j1] : 0.f;
@@ -189,9 +153,9 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   }
   __syncthreads();
   // ---- the reverse iteration ----
-  float2v dSr[GR_P], dSc[GR_P];
+  float2v dSr[SKR_P], dSc[SKR_P];
 #pragma unroll
-  for (int k = 0; k < GR_P; ++k) {
+  for (int k = 0; k < SKR_P; ++k) {
     dSr[k] = float2v{0.f, 0.f};
     dSc[k] = float2v{0.f, 0.f};
   }
@@ -202,7 +166,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
       const float* vc = hv + static_cast<size_t>(tc) * GR_LS;
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < GR_P; ++k) {
+      for (int k = 0; k < SKR_P; ++k) {
         const int j0 = 8 * k + part, j1 = j0 + 4;
         const float2 n0 = s_nu[j0], n1 = s_nu[j1];
         const float t0 = exp2_hw((R[k].x + ui) + (vc[j0] - n0.x)) * n0.y;
@@ -221,7 +185,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
       const float* uc = hu + static_cast<size_t>(min(t, t_last) - 1) * GR_LS;
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < GR_P; ++k) {
+      for (int k = 0; k < SKR_P; ++k) {
         const int i0 = 8 * k + part, i1 = i0 + 4;
         const float2 m0 = s_mu[i0], m1 = s_mu[i1];
         const float t0 = exp2_hw((C[k].x + vj) + (uc[i0] - m0.x)) * m0.y;
@@ -238,7 +202,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   // ---- dS = G - dSr - dSc^T: the column part through the output buffer, then one pass in the row layout ----
   if (line < N1) {
 #pragma unroll
-    for (int k = 0; k < GR_P; ++k) {
+    for (int k = 0; k < SKR_P; ++k) {
       const int i0 = 8 * k + part, i1 = i0 + 4;
       if (i0 < M1) dg[i0 * N1 + line] = dSc[k].x;
       if (i1 < M1) dg[i1 * N1 + line] = dSc[k].y;
@@ -248,7 +212,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   float da = 0.f;                                   // this thread's share of the dustbin row and column
   if (line < M1) {
 #pragma unroll
-    for (int k = 0; k < GR_P; ++k) {
+    for (int k = 0; k < SKR_P; ++k) {
       const int j0 = 8 * k + part, j1 = j0 + 4;
       if (j0 < N1) {
         const float g = R[k].x > -INFINITY ? gg[line * N1 + j0] : 0.f;
@@ -269,7 +233,7 @@ __global__ __launch_bounds__(GR_T) void k_sinkhorn_grad_res(const float* __restr
   if (tid < 64) {
     float s = 0.f;
 #pragma unroll
-    for (int q = 0; q < GR_T / 64; ++q) s += s_red[tid + 64 * q];
+    for (int q = 0; q < SKR_T / 64; ++q) s += s_red[tid + 64 * q];
     s = wave_sum(s);
     if (tid == 0) d_alpha_part[b] = s;
   }
@@ -475,7 +439,7 @@ static GenWs gen_carve(void* ws, size_t cap, int64_t B, int M, int N, int iters,
 }
 static Plan skg_plan(int64_t B, int M, int N, int iters) {
   Plan p = {1, false, 0, 0};
-  if (M + 1 <= GR_LINES && N + 1 <= GR_LINES) {
+  if (M + 1 <= SKR_LINES && N + 1 <= SKR_LINES) {
     p.form = 0;
     p.hist_floats = (2 * static_cast<size_t>(iters) + 1) * GR_LS;
     p.hist_lds = p.hist_floats * sizeof(float) <= GR_LDS_ROOM;
@@ -525,10 +489,10 @@ extern "C" int lcr_log_sinkhorn_grad(const float* S0, const float* G, const uint
         set_error("lcr_log_sinkhorn_grad: cannot reserve dynamic LDS for the recorded duals");
         return LCR_EHIP;
       }
-      hipLaunchKernelGGL(skg::k_sinkhorn_grad_res<true>, grid, dim3(skg::GR_T), p.hist_floats * sizeof(float), st, S0, G, row_mask, col_mask, M, N,
+      hipLaunchKernelGGL(skg::k_sinkhorn_grad_res<true>, grid, dim3(SKR_T), p.hist_floats * sizeof(float), st, S0, G, row_mask, col_mask, M, N,
                          iters, dS, d_alpha_part, static_cast<float*>(nullptr));
     } else {
-      hipLaunchKernelGGL(skg::k_sinkhorn_grad_res<false>, grid, dim3(skg::GR_T), 0, st, S0, G, row_mask, col_mask, M, N, iters, dS, d_alpha_part,
+      hipLaunchKernelGGL(skg::k_sinkhorn_grad_res<false>, grid, dim3(SKR_T), 0, st, S0, G, row_mask, col_mask, M, N, iters, dS, d_alpha_part,
                          static_cast<float*>(ws));
     }
     return check_launch("lcr_log_sinkhorn_grad");
