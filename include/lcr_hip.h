@@ -664,6 +664,23 @@ int lcr_top1_matching_ex(const float* logS, int64_t B, int M, int N, const uint8
 int lcr_patch_scores(const float* feats_a, int64_t Na, const float* feats_b, int64_t Nb, int C, const int64_t* idx_a, const int64_t* idx_b,
                      const uint8_t* mask_a, const uint8_t* mask_b, int64_t P, int K, float scale, const float* alpha, float inf_val, float* S,
                      void* stream);
+/* Reverse pass of lcr_patch_scores with respect to the two feature tensors (csrc/patch_scores.hip).  dS f32[P,K+1,K+1] is what
+ * lcr_log_sinkhorn_grad returns; feats / idx / mask / scale are the forward's.  G[p] = scale * dS[p][:K,:K] with every entry of a masked row or
+ * column taken as zero BY SELECT (dS may hold anything there, NaN included); the dustbin row and column are never read (d_alpha stays with the
+ * transport's d_alpha_part).  dA_g[p] = G[p] . gather(feats_b, idx_b[p]), dB_g[p] = G[p]^T . gather(feats_a, idx_a[p]) on the fp32 matrix cores,
+ * contraction index ascending; d_feats_a f32[Na,C] row n = the sum of dA_g[p][i] over the slots with idx_a[p,i] == n in ascending p K + i,
+ * d_feats_b likewise.  The shadow index (== N*) and any index outside [0, N*) receive nothing; a row nobody lists is exactly zero.  idx is
+ * general: a row may be listed by several patches and several times by one.  (row_start_*, edges_*) = lcr_neighbor_transpose of idx_* viewed
+ * as [P,K] over N* rows.  Either gradient may be NULL (its list is then not read).  No floating-point atomics, every output element written
+ * once, results repeat to the bit and a patch's products do not depend on its batch.  Domain as the forward: K = 128, C % 32 == 0, features,
+ * gradients and workspace 16-byte aligned, P * K < 2^30; LCR_EARG with text outside it.  P == 0 zero-fills the gradients.  ws:
+ * lcr_patch_scores_grad_ws_bytes(P, K, C) = 2 P K C floats, host-only query (8 MB per pair and side at the training sizes P <= 128, C = 128:
+ * not chunked). */
+int lcr_patch_scores_grad_ws_bytes(int64_t P, int K, int C, size_t* bytes);
+int lcr_patch_scores_grad(const float* dS, const float* feats_a, int64_t Na, const float* feats_b, int64_t Nb, int C, const int64_t* idx_a,
+                          const int64_t* idx_b, const uint8_t* mask_a, const uint8_t* mask_b, int64_t P, int K, float scale,
+                          const int32_t* row_start_a, const uint32_t* edges_a, const int32_t* row_start_b, const uint32_t* edges_b,
+                          float* d_feats_a, float* d_feats_b, void* ws, size_t ws_bytes, void* stream);
 /* Dustbin top-K matching for K >= 1 (LocalGlobalRegistration(k=K), local_global_registration.py:56-82; K = 1 in the shipped configuration):
  * (i, j) is kept from the row side if P[i][j] is among the K largest of row i — dustbin column included, equal values in index order — and
  * beats the row's dustbin; from the column side likewise; `mutual` as above.  Two-phase and row-major like lcr_top1_matching. */

@@ -13,6 +13,7 @@ def make_cfg():
         "model": {"num_points_in_patch": 128, "num_sinkhorn_iterations": 100, "ground_truth_matching_radius": 0.45,
                   "ground_truth_corres_radius": 2.4},
         "Vote": {"MAX_TRANSLATE_RANGE": 4.2, "MLPS": [512, 256], "NMS_radius": 2.4},
+        "coarse_matching": {"num_targets": 128, "overlap_threshold": 0.1},      # config_model.py:57-58, the training targets
         "fine_matching": {"acceptance_radius": 0.45, "mutual": False, "topk": 1, "confidence_threshold": 0, "use_dustbin": True,
                           "use_global_score": False, "correspondence_threshold": 3, "correspondence_limit": None, "num_refinement_steps": 5},
         "neighbor_limits": [64, 65, 74, 80],     # dataset_loop_detection.py:25,80 (training default)

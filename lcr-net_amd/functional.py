@@ -2,7 +2,8 @@
 allocates the outputs with torch and launches HIP kernels on the current stream.  Inference only (no autograd), with two exceptions:
 gap_loss / min_dist have the gradient launchers gap_loss_grad / min_dist_grad beside them, which losses.py wraps in
 torch.autograd.Functions (gradients to the scores and to the queries only); and log_optimal_transport / patch_log_optimal_transport
-are differentiable (_TransportFn over lcr_log_sinkhorn_grad: gradients to the raw scores and to alpha); and the ops of the 3D-RoFormer —
+are differentiable (_TransportFn over lcr_log_sinkhorn_grad: gradients to the raw scores and to alpha; _PatchTransportFn adds
+lcr_patch_scores_grad: gradients to the two point-feature tensors); bmm_nt and the plain gemm(a, b, trans_b=True) carry a graph; and the ops of the 3D-RoFormer —
 linear, rotary_embed, attention, add_layernorm — return a graph when grad mode is on and an input requires grad (backwards in
 csrc/attention_grad.hip and on lcr_gemm_f32), and otherwise make exactly the calls of the inference path."""
 import ctypes
@@ -144,11 +145,14 @@ def _gemm_out(M, N, seg_len, groups, device, always_seg=False):
 def gemm(a, b, trans_b=False, trans_a=False, bias=None, rowdiv=None, seg_len=None, groups=0, row_mask=None):
     """C = A·B (+ fused epilogue).  a: [M,K] ([K,M] if trans_a); b: [K,N] ([N,K] if trans_b, i.e. an nn.Linear weight).
     Returns (C, stats) where stats is the fp64 [GN_REPLICAS,S,groups,2] GroupNorm accumulator (sum the replicas; None if
-    groups == 0).  row_mask: the int16 [M] mask of kpconv_aggregate(emit_mask=True) for a = its aggregate (trans_b only): blocks
+    groups == 0).  The plain form a . b^T (trans_b alone, no epilogue) carries a graph when a or b requires grad and grad mode is on
+    (_GemmNTFn: both gradient products on lcr_gemm_f32); every other form is a plain launch.  row_mask: the int16 [M] mask of kpconv_aggregate(emit_mask=True) for a = its aggregate (trans_b only): blocks
     whose bit is clear are read as zeros (lcr_gemm_f32_masked; where kpconv_mask_ok(M, N, K, False) holds)."""
     if row_mask is not None:
         return _gemm_masked(a, b, trans_b, trans_a, bias, rowdiv, seg_len, groups, row_mask)
     _lib.require_cuda(a, b)
+    if trans_b and not trans_a and bias is None and rowdiv is None and seg_len is None and not groups and _wants_grad(a, b):
+        return _GemmNTFn.apply(a, b), None          # the plain product A.B^T (the node-level scores): differentiable in both factors
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     N = b.shape[0] if trans_b else b.shape[1]
@@ -1375,26 +1379,93 @@ PATCH_SCORES_FUSED = [os.environ.get("LCR_PATCH_SCORES_FUSED", "1") != "0"]     
 def patch_log_optimal_transport(feats_a, idx_a, feats_b, idx_b, mask_a, mask_b, alpha, scale=1.0, iters=100, inf=1e12):
     """The patch-level transport of DenseMatchingHEAD (LCRNet.py:236-250): log scores [P,K+1,K+1] of P patch pairs whose point features are
     rows idx_a[p] of feats_a / idx_b[p] of feats_b (index == number of rows: the zero row of the padded tensor).  The gathers, the batched
-    product, the scaling and the dustbin / mask padding are ONE kernel (lcr_patch_scores); LCR_PATCH_SCORES_FUSED=0 runs them apart."""
+    product, the scaling and the dustbin / mask padding are ONE kernel (lcr_patch_scores); LCR_PATCH_SCORES_FUSED=0 runs them apart.
+    Differentiable in feats_a, feats_b and alpha: where the fused form applies the graph is _PatchTransportFn (lcr_log_sinkhorn_grad, then
+    lcr_patch_scores_grad) and the bytes are the no-grad call's."""
     P, K = idx_a.shape
     if _wants_grad(feats_a, feats_b, alpha):
-        # training: the gather (on the zero-row-padded features) and the product are torch's, which differentiates them; the transport
-        # and its reverse pass are the library's
+        if PATCH_SCORES_FUSED[0] and K == 128 and feats_a.shape[1] % 32 == 0 and P > 0:
+            # training: the forward's one kernel, and its reverse lcr_patch_scores_grad behind the transport's
+            return _PatchTransportFn.apply(feats_a, feats_b, alpha, idx_a, idx_b, mask_a, mask_b, float(scale), int(iters), float(inf))
+        # outside the fused form: the gather (on the zero-row-padded features) and the product are torch's, which differentiates them; the
+        # transport and its reverse pass are the library's
         fa = torch.cat([feats_a, feats_a.new_zeros(1, feats_a.shape[1])])[idx_a]
         fb = torch.cat([feats_b, feats_b.new_zeros(1, feats_b.shape[1])])[idx_b]
         return log_optimal_transport(torch.bmm(fa, fb.transpose(1, 2)), mask_a, mask_b, alpha, scale=scale, iters=iters, inf=inf)
     if not PATCH_SCORES_FUSED[0] or K != 128 or feats_a.shape[1] % 32 != 0 or P == 0:
         fa, fb = gather_rows(feats_a, idx_a.contiguous()), gather_rows(feats_b, idx_b.contiguous())
         return log_optimal_transport(bmm_nt(fa, fb), mask_a, mask_b, alpha, scale=scale, iters=iters, inf=inf)
-    dev = feats_a.device
-    fa, fb = feats_a.contiguous(), feats_b.contiguous()
-    ia, ib = idx_a.contiguous(), idx_b.contiguous()
-    assert ia.dtype == torch.int64 and ib.dtype == torch.int64 and fa.dtype == torch.float32 and fa.shape[1] == fb.shape[1]
     rm, cm = mask_a.to(torch.uint8).contiguous(), mask_b.to(torch.uint8).contiguous()
-    S = torch.empty((P, K + 1, K + 1), dtype=torch.float32, device=dev)
-    _lib.call.lcr_patch_scores(_lib.ptr(fa), fa.shape[0], _lib.ptr(fb), fb.shape[0], fa.shape[1], _lib.ptr(ia), _lib.ptr(ib), _lib.ptr(rm),
-                               _lib.ptr(cm), P, K, float(scale), _lib.ptr(alpha.reshape(1).float()), float(inf), _lib.ptr(S), _lib.stream_ptr(S.device))
+    S = _patch_scores(feats_a.contiguous(), feats_b.contiguous(), idx_a.contiguous(), idx_b.contiguous(), rm, cm, alpha, scale, inf)
     return _transport_padded(S, rm, cm, iters, inf)
+
+
+def _patch_scores(fa, fb, ia, ib, rm, cm, alpha, scale, inf):
+    """lcr_patch_scores on checked, contiguous operands -> the padded scores S0 [P,K+1,K+1]"""
+    P, K = ia.shape
+    assert ia.dtype == torch.int64 and ib.dtype == torch.int64 and fa.dtype == torch.float32 and fa.shape[1] == fb.shape[1]
+    S = torch.empty((P, K + 1, K + 1), dtype=torch.float32, device=fa.device)
+    a1 = alpha.reshape(1).float()                     # named: a copy must outlive the argument list
+    _lib.call.lcr_patch_scores(_lib.ptr(fa), fa.shape[0], _lib.ptr(fb), fb.shape[0], fa.shape[1], _lib.ptr(ia), _lib.ptr(ib), _lib.ptr(rm),
+                               _lib.ptr(cm), P, K, float(scale), _lib.ptr(a1), float(inf), _lib.ptr(S), _lib.stream_ptr(S.device))
+    return S
+
+
+def patch_scores_grad(dS, feats_a, feats_b, idx_a, idx_b, mask_a, mask_b, scale, inv_a=None, inv_b=None, want_a=True, want_b=True):
+    """(d_feats_a [Na,C] or None, d_feats_b [Nb,C] or None) of lcr_patch_scores_grad from dS [P,K+1,K+1] (what log_sinkhorn_grad returns) and
+    the operands of the forward; inv_*: the InvertedList (or (row_start, edges)) of idx_* as a [P,K] list over the rows of feats_* (built here
+    when None).  No host synchronisation."""
+    _lib.require_cuda(dS, feats_a, feats_b, idx_a, idx_b, mask_a, mask_b)
+    P, K = idx_a.shape
+    Na, Nb, C = feats_a.shape[0], feats_b.shape[0], feats_a.shape[1]
+    assert dS.dtype == torch.float32 and dS.is_contiguous() and tuple(dS.shape) == (P, K + 1, K + 1)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (feats_a, feats_b)) and feats_b.shape[1] == C
+    assert all(t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (P, K) for t in (idx_a, idx_b))
+    assert all(t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (P, K) for t in (mask_a, mask_b))
+    ra = ea = rb = eb = None
+    if want_a and P > 0:
+        ra, ea = _inv_args(inv_a if inv_a is not None else inverted(idx_a, Na), P, K, Na)
+    if want_b and P > 0:
+        rb, eb = _inv_args(inv_b if inv_b is not None else inverted(idx_b, Nb), P, K, Nb)
+    da = torch.empty((Na, C), dtype=torch.float32, device=dS.device) if want_a else None
+    db = torch.empty((Nb, C), dtype=torch.float32, device=dS.device) if want_b else None
+    ws = _lib.ws("lcr_patch_scores_grad_ws_bytes", P, K, C, device=dS.device)
+    _lib.call.lcr_patch_scores_grad(_lib.ptr(dS), _lib.ptr(feats_a), Na, _lib.ptr(feats_b), Nb, C, _lib.ptr(idx_a), _lib.ptr(idx_b), _lib.ptr(mask_a),
+                                    _lib.ptr(mask_b), P, K, float(scale), _lib.ptr(ra), _lib.ptr(ea), _lib.ptr(rb), _lib.ptr(eb), _lib.ptr(da),
+                                    _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dS.device))
+    return da, db
+
+
+class _PatchTransportFn(torch.autograd.Function):
+    """patch_log_optimal_transport with a backward, in the manner of _TransportFn: the forward writes the padded scores S0 straight from the
+    feature tensors (lcr_patch_scores), keeps them and runs the transport on a copy; the backward is lcr_log_sinkhorn_grad on S0, then
+    lcr_patch_scores_grad (the gathered feature copies exist in neither direction), d_alpha = the fp64 sum of the per-problem dustbin sums.
+    The inverted lists come through inverted(): a stack call (feats_a is feats_b) inside an inverted_lists() context builds each once."""
+
+    @staticmethod
+    def forward(ctx, feats_a, feats_b, alpha, idx_a, idx_b, mask_a, mask_b, scale, iters, inf):
+        _lib.require_cuda(feats_a, feats_b, alpha, idx_a, idx_b, mask_a, mask_b)
+        fa, fb = feats_a.detach().contiguous(), feats_b.detach().contiguous()
+        ia, ib = idx_a.contiguous(), idx_b.contiguous()
+        rm, cm = mask_a.to(torch.uint8).contiguous(), mask_b.to(torch.uint8).contiguous()
+        S0 = _patch_scores(fa, fb, ia, ib, rm, cm, alpha.detach(), scale, inf)
+        ctx.save_for_backward(S0, fa, fb, ia, ib, rm, cm)
+        ctx.inv_a = inverted(ia, fa.shape[0]) if ctx.needs_input_grad[0] else None
+        ctx.inv_b = inverted(ib, fb.shape[0]) if ctx.needs_input_grad[1] else None
+        ctx.scale, ctx.iters, ctx.inf, ctx.alpha_shape = scale, iters, inf, alpha.shape
+        return _transport_padded(S0.clone(), rm, cm, iters, inf)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        S0, fa, fb, ia, ib, rm, cm = ctx.saved_tensors
+        dS, part = log_sinkhorn_grad(S0, G.contiguous().float(), rm, cm, ctx.iters, ctx.inf)
+        da = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            da, db = patch_scores_grad(dS, fa, fb, ia, ib, rm, cm, ctx.scale, ctx.inv_a, ctx.inv_b, want_a=ctx.needs_input_grad[0],
+                                       want_b=ctx.needs_input_grad[1])
+        d_alpha = part.double().sum().float().reshape(ctx.alpha_shape) if ctx.needs_input_grad[2] else None
+        return da, db, d_alpha, None, None, None, None, None, None, None
 
 
 def _transport_padded(S, rm, cm, iters, inf):
@@ -1525,16 +1596,75 @@ def gather_rows(src, idx):
 
 
 def bmm_nt(a, b):
-    """[P,M,K] x [P,N,K]^T -> [P,M,N] on the MFMA GEMM (einsum 'bnd,bmd->bnm')."""
-    P, M, K = a.shape
-    N = b.shape[1]
+    """[P,M,K] x [P,N,K]^T -> [P,M,N] on the MFMA GEMM (einsum 'bnd,bmd->bnm').  With a graph when a or b requires grad and grad mode is on
+    (_BmmNTFn: both gradient products on the same batched GEMM)."""
+    if _wants_grad(a, b):
+        return _BmmNTFn.apply(a, b)
+    return _bmm(a.contiguous(), b.contiguous(), False, True)
+
+
+def _bmm(a, b, trans_a, trans_b):
+    """C_z = op(a_z) . op(b_z) on lcr_gemm_f32_strided_batched: a [P,M,K] ([P,K,M] with trans_a), b [P,K,N] ([P,N,K] with trans_b), both
+    contiguous.  The entry wants leading dimensions and strides of a and b in multiples of 4 floats."""
+    P = a.shape[0]
+    M, K = (a.shape[2], a.shape[1]) if trans_a else (a.shape[1], a.shape[2])
+    N = b.shape[1] if trans_b else b.shape[2]
     c = torch.empty((P, M, N), dtype=torch.float32, device=a.device)
-    a, b = a.contiguous(), b.contiguous()
     for z0 in range(0, P, 65535):
         cnt = min(65535, P - z0)
-        _lib.call.lcr_gemm_f32_strided_batched(_lib.ptr(a[z0:]), _lib.ptr(b[z0:]), _lib.ptr(c[z0:]), M, N, K, 0, 1, M * K, N * K, M * N, cnt,
-                                               _lib.stream_ptr(a.device))
+        _lib.call.lcr_gemm_f32_strided_batched(_lib.ptr(a[z0:]), _lib.ptr(b[z0:]), _lib.ptr(c[z0:]), M, N, K, int(trans_a), int(trans_b), M * K, N * K,
+                                               M * N, cnt, _lib.stream_ptr(a.device))
     return c
+
+
+class _BmmNTFn(torch.autograd.Function):
+    """bmm_nt with a backward: for C = A.B^T, dA = dC.B and dB = dC^T.A on lcr_gemm_f32_strided_batched.  That entry reads dC with leading
+    dimension N and stride M N, which it wants in multiples of 4 floats: where N % 4 != 0 the cotangent batch is padded with zero columns to
+    the next multiple (and B with zero rows for dA, whose contraction runs over them: exact zeros added last), and dB drops the rows."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        _lib.require_cuda(a, b)
+        ac, bc = a.detach().contiguous(), b.detach().contiguous()
+        ctx.save_for_backward(ac, bc)
+        return _bmm(ac, bc, False, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dc):
+        a, b = ctx.saved_tensors
+        N = b.shape[1]
+        dc = dc.contiguous().float()
+        pad = -N % 4
+        if pad:
+            dc = torch.nn.functional.pad(dc, (0, pad))
+        da = db = None
+        if ctx.needs_input_grad[0]:
+            da = _bmm(dc, torch.nn.functional.pad(b, (0, 0, 0, pad)) if pad else b, False, False)
+        if ctx.needs_input_grad[1]:
+            db = _bmm(dc, a, True, False)
+            if pad:
+                db = db[:, :N].contiguous()
+        return da, db
+
+
+class _GemmNTFn(torch.autograd.Function):
+    """gemm(a, b, trans_b=True) with a backward on the same entry: dA = dC.B, dB = dC^T.A (lcr_gemm_f32 with trans_a)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ac, bc = a.detach().contiguous(), b.detach().contiguous()
+        ctx.save_for_backward(ac, bc)
+        return gemm(ac, bc, trans_b=True)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dc):
+        a, b = ctx.saved_tensors
+        dc = dc.contiguous().float()
+        da = gemm(dc, b)[0] if ctx.needs_input_grad[0] else None
+        db = gemm(dc, a, trans_a=True)[0] if ctx.needs_input_grad[1] else None
+        return da, db
 
 
 def procrustes(src, ref, w, start=None):

@@ -215,6 +215,12 @@ class LCRNet(nn.Module):
         matching / registration tail, whose tensor shapes depend on each pair's data, runs pair by pair."""
         if self.training:
             raise RuntimeError("lcr-net_amd implements inference only; call .eval()")
+        return self._forward_pairs(data_dict, pose, False)
+
+    def _forward_pairs(self, data_dict, pose, training, transforms=None):
+        """The body of forward_pairs.  training=False: the inference path.  training=True (LCRNet_Matching, whose forward_pairs passes the
+        ground-truth `transforms` [P,4,4]): the same batched launches with a graph, and the matching head of the reference's training branch
+        (_dense_matching_train) in place of matching + registration."""
         feats = data_dict["features"].detach()
         lens_dev = data_dict["lengths"]
         B = lens_dev[-1].numel()
@@ -251,9 +257,14 @@ class LCRNet(nn.Module):
             idx0 = F.host_tensor(torch.cat([torch.arange(off_c[2 * p], off_c[2 * p + 1]) for p in range(P)]), feats_c.device)
             idx1 = F.host_tensor(torch.cat([torch.arange(off_c[2 * p + 1], off_c[2 * p + 2]) for p in range(P)]), feats_c.device)
             e0, e1, t0, t1 = self.transformer(points_c[idx0], points_c[idx1], feats_c[idx0], feats_c[idx1], pos_lens, anc_lens, return_pos_emb=True)
-            enhanced = torch.empty((n_c, e0.shape[1]), dtype=e0.dtype, device=e0.device)
-            enhanced[idx0] = e0
-            enhanced[idx1] = e1
+            if training:                                             # the same rows by one differentiable gather (no in-place writes in the graph)
+                back = torch.empty(n_c, dtype=torch.int64, device=e0.device)
+                back[torch.cat([idx0, idx1])] = torch.arange(n_c, device=e0.device)
+                enhanced = torch.cat([e0, e1], 0)[back]
+            else:
+                enhanced = torch.empty((n_c, e0.shape[1]), dtype=e0.dtype, device=e0.device)
+                enhanced[idx0] = e0
+                enhanced[idx1] = e1
             po, ao = [0], [0]
             for p in range(P):
                 po.append(po[-1] + pos_lens[p])
@@ -293,7 +304,9 @@ class LCRNet(nn.Module):
         feats_f = self.kpdecoder(fl, data_dict, pairs=P)[0]
         # ---- DenseMatchingHEAD (:161-272)
         sl = lambda off, i: slice(off[i], off[i + 1])
-        if P == 1:
+        if training:
+            self._dense_matching_train(outs, P, pts_f, feats_f, off_f, vd, off_m, transforms)
+        elif P == 1:
             self._dense_matching(outs[0], pts_f[sl(off_f, 0)].contiguous(), pts_f[sl(off_f, 1)].contiguous(),
                                  feats_f[sl(off_f, 0)].contiguous(), feats_f[sl(off_f, 1)].contiguous(),
                                  vd["points_c"][sl(off_m, 0)].contiguous(), vd["points_c"][sl(off_m, 1)].contiguous(),
@@ -309,17 +322,11 @@ class LCRNet(nn.Module):
                     outs[p].pop(k, None)
         return outs
 
-    def _dense_matching_group(self, outs, P, pts_f, feats_f, off_f, vd, off_m):
-        """DenseMatchingHEAD for P pairs, stage by stage: the node-level optimal transport of all pairs in ONE batched problem set
-        (matrices padded to the largest pair with masked rows / columns — LearnableLogOptimalTransport excludes masked entries and
-        normalises by the valid counts, learnable_sinkhorn.py:20-66, so the valid block is the unpadded result), its top-1 matching
-        in one call, the patch gathers over the whole stack, the patch-level transport of all pairs' patches in one call; only the
-        local-to-global registration, whose hypotheses compete inside a pair, runs pair by pair.  Per pair that is 200 / P Sinkhorn
-        launches instead of 200."""
+    def _node_transport_group(self, P, pts_f, off_f, vd, off_m):
+        """The first half of the matching head for P pairs, shared by inference and training: the point-to-node partition of the stack and the
+        node-level transport of all pairs as one padded batch.  -> (per-cloud (node mask, knn, knn mask), the three stacked, node counts m,
+        Mx, Nx, the per-node-row table [row in the padded batch, first fine point, fine points, side], log scores ns [P, Mx + 1, Nx + 1])."""
         K = self.num_points_in_patch
-        dev = pts_f.device
-        n_all = pts_f.shape[0]
-        import numpy as np
         parts, stacks = [], []
         for g0 in range(0, 2 * P, 64):                                  # one launch sequence per 64 clouds of the stack
             g1 = min(2 * P, g0 + 64)
@@ -329,9 +336,16 @@ class LCRNet(nn.Module):
                 lo, hi = off_m[c] - off_m[g0], off_m[c + 1] - off_m[g0]
                 parts.append((nm[lo:hi], knn[lo:hi], km[lo:hi]))
         nm_all, knn_all, km_all = (stacks[0] if len(stacks) == 1 else tuple(torch.cat([st[i] for st in stacks]) for i in range(3)))
+        m, Mx, Nx, tab, ns = self._node_transport_padded(P, vd["feats_c"], nm_all, off_f, off_m)
+        return parts, nm_all, knn_all, km_all, m, Mx, Nx, tab, ns
+
+    def _node_transport_padded(self, P, fc, nm_all, off_f, off_m):
+        """The node-level transport of P pairs as ONE padded batch from the stacked node features fc and node masks nm_all (differentiable in
+        fc and the node-level alpha) -> (node counts m, Mx, Nx, the per-node-row table, log scores ns [P, Mx + 1, Nx + 1])."""
+        import numpy as np
+        dev = fc.device
         m = [off_m[c + 1] - off_m[c] for c in range(2 * P)]
         Mx, Nx = max(m[0::2]), max(m[1::2])
-        fc = vd["feats_c"]
         # ---- the padded (P, Mx | Nx) node batches and everything per node row, for ALL pairs at once: the row maps are built on the host
         # (plain index arithmetic on the offset lists) and uploaded in ONE copy; a per-pair / per-side loop of torch ops was ~120 launches
         # of 5-10 us per 8-pair call (profiles/r05_pair_model_kernel_summary.md)
@@ -356,6 +370,27 @@ class LCRNet(nn.Module):
         fp, fa, rm, cm = fp.view(P, Mx, -1), fa.view(P, Nx, -1), rm.view(P, Mx), cm.view(P, Nx)
         ns = F.log_optimal_transport(F.bmm_nt(fp, fa), rm, cm, self.node_optimal_transport.alpha,
                                      scale=1.0 / fc.shape[1] ** 0.5, iters=self.node_optimal_transport.num_iterations)
+        return m, Mx, Nx, tab, ns
+
+    @staticmethod
+    def _pair_node_scores(ns, p, mp, ma, Mx, Nx):
+        """pair p's (mp + 1) x (ma + 1) block of the padded node-level log scores: its valid rows / columns and the two dustbins"""
+        if Mx == mp and Nx == ma:
+            return ns[p, :mp + 1, :ma + 1]
+        return torch.cat([torch.cat([ns[p, :mp, :ma], ns[p, :mp, Nx:Nx + 1]], 1),
+                          torch.cat([ns[p, Mx:Mx + 1, :ma], ns[p, Mx:Mx + 1, Nx:Nx + 1]], 1)], 0)
+
+    def _dense_matching_group(self, outs, P, pts_f, feats_f, off_f, vd, off_m):
+        """DenseMatchingHEAD for P pairs, stage by stage: the node-level optimal transport of all pairs in ONE batched problem set
+        (matrices padded to the largest pair with masked rows / columns — LearnableLogOptimalTransport excludes masked entries and
+        normalises by the valid counts, learnable_sinkhorn.py:20-66, so the valid block is the unpadded result), its top-1 matching
+        in one call, the patch gathers over the whole stack, the patch-level transport of all pairs' patches in one call; only the
+        local-to-global registration, whose hypotheses compete inside a pair, runs pair by pair.  Per pair that is 200 / P Sinkhorn
+        launches instead of 200."""
+        dev = pts_f.device
+        n_all = pts_f.shape[0]
+        parts, nm_all, knn_all, km_all, m, Mx, Nx, tab, ns = self._node_transport_group(P, pts_f, off_f, vd, off_m)
+        fc = vd["feats_c"]
         nbij, nscore = F.top1_matching(ns)                              # rows (pair, i, j), pair-major; padding never beats a dustbin
         nb = nbij.long()
         per_pair = torch.bincount(nb[:, 0], minlength=P).tolist()                   # host sync: node correspondences per pair
@@ -390,9 +425,7 @@ class LCRNet(nn.Module):
                 "pos_node_corr_knn_points": pkp[q], "anc_node_corr_knn_points": akp[q], "pos_node_corr_knn_masks": pkm[q],
                 "anc_node_corr_knn_masks": akm[q], "matching_scores": ms[q],
                 "pos_corr_points": rp, "anc_corr_points": sp, "corr_scores": sc, "estimated_transform": T,
-                "node_matching_scores": ns[p, :m[c] + 1, :m[c + 1] + 1] if Mx == m[c] and Nx == m[c + 1] else
-                torch.cat([torch.cat([ns[p, :m[c], :m[c + 1]], ns[p, :m[c], Nx:Nx + 1]], 1),
-                           torch.cat([ns[p, Mx:Mx + 1, :m[c + 1]], ns[p, Mx:Mx + 1, Nx:Nx + 1]], 1)], 0),
+                "node_matching_scores": self._pair_node_scores(ns, p, m[c], m[c + 1], Mx, Nx),
                 "pos_node_masks": parts[c][0], "anc_node_masks": parts[c + 1][0]})
 
     def _dense_matching(self, out, pos_f, anc_f, pos_ff, anc_ff, pos_nodes, anc_nodes, pos_fc, anc_fc):
