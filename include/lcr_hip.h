@@ -22,7 +22,8 @@
  * Shape domain (what the kernels are built for = every shape of the shipped configuration, experiments/lcrnet/config_model.py:33-43 with
  * best-model-mixed.tar, and of BASELINE.json's configs; a call outside it returns LCR_EARG with a message, it never computes something else):
  *   - clouds per call (B): 1..64 for the support grids / radius searches / lcr_precompute_batch (GRID_MAX_B); batches of more scans are
- *     split by the caller (lcr-net_amd/pipeline.py feeds 8 per call, PairPipeline at most 32 pairs = 64 clouds);
+ *     split by the caller (lcr-net_amd/pipeline.py feeds 8 per call, PairPipeline at most 32 pairs = 64 clouds); 1..128 for
+ *     lcr_augment_clouds (a loop-detection training batch is 6 x 13 = 78 clouds; the training head's own cap is 128 segments);
  *   - neighbour columns per row (`limit`, H): 1..128 for the KPConv aggregation / C_in = 1 KPConv / max-pool (KP_HMAX; the reference's
  *     calibrated limits are 64..80); the radius search itself accepts any limit >= 1 (balls with more than 512 hits take an exact
  *     storage-free path) and limit <= 0 = count-only;
@@ -139,6 +140,36 @@ int lcr_voxel_down_sample_ws_bytes(int64_t n_cap, int B, size_t* bytes);
 int lcr_voxel_down_sample(const float* rows, int row_floats, int out_cols, const int64_t* len, int B, int64_t n_cap, double voxel,
                           int key_bits_hint, float* out_f32, double* out_f64, int64_t* out_len, uint32_t* status,
                           void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * a-1t  training augmentation and point-limit sampling — what the training datasets apply per cloud in NumPy
+ *       (datasets/registration/kitti/dataset.py:73-115 `_augment_point_cloud` / `_load_point_cloud`,
+ *       datasets/loop_detection/kitti/dataset_overlap_online.py:123-153), for B = 1 .. 128 stacked clouds in one call.
+ * Random words are Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85) with
+ *   key     = (low, high) half of `seed`;
+ *   counter = (ORIGINAL index of the point inside its cloud, 0, sample_id[b], stream), stream 0 = noise, stream 1 = selection;
+ *   uniform = (word >> 8) * 2^-24 in fp32; words 0 .. 2 of stream 0 are the uniforms of x, y, z.
+ * Per kept point, fp32, every operation rounded once (no contraction), in this order:
+ *   n   = p + (u - 0.5) * noise[b]                 (the product first)
+ *   r_i = (R_i0 n_x + R_i1 n_y) + R_i2 n_z         (R = rotation[b], row-major)
+ *   out = r * scale[b] + shift[b]
+ * Point limit (`limit` <= 0: none, and no sort is launched): a cloud of L <= limit points passes through in its order; a longer
+ * one keeps the `limit` points with the smallest (word 0 of stream 1, original index) pairs, written in ascending pair order —
+ * one stable radix sort per call with the cloud number above the 32 random bits.  out_len[b] = min(L, limit).
+ * Because the counter holds sample_id and the original index, a cloud gives the same bytes alone and inside any stack, and the
+ * augmented value of source point i does not depend on `limit`.  Columns 3 .. row_floats-1 are not read (the reference returns [:, :3]).
+ *   rows       f32[n_cap, row_floats]  3 <= row_floats <= 64, x, y, z first; len i64[B]; n_cap <= 2^31-2
+ *   sample_id  u32[B]; rotation f32[B,9]; scale f32[B]; shift f32[B,3]; noise f32[B]
+ *   out_xyz    f32[out_cap,3], 0 <= out_cap <= n_cap: the first sum(out_len) rows are written, none at or beyond out_cap
+ *   out_len    i64[B]
+ *   status     u32[1]  LCR_STATUS_LEN_MISMATCH: a negative length, sum(len) > n_cap or sum(out_len) > out_cap (lengths are clamped)
+ * Every refusal of this entry — a too-small workspace included — is LCR_EARG with text, before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int lcr_augment_clouds_ws_bytes(int64_t n_cap, int B, int64_t limit, size_t* bytes);
+int lcr_augment_clouds(const float* rows, int row_floats, const int64_t* len, int B, int64_t n_cap, const uint32_t* sample_id,
+                       const float* rotation, const float* scale, const float* shift, const float* noise, uint64_t seed, int64_t limit,
+                       float* out_xyz, int64_t out_cap, int64_t* out_len, uint32_t* status,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a-2  radius search — replaces utils.ext.radius_neighbors + the [:, :limit] slice of

@@ -20,6 +20,9 @@ void lcr_gemm_debug_streamk(int mode);
 void lcr_groupnorm_debug_general(int on);
 /* KPConv aggregation: 1 = force 64-bit gather offsets where the host could guarantee 32-bit ones (bit-identity test of the two forms). */
 void lcr_kpconv_debug_off64(int on);
+/* lcr_augment_clouds: mask applied to the selection word before it enters the sort key (default all ones); 0xF leaves 16 distinct
+ * words, so that ties — broken by the original index — abound in tests. */
+void lcr_augment_debug_select_mask(uint32_t mask);
 
 #ifdef __cplusplus
 }

@@ -2251,3 +2251,54 @@ def adan_step(table, hyper, clip, device):
     """lcr_adan_step: one fused pass over the tensors of `table` (adan_table); hyper = AdanHyper, clip = a device float32 tensor of one
     element (the second entry of adan_grad_norm's result) or None.  No host synchronisation."""
     _lib.call.lcr_adan_step(table.ctypes.data, len(table), ctypes.addressof(hyper), _lib.ptr(clip), _lib.stream_ptr(device))
+
+
+AUGMENT_MAX_CLOUDS = 128   # clouds per lcr_augment_clouds call (AUG_MAX_B in csrc/augment.hip)
+
+
+def augment_clouds(rows, lengths, sample_id, rotation, scale, shift, noise, seed, limit=0):
+    """Training augmentation and point-limit sampling (include/lcr_hip.h, lcr_augment_clouds) of B <= 128 stacked clouds in one native
+    call: rows f32 [N, C] on the device (C = 3 .. 64, x, y, z first: an [N,4] xyzi scan as it lies), lengths host ints [B]; per cloud, host
+    arrays (any float type, narrowed to fp32) sample_id [B], rotation [B,3,3], scale [B], shift [B,3], noise [B]; a 64-bit seed;
+    limit <= 0 = no point limit -> (points f32 [M,3], lengths i64 [B]) on the device, M = sum(min(L, limit)).  The host knows every
+    length, so a limit that cuts no cloud is passed as 0 (no sort is launched) and nothing is read back: the per-cloud values travel in
+    one pinned upload and the call is asynchronous on the current stream."""
+    _lib.require_cuda(rows)
+    if rows.dim() != 2 or not 3 <= rows.shape[1] <= 64 or rows.dtype != torch.float32:
+        raise ValueError("augment_clouds: rows must be float32 [N, C] with 3 <= C <= 64 (x, y, z first)")
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    B, n = len(ln), int(rows.shape[0])
+    if not 1 <= B <= AUGMENT_MAX_CLOUDS:
+        raise ValueError("augment_clouds: %d clouds (1 .. %d per call)" % (B, AUGMENT_MAX_CLOUDS))
+    if (ln < 0).any() or int(ln.sum()) != n:
+        raise ValueError("augment_clouds: lengths must be non-negative and sum to the number of rows")
+    limit = int(limit) if limit is not None else 0
+    out_ln = np.minimum(ln, limit) if limit > 0 else ln
+    if limit > 0 and int(ln.max()) <= limit:
+        limit = 0
+    m = int(out_ln.sum())
+    # one host record -> one asynchronous upload: [len i64 B | sample_id u32 B | rotation f32 9B | scale B | shift 3B | noise B]
+    fields = [(ln, np.int64, B), (sample_id, np.uint32, B), (rotation, np.float32, 9 * B), (scale, np.float32, B), (shift, np.float32, 3 * B),
+              (noise, np.float32, B)]
+    host = torch.empty(8 * B + 4 * 16 * B, dtype=torch.uint8).pin_memory()
+    hv, offs, o = host.numpy(), [], 0
+    for value, dtype, count in fields:
+        a = np.ascontiguousarray(np.asarray(value).astype(dtype, copy=False).reshape(-1))
+        if a.size != count:
+            raise ValueError("augment_clouds: a per-cloud argument has %d values, %d expected" % (a.size, count))
+        nbytes = count * a.itemsize
+        hv[o:o + nbytes] = a.view(np.uint8)
+        offs.append(o)
+        o += nbytes
+    dev = rows.device
+    rec = host.to(dev, non_blocking=True)
+    base = rec.data_ptr()
+    rows = rows.contiguous()
+    out = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    out_len = torch.empty((B,), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.ws("lcr_augment_clouds_ws_bytes", n, B, limit, device=dev)
+    _lib.call.lcr_augment_clouds(_lib.ptr(rows), int(rows.shape[1]), base + offs[0], B, n, base + offs[1], base + offs[2], base + offs[3],
+                                 base + offs[4], base + offs[5], int(seed) & 0xFFFFFFFFFFFFFFFF, limit, _lib.ptr(out), m, _lib.ptr(out_len),
+                                 _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return out, out_len
