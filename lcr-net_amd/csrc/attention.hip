@@ -364,7 +364,12 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const float* __restrict__
       s += t;
     }
     s = wave_sum(s);
-    const float mean = s / D;
+    float mean = s / D;
+    // The rounded sum leaves `mean` off by ~1e-7 |mean|, and with the variance below eps rstd is up to 316: a constant row came out as
+    // beta + 3e-4 gamma at D = 1000.  One correction step from the residuals (their sum is exact when the row is constant).
+    float sr = 0.f;
+    for (int i = 0; i < cnt; ++i) sr += vals[i] - mean;
+    mean += wave_sum(sr) / D;
     float ss = 0.f;
     for (int i = 0; i < cnt; ++i) {
       const float d = vals[i] - mean;

@@ -313,7 +313,12 @@ __global__ __launch_bounds__(256) void k_ln_grad(const float* __restrict__ a, co
       }
     }
     s = wave_sum(s);
-    const float mean = s / D;
+    float mean = s / D;
+    float sr = 0.f;                                      // k_add_layernorm's correction step of the mean
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (lane + 64 * i < D) sr += vals[i] - mean;
+    mean += wave_sum(sr) / D;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
