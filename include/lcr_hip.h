@@ -1149,6 +1149,50 @@ int lcr_adan_grad_norm(const LcrAdanTensor* t, int T, double max_grad_norm, doub
                        void* stream);
 int lcr_adan_step(const LcrAdanTensor* t, int T, const LcrAdanHyper* h, const float* clip, void* stream);
 
+/* TEASER-style robust registration from correspondences (experiments/registration/eval.py:197-218 runs TEASER++ with GNC-TLS rotation and
+ * noise_bound 0.01, cbar2 1, gnc_factor 1.4, 100 iterations, cost threshold 1e-12), for S problems in one call (csrc/teaser.hip).  The
+ * layout is that of lcr_ransac_correspondences: src / ref f32 [n,3] stacked problem-major, start int32 [S+1], problem s has
+ * N = start[s+1] - start[s] rows; the result maps src onto ref.  No TEASER++ binary was available: this text is the contract, the fp64
+ * NumPy restatement of tests/teaser_restatement.py the oracle.  All arithmetic is fp64 on the fp32 rows; T is stored as fp32.
+ *   1. Consistency graph (mode 0 = kcore).  For i < j: a = |src_j - src_i|, b = |ref_j - ref_i| (sqrt((dx dx + dy dy) + dz dz)); an edge
+ *      iff |a - b| <= beta, beta = 2 noise_bound sqrt(cbar2).
+ *   2. Selection.  mode 0: the core number of a vertex is the largest k such that it lies in a subgraph of minimum degree k; k_max is
+ *      the largest core number and the selected rows are {v : core(v) = k_max} in ascending order (TEASER++'s k-core mode; the exact
+ *      maximum clique is not computed).  mode 1 = none: every row is selected, steps 1-2 are skipped and core is written as 0.  K = number
+ *      of selected rows.  A problem with k_max < 1 (no edge), K < 3 or N > max_rows is invalid: identity, valid 0, every count 0,
+ *      selected_mask 0 (core is still the graph's).
+ *   3. Rotation by GNC-TLS over the K (K - 1) / 2 measurements a_m = src_j - src_i, b_m = ref_j - ref_i of all pairs i < j of the selected
+ *      rows (not only graph edges).  w = 1, c2 = noise_bound^2, cost_prev = inf; for it = 0 .. max_iterations - 1:
+ *        R = rotation_from_H(sum_m w_m a_m b_m^T) (csrc/rigid3.h: V diag(1, 1, det(V U^T)) U^T of the fp64 SVD H = U S V^T);
+ *        r_m = |b_m - R a_m|^2;   on it = 0 only: mu = 1 / (2 max_m r_m / c2 - 1), and if not mu > 0: stop and keep R;
+ *        th1 = (mu + 1) / mu c2, th2 = mu / (mu + 1) c2, cost = sum_m w_m r_m with the weights that produced R;
+ *        w_m = 0 if r_m >= th1, 1 if r_m <= th2, else sqrt(c2 mu (mu + 1) / r_m) - mu;
+ *        d = |cost - cost_prev|; mu *= gnc_factor; cost_prev = cost; stop if d < cost_threshold.
+ *      rot_inliers = the number of measurements whose final w >= 0.5; iterations = it + 1 at the stop; cost = the last cost (for the stop
+ *      at it = 0 on mu: sum_m r_m under that R, with rot_inliers = K (K - 1) / 2).
+ *   4. Translation, one axis at a time.  x_v = (ref_v - R src_v)[axis] for the K selected rows, rho = noise_bound sqrt(cbar2).  The 2K
+ *      endpoints are listed as x_0 - rho .. x_{K-1} - rho (enter), then x_0 + rho .. x_{K-1} + rho (leave), and sorted by (value, position
+ *      in that list).  After each endpoint C is the set of rows that have entered and not left; for every non-empty C
+ *      xhat = mean of x over C and cost = sum_C (x - xhat)^2 + rho^2 (K - |C|) (computed from ordered prefix sums of x - x_0 and its square).
+ *      The axis estimate is xhat of the smallest cost, the earliest endpoint on ties; t_count[axis] = |C| there.
+ *   The bottom row of T is (0, 0, 0, 1) (the reference writes ones into est_transform[3,:3], which no metric reads).
+ * max_rows is the caller's bound on the rows of one problem (the entry never reads start on the host); it sizes the workspace and the
+ * grids, not the arithmetic: every sum's order depends on its own problem alone, no floating-point atomic is used, so a call returns the
+ * same bytes run to run and a problem the same bytes alone or inside any batch.  One kernel form for every size.
+ * Outputs: T f32 [S,4,4], valid / n_selected int32 [S], rot_inliers int64 [S], t_count int32 [S,3]; nullable detail: iterations int32 [S],
+ * cost f64 [S], selected_mask uint8 [n], core int32 [n].  Rows with a NaN or infinite coordinate give an unspecified transform, never
+ * an access outside the tables.
+ * 2 (max_iterations + 2) + 5 stream-ordered launches, no host synchronisation: the exit test runs on the device, and a stopped problem's
+ * remaining launches exit at once.  Device loops are bounded by max_iterations (GNC) and N rounds (the peel).
+ * Domain: 1 <= S <= 65535, 0 <= max_rows <= 4096, 0 <= n <= S max_rows, mode 0 or 1, noise_bound > 0, cbar2 > 0, gnc_factor > 1 (all
+ * finite), 1 <= max_iterations <= 1000, 0 <= cost_threshold finite; LCR_EARG with text and no launch outside it, LCR_ESPACE for a
+ * workspace below lcr_teaser_ws_bytes (host only: ~ max_rows^2 / 8 + 124 max_rows bytes per problem in mode 0). */
+int lcr_teaser_ws_bytes(int S, int64_t n, int max_rows, int mode, size_t* bytes);
+int lcr_teaser_registration(const float* src, const float* ref, const int32_t* start, int S, int64_t n, int max_rows, double noise_bound,
+                            double cbar2, double gnc_factor, int max_iterations, double cost_threshold, int mode, float* T, int32_t* valid,
+                            int32_t* n_selected, int64_t* rot_inliers, int32_t* t_count, int32_t* iterations, double* cost,
+                            uint8_t* selected_mask, int32_t* core, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1877,6 +1877,49 @@ def ransac_sample_host(seed, h0, count, ransac_n, n):
     return out
 
 
+TEASER_MAX_ROWS = 4096                                   # rows per problem at most (csrc/teaser.hip TZ_MAX_ROWS)
+TEASER_MODES = {"kcore": 0, "none": 1}
+
+
+def teaser_registration(src, ref, start, noise_bound=0.01, cbar2=1.0, gnc_factor=1.4, max_iterations=100, cost_threshold=1e-12,
+                        inlier_selection="kcore", max_rows=None, want_details=False):
+    """TEASER-style robust registration (include/lcr_hip.h, lcr_teaser_registration) for S problems in one native call: src / ref f32 [n,3]
+    stacked problem-major, start int32 [S+1] -> T f32 [S,4,4] (src onto ref), valid int32 [S], n_selected int32 [S], rot_inliers int64 [S],
+    t_count int32 [S,3] (and with want_details iterations int32 [S], cost f64 [S], selected_mask uint8 [n], core int32 [n]).  max_rows: an
+    upper bound on the rows of one problem (default min(n, 4096); a problem above it comes back invalid).  Nothing is read back."""
+    if inlier_selection not in TEASER_MODES:
+        raise ValueError("teaser_registration: inlier_selection must be 'kcore' or 'none', got %r" % (inlier_selection,))
+    nb, cb, gf, ct, mi = float(noise_bound), float(cbar2), float(gnc_factor), float(cost_threshold), int(max_iterations)
+    if not (np.isfinite([nb, cb, gf, ct]).all() and nb > 0 and cb > 0 and gf > 1 and ct >= 0 and 1 <= mi <= 1000):
+        raise ValueError("teaser_registration: needs noise_bound > 0, cbar2 > 0, gnc_factor > 1, 1 <= max_iterations <= 1000 and "
+                         "cost_threshold >= 0 (noise_bound=%r cbar2=%r gnc_factor=%r max_iterations=%r cost_threshold=%r)"
+                         % (noise_bound, cbar2, gnc_factor, max_iterations, cost_threshold))
+    _lib.require_cuda(src, ref, start)
+    if src.dtype != torch.float32 or ref.dtype != torch.float32 or src.dim() != 2 or src.shape[1] != 3 or src.shape != ref.shape:
+        raise ValueError("teaser_registration: src and ref must be float32 [n,3] of the same shape")
+    if start.dtype != torch.int32 or start.dim() != 1 or start.numel() < 2:
+        raise ValueError("teaser_registration: start must be int32 [S+1] with S >= 1")
+    dev = src.device
+    S, n, mode = start.numel() - 1, src.shape[0], TEASER_MODES[inlier_selection]
+    max_rows = min(n, TEASER_MAX_ROWS) if max_rows is None else int(max_rows)
+    ws = _lib.ws("lcr_teaser_ws_bytes", S, n, max_rows, mode, device=dev)
+    T = torch.empty((S, 4, 4), dtype=torch.float32, device=dev)
+    valid = torch.empty((S,), dtype=torch.int32, device=dev)
+    nsel = torch.empty((S,), dtype=torch.int32, device=dev)
+    rot = torch.empty((S,), dtype=torch.int64, device=dev)
+    tcount = torch.empty((S, 3), dtype=torch.int32, device=dev)
+    iters = torch.empty((S,), dtype=torch.int32, device=dev) if want_details else None
+    cost = torch.empty((S,), dtype=torch.float64, device=dev) if want_details else None
+    mask = torch.empty((n,), dtype=torch.uint8, device=dev) if want_details else None
+    core = torch.empty((n,), dtype=torch.int32, device=dev) if want_details else None
+    _lib.call.lcr_teaser_registration(_lib.ptr(src.contiguous()), _lib.ptr(ref.contiguous()), _lib.ptr(start.contiguous()), S, n, max_rows, nb, cb,
+                                      gf, mi, ct, mode, _lib.ptr(T), _lib.ptr(valid), _lib.ptr(nsel), _lib.ptr(rot), _lib.ptr(tcount),
+                                      _lib.ptr(iters), _lib.ptr(cost), _lib.ptr(mask), _lib.ptr(core), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_ptr(dev))
+    out = (T, valid, nsel, rot, tcount)
+    return out + (iters, cost, mask, core) if want_details else out
+
+
 def icp_point_to_point(src, src_len, tgt, tgt_len, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
                        check_every=16, want_corr=False, want_history=False):
     """Point-to-point ICP (include/lcr_hip.h, lcr_icp_point_to_point) for S <= 64 pairs in one native call: src f32 [ns,3] / tgt f32 [nt,3]

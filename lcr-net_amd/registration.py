@@ -17,7 +17,11 @@ generators run for their ground truth, data/Kitti/generate_kitti_pairs.py:145-14
 `icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states.
 Both also run point-to-plane ICP (estimation_method="point_to_plane", Open3D's TransformationEstimationPointToPlane), which needs target
 normals: `estimate_normals` / `estimate_normals_batched` compute them on the GPU (csrc/normals.hip; utils/utils/open3d.py:53-58 with a
-radius, KDTreeSearchParamHybrid)."""
+radius, KDTreeSearchParamHybrid).
+
+TEASER-style robust registration (experiments/registration/eval.py:197-218, `--method teaser`): `teaser_batched` /
+`registration_with_teaser_from_correspondences` (csrc/teaser.hip; consistency graph, k-core selection, GNC-TLS rotation, voted
+translation, as include/lcr_hip.h states under lcr_teaser_registration)."""
 import numpy as np
 import torch
 
@@ -290,3 +294,51 @@ def fpfh_ransac_batched(src, src_len, ref, ref_len, normal_radius, normal_max_nn
         nrm = estimate_normals_batched(pts, ln, normal_radius, normal_max_nn, vp)["normals"]
         feats.append(compute_fpfh_feature_batched(pts, nrm, ln, feature_radius, feature_max_nn))
     return ransac_from_feats_batched(src, ref, feats[0], feats[1], src_len, ref_len, **ransac_kw)
+
+
+# ---- TEASER-style robust registration (experiments/registration/eval.py:197-218, `--method teaser`) ----
+# The reference's solver settings (eval.py:199-208).
+REF_TEASER_NOISE_BOUND = 0.01
+REF_TEASER_CBAR2 = 1.0
+REF_TEASER_GNC_FACTOR = 1.4
+REF_TEASER_MAX_ITERATIONS = 100
+REF_TEASER_COST_THRESHOLD = 1e-12
+
+
+def teaser_batched(src, ref, start, noise_bound=REF_TEASER_NOISE_BOUND, cbar2=REF_TEASER_CBAR2, gnc_factor=REF_TEASER_GNC_FACTOR,
+                   max_iterations=REF_TEASER_MAX_ITERATIONS, cost_threshold=REF_TEASER_COST_THRESHOLD, inlier_selection="kcore",
+                   max_rows=None):
+    """S problems in one native call (csrc/teaser.hip; the definition is in include/lcr_hip.h, lcr_teaser_registration): consistency
+    graph, k-core selection (inlier_selection "kcore", or "none" for every row), GNC-TLS rotation over all pairs of the selected rows and a
+    truncated-least-squares vote per translation axis.  src / ref: f32 [n,3] device tensors stacked problem-major, start: int32 [S+1]
+    device tensor, at most 4096 rows per problem.  -> dict of device tensors, nothing synchronised: T f32 [S,4,4] (src onto ref),
+    valid int32 [S] (0: no edge or fewer than 3 selected rows, identity), n_selected int32 [S], rot_inliers int64 [S], t_count int32 [S,3]."""
+    T, valid, nsel, rot, tcount = F.teaser_registration(src, ref, start, noise_bound, cbar2, gnc_factor, max_iterations, cost_threshold,
+                                                        inlier_selection, max_rows)
+    return {"T": T, "valid": valid, "n_selected": nsel, "rot_inliers": rot, "t_count": tcount}
+
+
+def registration_with_teaser_from_correspondences(src_corr_points, ref_corr_points, noise_bound=0.01, cbar2=1.0, rotation_gnc_factor=1.4,
+                                                  rotation_max_iterations=100, rotation_cost_threshold=1e-12, inlier_selection="kcore"):
+    """What eval.py:197-218 asks of TEASER++ for one pair, in the argument order of registration_with_ransac_from_correspondences:
+    src_corr_points / ref_corr_points are numpy arrays or torch tensors [N,3], row i of one corresponding to row i of the other (at most
+    4096 rows).  Returns the float64 (4,4) ndarray transform from src to ref with the bottom row (0, 0, 0, 1); the identity when the
+    problem is invalid."""
+    if inlier_selection not in F.TEASER_MODES:
+        raise ValueError("inlier_selection must be 'kcore' or 'none', got %r" % (inlier_selection,))
+    n_src, n_ref = (int(np.prod(x.shape)) // 3 for x in (src_corr_points, ref_corr_points))
+    if n_src != n_ref:
+        raise ValueError("src_corr_points and ref_corr_points need the same number of rows (%d vs %d)" % (n_src, n_ref))
+    if n_src > F.TEASER_MAX_ROWS:
+        raise ValueError("at most %d correspondences per problem (%d given): keep the best by score first" % (F.TEASER_MAX_ROWS, n_src))
+    dev = ref_corr_points.device if torch.is_tensor(ref_corr_points) and ref_corr_points.is_cuda else None
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("lcr-net_amd ops run on the GPU only (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    src = _device_points(src_corr_points, dev)
+    ref = _device_points(ref_corr_points, dev)
+    start = torch.tensor([0, src.shape[0]], dtype=torch.int32, device=dev)
+    r = teaser_batched(src, ref, start, noise_bound, cbar2, rotation_gnc_factor, rotation_max_iterations, rotation_cost_threshold,
+                       inlier_selection)
+    return r["T"][0].cpu().numpy().astype(np.float64)

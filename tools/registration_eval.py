@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """Registration evaluation over saved pair files: the counterpart of experiments/registration/eval.py.
 
-    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|ransac_featurematch|fpfh_ransac] [--num_corr K] [--seed S]
+    python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|teaser|ransac_featurematch|fpfh_ransac] [--num_corr K] [--seed S]
                                       [--pairs-per-call P] [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000]
                                       [--write-back] [--mutual-filter] [--edge-similarity 0.9]
                                       [--refine icp|icp_plane [--icp-distance 0.5] [--icp-iterations 30]
                                                               [--normal-radius 1.0] [--normal-max-nn 30]]
                                       [--fpfh-radius 2.5] [--fpfh-max-nn 100]
+                                      [--noise-bound 0.01] [--inlier-selection kcore|none]
 
 Reads every `{seq}_{anc}_{pos}.npz` of FEATURES_DIR (what io_formats.save_registration / demo.py write; both the pos_/anc_ and the
 ref_/src_ key families of eval.py:96-110 are accepted), keeps the top --num_corr correspondences by corr_scores (:114-118), and
@@ -16,6 +17,12 @@ registers the anchor onto the positive:
           (config_reg.py:69-73: 0.3 m, 4 points, 50 000 iterations); --pairs-per-call pairs go into one native call;
           --write-back stores `estimated_transform_ransac` in the file as :184-185 do;
   svd     weighted Procrustes over all correspondences with corr_scores as weights (:186-193), one batched native call per group;
+  teaser  eval.py:197-218 (TEASER++ with GNC-TLS rotation, noise_bound 0.01, cbar2 1, gnc factor 1.4, 100 iterations, cost threshold
+          1e-12) as the GPU operator of lcrnet_amd.registration.teaser_batched states it: consistency graph, k-core selection
+          (--inlier-selection none: every correspondence), GNC-TLS rotation, voted translation; --noise-bound sets the bound, pair files
+          are grouped per native call as for ransac.  At most 4096 correspondences per pair enter (the best by corr_scores when a file
+          holds more or --num_corr asks for more).  The JSON line carries the parameters, the number of invalid pairs (identity
+          returned) and the mean number of selected correspondences;
   ransac_featurematch
           eval.py's fourth choice (utils/utils/open3d.py:109-142): every point of `anc_points_f` is matched to its exact nearest
           neighbour among `pos_feats_f` in feature space (--mutual-filter keeps only matches that point back), and the RANSAC runs on
@@ -100,6 +107,17 @@ def estimate_group(method, items, args, device):
     return T.cpu().numpy().astype(np.float64)
 
 
+def estimate_teaser(items, args, device):
+    """TEASER-style registration for a group of pairs in one native call: (transforms (S,4,4) float64, valid [S], n_selected [S])."""
+    import torch
+    from lcrnet_amd.registration import teaser_batched
+    src, ref, _, start = stacked(items, device)
+    r = teaser_batched(src, ref, start, noise_bound=args.noise_bound, inlier_selection=args.inlier_selection,
+                       max_rows=max([len(s) for s, _, _ in items] + [0]))
+    torch.cuda.synchronize(device)
+    return r["T"].cpu().numpy().astype(np.float64), r["valid"].cpu().numpy(), r["n_selected"].cpu().numpy()
+
+
 def estimate_featurematch(group, args, device):
     """Feature-matching RANSAC for a group of pairs in one native call sequence: (transforms (S,4,4) float64, num_corr [S],
     reject codes uint8 [S, iterations])."""
@@ -174,7 +192,7 @@ def coarse_block(dicts):
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("features_dir")
-    p.add_argument("--method", choices=["lgr", "ransac", "svd", "ransac_featurematch", "fpfh_ransac"], default="lgr")
+    p.add_argument("--method", choices=["lgr", "ransac", "svd", "teaser", "ransac_featurematch", "fpfh_ransac"], default="lgr")
     p.add_argument("--num_corr", type=int, default=None)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--pairs-per-call", type=int, default=16)
@@ -192,6 +210,8 @@ def main(argv=None):
     p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane / fpfh_ransac: neighbours per normal at most")
     p.add_argument("--fpfh-radius", type=float, default=2.5, help="fpfh_ransac: FPFH search radius")
     p.add_argument("--fpfh-max-nn", type=int, default=100, help="fpfh_ransac: neighbours per FPFH row at most")
+    p.add_argument("--noise-bound", type=float, default=0.01, help="teaser: noise bound in metres (eval.py:201)")
+    p.add_argument("--inlier-selection", choices=["kcore", "none"], default="kcore", help="teaser: rows that enter the GNC-TLS fit")
     args = p.parse_args(argv)
     if args.pairs_per_call < 1:
         p.error("--pairs-per-call must be >= 1")
@@ -202,7 +222,11 @@ def main(argv=None):
         seq, anc, pos = parse_name(f)
         if seq == 8 and anc == 15 and pos == 58:          # eval.py:92-94 ("delete bad data")
             continue
-        d, pos_pts, anc_pts, scores = load_pair(f, args.num_corr, need_corr=args.method != "fpfh_ransac")
+        num_corr = args.num_corr
+        if args.method == "teaser":
+            from lcrnet_amd.functional import TEASER_MAX_ROWS
+            num_corr = TEASER_MAX_ROWS if num_corr is None else min(num_corr, TEASER_MAX_ROWS)
+        d, pos_pts, anc_pts, scores = load_pair(f, num_corr, need_corr=args.method != "fpfh_ransac")
         if args.method == "fpfh_ransac":
             missing = [k for k in ("pos_points_f", "anc_points_f", "transform") if k not in d]
             if missing:
@@ -220,7 +244,7 @@ def main(argv=None):
     else:
         import torch
         device = torch.device("cuda", torch.cuda.current_device())
-        est, fm_corr, fm_reject = [], [], []
+        est, fm_corr, fm_reject, tz_valid, tz_selected = [], [], [], [], []
         for g in range(0, len(pairs), args.pairs_per_call):
             group = pairs[g:g + args.pairs_per_call]
             if args.method == "ransac_featurematch":
@@ -232,6 +256,11 @@ def main(argv=None):
                 T, nc = estimate_fpfh(group, args, device)
                 est += list(T)
                 fm_corr += list(nc)
+            elif args.method == "teaser":
+                T, ok, nsel = estimate_teaser([(a, b, s) for _, _, b, a, s in group], args, device)
+                est += list(T)
+                tz_valid += list(ok)
+                tz_selected += list(nsel)
             else:
                 est += list(estimate_group(args.method, [(a, b, s) for _, _, b, a, s in group], args, device))
     scored = est                                          # --write-back stores the method's own estimate, refined or not
@@ -265,6 +294,12 @@ def main(argv=None):
         out["coarse_matching"] = coarse
     if args.method == "ransac":
         out["ransac"] = {"distance_threshold": args.distance_threshold, "ransac_n": args.ransac_n, "num_iterations": args.num_iterations}
+    if args.method == "teaser":
+        from lcrnet_amd import registration as reg_mod
+        out["teaser"] = {"noise_bound": args.noise_bound, "cbar2": reg_mod.REF_TEASER_CBAR2, "gnc_factor": reg_mod.REF_TEASER_GNC_FACTOR,
+                         "max_iterations": reg_mod.REF_TEASER_MAX_ITERATIONS, "cost_threshold": reg_mod.REF_TEASER_COST_THRESHOLD,
+                         "inlier_selection": args.inlier_selection, "invalid": int(sum(1 for v in tz_valid if not v)),
+                         "n_selected": float(np.mean(tz_selected)) if tz_selected else float("nan")}
     if args.method == "ransac_featurematch":
         rej = np.concatenate(fm_reject) if fm_reject else np.zeros((0, args.num_iterations), np.uint8)
         share = lambda code: float((rej == code).mean()) if rej.size else float("nan")
