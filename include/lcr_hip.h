@@ -17,7 +17,14 @@
  *   - stacked ("stack mode") clouds: points f32[N,3] row-major, lengths i64[B] (reference layout,
  *     utils/extensions/cpu/grid_subsampling/grid_subsampling.cpp:20-30);
  *   - return value: 0 ok, -1 bad argument, -2 workspace/output too small, -3 HIP launch error
- *     (text via lcr_last_error()).  Data-dependent conditions are reported through the `status` words.
+ *     (text via lcr_last_error()).  Data-dependent conditions are reported through the `status` words;
+ *   - every nonzero code comes with a text of the form `<called entry>: ...` — the name is that of the entry point the caller called,
+ *     also where a legacy entry forwards to its `_ex` / `_rows` twin or one entry sizes or builds something through another's body.
+ *     One exception: the native drivers (lcr_encoder_forward[_ex], lcr_roformer_forward, lcr_precompute_batch[_rows[_ex]],
+ *     lcr_netvlad_forward / _train_forward / _backward) check their own arguments in their own name but run their operators through the
+ *     public entries of this header, so what an operator refuses — a launch error, or a weight table whose widths are outside the
+ *     operator's domain — carries the OPERATOR's name (`lcr_kpconv_aggregate_mask: C must be ...` out of lcr_encoder_forward_ex).
+ *     The text is per host thread, and a successful call does not clear it: read lcr_last_error() only after a nonzero code.
  *
  * Shape domain (what the kernels are built for = every shape of the shipped configuration, experiments/lcrnet/config_model.py:33-43 with
  * best-model-mixed.tar, and of BASELINE.json's configs; a call outside it returns LCR_EARG with a message, it never computes something else):

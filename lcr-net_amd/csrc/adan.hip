@@ -187,33 +187,18 @@ using namespace lcr;
 
 // Validates the table; *chunks = the workgroups the whole list needs.
 static int adan_check(const char* entry, const LcrAdanTensor* t, int T, bool grads_only, int64_t* chunks) {
-  if (T < 0 || (T > 0 && !t)) {
-    set_error("%s: T = %d tensors with %s table", entry, T, t ? "a" : "no");
-    return LCR_EARG;
-  }
+  if (T < 0 || (T > 0 && !t)) return refuse(LCR_EARG, "%s: T = %d tensors with %s table", entry, T, t ? "a" : "no");
   int64_t total = 0;
   for (int i = 0; i < T; ++i) {
     const float* ptrs[6] = {t[i].g, t[i].p, t[i].m, t[i].n, t[i].d, t[i].pg};
     const int np = grads_only ? 1 : 6;
-    if (t[i].numel < 0) {
-      set_error("%s: tensor %d has numel %lld", entry, i, static_cast<long long>(t[i].numel));
-      return LCR_EARG;
-    }
+    if (t[i].numel < 0) return refuse(LCR_EARG, "%s: tensor %d has numel %lld", entry, i, static_cast<long long>(t[i].numel));
     for (int k = 0; k < np; ++k) {
-      if (t[i].numel > 0 && !ptrs[k]) {
-        set_error("%s: tensor %d has a null pointer", entry, i);
-        return LCR_EARG;
-      }
-      if (reinterpret_cast<uintptr_t>(ptrs[k]) & 3u) {
-        set_error("%s: tensor %d has a pointer that is not 4-byte aligned", entry, i);
-        return LCR_EARG;
-      }
+      if (t[i].numel > 0 && !ptrs[k]) return refuse(LCR_EARG, "%s: tensor %d has a null pointer", entry, i);
+      if (reinterpret_cast<uintptr_t>(ptrs[k]) & 3u) return refuse(LCR_EARG, "%s: tensor %d has a pointer that is not 4-byte aligned", entry, i);
     }
     const int64_t c = (t[i].numel + ADAN_CHUNK - 1) / ADAN_CHUNK;
-    if (c > ADAN_MAX_GRID) {
-      set_error("%s: tensor %d has more than 2^35 elements", entry, i);
-      return LCR_EARG;
-    }
+    if (c > ADAN_MAX_GRID) return refuse(LCR_EARG, "%s: tensor %d has more than 2^35 elements", entry, i);
     total += c;
   }
   *chunks = total;
@@ -222,10 +207,7 @@ static int adan_check(const char* entry, const LcrAdanTensor* t, int T, bool gra
 
 extern "C" int lcr_adan_ws_bytes(const LcrAdanTensor* t, int T, size_t* bytes) {
   int64_t chunks = 0;
-  if (!bytes) {
-    set_error("lcr_adan_ws_bytes: null pointer");
-    return LCR_EARG;
-  }
+  if (!bytes) return refuse(LCR_EARG, "lcr_adan_ws_bytes: null pointer");
   const int rc = adan_check("lcr_adan_ws_bytes", t, T, true, &chunks);
   if (rc != LCR_OK) return rc;
   *bytes = align_up(static_cast<size_t>(std::max<int64_t>(chunks, 1)) * sizeof(double));
@@ -237,14 +219,9 @@ extern "C" int lcr_adan_grad_norm(const LcrAdanTensor* t, int T, double max_grad
   int64_t chunks = 0;
   const int rc = adan_check("lcr_adan_grad_norm", t, T, true, &chunks);
   if (rc != LCR_OK) return rc;
-  if (!norm_clip || !ws || !(max_grad_norm >= 0) || !(eps >= 0)) {
-    set_error("lcr_adan_grad_norm: null pointer, or max_grad_norm / eps negative or NaN");
-    return LCR_EARG;
-  }
-  if (static_cast<size_t>(chunks) * sizeof(double) > ws_bytes) {
-    set_error("lcr_adan_grad_norm: workspace of %zu bytes, %zu needed", ws_bytes, static_cast<size_t>(chunks) * sizeof(double));
-    return LCR_ESPACE;
-  }
+  if (!norm_clip || !ws || !(max_grad_norm >= 0) || !(eps >= 0)) return refuse(LCR_EARG, "lcr_adan_grad_norm: null pointer, or max_grad_norm / eps negative or NaN");
+  if (static_cast<size_t>(chunks) * sizeof(double) > ws_bytes)
+    return refuse_ws(LCR_ESPACE, "lcr_adan_grad_norm", ws_bytes, static_cast<size_t>(chunks) * sizeof(double));
   hipStream_t st = ST(stream);
   AdanNormArgs a;
   a.partial = static_cast<double*>(ws);
@@ -281,10 +258,7 @@ extern "C" int lcr_adan_step(const LcrAdanTensor* t, int T, const LcrAdanHyper* 
   int64_t chunks = 0;
   const int rc = adan_check("lcr_adan_step", t, T, false, &chunks);
   if (rc != LCR_OK) return rc;
-  if (!h || (reinterpret_cast<uintptr_t>(clip) & 3u)) {
-    set_error("lcr_adan_step: no hyper-parameters, or a clip pointer that is not 4-byte aligned");
-    return LCR_EARG;
-  }
+  if (!h || (reinterpret_cast<uintptr_t>(clip) & 3u)) return refuse(LCR_EARG, "lcr_adan_step: no hyper-parameters, or a clip pointer that is not 4-byte aligned");
   hipStream_t st = ST(stream);
   AdanStepArgs a;
   a.clip = clip;

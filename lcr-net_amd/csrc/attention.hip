@@ -392,10 +392,7 @@ __global__ __launch_bounds__(256) void k_relu_inplace(float* __restrict__ x, int
 using namespace lcr;
 
 extern "C" int lcr_rotary_embed(float* x, const float* theta, int64_t N, int heads, void* stream) {
-  if (!x || !theta || N < 0 || heads < 1) {
-    set_error("lcr_rotary_embed: bad argument");
-    return LCR_EARG;
-  }
+  if (!x || !theta || N < 0 || heads < 1) return refuse(LCR_EARG, "lcr_rotary_embed: bad argument");
   if (N == 0) return LCR_OK;
   const int64_t total = N * heads * 16;
   hipLaunchKernelGGL(k_rotary, dim3(static_cast<int>(std::min<int64_t>((total + 255) / 256, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream), x,
@@ -405,10 +402,8 @@ extern "C" int lcr_rotary_embed(float* x, const float* theta, int64_t N, int hea
 
 extern "C" int lcr_attention_f32(const float* q, const float* k, const float* v, int64_t Nq, int64_t Nk, int heads, int head_dim, float* out,
                                  void* stream) {
-  if (!q || !k || !v || !out || Nq < 0 || Nk < 1 || heads < 1 || head_dim != AT_D) {
-    set_error("lcr_attention_f32: bad argument (head_dim must be %d, Nk >= 1)", AT_D);
-    return LCR_EARG;
-  }
+  if (!q || !k || !v || !out || Nq < 0 || Nk < 1 || heads < 1 || head_dim != AT_D)
+    return refuse(LCR_EARG, "lcr_attention_f32: bad argument (head_dim must be %d, Nk >= 1)", AT_D);
   if (Nq == 0) return LCR_OK;
   const float scale = 1.f / sqrtf(static_cast<float>(head_dim));
   KernelTimerScope timed(KT_ATTENTION, static_cast<hipStream_t>(stream), Nq * Nk, 1, heads, head_dim);
@@ -419,29 +414,22 @@ extern "C" int lcr_attention_f32(const float* q, const float* k, const float* v,
 
 extern "C" int lcr_attention_seg_f32(const float* q, const float* k, const float* v, const int64_t* q_len_host, const int64_t* k_len_host,
                                      int P, int heads, int head_dim, float* out, void* stream) {
-  if (!q || !k || !v || !out || !q_len_host || !k_len_host || P < 1 || P > AT_MAX_P || heads < 1 || head_dim != AT_D) {
-    set_error("lcr_attention_seg_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
-    return LCR_EARG;
-  }
+  if (!q || !k || !v || !out || !q_len_host || !k_len_host || P < 1 || P > AT_MAX_P || heads < 1 || head_dim != AT_D)
+    return refuse(LCR_EARG, "lcr_attention_seg_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
   AttnSeg seg;
   seg.P = P;
   int64_t qo = 0, ko = 0, to = 0;
   for (int p = 0; p < P; ++p) {
-    if (q_len_host[p] < 0 || k_len_host[p] < 1) {
-      set_error("lcr_attention_seg_f32: problem %d has %lld queries / %lld keys (keys >= 1)", p, static_cast<long long>(q_len_host[p]),
-                static_cast<long long>(k_len_host[p]));
-      return LCR_EARG;
-    }
+    if (q_len_host[p] < 0 || k_len_host[p] < 1)
+      return refuse(LCR_EARG, "lcr_attention_seg_f32: problem %d has %lld queries / %lld keys (keys >= 1)", p, static_cast<long long>(q_len_host[p]),
+                    static_cast<long long>(k_len_host[p]));
     seg.q_off[p] = static_cast<int>(qo);
     seg.k_off[p] = static_cast<int>(ko);
     seg.tile_off[p] = static_cast<int>(to);
     qo += q_len_host[p];
     ko += k_len_host[p];
     to += (q_len_host[p] + 31) / 32;
-    if (qo > 2147483647 || ko > 2147483647) {
-      set_error("lcr_attention_seg_f32: more than 2^31-1 stacked rows");
-      return LCR_EARG;
-    }
+    if (qo > 2147483647 || ko > 2147483647) return refuse(LCR_EARG, "lcr_attention_seg_f32: more than 2^31-1 stacked rows");
   }
   seg.q_off[P] = static_cast<int>(qo);
   seg.k_off[P] = static_cast<int>(ko);
@@ -458,28 +446,21 @@ extern "C" int lcr_attention_seg_f32(const float* q, const float* k, const float
 // top-k sparsified attention (rpetransformer.py:19-39 with k != None): problem p keeps, per query and head, its kk_host[p] largest scores
 extern "C" int lcr_attention_topk_f32(const float* q, const float* k, const float* v, const int64_t* q_len_host, const int64_t* k_len_host,
                                       const int* kk_host, int P, int heads, int head_dim, float* out, void* stream) {
-  if (!q || !k || !v || !out || !q_len_host || !k_len_host || !kk_host || P < 1 || P > AT_MAX_P || heads < 1 || head_dim != AT_D) {
-    set_error("lcr_attention_topk_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
-    return LCR_EARG;
-  }
+  if (!q || !k || !v || !out || !q_len_host || !k_len_host || !kk_host || P < 1 || P > AT_MAX_P || heads < 1 || head_dim != AT_D)
+    return refuse(LCR_EARG, "lcr_attention_topk_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
   AttnTopkSeg seg;
   seg.P = P;
   int64_t qo = 0, ko = 0;
   for (int p = 0; p < P; ++p) {
-    if (q_len_host[p] < 0 || k_len_host[p] < 1 || k_len_host[p] > ATK_MAXK || kk_host[p] < 0) {
-      set_error("lcr_attention_topk_f32: problem %d has %lld queries / %lld keys (1 <= keys <= %d), k = %d", p, static_cast<long long>(q_len_host[p]),
-                static_cast<long long>(k_len_host[p]), ATK_MAXK, kk_host[p]);
-      return LCR_EARG;
-    }
+    if (q_len_host[p] < 0 || k_len_host[p] < 1 || k_len_host[p] > ATK_MAXK || kk_host[p] < 0)
+      return refuse(LCR_EARG, "lcr_attention_topk_f32: problem %d has %lld queries / %lld keys (1 <= keys <= %d), k = %d", p, static_cast<long long>(q_len_host[p]),
+                    static_cast<long long>(k_len_host[p]), ATK_MAXK, kk_host[p]);
     seg.q_off[p] = static_cast<int>(qo);
     seg.k_off[p] = static_cast<int>(ko);
     seg.kk[p] = kk_host[p];
     qo += q_len_host[p];
     ko += k_len_host[p];
-    if (qo > 2147483647 || ko > 2147483647) {
-      set_error("lcr_attention_topk_f32: more than 2^31-1 stacked rows");
-      return LCR_EARG;
-    }
+    if (qo > 2147483647 || ko > 2147483647) return refuse(LCR_EARG, "lcr_attention_topk_f32: more than 2^31-1 stacked rows");
   }
   seg.q_off[P] = static_cast<int>(qo);
   seg.k_off[P] = static_cast<int>(ko);
@@ -492,10 +473,7 @@ extern "C" int lcr_attention_topk_f32(const float* q, const float* k, const floa
 
 extern "C" int lcr_add_layernorm(const float* a, const float* b, const float* gamma, const float* beta, int64_t N, int D, float eps, float* y,
                                  void* stream) {
-  if (!a || !gamma || !beta || !y || N < 0 || D < 1 || D > 1024) {
-    set_error("lcr_add_layernorm: bad argument (D <= 1024)");
-    return LCR_EARG;
-  }
+  if (!a || !gamma || !beta || !y || N < 0 || D < 1 || D > 1024) return refuse(LCR_EARG, "lcr_add_layernorm: bad argument (D <= 1024)");
   if (N == 0) return LCR_OK;
   hipLaunchKernelGGL(k_add_layernorm, dim3(static_cast<int>(std::min<int64_t>((N + 3) / 4, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream), a, b,
                      gamma, beta, N, D, eps, y);
@@ -503,7 +481,7 @@ extern "C" int lcr_add_layernorm(const float* a, const float* b, const float* ga
 }
 
 extern "C" int lcr_relu_inplace(float* x, int64_t n, void* stream) {
-  if (!x || n < 0) return LCR_EARG;
+  if (!x || n < 0) return refuse(LCR_EARG, "lcr_relu_inplace: null pointer or a negative count: n=%lld", static_cast<long long>(n));
   if (n == 0) return LCR_OK;
   hipLaunchKernelGGL(k_relu_inplace, dim3(static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream), x, n);
   return check_launch("lcr_relu_inplace");

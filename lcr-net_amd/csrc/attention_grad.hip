@@ -380,10 +380,7 @@ __global__ __launch_bounds__(256) void k_ln_grad_reduce(const float* __restrict_
 using namespace lcr;
 
 extern "C" int lcr_attention_grad_ws_bytes(int64_t n_queries, int heads, size_t* bytes) {
-  if (!bytes || n_queries < 0 || heads < 1) {
-    set_error("lcr_attention_grad_ws_bytes: bad argument");
-    return LCR_EARG;
-  }
+  if (!bytes || n_queries < 0 || heads < 1) return refuse(LCR_EARG, "lcr_attention_grad_ws_bytes: bad argument");
   *bytes = align_up(static_cast<size_t>(2) * static_cast<size_t>(heads) * static_cast<size_t>(n_queries) * sizeof(float));
   return LCR_OK;
 }
@@ -392,19 +389,15 @@ extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const 
                                           const int64_t* q_len_host, const int64_t* k_len_host, int P, int heads, int head_dim, float* dq, float* dk,
                                           float* dv, void* ws, size_t ws_bytes, void* stream) {
   if (!q || !k || !v || !out || !d_out || !dq || !dk || !dv || !q_len_host || !k_len_host || P < 1 || P > AT_MAX_P || heads < 1 || heads > 65535 ||
-      head_dim != AT_D) {
-    set_error("lcr_attention_seg_grad_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
-    return LCR_EARG;
-  }
+      head_dim != AT_D)
+    return refuse(LCR_EARG, "lcr_attention_seg_grad_f32: bad argument (head_dim must be %d, 1 <= P <= %d)", AT_D, AT_MAX_P);
   AgSeg seg;
   seg.P = P;
   int64_t qo = 0, ko = 0, qt = 0, kt = 0;
   for (int p = 0; p < P; ++p) {
-    if (q_len_host[p] < 0 || k_len_host[p] < 1) {
-      set_error("lcr_attention_seg_grad_f32: problem %d has %lld queries / %lld keys (keys >= 1)", p, static_cast<long long>(q_len_host[p]),
-                static_cast<long long>(k_len_host[p]));
-      return LCR_EARG;
-    }
+    if (q_len_host[p] < 0 || k_len_host[p] < 1)
+      return refuse(LCR_EARG, "lcr_attention_seg_grad_f32: problem %d has %lld queries / %lld keys (keys >= 1)", p, static_cast<long long>(q_len_host[p]),
+                    static_cast<long long>(k_len_host[p]));
     seg.q_off[p] = static_cast<int>(qo);
     seg.k_off[p] = static_cast<int>(ko);
     seg.qt_off[p] = static_cast<int>(qt);
@@ -413,10 +406,7 @@ extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const 
     ko += k_len_host[p];
     qt += (q_len_host[p] + 31) / 32;
     kt += (k_len_host[p] + 31) / 32;
-    if (qo > 2147483647 || ko > 2147483647) {
-      set_error("lcr_attention_seg_grad_f32: more than 2^31-1 stacked rows");
-      return LCR_EARG;
-    }
+    if (qo > 2147483647 || ko > 2147483647) return refuse(LCR_EARG, "lcr_attention_seg_grad_f32: more than 2^31-1 stacked rows");
   }
   seg.q_off[P] = static_cast<int>(qo);
   seg.k_off[P] = static_cast<int>(ko);
@@ -424,10 +414,7 @@ extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const 
   seg.kt_off[P] = static_cast<int>(kt);
   size_t need = 0;
   lcr_attention_grad_ws_bytes(qo, heads, &need);
-  if (qo > 0 && (!ws || ws_bytes < need)) {
-    set_error("lcr_attention_seg_grad_f32: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  if (qo > 0 && (!ws || ws_bytes < need)) return refuse_ws(LCR_ESPACE, "lcr_attention_seg_grad_f32", ws_bytes, need);
   const float scale = 1.f / sqrtf(static_cast<float>(head_dim));
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* Lq = static_cast<float*>(ws);
@@ -439,10 +426,7 @@ extern "C" int lcr_attention_seg_grad_f32(const float* q, const float* k, const 
 }
 
 extern "C" int lcr_rotary_embed_grad(const float* y, const float* dy, const float* theta, int64_t N, int heads, float* dx, float* dtheta, void* stream) {
-  if (!y || !dy || !theta || !dx || !dtheta || N < 0 || heads < 1) {
-    set_error("lcr_rotary_embed_grad: bad argument");
-    return LCR_EARG;
-  }
+  if (!y || !dy || !theta || !dx || !dtheta || N < 0 || heads < 1) return refuse(LCR_EARG, "lcr_rotary_embed_grad: bad argument");
   if (N == 0) return LCR_OK;
   const int64_t total = N * heads * 16;
   hipLaunchKernelGGL(k_rotary_grad, dim3(static_cast<int>(std::min<int64_t>((total + 255) / 256, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream), y,
@@ -451,10 +435,7 @@ extern "C" int lcr_rotary_embed_grad(const float* y, const float* dy, const floa
 }
 
 extern "C" int lcr_add_layernorm_grad_ws_bytes(int64_t N, int D, size_t* bytes) {
-  if (!bytes || N < 0 || D < 1 || D > 1024) {
-    set_error("lcr_add_layernorm_grad_ws_bytes: bad argument (D <= 1024)");
-    return LCR_EARG;
-  }
+  if (!bytes || N < 0 || D < 1 || D > 1024) return refuse(LCR_EARG, "lcr_add_layernorm_grad_ws_bytes: bad argument (D <= 1024)");
   const size_t parts = static_cast<size_t>((N + LNG_ROWS - 1) / LNG_ROWS);
   *bytes = align_up(parts * 2 * static_cast<size_t>(D) * sizeof(float));
   return LCR_OK;
@@ -462,22 +443,13 @@ extern "C" int lcr_add_layernorm_grad_ws_bytes(int64_t N, int D, size_t* bytes) 
 
 extern "C" int lcr_add_layernorm_grad(const float* a, const float* b, const float* gamma, const float* dy, int64_t N, int D, float eps, float* dx,
                                       float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
-  if (!a || !gamma || !dy || !dx || !dgamma || !dbeta || N < 0 || D < 1 || D > 1024) {
-    set_error("lcr_add_layernorm_grad: bad argument (D <= 1024)");
-    return LCR_EARG;
-  }
+  if (!a || !gamma || !dy || !dx || !dgamma || !dbeta || N < 0 || D < 1 || D > 1024) return refuse(LCR_EARG, "lcr_add_layernorm_grad: bad argument (D <= 1024)");
   size_t need = 0;
   lcr_add_layernorm_grad_ws_bytes(N, D, &need);
-  if (N > 0 && (!ws || ws_bytes < need)) {
-    set_error("lcr_add_layernorm_grad: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  if (N > 0 && (!ws || ws_bytes < need)) return refuse_ws(LCR_ESPACE, "lcr_add_layernorm_grad", ws_bytes, need);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t parts = (N + LNG_ROWS - 1) / LNG_ROWS;
-  if (parts > 4 * static_cast<int64_t>(2147483647)) {
-    set_error("lcr_add_layernorm_grad: too many rows");
-    return LCR_EARG;
-  }
+  if (parts > 4 * static_cast<int64_t>(2147483647)) return refuse(LCR_EARG, "lcr_add_layernorm_grad: too many rows");
   if (N > 0)
     hipLaunchKernelGGL(k_ln_grad, dim3(static_cast<int>((parts + 3) / 4)), dim3(256), 0, st, a, b, gamma, dy, N, D, eps, dx, static_cast<float*>(ws));
   hipLaunchKernelGGL(k_ln_grad_reduce, dim3((2 * D + 3) / 4), dim3(256), 0, st, static_cast<const float*>(ws), parts, D, dgamma, dbeta);   // N == 0: zeros

@@ -190,22 +190,13 @@ using namespace lcr;
 extern "C" void lcr_augment_debug_select_mask(uint32_t mask) { g_aug_select_mask.store(mask, std::memory_order_relaxed); }
 
 static int aug_check_shape(const char* who, int B, int64_t n_cap) {
-  if (B < 1 || B > AUG_MAX_B) {
-    set_error("%s: %d clouds (1 .. %d per call)", who, B, AUG_MAX_B);
-    return LCR_EARG;
-  }
-  if (n_cap < 0 || n_cap > (int64_t(1) << 31) - 2) {
-    set_error("%s: capacity of %lld rows (0 .. 2^31-2)", who, static_cast<long long>(n_cap));
-    return LCR_EARG;
-  }
+  if (B < 1 || B > AUG_MAX_B) return refuse(LCR_EARG, "%s: %d clouds (1 .. %d per call)", who, B, AUG_MAX_B);
+  if (n_cap < 0 || n_cap > (int64_t(1) << 31) - 2) return refuse(LCR_EARG, "%s: capacity of %lld rows (0 .. 2^31-2)", who, static_cast<long long>(n_cap));
   return LCR_OK;
 }
 
 extern "C" int lcr_augment_clouds_ws_bytes(int64_t n_cap, int B, int64_t limit, size_t* bytes) {
-  if (!bytes) {
-    set_error("lcr_augment_clouds_ws_bytes: null size pointer");
-    return LCR_EARG;
-  }
+  if (!bytes) return refuse(LCR_EARG, "lcr_augment_clouds_ws_bytes: null size pointer");
   const int rc = aug_check_shape("lcr_augment_clouds_ws_bytes", B, n_cap);
   if (rc) return rc;
   *bytes = aug_layout(nullptr, n_cap, limit > 0).bytes;
@@ -216,25 +207,17 @@ extern "C" int lcr_augment_clouds(const float* rows, int row_floats, const int64
                                   const float* rotation, const float* scale, const float* shift, const float* noise, uint64_t seed,
                                   int64_t limit, float* out_xyz, int64_t out_cap, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes,
                                   void* stream) {
-  if (row_floats < 3 || row_floats > 64) {
-    set_error("lcr_augment_clouds: rows of %d floats (3 .. 64: x, y, z first)", row_floats);
-    return LCR_EARG;
-  }
+  if (row_floats < 3 || row_floats > 64) return refuse(LCR_EARG, "lcr_augment_clouds: rows of %d floats (3 .. 64: x, y, z first)", row_floats);
   const int rc = aug_check_shape("lcr_augment_clouds", B, n_cap);
   if (rc) return rc;
-  if (out_cap < 0 || out_cap > n_cap) {
-    set_error("lcr_augment_clouds: output capacity of %lld rows (0 .. n_cap = %lld)", static_cast<long long>(out_cap), static_cast<long long>(n_cap));
-    return LCR_EARG;
-  }
-  if (!len || !sample_id || !rotation || !scale || !shift || !noise || !out_len || !status || !ws || (n_cap > 0 && !rows) || (out_cap > 0 && !out_xyz)) {
-    set_error("lcr_augment_clouds: null argument");
-    return LCR_EARG;
-  }
+  if (out_cap < 0 || out_cap > n_cap)
+    return refuse(LCR_EARG, "lcr_augment_clouds: output capacity of %lld rows (0 .. n_cap = %lld)", static_cast<long long>(out_cap), static_cast<long long>(n_cap));
+  if (!len || !sample_id || !rotation || !scale || !shift || !noise || !out_len || !status || !ws || (n_cap > 0 && !rows) || (out_cap > 0 && !out_xyz))
+    return refuse(LCR_EARG, "lcr_augment_clouds: null argument");
   const bool select = limit > 0;
   const AugLayout L = aug_layout(ws, n_cap, select);
   if (L.bytes > ws_bytes) {                    // refused like every other argument of this entry: nothing is launched
-    set_error("lcr_augment_clouds: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
-    return LCR_EARG;
+    return refuse(LCR_EARG, "lcr_augment_clouds: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
   }
   hipStream_t st = ST(stream);
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
@@ -245,7 +228,7 @@ extern "C" int lcr_augment_clouds(const float* rows, int row_floats, const int64
   if (select) {
     hipLaunchKernelGGL(k_aug_keys, dim3(blocks_for(n_cap, 256, 2048)), dim3(256), 0, st, L.hdr, sample_id, k0, k1,
                        g_aug_select_mask.load(std::memory_order_relaxed), L.keyA, L.valA);
-    const int src = radix_sort_pairs(&L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, radix_passes(32 + cbits), L.hist, L.scan_ws, st);
+    const int src = radix_sort_pairs("lcr_augment_clouds", &L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, radix_passes(32 + cbits), L.hist, L.scan_ws, st);
     if (src) return src;
   }
   hipLaunchKernelGGL(k_aug_apply, dim3(blocks_for(out_cap, 256, 2048)), dim3(256), 0, st, L.hdr, rows, row_floats, sample_id, rotation, scale, shift,

@@ -23,7 +23,11 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));   // a lane's share
 constexpr int GN_REPLICAS = 8;
 constexpr int GN_MAX_SEG = 256;  // segments per GroupNorm call
 
-void set_error(const char* fmt, ...);
+// The one exit of every nonzero code: sets this thread's error text (what lcr_last_error returns) and returns `code`.
+//   return refuse(LCR_EARG, "%s: ...", who, ...);      `who` = the entry point the caller called
+int refuse(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// the text of every too-small workspace
+inline int refuse_ws(int code, const char* who, size_t have, size_t need) { return refuse(code, "%s: workspace of %zu bytes, %zu needed", who, have, need); }
 
 // B stacked clouds (or pairs) given by host lengths: exclusive row offsets, off[B] = total rows.  Passed by value in kernel arguments.
 constexpr int GRID_MAX_B = 64;   // clouds per call
@@ -32,18 +36,14 @@ struct Stack {
   int64_t off[GRID_MAX_B + 1];
 };
 // The domain of every such table: 1 <= B <= GRID_MAX_B, lengths non-null, each length and the total in [0, 2^31-1].  Fills *out and
-// returns LCR_OK, or sets the error text in the name of entry point `who` and returns LCR_EARG.  No HIP call.
+// returns LCR_OK, or refuses with LCR_EARG in the name of entry point `who`.  No HIP call.
 int stack_from_lengths(const char* who, const int64_t* lengths, int B, Stack* out);
 // One launch of one workgroup: the table's lengths to len[B] and / or its offsets to off[B + 1], *status cleared (each may be null).
 int stack_to_device(const char* who, const Stack& C, int64_t* len, int64_t* off, int32_t* status, hipStream_t st);
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return LCR_EHIP;
-  }
-  return LCR_OK;
+  return e == hipSuccess ? LCR_OK : refuse(LCR_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
@@ -361,14 +361,14 @@ struct KernelTimerScope {
 
 // ---- device-wide exclusive scan of int32 (n known on the host as a capacity) ---------------------
 // out[i] = sum(in[0..i-1]); out may alias in; total (i64) written to *total if non-null.
-// ws needs scan_ws_bytes(n) bytes.
+// ws needs scan_ws_bytes(n) bytes.  `who`: the entry point on whose behalf it runs (the name in a launch error).
 size_t scan_ws_bytes(int64_t n);
-int exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int64_t* total, void* ws, hipStream_t st);
+int exclusive_scan_i32(const char* who, const int32_t* in, int32_t* out, int64_t n, int64_t* total, void* ws, hipStream_t st);
 // A caller that issues many scans back to back (the native pre-processing driver) can lend them a region it has ALREADY zeroed
 // for their tile-state words: each scan then skips its own fill launch.  Per host thread; nullptr / 0 ends the loan.
 void scan_state_pool(void* zeroed, size_t bytes);
 // same, over min(n, *n_dev + n_add) entries (n_dev: device-side count; launches are sized for n and exit early beyond it)
-int exclusive_scan_i32_dev(const int32_t* in, int32_t* out, int64_t n, const int32_t* n_dev, int n_add, int64_t* total, void* ws,
-                           hipStream_t st);
+int exclusive_scan_i32_dev(const char* who, const int32_t* in, int32_t* out, int64_t n, const int32_t* n_dev, int n_add, int64_t* total,
+                           void* ws, hipStream_t st);
 
 }  // namespace lcr

@@ -14,31 +14,25 @@ namespace lcr {
 
 static thread_local char g_err[512] = "";
 
-void set_error(const char* fmt, ...) {
+int refuse(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+  return code;
 }
 
 int stack_from_lengths(const char* who, const int64_t* lengths, int B, Stack* out) {
-  if (B < 1 || B > GRID_MAX_B || !lengths) {
-    set_error("%s: outside the domain (1 <= B <= %d, lengths non-null): B=%d%s", who, GRID_MAX_B, B, lengths ? "" : ", null lengths");
-    return LCR_EARG;
-  }
+  if (B < 1 || B > GRID_MAX_B || !lengths)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= B <= %d, lengths non-null): B=%d%s", who, GRID_MAX_B, B, lengths ? "" : ", null lengths");
   out->B = B;
   out->off[0] = 0;
   for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > INT32_MAX) {
-      set_error("%s: cloud %d has a negative or too large length (%lld)", who, b, static_cast<long long>(lengths[b]));
-      return LCR_EARG;
-    }
+    if (lengths[b] < 0 || lengths[b] > INT32_MAX)
+      return refuse(LCR_EARG, "%s: cloud %d has a negative or too large length (%lld)", who, b, static_cast<long long>(lengths[b]));
     out->off[b + 1] = out->off[b] + lengths[b];
   }
-  if (out->off[B] > INT32_MAX) {
-    set_error("%s: more than 2^31-1 rows (%lld)", who, static_cast<long long>(out->off[B]));
-    return LCR_EARG;
-  }
+  if (out->off[B] > INT32_MAX) return refuse(LCR_EARG, "%s: more than 2^31-1 rows (%lld)", who, static_cast<long long>(out->off[B]));
   return LCR_OK;
 }
 
@@ -288,12 +282,12 @@ void scan_state_pool(void* zeroed, size_t bytes) {
 
 size_t scan_ws_bytes(int64_t n) { return align_up(sizeof(uint64_t) * (static_cast<size_t>((n + SCAN_TILE - 1) / SCAN_TILE) + 2)); }
 
-int exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int64_t* total, void* ws, hipStream_t st) {
-  return exclusive_scan_i32_dev(in, out, n, nullptr, 0, total, ws, st);
+int exclusive_scan_i32(const char* who, const int32_t* in, int32_t* out, int64_t n, int64_t* total, void* ws, hipStream_t st) {
+  return exclusive_scan_i32_dev(who, in, out, n, nullptr, 0, total, ws, st);
 }
 
-int exclusive_scan_i32_dev(const int32_t* in, int32_t* out, int64_t n, const int32_t* n_dev, int n_add, int64_t* total, void* ws,
-                           hipStream_t st) {
+int exclusive_scan_i32_dev(const char* who, const int32_t* in, int32_t* out, int64_t n, const int32_t* n_dev, int n_add, int64_t* total,
+                           void* ws, hipStream_t st) {
   if (n <= 0) {
     if (total) hipMemsetAsync(total, 0, sizeof(int64_t), st);
     return LCR_OK;
@@ -311,13 +305,13 @@ int exclusive_scan_i32_dev(const int32_t* in, int32_t* out, int64_t n, const int
     }
     uint32_t* ticket = reinterpret_cast<uint32_t*>(state + nt);
     hipLaunchKernelGGL(k_scan_lookback, dim3(nt), dim3(SCAN_T), 0, st, in, out, n, n_dev, n_add, total, state, ticket);
-    return check_launch("exclusive_scan_i32");
+    return check_launch(who);
   }
   int32_t* sums = static_cast<int32_t*>(ws);
   hipLaunchKernelGGL(k_scan_tile_sums, dim3(nt), dim3(SCAN_T), 0, st, in, n, sums, n_dev, n_add);
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_T), 0, st, sums, nt, total, n_dev, n_add);
   hipLaunchKernelGGL(k_scan_apply, dim3(nt), dim3(SCAN_T), 0, st, in, out, n, sums, n_dev, n_add);
-  return check_launch("exclusive_scan_i32");
+  return check_launch(who);
 }
 
 }  // namespace lcr
@@ -331,9 +325,9 @@ __global__ void k_spin(long long ticks) {
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
 extern "C" int lcr_stream_spin(int microseconds, void* stream) {
-  if (microseconds < 0 || microseconds > 100000) return LCR_EARG;
+  if (microseconds < 0 || microseconds > 100000) return lcr::refuse(LCR_EARG, "lcr_stream_spin: outside the domain (0 <= microseconds <= 100000): %d", microseconds);
   hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<long long>(microseconds) * 100);
-  return hipGetLastError() == hipSuccess ? LCR_OK : LCR_EHIP;
+  return lcr::check_launch("lcr_stream_spin");
 }
 
 // Time only every n-th launch of each kind (n >= 1).  A timed launch costs four event records and a profiled dispatch (its

@@ -27,12 +27,16 @@ constexpr float ENC_SLOPE = 0.1f;
 struct Arena {
   char*  base;
   size_t off, cap;
+  const char* who;        // the entry point that carves, for spent()
+  int    block;           // the residual block it carves for (-1: the driver's own buffers)
   template <typename T>
   T* take(size_t n) {
     const size_t o = off;
     off = align_up(off + n * sizeof(T));
     return (base && off <= cap) ? reinterpret_cast<T*>(base + o) : nullptr;
   }
+  // a carve (or the statistics pool beside it) came back empty: lcr_encoder_ws_bytes sizes both, so this should not happen
+  int spent() const { return refuse(LCR_ESPACE, "%s: block %d ran out of workspace", who, block); }
 };
 
 struct StageIO {
@@ -63,7 +67,7 @@ static int unary_raw(const LcrUnaryW& u, const float* x, int64_t n, int cin, int
                      float** y_out, double** stats_out, hipStream_t s) {
   float* y = ws.take<float>(static_cast<size_t>(n) * cout);
   double* stats = sp.take();
-  if (!y || !stats) return LCR_ESPACE;
+  if (!y || !stats) return ws.spent();
   // on the bf16 matrix cores where the one dispatch rule says so (lcr_gemm_split_ok) and the caller provides the weight's three bf16 terms
   // (fp32-faithful, gemm_split.hip)
   const bool split = u.w_split && lcr_gemm_split_ok(cout, cin);
@@ -82,13 +86,13 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
   // 1. unary1 on the SUPPORT rows (+ the positive-row flags KPConv's neighbour count needs)
   const float* x = s_feats;
   uint8_t* pos = ws.take<uint8_t>(static_cast<size_t>(Ns));
-  if (!pos) return LCR_ESPACE;
+  if (!pos) return ws.spent();
   if (b.unary1.w) {
     float* y1;
     double* st1;
     if ((rc = unary_raw(b.unary1, s_feats, Ns, b.cin, mid, sup, sp, ws, &y1, &st1, s))) return rc;
     float* x1 = ws.take<float>(static_cast<size_t>(Ns) * mid);
-    if (!x1) return LCR_ESPACE;
+    if (!x1) return ws.spent();
     if ((rc = TURN(lcr_groupnorm_apply(y1, st1, b.unary1.gn_w, b.unary1.gn_b, nullptr, nullptr, nullptr, nullptr, x1, Ns, mid, g, sup.seg, sp.S,
                                   ENC_GN_EPS, ENC_SLOPE, 1, pos, s))))
       return rc;
@@ -102,7 +106,7 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
   float* kpo = ws.take<float>(static_cast<size_t>(M) * mid);
   uint16_t* kmask = ws.take<uint16_t>(static_cast<size_t>(M));
   double* stc = sp.take();
-  if (!A || !nn || !kpo || !kmask || !stc) return LCR_ESPACE;
+  if (!A || !nn || !kpo || !kmask || !stc) return ws.spent();
   // lists that come from a radius search (the reference's radius_neighbors and ours alike) hold their valid entries first, padding (= Ns)
   // behind them: the CALLER says so with LCR_ENC_LISTS_VALID_FIRST and the aggregation may then stop at the first chunk with a hole.
   // Without the flag every chunk is scanned (rows with interior padding are legal input).  LCR_KP_VALID_FIRST=0 ignores the flag.
@@ -139,7 +143,7 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
   if (!no_anorm && mid <= 256 && mid % 4 == 0 && b.cout > 32 && q.min_rows >= 64) {
     y = ws.take<float>(static_cast<size_t>(M) * b.cout);
     sty = sp.take();
-    if (!y || !sty) return LCR_ESPACE;
+    if (!y || !sty) return ws.spent();
     const bool split2 = b.unary2.w_split && lcr_gemm_split_ok(b.cout, mid);     // the same rule as unary_raw
     if ((rc = split2 ? TURN(lcr_gemm_f32_bsplit_anorm(kpo, b.unary2.w_split, y, M, b.cout, mid, b.unary2.b, stc, b.normconv_w, b.normconv_b, g,
                                                       ENC_GN_EPS, ENC_SLOPE, q.seg, sp.S, g, sty, s))
@@ -148,7 +152,7 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
       return rc;
   } else {
     float* x2 = ws.take<float>(static_cast<size_t>(M) * mid);
-    if (!x2) return LCR_ESPACE;
+    if (!x2) return ws.spent();
     if ((rc = TURN(lcr_groupnorm_apply(kpo, stc, b.normconv_w, b.normconv_b, nullptr, nullptr, nullptr, nullptr, x2, M, mid, g, q.seg, sp.S, ENC_GN_EPS,
                                   ENC_SLOPE, 1, nullptr, s))))
       return rc;
@@ -158,7 +162,7 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
   const float* res = s_feats;
   if (b.strided) {
     float* pooled = ws.take<float>(static_cast<size_t>(M) * b.cin);
-    if (!pooled) return LCR_ESPACE;
+    if (!pooled) return ws.spent();
     if ((rc = TURN(lcr_maxpool(s_feats, idx, 0, M, Ns, H, b.cin, pooled, q.order, s)))) return rc;
     res = pooled;
   }
@@ -177,7 +181,7 @@ static int residual_block(const LcrBlockW& b, const float* s_feats, const StageI
 
 // workspace of one block (worst case over the blocks), + two ping-pong block outputs + the statistics arena
 static size_t block_ws_bytes(const LcrBlockW& b, int64_t M, int64_t Ns) {
-  Arena a{nullptr, 0, ~size_t(0)};
+  Arena a{nullptr, 0, ~size_t(0), "", -1};
   const int mid = b.cout / 4;
   a.take<uint8_t>(Ns);
   a.take<float>(static_cast<size_t>(Ns) * mid);
@@ -197,12 +201,8 @@ static size_t block_ws_bytes(const LcrBlockW& b, int64_t M, int64_t Ns) {
 static const int BLOCK_Q[LCR_ENC_BLOCKS] = {0, 1, 1, 1, 2, 2, 2, 3, 3, 3};
 static const int BLOCK_S[LCR_ENC_BLOCKS] = {0, 0, 1, 1, 1, 2, 2, 2, 3, 3};
 
-}  // namespace lcr
-
-using namespace lcr;
-
-extern "C" int lcr_encoder_ws_bytes(const LcrEncoderW* W, const int64_t* n_host, int S, size_t* bytes) {
-  if (!W || !n_host || !bytes || S < 1) return LCR_EARG;
+static int encoder_ws_bytes(const char* who, const LcrEncoderW* W, const int64_t* n_host, int S, size_t* bytes) {
+  if (!W || !n_host || !bytes || S < 1) return refuse(LCR_EARG, "%s: null pointer or S < 1: S=%d", who, S);
   size_t blk = 0, pp = 0;
   for (int i = 0; i < LCR_ENC_BLOCKS; ++i) {
     blk = std::max(blk, block_ws_bytes(W->blocks[i], n_host[BLOCK_Q[i]], n_host[BLOCK_S[i]]));
@@ -213,33 +213,21 @@ extern "C" int lcr_encoder_ws_bytes(const LcrEncoderW* W, const int64_t* n_host,
   return LCR_OK;
 }
 
-extern "C" int lcr_encoder_forward(const LcrEncoderW* W, const float* feats0, const float* const* points, const int32_t* const* neighbors,
-                                   const int32_t* const* subsampling, const int32_t* const* order, const int64_t* const* seg_len, int S,
-                                   const int64_t* n_host, const int64_t* seg_min_rows_host, const int* limits, float* const* out_feats,
-                                   void* ws, size_t ws_bytes, void* stream) {
-  return lcr_encoder_forward_ex(W, feats0, points, neighbors, subsampling, order, seg_len, S, n_host, seg_min_rows_host, limits, out_feats, 0u, ws,
-                                ws_bytes, stream);
-}
-
-extern "C" int lcr_encoder_forward_ex(const LcrEncoderW* W, const float* feats0, const float* const* points, const int32_t* const* neighbors,
-                                      const int32_t* const* subsampling, const int32_t* const* order, const int64_t* const* seg_len, int S,
-                                      const int64_t* n_host, const int64_t* seg_min_rows_host, const int* limits, float* const* out_feats,
-                                      unsigned flags, void* ws, size_t ws_bytes, void* stream) {
-  if (!W || !feats0 || !points || !neighbors || !subsampling || !seg_len || !n_host || !limits || !out_feats || !ws || S < 1) {
-    set_error("lcr_encoder_forward: bad argument");
-    return LCR_EARG;
-  }
+// the body of lcr_encoder_forward and lcr_encoder_forward_ex; `who` = the one that was called
+static int encoder_forward(const char* who, const LcrEncoderW* W, const float* feats0, const float* const* points, const int32_t* const* neighbors,
+                           const int32_t* const* subsampling, const int32_t* const* order, const int64_t* const* seg_len, int S,
+                           const int64_t* n_host, const int64_t* seg_min_rows_host, const int* limits, float* const* out_feats, unsigned flags,
+                           void* ws, size_t ws_bytes, void* stream) {
+  if (!W || !feats0 || !points || !neighbors || !subsampling || !seg_len || !n_host || !limits || !out_feats || !ws || S < 1)
+    return refuse(LCR_EARG, "%s: bad argument", who);
   size_t need = 0;
-  lcr_encoder_ws_bytes(W, n_host, S, &need);
-  if (ws_bytes < need) {
-    set_error("lcr_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  encoder_ws_bytes(who, W, n_host, S, &need);
+  if (ws_bytes < need) return refuse(LCR_ESPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   StageIO st[4];
   for (int i = 0; i < 4; ++i) st[i] = StageIO{points[i], seg_len[i], order ? order[i] : nullptr, n_host[i], seg_min_rows_host ? seg_min_rows_host[i] : 0};
   // layout: [statistics arena][ping][pong][block scratch]
-  Arena top{static_cast<char*>(ws), 0, ws_bytes};
+  Arena top{static_cast<char*>(ws), 0, ws_bytes, who, -1};
   StatsPool sp{top.take<double>(stats_doubles(S, W->groups)), 0, stats_doubles(S, W->groups), S, W->groups};
   size_t pp = 0;
   for (int i = 0; i < LCR_ENC_BLOCKS; ++i) pp = std::max(pp, sizeof(float) * static_cast<size_t>(n_host[BLOCK_Q[i]]) * W->blocks[i].cout);
@@ -247,7 +235,7 @@ extern "C" int lcr_encoder_forward_ex(const LcrEncoderW* W, const float* feats0,
   float* ping = reinterpret_cast<float*>(top.take<char>(pp));
   float* pong = reinterpret_cast<float*>(top.take<char>(pp));
   const size_t scratch0 = top.off;
-  if (!sp.base || !ping || !pong) return LCR_ESPACE;
+  if (!sp.base || !ping || !pong) return top.spent();
   hipMemsetAsync(sp.base, 0, sizeof(double) * sp.cap, s);
 
   int rc;
@@ -278,12 +266,33 @@ extern "C" int lcr_encoder_forward_ex(const LcrEncoderW* W, const float* feats0,
     for (int k = 0; k < 4; ++k)
       if (STAGE_LAST[k] == i) out = out_feats[k];
     if (!out) out = (cur >= ping && cur < ping + pp / sizeof(float)) ? pong : ping;
-    Arena scratch{static_cast<char*>(ws), scratch0, ws_bytes};
-    if ((rc = residual_block(W->blocks[i], cur, st[qs], st[ss], idx, H, sp, scratch, out, flags, s))) {
-      if (rc == LCR_ESPACE) set_error("lcr_encoder_forward: block %d ran out of workspace", i);
-      return rc;
-    }
+    Arena scratch{static_cast<char*>(ws), scratch0, ws_bytes, who, i};
+    if ((rc = residual_block(W->blocks[i], cur, st[qs], st[ss], idx, H, sp, scratch, out, flags, s))) return rc;
     cur = out;
   }
-  return check_launch("lcr_encoder_forward");
+  return check_launch(who);
+}
+
+}  // namespace lcr
+
+using namespace lcr;
+
+extern "C" int lcr_encoder_ws_bytes(const LcrEncoderW* W, const int64_t* n_host, int S, size_t* bytes) {
+  return encoder_ws_bytes("lcr_encoder_ws_bytes", W, n_host, S, bytes);
+}
+
+extern "C" int lcr_encoder_forward(const LcrEncoderW* W, const float* feats0, const float* const* points, const int32_t* const* neighbors,
+                                   const int32_t* const* subsampling, const int32_t* const* order, const int64_t* const* seg_len, int S,
+                                   const int64_t* n_host, const int64_t* seg_min_rows_host, const int* limits, float* const* out_feats,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  return encoder_forward("lcr_encoder_forward", W, feats0, points, neighbors, subsampling, order, seg_len, S, n_host, seg_min_rows_host, limits,
+                         out_feats, 0u, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_encoder_forward_ex(const LcrEncoderW* W, const float* feats0, const float* const* points, const int32_t* const* neighbors,
+                                      const int32_t* const* subsampling, const int32_t* const* order, const int64_t* const* seg_len, int S,
+                                      const int64_t* n_host, const int64_t* seg_min_rows_host, const int* limits, float* const* out_feats,
+                                      unsigned flags, void* ws, size_t ws_bytes, void* stream) {
+  return encoder_forward("lcr_encoder_forward_ex", W, feats0, points, neighbors, subsampling, order, seg_len, S, n_host, seg_min_rows_host, limits,
+                         out_feats, flags, ws, ws_bytes, stream);
 }

@@ -243,11 +243,9 @@ __global__ __launch_bounds__(256) void k_fc_write(const int32_t* __restrict__ nn
 using namespace lcr;
 
 static int fnn_domain(int S, int C, int64_t nq, int64_t nd, const char* what) {
-  if (S < 1 || S > 65535 || C < 1 || C > 1024 || nq < 0 || nd < 0 || nq > INT32_MAX || nd > INT32_MAX) {
-    set_error("%s: outside the domain (1 <= S <= 65535, 1 <= C <= 1024, 0 <= nq, nd <= 2^31-1): S=%d C=%d nq=%lld nd=%lld", what, S, C,
-              static_cast<long long>(nq), static_cast<long long>(nd));
-    return LCR_EARG;
-  }
+  if (S < 1 || S > 65535 || C < 1 || C > 1024 || nq < 0 || nd < 0 || nq > INT32_MAX || nd > INT32_MAX)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= S <= 65535, 1 <= C <= 1024, 0 <= nq, nd <= 2^31-1): S=%d C=%d nq=%lld nd=%lld", what, S, C,
+                  static_cast<long long>(nq), static_cast<long long>(nd));
   return LCR_OK;
 }
 
@@ -280,28 +278,22 @@ static FnnLayout fnn_layout(void* ws, int S, int64_t nq, int64_t nd) {
 }
 
 extern "C" int lcr_feature_nn_ws_bytes(int S, int64_t nq, int64_t nd, size_t* bytes) {
-  if (!bytes) return LCR_EARG;
-  if (fnn_domain(S, 1, nq, nd, "lcr_feature_nn_ws_bytes") != LCR_OK) return LCR_EARG;
+  if (!bytes) return refuse(LCR_EARG, "lcr_feature_nn_ws_bytes: null pointer");
+  if (int rc = fnn_domain(S, 1, nq, nd, "lcr_feature_nn_ws_bytes")) return rc;
   *bytes = fnn_layout(nullptr, S, nq, nd).bytes;
   return LCR_OK;
 }
 
 extern "C" int lcr_feature_nn(const float* qf, const float* df, const int32_t* q_start, const int32_t* d_start, int S, int C, int64_t nq,
                               int64_t nd, int32_t* nn, float* d2, void* ws, size_t ws_bytes, void* stream) {
-  if (fnn_domain(S, C, nq, nd, "lcr_feature_nn") != LCR_OK) return LCR_EARG;
-  if (!q_start || !d_start || !ws || (nq > 0 && (!qf || !nn || !d2)) || (nd > 0 && !df)) {
-    set_error("lcr_feature_nn: null pointer");
-    return LCR_EARG;
-  }
+  if (int rc = fnn_domain(S, C, nq, nd, "lcr_feature_nn")) return rc;
+  if (!q_start || !d_start || !ws || (nq > 0 && (!qf || !nn || !d2)) || (nd > 0 && !df)) return refuse(LCR_EARG, "lcr_feature_nn: null pointer");
   const FnnLayout L = fnn_layout(ws, S, nq, nd);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_feature_nn: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_feature_nn", ws_bytes, L.bytes);
   if (nq == 0) return LCR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_fnn_count_tiles, dim3(div_up(S + 1, 256)), dim3(256), 0, st, q_start, S, L.tiles);
-  int rc = exclusive_scan_i32(L.tiles, L.tiles, S + 1, nullptr, L.scan_ws, st);
+  int rc = exclusive_scan_i32("lcr_feature_nn", L.tiles, L.tiles, S + 1, nullptr, L.scan_ws, st);
   if (rc != LCR_OK) return rc;
   const int64_t wgs = (nq + FN_TQ - 1) / FN_TQ + S;                   // upper bound of sum ceil(nq_s / 128); the surplus exits at once
   hipLaunchKernelGGL(k_fnn_tiles, dim3(static_cast<unsigned>(wgs), L.Z), dim3(256), 0, st, qf, df, q_start, d_start, L.tiles, S, C, nq, L.pd, L.pj);
@@ -325,10 +317,7 @@ static FcLayout fc_layout(void* ws, int S) {
 }
 
 extern "C" int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes) {
-  if (!bytes || S < 1 || S > 65535) {
-    set_error("lcr_feature_correspondences_ws_bytes: null pointer or S outside 1..65535 (S=%d)", S);
-    return LCR_EARG;
-  }
+  if (!bytes || S < 1 || S > 65535) return refuse(LCR_EARG, "lcr_feature_correspondences_ws_bytes: null pointer or S outside 1..65535 (S=%d)", S);
   *bytes = fc_layout(nullptr, S).bytes;
   return LCR_OK;
 }
@@ -336,18 +325,13 @@ extern "C" int lcr_feature_correspondences_ws_bytes(int S, size_t* bytes) {
 extern "C" int lcr_feature_correspondences(const int32_t* nn_sr, const int32_t* src_start, const int32_t* nn_rs, const int32_t* ref_start, int S,
                                            int min_rows, int32_t* corr, int32_t* start, int32_t* mutual_used, void* ws, size_t ws_bytes,
                                            void* stream) {
-  if (S < 1 || S > 65535 || min_rows < 0 || !nn_sr || !src_start || !ref_start || !corr || !start || !ws) {
-    set_error("lcr_feature_correspondences: null pointer or outside the domain (1 <= S <= 65535, min_rows >= 0): S=%d min_rows=%d", S, min_rows);
-    return LCR_EARG;
-  }
+  if (S < 1 || S > 65535 || min_rows < 0 || !nn_sr || !src_start || !ref_start || !corr || !start || !ws)
+    return refuse(LCR_EARG, "lcr_feature_correspondences: null pointer or outside the domain (1 <= S <= 65535, min_rows >= 0): S=%d min_rows=%d", S, min_rows);
   const FcLayout L = fc_layout(ws, S);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_feature_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_feature_correspondences", ws_bytes, L.bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_fc_count, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, S, min_rows, L.count, L.use);
-  int rc = exclusive_scan_i32(L.count, start, S + 1, nullptr, L.scan_ws, st);
+  int rc = exclusive_scan_i32("lcr_feature_correspondences", L.count, start, S + 1, nullptr, L.scan_ws, st);
   if (rc != LCR_OK) return rc;
   hipLaunchKernelGGL(k_fc_write, dim3(S), dim3(256), 0, st, nn_sr, src_start, nn_rs, ref_start, start, L.use, corr, mutual_used);
   return check_launch("lcr_feature_correspondences");

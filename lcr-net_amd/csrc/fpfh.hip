@@ -196,45 +196,36 @@ FpfhLayout fpfh_layout(void* ws, int B, int64_t n, int max_nn, size_t grid_bytes
 }  // namespace
 
 extern "C" int lcr_fpfh_ws_bytes(int B, int64_t n, int max_nn, size_t* bytes) {
-  if (!bytes || B < 1 || B > GRID_MAX_B || n < 0 || n > INT32_MAX || max_nn < 2 || max_nn > FP_MAX_NN) {
-    set_error("lcr_fpfh_ws_bytes: outside the domain (1 <= B <= %d, 0 <= n <= 2^31-1, 2 <= max_nn <= %d): B=%d n=%lld max_nn=%d", GRID_MAX_B,
-              FP_MAX_NN, B, static_cast<long long>(n), max_nn);
-    return LCR_EARG;
-  }
+  if (!bytes || B < 1 || B > GRID_MAX_B || n < 0 || n > INT32_MAX || max_nn < 2 || max_nn > FP_MAX_NN)
+    return refuse(LCR_EARG, "lcr_fpfh_ws_bytes: outside the domain (1 <= B <= %d, 0 <= n <= 2^31-1, 2 <= max_nn <= %d): B=%d n=%lld max_nn=%d", GRID_MAX_B,
+                  FP_MAX_NN, B, static_cast<long long>(n), max_nn);
   size_t g = 0;
-  if (lcr_support_grid_ws_bytes(n, B, &g) != LCR_OK) return LCR_EARG;
+  if (int rc = support_grid_ws_bytes("lcr_fpfh_ws_bytes", n, B, &g)) return rc;
   *bytes = fpfh_layout(nullptr, B, n, max_nn, g).bytes;
   return LCR_OK;
 }
 
 extern "C" int lcr_fpfh(const float* points, const float* normals, const int64_t* lengths, int B, float radius, int max_nn, float* features,
                         float* spfh, int32_t* count, void* ws, size_t ws_bytes, void* stream) {
-  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 2 || max_nn > FP_MAX_NN) {
-    set_error("lcr_fpfh: outside the domain (radius > 0 with radius*radius finite, 2 <= max_nn <= %d): radius=%g max_nn=%d", FP_MAX_NN,
-              static_cast<double>(radius), max_nn);
-    return LCR_EARG;
-  }
+  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 2 || max_nn > FP_MAX_NN)
+    return refuse(LCR_EARG, "lcr_fpfh: outside the domain (radius > 0 with radius*radius finite, 2 <= max_nn <= %d): radius=%g max_nn=%d", FP_MAX_NN,
+                  static_cast<double>(radius), max_nn);
   Stack C;
-  if (stack_from_lengths("lcr_fpfh", lengths, B, &C)) return LCR_EARG;
+  if (int rc = stack_from_lengths("lcr_fpfh", lengths, B, &C)) return rc;
   const int64_t n = C.off[B];
-  if (!ws || (n > 0 && (!points || !normals || !features))) {
-    set_error("lcr_fpfh: null workspace, or a null point / normal / feature array (n=%lld)", static_cast<long long>(n));
-    return LCR_EARG;
-  }
+  if (!ws || (n > 0 && (!points || !normals || !features)))
+    return refuse(LCR_EARG, "lcr_fpfh: null workspace, or a null point / normal / feature array (n=%lld)", static_cast<long long>(n));
   size_t grid_bytes = 0;
-  lcr_support_grid_ws_bytes(n, B, &grid_bytes);
+  support_grid_ws_bytes("lcr_fpfh", n, B, &grid_bytes);
   const FpfhLayout L = fpfh_layout(ws, B, n, max_nn, grid_bytes);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_fpfh: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_fpfh", ws_bytes, L.bytes);
   if (n == 0) return LCR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = stack_to_device("lcr_fpfh (init)", C, L.len, nullptr, nullptr, st);
+  int rc = stack_to_device("lcr_fpfh", C, L.len, nullptr, nullptr, st);
   if (rc) return rc;
-  rc = lcr_support_grid_build(points, L.len, B, n, radius, nullptr, ws, grid_bytes, stream);
+  rc = support_grid_build("lcr_fpfh", points, L.len, B, n, radius, nullptr, ws, grid_bytes, nullptr, stream);
   if (rc) return rc;
-  rc = lcr_radius_query_ordered(points, L.len, B, n, ws, n, radius, max_nn, nullptr, L.nbr, nullptr, nullptr, stream);
+  rc = radius_query("lcr_fpfh", points, L.len, B, n, ws, n, radius, max_nn, nullptr, L.nbr, nullptr, nullptr, stream);
   if (rc) return rc;
   const dim3 grid(div_up(n, FP_WAVES)), block(FP_WAVES * 64);
   hipLaunchKernelGGL(k_spfh, grid, block, 0, st, points, normals, n, max_nn, L.nbr, L.spfh, spfh, count);

@@ -274,13 +274,12 @@ __device__ __forceinline__ void gemm_epilogue(floatx16 (&acc)[NT], float* __rest
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 inline int env_int(const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; }
 
-// The domain of the epilogue's statistics, for every entry point that takes a `stats` table.  Sets the error text in the name of
-// entry point `who` and returns false outside it.
-inline bool gemm_stats_ok(const char* who, const double* stats, const int64_t* seg_len, int S, int groups, int N) {
-  if (!stats) return true;
-  if (seg_len && S >= 1 && groups >= 1 && N % groups == 0 && ((N / groups) & (N / groups - 1)) == 0) return true;
-  set_error("%s: statistics need seg_len, S >= 1 and groups dividing N into power-of-two sized groups", who);
-  return false;
+// The domain of the epilogue's statistics, for every entry point that takes a `stats` table: LCR_OK, or a refusal in the name of
+// entry point `who` outside it.
+inline int gemm_stats_domain(const char* who, const double* stats, const int64_t* seg_len, int S, int groups, int N) {
+  if (!stats) return LCR_OK;
+  if (seg_len && S >= 1 && groups >= 1 && N % groups == 0 && ((N / groups) & (N / groups - 1)) == 0) return LCR_OK;
+  return refuse(LCR_EARG, "%s: statistics need seg_len, S >= 1 and groups dividing N into power-of-two sized groups", who);
 }
 
 // workgroups of a BM x BN tiling in the XCD-aware tile order: the row-block count is padded to a multiple of 8 (see k_gemm_f32)
@@ -295,7 +294,7 @@ inline int mask_kshift(int K, int block_k) {
 
 // The K-deep form (gemm_deep.hip) for C = A[M,K] · B[N,K]^T, K % 32 == 0, M*K and N*K < 2^30; amask / kshift: row-masked A or null.
 // Owns the tile choice (N <= 32: 128x32, else 64x64).
-int gemm_deep_launch(const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st,
+int gemm_deep_launch(const char* who, const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st,
                      const uint16_t* amask, int kshift);
 
 }  // namespace lcr

@@ -248,11 +248,11 @@ static void launch_gemm_deep(const float* A, const float* B, float* C, int64_t M
   else LCR_LAUNCH_TIMED((k_gemm_f32_deep<BM, BN, WM, WN>), grid, block, 0, st, A, B, C, M, N, K, ep, amask, kshift);
 }
 
-int gemm_deep_launch(const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st,
+int gemm_deep_launch(const char* who, const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st,
                      const uint16_t* amask, int kshift) {
   if (N <= 32) launch_gemm_deep<128, 32, 4, 1>(A, B, C, M, N, K, ep, st, amask, kshift);
   else launch_gemm_deep<64, 64, 2, 2>(A, B, C, M, N, K, ep, st, amask, kshift);
-  return check_launch("lcr_gemm_f32");
+  return check_launch(who);
 }
 
 }  // namespace lcr
@@ -264,15 +264,13 @@ extern "C" int lcr_gemm_f32_masked(const float* A, const float* B, float* C, int
                                    const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask, int block_k, void* stream) {
   const int ks = mask_kshift(K, block_k);
   if (!A || !B || !C || !row_mask || M < 0 || N <= 0 || K <= 0 || K % GM_BK != 0 || ks < 0 || M * static_cast<int64_t>(K) >= (int64_t(1) << 30) ||
-      static_cast<int64_t>(N) * K >= (int64_t(1) << 30) || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(B) % 16 != 0) {
-    set_error("lcr_gemm_f32_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, K %% 32 == 0, M*K and N*K < 2^30, "
-              "16-byte aligned operands");
-    return LCR_EARG;
-  }
-  if (!gemm_stats_ok("lcr_gemm_f32_masked", stats, seg_len, S, groups, N)) return LCR_EARG;
+      static_cast<int64_t>(N) * K >= (int64_t(1) << 30) || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(B) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_gemm_f32_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, K %% 32 == 0, M*K and N*K < 2^30, "
+                  "16-byte aligned operands");
+  if (int rc = gemm_stats_domain("lcr_gemm_f32_masked", stats, seg_len, S, groups, N)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_GEMM, st, M, N, K);
   if (M == 0) return LCR_OK;
   GemmEpilogue ep{bias, rowdiv, seg_len, S, groups, stats};
-  return gemm_deep_launch(A, B, C, M, N, K, ep, st, row_mask, ks);
+  return gemm_deep_launch("lcr_gemm_f32_masked", A, B, C, M, N, K, ep, st, row_mask, ks);
 }

@@ -598,7 +598,7 @@ __global__ __launch_bounds__(GM_T, 3) void k_gemm_f32_sk(const float* __restrict
 }
 
 template <int BM, int BN, int WM, int WN, bool VEC, bool SHORT = false>
-static int launch_gemm(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const GemmEpilogue& ep,
+static int launch_gemm(const char* who, const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const GemmEpilogue& ep,
                        hipStream_t st, const GemmBatch* batch = nullptr) {
   static const GemmBatch no_batch = {};
   const GemmBatch& bt = batch ? *batch : no_batch;
@@ -608,7 +608,7 @@ static int launch_gemm(const float* A, const float* B, float* C, int64_t M, int 
   else if (!transA && transB) LCR_LAUNCH_TIMED((k_gemm_f32<BM, BN, WM, WN, false, true, VEC, SHORT>), grid, block, 0, st, A, B, C, M, N, K, ep, bt, ANorm{});
   else if (transA && !transB) LCR_LAUNCH_TIMED((k_gemm_f32<BM, BN, WM, WN, true, false, VEC, SHORT>), grid, block, 0, st, A, B, C, M, N, K, ep, bt, ANorm{});
   else LCR_LAUNCH_TIMED((k_gemm_f32<BM, BN, WM, WN, true, true, VEC, SHORT>), grid, block, 0, st, A, B, C, M, N, K, ep, bt, ANorm{});
-  return check_launch("lcr_gemm_f32");
+  return check_launch(who);
 }
 
 // Scratch of the stream-K launches, one per stream (launches on one stream are ordered, so they can share it): the parked
@@ -642,7 +642,7 @@ static bool sk_worth(int64_t M, int N, int K) {
   return worst / avg >= 1.10;
 }
 
-static int launch_gemm_sk(const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st) {
+static int launch_gemm_sk(const char* who, const float* A, const float* B, float* C, int64_t M, int N, int K, const GemmEpilogue& ep, hipStream_t st) {
   const int cus = sk_cu_count();
   const int64_t iters = static_cast<int64_t>(div_up(M, 64)) * div_up(N, 64) * div_up(K, GM_BK);
   // persistent workgroups: 3, 2 or 1 per CU — as many as still get >= 24 K-steps each
@@ -660,10 +660,8 @@ static int launch_gemm_sk(const float* A, const float* B, float* C, int64_t M, i
     SkScratch& sc = g_sk_scratch[{dev, st}];
     if (!sc.partial) {
       if (hipMalloc(reinterpret_cast<void**>(&sc.partial), sizeof(float) * 2 * 16 * GM_T * SK_MAX_GRID) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&sc.arrived), sizeof(uint32_t) * SK_MAX_TILES) != hipSuccess) {
-        set_error("lcr_gemm_f32: cannot allocate the stream-K scratch");
-        return LCR_EHIP;
-      }
+          hipMalloc(reinterpret_cast<void**>(&sc.arrived), sizeof(uint32_t) * SK_MAX_TILES) != hipSuccess)
+        return refuse(LCR_EHIP, "%s: cannot allocate the stream-K scratch", who);
       hipMemsetAsync(sc.arrived, 0, sizeof(uint32_t) * SK_MAX_TILES, st);     // once: every launch leaves the counters at zero
     }
     sk.partial = sc.partial;
@@ -671,7 +669,7 @@ static int launch_gemm_sk(const float* A, const float* B, float* C, int64_t M, i
     sk.U = U;
   }
   LCR_LAUNCH_TIMED((k_gemm_f32_sk<64, 64, 2, 2>), dim3(8 * U), dim3(GM_T), 0, st, A, B, C, M, N, K, ep, sk);
-  return check_launch("lcr_gemm_f32");
+  return check_launch(who);
 }
 
 }  // namespace lcr
@@ -745,11 +743,9 @@ extern "C" int lcr_gemm_f32_anorm(const float* A, const float* B, float* C, int6
                                   const double* a_stats, const float* a_gamma, const float* a_beta, int a_groups, float a_eps,
                                   float a_slope, const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
   if (!A || !B || !C || M < 0 || N <= 32 || K <= 0 || K > AN_KMAX || K % 4 != 0 || !a_stats || !a_gamma || !a_beta || a_groups < 1 ||
-      K % a_groups != 0 || a_groups > 64 || !seg_len || S < 1 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(B) % 16 != 0) {
-    set_error("lcr_gemm_f32_anorm: needs 32 < N, K <= 256, K % 4 == 0, a_groups dividing K, a segment table and 16-byte aligned operands");
-    return LCR_EARG;
-  }
-  if (!gemm_stats_ok("lcr_gemm_f32_anorm", stats, seg_len, S, groups, N)) return LCR_EARG;
+      K % a_groups != 0 || a_groups > 64 || !seg_len || S < 1 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(B) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_gemm_f32_anorm: needs 32 < N, K <= 256, K %% 4 == 0, a_groups dividing K, a segment table and 16-byte aligned operands");
+  if (int rc = gemm_stats_domain("lcr_gemm_f32_anorm", stats, seg_len, S, groups, N)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_GEMM, st, M, N, K);
   if (M == 0) return LCR_OK;
@@ -762,11 +758,8 @@ extern "C" int lcr_gemm_f32_anorm(const float* A, const float* B, float* C, int6
 
 extern "C" int lcr_gemm_f32(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB, const float* bias,
                             const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
-  if (!A || !B || !C || M < 0 || N <= 0 || K <= 0) {
-    set_error("lcr_gemm_f32: bad argument");
-    return LCR_EARG;
-  }
-  if (!gemm_stats_ok("lcr_gemm_f32", stats, seg_len, S, groups, N)) return LCR_EARG;
+  if (!A || !B || !C || M < 0 || N <= 0 || K <= 0) return refuse(LCR_EARG, "lcr_gemm_f32: bad argument");
+  if (int rc = gemm_stats_domain("lcr_gemm_f32", stats, seg_len, S, groups, N)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_GEMM, st, M, N, K);
   // `stats` ACCUMULATES: the caller passes a zeroed table (one fill per forward pass for all layers, instead of a fill
@@ -778,29 +771,29 @@ extern "C" int lcr_gemm_f32(const float* A, const float* B, float* C, int64_t M,
   const int64_t lda = transA ? M : K, ldb = transB ? K : N;
   const bool vec = (lda % 4 == 0) && (ldb % 4 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (reinterpret_cast<uintptr_t>(B) % 16 == 0);
   switch (gemm_form(M, N, K, transA, transB, vec)) {
-    case GF_SCALAR: return launch_gemm<128, 64, 4, 1, false>(A, B, C, M, N, K, transA, transB, ep, st);
+    case GF_SCALAR: return launch_gemm<128, 64, 4, 1, false>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
     case GF_FORCED_TILE:
       switch (g_force_tile) {
-        case 1: return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-        case 2: return launch_gemm<128, 64, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-        case 3: return launch_gemm<128, 32, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-        case 4: return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
-        default: return launch_gemm<64, 128, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
+        case 1: return launch_gemm<128, 128, 4, 1, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+        case 2: return launch_gemm<128, 64, 4, 1, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+        case 3: return launch_gemm<128, 32, 4, 1, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+        case 4: return launch_gemm<64, 64, 2, 2, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+        default: return launch_gemm<64, 128, 2, 2, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
       }
     case GF_SHORT:
-      if (N <= 32) return launch_gemm<128, 32, 4, 1, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
-      return launch_gemm<64, 64, 2, 2, true, true>(A, B, C, M, N, K, transA, transB, ep, st);
-    case GF_DEEP: return gemm_deep_launch(A, B, C, M, N, K, ep, st, nullptr, 0);
-    case GF_STREAMK: return launch_gemm_sk(A, B, C, M, N, K, ep, st);
+      if (N <= 32) return launch_gemm<128, 32, 4, 1, true, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+      return launch_gemm<64, 64, 2, 2, true, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+    case GF_DEEP: return gemm_deep_launch("lcr_gemm_f32", A, B, C, M, N, K, ep, st, nullptr, 0);
+    case GF_STREAMK: return launch_gemm_sk("lcr_gemm_f32", A, B, C, M, N, K, ep, st);
     case GF_TILE: break;
   }
   // Tile choice from tools/gemm_bench.py --tiles on MI355X: 64x64 (2x2 wavefronts) wins or ties on every encoder shape with
   // N >= 64 (enough workgroups for two per CU matters more than per-tile reuse at these M); N = 32 wants the 128-row tile;
   // only large, deep problems (>= 512 tiles of 128x128 and K >= 512) pay for the big tile.
-  if (N <= 32) return launch_gemm<128, 32, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
+  if (N <= 32) return launch_gemm<128, 32, 4, 1, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
   const int64_t b128 = (M + 127) / 128, nb128 = (N + 127) / 128;
-  if (K >= 512 && b128 * nb128 >= 512) return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, st);
-  return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, st);
+  if (K >= 512 && b128 * nb128 >= 512) return launch_gemm<128, 128, 4, 1, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
+  return launch_gemm<64, 64, 2, 2, true>("lcr_gemm_f32", A, B, C, M, N, K, transA, transB, ep, st);
 }
 
 // Whether the contraction C[M,N] = A[M,K] . B[N,K]^T of a KPConv with C_in = K / 15 can read a row-masked aggregate and still compute what
@@ -816,10 +809,8 @@ extern "C" int lcr_kpconv_mask_ok(int64_t M, int N, int K, int split) {
 // Batched C_z = A_z^T·B_z (transA) with per-entry K — NetVLAD's per-scan aggregation (NetVlad.py:68): one launch for S scans.
 extern "C" int lcr_gemm_f32_batched_ta(const float* A, const float* B, float* C, int64_t M, int N, int count, const int* k_host,
                                        const int64_t* a_off_host, const int64_t* b_off_host, const int64_t* c_off_host, void* stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || count < 1 || count > GM_MAX_BATCH || !k_host || !a_off_host || !b_off_host || !c_off_host) {
-    set_error("lcr_gemm_f32_batched_ta: bad argument (count <= %d)", GM_MAX_BATCH);
-    return LCR_EARG;
-  }
+  if (!A || !B || !C || M <= 0 || N <= 0 || count < 1 || count > GM_MAX_BATCH || !k_host || !a_off_host || !b_off_host || !c_off_host)
+    return refuse(LCR_EARG, "lcr_gemm_f32_batched_ta: bad argument (count <= %d)", GM_MAX_BATCH);
   GemmBatch bt = {};
   bt.count = count;
   for (int i = 0; i < count; ++i) {
@@ -827,32 +818,21 @@ extern "C" int lcr_gemm_f32_batched_ta(const float* A, const float* B, float* C,
     bt.a_off[i] = a_off_host[i];
     bt.b_off[i] = b_off_host[i];
     bt.c_off[i] = c_off_host[i];
-    if (a_off_host[i] % 4 || b_off_host[i] % 4 || k_host[i] < 1) {
-      set_error("lcr_gemm_f32_batched_ta: offsets must be multiples of 4 floats and K >= 1");
-      return LCR_EARG;
-    }
+    if (a_off_host[i] % 4 || b_off_host[i] % 4 || k_host[i] < 1) return refuse(LCR_EARG, "lcr_gemm_f32_batched_ta: offsets must be multiples of 4 floats and K >= 1");
   }
-  if ((M % 4) || (N % 4)) {
-    set_error("lcr_gemm_f32_batched_ta: M and N must be multiples of 4");
-    return LCR_EARG;
-  }
+  if ((M % 4) || (N % 4)) return refuse(LCR_EARG, "lcr_gemm_f32_batched_ta: M and N must be multiples of 4");
   GemmEpilogue ep{nullptr, nullptr, nullptr, 0, 0, nullptr};
-  return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, /*K (per entry)*/ 1, 1, 0, ep, static_cast<hipStream_t>(stream), &bt);
+  return launch_gemm<64, 64, 2, 2, true>("lcr_gemm_f32_batched_ta", A, B, C, M, N, /*K (per entry)*/ 1, 1, 0, ep, static_cast<hipStream_t>(stream), &bt);
 }
 
 // Uniform batch: C_z[M,N] = op(A_z)·op(B_z), z < count (<= 65535), constant strides (in floats, multiples of 4) — the per-patch
 // feature products of the dense matching stage (LCRNet.py:237-238: einsum('bnd,bmd->bnm')).
 extern "C" int lcr_gemm_f32_strided_batched(const float* A, const float* B, float* C, int64_t M, int N, int K, int transA, int transB,
                                             int64_t strideA, int64_t strideB, int64_t strideC, int count, void* stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || count < 1 || count > 65535 || (strideA % 4) || (strideB % 4)) {
-    set_error("lcr_gemm_f32_strided_batched: bad argument");
-    return LCR_EARG;
-  }
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || count < 1 || count > 65535 || (strideA % 4) || (strideB % 4))
+    return refuse(LCR_EARG, "lcr_gemm_f32_strided_batched: bad argument");
   const int64_t lda = transA ? M : K, ldb = transB ? K : N;
-  if ((lda % 4) || (ldb % 4)) {
-    set_error("lcr_gemm_f32_strided_batched: leading dimensions must be multiples of 4");
-    return LCR_EARG;
-  }
+  if ((lda % 4) || (ldb % 4)) return refuse(LCR_EARG, "lcr_gemm_f32_strided_batched: leading dimensions must be multiples of 4");
   GemmBatch bt = {};
   bt.count = count;
   bt.strided = 1;
@@ -867,8 +847,8 @@ extern "C" int lcr_gemm_f32_strided_batched(const float* A, const float* B, floa
   // +4 % pairs/s across two gpurun sessions (590 -> 616), is -3 % in a same-session A/B (648 / 644 vs 632 / 623 pairs/s at 16 pairs per call) and
   // 1.29 vs 0.96 ms per call alone: off by default, kept as the switch that measured it
   static const int batch_tile = env_int("LCR_GEMM_BATCH_TILE", 64);
-  if (batch_tile == 128 && M >= 128 && N >= 128) return launch_gemm<128, 128, 4, 1, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
+  if (batch_tile == 128 && M >= 128 && N >= 128) return launch_gemm<128, 128, 4, 1, true>("lcr_gemm_f32_strided_batched", A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
   static const bool batch_short = env_int("LCR_GEMM_BATCH_SHORT", 1) != 0;
-  if (batch_short && K <= 256 && !transA) return launch_gemm<64, 64, 2, 2, true, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
-  return launch_gemm<64, 64, 2, 2, true>(A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
+  if (batch_short && K <= 256 && !transA) return launch_gemm<64, 64, 2, 2, true, true>("lcr_gemm_f32_strided_batched", A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
+  return launch_gemm<64, 64, 2, 2, true>("lcr_gemm_f32_strided_batched", A, B, C, M, N, K, transA, transB, ep, static_cast<hipStream_t>(stream), &bt);
 }

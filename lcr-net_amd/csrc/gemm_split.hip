@@ -327,10 +327,7 @@ using namespace lcr;
 
 // fp32 array -> its three bf16 terms, planes [3][n] (bf16 bit patterns); once per constant operand (weights)
 extern "C" int lcr_split_bf16x3(const float* w, int64_t n, uint16_t* planes, void* stream) {
-  if (!w || !planes || n < 0) {
-    set_error("lcr_split_bf16x3: bad argument");
-    return LCR_EARG;
-  }
+  if (!w || !planes || n < 0) return refuse(LCR_EARG, "lcr_split_bf16x3: bad argument");
   if (n == 0) return LCR_OK;
   hipLaunchKernelGGL(k_split_bf16x3, dim3(min(div_up(n, 512), 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), w, n, planes);
   return check_launch("lcr_split_bf16x3");
@@ -338,23 +335,20 @@ extern "C" int lcr_split_bf16x3(const float* w, int64_t n, uint16_t* planes, voi
 
 // weights [N,K] (K % 32 == 0) -> the tiled planes lcr_gemm_f32_bsplit takes: u16[ceil(N/64)][K/32][3][64][32] (12 KB per block)
 extern "C" int lcr_split_bf16x3_tiles(const float* w, int N, int K, uint16_t* tiles, void* stream) {
-  if (!w || !tiles || N < 1 || K < GM_BK || K % GM_BK != 0 || reinterpret_cast<uintptr_t>(w) % 16 != 0 || reinterpret_cast<uintptr_t>(tiles) % 16 != 0) {
-    set_error("lcr_split_bf16x3_tiles: needs K %% 32 == 0 and 16-byte aligned buffers");
-    return LCR_EARG;
-  }
+  if (!w || !tiles || N < 1 || K < GM_BK || K % GM_BK != 0 || reinterpret_cast<uintptr_t>(w) % 16 != 0 || reinterpret_cast<uintptr_t>(tiles) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_split_bf16x3_tiles: needs K %% 32 == 0 and 16-byte aligned buffers");
   hipLaunchKernelGGL(k_split_bf16x3_tiles, dim3(div_up(N, 64) * (K / GM_BK)), dim3(256), 0, static_cast<hipStream_t>(stream), w, N, K, tiles);
   return check_launch("lcr_split_bf16x3_tiles");
 }
 
 // C = A[M,K] · B[N,K]^T with B given as the TILED bf16 planes of lcr_split_bf16x3_tiles; epilogue as lcr_gemm_f32.
-static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
+// The body of lcr_gemm_f32_bsplit and lcr_gemm_f32_bsplit_masked; `who` = the one that was called.
+static int bsplit_impl(const char* who, const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
                        const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* amask, int kshift, void* stream) {
   if (!A || !Bs || !C || M < 0 || N <= 0 || K <= 0 || K % GM_BK != 0 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(Bs) % 16 != 0 ||
-      K < GM_BK) {
-    set_error("lcr_gemm_f32_bsplit: needs K %% 32 == 0 and 16-byte aligned operands");
-    return LCR_EARG;
-  }
-  if (!gemm_stats_ok("lcr_gemm_f32_bsplit", stats, seg_len, S, groups, N)) return LCR_EARG;
+      K < GM_BK)
+    return refuse(LCR_EARG, "%s: needs K %% 32 == 0 and 16-byte aligned operands", who);
+  if (int rc = gemm_stats_domain(who, stats, seg_len, S, groups, N)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_GEMM, st, M, N, K);
   if (M == 0) return LCR_OK;
@@ -363,7 +357,7 @@ static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, 
   const dim3 grid(gemm_grid(M, N, 64, 64)), block(256);
   if (amask) {
     LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0, true>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{});
-    return check_launch("lcr_gemm_f32_bsplit_masked");
+    return check_launch(who);
   }
   switch (abl) {
     case 1: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<1>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
@@ -376,12 +370,12 @@ static int bsplit_impl(const float* A, const uint16_t* Bs, float* C, int64_t M, 
     case 32: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<32>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
     default: LCR_LAUNCH_TIMED((k_gemm_f32_bsplit_p<0>), grid, block, 0, st, A, Bs, C, M, N, K, ep, amask, kshift, ANorm{}); break;
   }
-  return check_launch("lcr_gemm_f32_bsplit");
+  return check_launch(who);
 }
 
 extern "C" int lcr_gemm_f32_bsplit(const float* A, const uint16_t* Bs, float* C, int64_t M, int N, int K, const float* bias, const float* rowdiv,
                                    const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
-  return bsplit_impl(A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, nullptr, 0, stream);
+  return bsplit_impl("lcr_gemm_f32_bsplit", A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, nullptr, 0, stream);
 }
 
 // C = leaky(GroupNorm(A)) · B^T (+ bias, + statistics of C) on the split form: lcr_gemm_f32_anorm's arguments with the tiled planes in place of
@@ -390,11 +384,9 @@ extern "C" int lcr_gemm_f32_bsplit_anorm(const float* A, const uint16_t* Bs, flo
                                          const double* a_stats, const float* a_gamma, const float* a_beta, int a_groups, float a_eps,
                                          float a_slope, const int64_t* seg_len, int S, int groups, double* stats, void* stream) {
   if (!A || !Bs || !C || M < 0 || N < 64 || K < GM_BK || K > AN_KMAX || K % GM_BK != 0 || !a_stats || !a_gamma || !a_beta || a_groups < 1 ||
-      K % a_groups != 0 || a_groups > 64 || !seg_len || S < 1 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(Bs) % 16 != 0) {
-    set_error("lcr_gemm_f32_bsplit_anorm: needs N >= 64, K <= 256, K %% 32 == 0, a_groups (<= 64) dividing K, a segment table and 16-byte aligned operands");
-    return LCR_EARG;
-  }
-  if (!gemm_stats_ok("lcr_gemm_f32_bsplit_anorm", stats, seg_len, S, groups, N)) return LCR_EARG;
+      K % a_groups != 0 || a_groups > 64 || !seg_len || S < 1 || reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(Bs) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_gemm_f32_bsplit_anorm: needs N >= 64, K <= 256, K %% 32 == 0, a_groups (<= 64) dividing K, a segment table and 16-byte aligned operands");
+  if (int rc = gemm_stats_domain("lcr_gemm_f32_bsplit_anorm", stats, seg_len, S, groups, N)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KernelTimerScope timed(KT_GEMM, st, M, N, K);
   if (M == 0) return LCR_OK;
@@ -409,9 +401,7 @@ extern "C" int lcr_gemm_f32_bsplit_masked(const float* A, const uint16_t* Bs, fl
                                           const float* rowdiv, const int64_t* seg_len, int S, int groups, double* stats, const uint16_t* row_mask,
                                           int block_k, void* stream) {
   const int ks = mask_kshift(K, block_k);
-  if (!row_mask || ks < 0 || M * static_cast<int64_t>(K) >= (int64_t(1) << 29)) {
-    set_error("lcr_gemm_f32_bsplit_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, and M*K < 2^29");
-    return LCR_EARG;
-  }
-  return bsplit_impl(A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, row_mask, ks, stream);
+  if (!row_mask || ks < 0 || M * static_cast<int64_t>(K) >= (int64_t(1) << 29))
+    return refuse(LCR_EARG, "lcr_gemm_f32_bsplit_masked: needs a row mask, block_k = 32 << s (s <= 3) with K <= 16 block_k, and M*K < 2^29");
+  return bsplit_impl("lcr_gemm_f32_bsplit_masked", A, Bs, C, M, N, K, bias, rowdiv, seg_len, S, groups, stats, row_mask, ks, stream);
 }

@@ -8,6 +8,14 @@
 
 namespace lcr {
 
+// The bodies of lcr_support_grid_ws_bytes, lcr_support_grid_build{,_ex} and lcr_radius_query{,_ordered} (radius_search.hip), for the
+// entry points that build or query a grid of their own: a refusal carries the name `who` of the entry point that was called.
+int support_grid_ws_bytes(const char* who, int64_t ns_cap, int B, size_t* bytes);
+int support_grid_build(const char* who, const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status, void* grid_ws,
+                       size_t grid_ws_bytes, int32_t* order, void* stream);
+int radius_query(const char* who, const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap, float radius,
+                 int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt, const int32_t* q_order, void* stream);
+
 constexpr int CELL_PER_PT = 32;  // cell budget = CELL_PER_PT * ns_cap + CELL_MIN * B
 constexpr int CELL_MIN = 4096;
 

@@ -914,83 +914,78 @@ __global__ __launch_bounds__(256) void k_vd_reduce(const GsHeader* __restrict__ 
 using namespace lcr;
 
 extern "C" int lcr_grid_subsample_ws_bytes(int64_t n_cap, int B, size_t* bytes) {
-  if (!bytes || n_cap < 0 || B < 1 || B > GS_MAX_B) return LCR_EARG;
+  if (!bytes || n_cap < 0 || B < 1 || B > GS_MAX_B)
+    return refuse(LCR_EARG, "lcr_grid_subsample_ws_bytes: null pointer or outside the domain (n_cap >= 0, 1 <= B <= %d): n_cap=%lld B=%d", GS_MAX_B,
+                  static_cast<long long>(n_cap), B);
   *bytes = gs_layout(nullptr, n_cap, B).bytes;
   return LCR_OK;
-}
-
-extern "C" int lcr_grid_subsample_rows(const float* xyz, int row_floats, const int64_t* len, int B, int64_t n_cap, float voxel, int key_bits_hint,
-                                       float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream);
-extern "C" int lcr_grid_subsample_ex(const float* xyz, const int64_t* len, int B, int64_t n_cap, float voxel, int key_bits_hint,
-                                     float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  return lcr_grid_subsample_rows(xyz, 3, len, B, n_cap, voxel, key_bits_hint, out_xyz, out_len, status, ws, ws_bytes, stream);
 }
 
 // The same on rows of `row_floats` >= 3 floats whose first three are x, y, z: a KITTI velodyne scan (f32 [N, 4]: x, y, z, intensity;
 // data/Kitti/downsample_pcd.py:21, dataset_overlap_online.py:245 takes [:, :3] on the host) is consumed as it lies in memory — the three
 // kernels that touch the input (bounding box, voxel keys, in-order sums) step over the unused columns; the output is f32 [M, 3].
-extern "C" int lcr_grid_subsample_rows(const float* xyz, int row_floats, const int64_t* len, int B, int64_t n_cap, float voxel, int key_bits_hint,
-                                       float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (row_floats < 3 || row_floats > 64) {
-    set_error("lcr_grid_subsample: rows of %d floats (3 .. 64: x, y, z first)", row_floats);
-    return LCR_EARG;
-  }
+// The body of lcr_grid_subsample{,_ex,_rows}; `who` = the one that was called.
+static int grid_subsample_rows(const char* who, const float* xyz, int row_floats, const int64_t* len, int B, int64_t n_cap, float voxel,
+                               int key_bits_hint, float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (row_floats < 3 || row_floats > 64) return refuse(LCR_EARG, "%s: rows of %d floats (3 .. 64: x, y, z first)", who, row_floats);
   const int rs = row_floats;
   if (!len || !out_len || !status || !ws || B < 1 || B > GS_MAX_B || n_cap < 0 || !(voxel > 0.f) || key_bits_hint < 0 ||
-      key_bits_hint > 64) {
-    set_error("lcr_grid_subsample: bad argument");
-    return LCR_EARG;
-  }
-  if (n_cap > (int64_t(1) << 31) - 2) {
-    set_error("lcr_grid_subsample: more than 2^31-2 points");
-    return LCR_EARG;
-  }
+      key_bits_hint > 64)
+    return refuse(LCR_EARG, "%s: bad argument", who);
+  if (n_cap > (int64_t(1) << 31) - 2) return refuse(LCR_EARG, "%s: more than 2^31-2 points", who);
   GsLayout L = gs_layout(ws, n_cap, B);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_grid_subsample: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse(LCR_ESPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, L.bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float inv_voxel = static_cast<float>(1.0 / static_cast<double>(voxel));   // `1. / voxel_size` narrowed by operator*(PointXYZ,float)
   const int nblk = n_cap > 0 ? min(div_up(n_cap, 256), 2048) : 1;
   hipLaunchKernelGGL(k_gs_init, dim3(1), dim3(64), 0, st, L.hdr, len, B, n_cap, status);
   if (n_cap == 0) {
     hipLaunchKernelGGL(k_gs_offsets, dim3(1), dim3(64), 0, st, L.hdr, static_cast<const int32_t*>(nullptr), out_len);
-    return check_launch("lcr_grid_subsample");
+    return check_launch(who);
   }
   // one workgroup per CU at most: every workgroup ends with 6 atomics on its cloud's box, and same-address atomics serialise
   hipLaunchKernelGGL(k_gs_bbox, dim3(n_cap > 0 ? min(div_up(n_cap, 1024), 512) : 1), dim3(256), 0, st, L.hdr, xyz, rs);
   hipLaunchKernelGGL(k_gs_params, dim3(1), dim3(64), 0, st, L.hdr, voxel, inv_voxel, key_bits_hint, status);
   hipLaunchKernelGGL(k_gs_keys, dim3(nblk), dim3(256), 0, st, L.hdr, xyz, rs, voxel, L.keyA, L.valA, status);
   const int max_passes = radix_passes(key_bits_hint > 0 ? key_bits_hint : 64);
-  int rc = radix_sort_pairs(&L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, max_passes, L.hist, L.scan_ws, st);
+  int rc = radix_sort_pairs(who, &L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, max_passes, L.hist, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_heads, dim3(nblk), dim3(256), 0, st, L.hdr, L.keyA, L.keyB, L.head, L.first, n_cap);
-  rc = exclusive_scan_i32(L.head, L.head, n_cap + 1, nullptr, L.scan_ws, st);
+  rc = exclusive_scan_i32(who, L.head, L.head, n_cap + 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_seg_starts, dim3(nblk), dim3(256), 0, st, L.hdr, L.head, L.seg_start);
   hipLaunchKernelGGL(k_gs_reduce, dim3(nblk), dim3(256), 0, st, L.hdr, xyz, rs, L.keyA, L.keyB, L.valA, L.valB, L.head, L.seg_start, L.bary,
                      L.seg_key, L.seg_first, L.first, out_len);
-  rc = exclusive_scan_i32(L.first, L.first, n_cap + 1, nullptr, L.scan_ws, st);
+  rc = exclusive_scan_i32(who, L.first, L.first, n_cap + 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_insertion, dim3(nblk), dim3(256), 0, st, L.hdr, L.first, L.seg_key, L.seg_first, L.ins_key, L.ins_seg);
   static DynLds hm_opt_in;
-  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitBary>), HM_LDS_BYTES) != hipSuccess) {
-    set_error("lcr_grid_subsample: cannot reserve %zu B of LDS for the hash-order kernel", HM_LDS_BYTES);
-    return LCR_EHIP;
-  }
+  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitBary>), HM_LDS_BYTES) != hipSuccess)
+    return refuse(LCR_EHIP, "%s: cannot reserve %zu B of LDS for the hash-order kernel", who, HM_LDS_BYTES);
   hipLaunchKernelGGL(k_gs_hashorder<HmEmitBary>, dim3(B), dim3(HM_T), HM_LDS_BYTES, st, L.hdr, L.ins_key, L.ins_seg, L.hm_t, L.hm_bk, L.hm_mem, L.hm_at,
                      L.hm_arr, L.hm_gmin, L.hm_cnt, L.hm_start, HmEmitBary{L.bary, out_xyz});
-  return check_launch("lcr_grid_subsample");
+  return check_launch(who);
+}
+
+extern "C" int lcr_grid_subsample_rows(const float* xyz, int row_floats, const int64_t* len, int B, int64_t n_cap, float voxel, int key_bits_hint,
+                                       float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return grid_subsample_rows("lcr_grid_subsample_rows", xyz, row_floats, len, B, n_cap, voxel, key_bits_hint, out_xyz, out_len, status, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_grid_subsample_ex(const float* xyz, const int64_t* len, int B, int64_t n_cap, float voxel, int key_bits_hint,
+                                     float* out_xyz, int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return grid_subsample_rows("lcr_grid_subsample_ex", xyz, 3, len, B, n_cap, voxel, key_bits_hint, out_xyz, out_len, status, ws, ws_bytes, stream);
 }
 
 extern "C" int lcr_grid_subsample(const float* xyz, const int64_t* len, int B, int64_t n_cap, float voxel, float* out_xyz,
                                   int64_t* out_len, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  return lcr_grid_subsample_ex(xyz, len, B, n_cap, voxel, 0, out_xyz, out_len, status, ws, ws_bytes, stream);
+  return grid_subsample_rows("lcr_grid_subsample", xyz, 3, len, B, n_cap, voxel, 0, out_xyz, out_len, status, ws, ws_bytes, stream);
 }
 
 extern "C" int lcr_voxel_down_sample_ws_bytes(int64_t n_cap, int B, size_t* bytes) {
-  if (!bytes || n_cap < 0 || B < 1 || B > GS_MAX_B) return LCR_EARG;
+  if (!bytes || n_cap < 0 || B < 1 || B > GS_MAX_B)
+    return refuse(LCR_EARG, "lcr_voxel_down_sample_ws_bytes: null pointer or outside the domain (n_cap >= 0, 1 <= B <= %d): n_cap=%lld B=%d", GS_MAX_B,
+                  static_cast<long long>(n_cap), B);
   *bytes = vd_layout(nullptr, n_cap, B).bytes;
   return LCR_OK;
 }
@@ -998,24 +993,14 @@ extern "C" int lcr_voxel_down_sample_ws_bytes(int64_t n_cap, int B, size_t* byte
 extern "C" int lcr_voxel_down_sample(const float* rows, int row_floats, int out_cols, const int64_t* len, int B, int64_t n_cap, double voxel,
                                      int key_bits_hint, float* out_f32, double* out_f64, int64_t* out_len, uint32_t* status, void* ws,
                                      size_t ws_bytes, void* stream) {
-  if (row_floats < 3 || row_floats > 64 || out_cols < 3 || out_cols > row_floats) {
-    set_error("lcr_voxel_down_sample: rows of %d floats, %d output columns (3 <= out_cols <= row_floats <= 64)", row_floats, out_cols);
-    return LCR_EARG;
-  }
+  if (row_floats < 3 || row_floats > 64 || out_cols < 3 || out_cols > row_floats)
+    return refuse(LCR_EARG, "lcr_voxel_down_sample: rows of %d floats, %d output columns (3 <= out_cols <= row_floats <= 64)", row_floats, out_cols);
   if (!len || !out_f32 || !out_len || !status || !ws || B < 1 || B > GS_MAX_B || n_cap < 0 || !(voxel > 0.0) || !(voxel < 1e300) ||
-      key_bits_hint < 0 || key_bits_hint > 64) {
-    set_error("lcr_voxel_down_sample: bad argument");
-    return LCR_EARG;
-  }
-  if (n_cap > (int64_t(1) << 31) - 2) {
-    set_error("lcr_voxel_down_sample: more than 2^31-2 points");
-    return LCR_EARG;
-  }
+      key_bits_hint < 0 || key_bits_hint > 64)
+    return refuse(LCR_EARG, "lcr_voxel_down_sample: bad argument");
+  if (n_cap > (int64_t(1) << 31) - 2) return refuse(LCR_EARG, "lcr_voxel_down_sample: more than 2^31-2 points");
   VdLayout V = vd_layout(ws, n_cap, B);
-  if (V.bytes > ws_bytes) {
-    set_error("lcr_voxel_down_sample: workspace too small (%zu < %zu)", ws_bytes, V.bytes);
-    return LCR_ESPACE;
-  }
+  if (V.bytes > ws_bytes) return refuse(LCR_ESPACE, "lcr_voxel_down_sample: workspace too small (%zu < %zu)", ws_bytes, V.bytes);
   const GsLayout& L = V.g;
   const int rs = row_floats;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1029,22 +1014,20 @@ extern "C" int lcr_voxel_down_sample(const float* rows, int row_floats, int out_
   hipLaunchKernelGGL(k_vd_params, dim3(1), dim3(64), 0, st, L.hdr, V.org, voxel, key_bits_hint, status);
   hipLaunchKernelGGL(k_vd_keys, dim3(nblk), dim3(256), 0, st, L.hdr, V.org, rows, rs, voxel, L.keyA, L.valA, status);
   const int max_passes = radix_passes(key_bits_hint > 0 ? key_bits_hint : 64);
-  int rc = radix_sort_pairs(&L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, max_passes, L.hist, L.scan_ws, st);
+  int rc = radix_sort_pairs("lcr_voxel_down_sample", &L.hdr->rx, L.keyA, L.keyB, L.valA, L.valB, n_cap, max_passes, L.hist, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_heads, dim3(nblk), dim3(256), 0, st, L.hdr, L.keyA, L.keyB, L.head, L.first, n_cap);
-  rc = exclusive_scan_i32(L.head, L.head, n_cap + 1, nullptr, L.scan_ws, st);
+  rc = exclusive_scan_i32("lcr_voxel_down_sample", L.head, L.head, n_cap + 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_seg_starts, dim3(nblk), dim3(256), 0, st, L.hdr, L.head, L.seg_start);
   hipLaunchKernelGGL(k_vd_segs, dim3(nblk), dim3(256), 0, st, L.hdr, V.org, rows, rs, voxel, L.valA, L.valB, L.head, L.seg_start, L.seg_key,
                      L.seg_first, L.first, out_len);
-  rc = exclusive_scan_i32(L.first, L.first, n_cap + 1, nullptr, L.scan_ws, st);
+  rc = exclusive_scan_i32("lcr_voxel_down_sample", L.first, L.first, n_cap + 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gs_insertion, dim3(nblk), dim3(256), 0, st, L.hdr, L.first, L.seg_key, L.seg_first, L.ins_key, L.ins_seg);
   static DynLds hm_opt_in;
-  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitRow>), HM_LDS_BYTES) != hipSuccess) {
-    set_error("lcr_voxel_down_sample: cannot reserve %zu B of LDS for the hash-order kernel", HM_LDS_BYTES);
-    return LCR_EHIP;
-  }
+  if (hm_opt_in.need(reinterpret_cast<const void*>(&k_gs_hashorder<HmEmitRow>), HM_LDS_BYTES) != hipSuccess)
+    return refuse(LCR_EHIP, "lcr_voxel_down_sample: cannot reserve %zu B of LDS for the hash-order kernel", HM_LDS_BYTES);
   hipLaunchKernelGGL(k_gs_hashorder<HmEmitRow>, dim3(B), dim3(HM_T), HM_LDS_BYTES, st, L.hdr, L.ins_key, L.ins_seg, L.hm_t, L.hm_bk, L.hm_mem, L.hm_at,
                      L.hm_arr, L.hm_gmin, L.hm_cnt, L.hm_start, HmEmitRow{V.seg_row});
   hipLaunchKernelGGL(k_vd_reduce, dim3(nblk), dim3(256), 0, st, L.hdr, rows, rs, out_cols, L.valA, L.valB, L.head, L.seg_start, V.seg_row, out_f32,
@@ -1054,7 +1037,9 @@ extern "C" int lcr_voxel_down_sample(const float* rows, int row_floats, int out_
 
 // Host: out[i] = codes[i] mod (the phase-th bucket count of the schedule), through the exact reduction hm_mod that hm_bucket uses.
 extern "C" int lcr_hashmap_bucket_host(const uint64_t* codes, int64_t n, int phase, int64_t* out) {
-  if (n < 0 || phase < 0 || phase >= N_SCHED || (n > 0 && (!codes || !out))) return LCR_EARG;
+  if (n < 0 || phase < 0 || phase >= N_SCHED || (n > 0 && (!codes || !out)))
+    return refuse(LCR_EARG, "lcr_hashmap_bucket_host: null pointer or outside the domain (n >= 0, 0 <= phase < %d): n=%lld phase=%d", N_SCHED,
+                  static_cast<long long>(n), phase);
   const uint64_t d = static_cast<uint64_t>(h_sched[phase]);
   for (int64_t i = 0; i < n; ++i) out[i] = static_cast<int64_t>(hm_mod(codes[i], d, h_magic[phase]));
   return LCR_OK;
@@ -1064,7 +1049,7 @@ extern "C" int lcr_hashmap_bucket_host(const uint64_t* codes, int64_t n, int pha
 // element in std::unordered_map iteration order.  Lets the CPU-only test suite pin the algorithm against the real
 // container without a GPU; it is not used by the device path.
 extern "C" int lcr_hashmap_order_host(const uint64_t* keys, int64_t n, int64_t* order) {
-  if (n < 0 || (n > 0 && (!keys || !order))) return LCR_EARG;
+  if (n < 0 || (n > 0 && (!keys || !order))) return refuse(LCR_EARG, "lcr_hashmap_order_host: null pointer or a negative count: n=%lld", static_cast<long long>(n));
   if (n == 0) return LCR_OK;
   std::vector<int64_t> t(n), pos(n), bk(n), mem(n);
   int64_t lo = 0;

@@ -322,21 +322,14 @@ extern "C" int lcr_groupnorm_apply(const float* x, const double* stats, const fl
                                    const double* res_stats, const float* res_gamma, const float* res_beta, float* y, int64_t N, int C,
                                    int groups, const int64_t* seg_len, int S, float eps, float slope, int act, uint8_t* pos, void* stream) {
   if (!x || !stats || !gamma || !beta || !y || !seg_len || N < 0 || C < 1 || groups < 1 || C % groups != 0 || S < 1 ||
-      (res_stats && (!res || !res_gamma || !res_beta))) {
-    set_error("lcr_groupnorm_apply: bad argument");
-    return LCR_EARG;
-  }
+      (res_stats && (!res || !res_gamma || !res_beta)))
+    return refuse(LCR_EARG, "lcr_groupnorm_apply: bad argument");
   if (N == 0) return LCR_OK;
   GnSide gx{stats, gamma, beta}, gr{res_stats, res_gamma, res_beta};
-  if (C % 4 != 0 || S * groups > GN_TABLE || S > GN_MAX_SEG) {
-    set_error("lcr_groupnorm_apply: C must be a multiple of 4, S*groups <= %d and S <= %d", GN_TABLE, GN_MAX_SEG);
-    return LCR_EARG;
-  }
+  if (C % 4 != 0 || S * groups > GN_TABLE || S > GN_MAX_SEG)
+    return refuse(LCR_EARG, "lcr_groupnorm_apply: C must be a multiple of 4, S*groups <= %d and S <= %d", GN_TABLE, GN_MAX_SEG);
   const int c4n = C / 4;
-  if (pos && (c4n > 64 || (c4n & (c4n - 1)) != 0)) {
-    set_error("lcr_groupnorm_apply: row flags need C/4 to be a power of two <= 64");
-    return LCR_EARG;
-  }
+  if (pos && (c4n > 64 || (c4n & (c4n - 1)) != 0)) return refuse(LCR_EARG, "lcr_groupnorm_apply: row flags need C/4 to be a power of two <= 64");
   // contiguous row ranges per workgroup, >= 2048 float4 pieces each (the per-block statistics fold is amortised over them)
   const int nblk = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((N * c4n + 2047) / 2048, 256 * 8)));
   const size_t tab_bytes = (sizeof(float2) + sizeof(float)) * 2 * static_cast<size_t>(S) * groups;
@@ -359,14 +352,10 @@ extern "C" int lcr_groupnorm_apply(const float* x, const double* stats, const fl
 }
 
 extern "C" int lcr_groupnorm_stats(const float* x, int64_t N, int C, int groups, const int64_t* seg_len, int S, double* stats, void* stream) {
-  if (!x || !stats || !seg_len || N < 0 || C < 1 || groups < 1 || C % groups != 0 || S < 1) {
-    set_error("lcr_groupnorm_stats: bad argument");
-    return LCR_EARG;
-  }
+  if (!x || !stats || !seg_len || N < 0 || C < 1 || groups < 1 || C % groups != 0 || S < 1) return refuse(LCR_EARG, "lcr_groupnorm_stats: bad argument");
   const int gs = C / groups;
   if ((gs & (gs - 1)) != 0) {               // k_gn_stats folds the lanes of a group with xor shuffles, like the GEMM epilogues
-    set_error("lcr_groupnorm_stats: channels per group must be a power of two");
-    return LCR_EARG;
+    return refuse(LCR_EARG, "lcr_groupnorm_stats: channels per group must be a power of two");
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   // `stats` accumulates into a caller-zeroed table, like lcr_gemm_f32

@@ -238,10 +238,8 @@ static bool gg_domain(int64_t N, int C, int groups, int S) {
 using namespace lcr;
 
 extern "C" int lcr_groupnorm_apply_grad_ws_bytes(int64_t N, int C, int groups, int S, size_t* bytes) {
-  if (!bytes || !gg_domain(N, C, groups, S)) {
-    set_error("lcr_groupnorm_apply_grad_ws_bytes: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
-    return LCR_EARG;
-  }
+  if (!bytes || !gg_domain(N, C, groups, S))
+    return refuse(LCR_EARG, "lcr_groupnorm_apply_grad_ws_bytes: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
   *bytes = gg_layout(nullptr, N, C, groups, S).bytes;
   return LCR_OK;
 }
@@ -249,19 +247,11 @@ extern "C" int lcr_groupnorm_apply_grad_ws_bytes(int64_t N, int C, int groups, i
 extern "C" int lcr_groupnorm_apply_grad(const float* x, const double* stats, const float* gamma, const float* y, const float* dy, int64_t N, int C,
                                         int groups, const int64_t* seg_len, int S, float eps, float slope, int act, float* dx, float* dgamma,
                                         float* dbeta, float* dz, void* ws, size_t ws_bytes, void* stream) {
-  if (!x || !stats || !gamma || !dy || !dx || !seg_len || !ws || (act && !y)) {
-    set_error("lcr_groupnorm_apply_grad: null argument (y is needed with act)");
-    return LCR_EARG;
-  }
-  if (!gg_domain(N, C, groups, S)) {
-    set_error("lcr_groupnorm_apply_grad: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
-    return LCR_EARG;
-  }
+  if (!x || !stats || !gamma || !dy || !dx || !seg_len || !ws || (act && !y)) return refuse(LCR_EARG, "lcr_groupnorm_apply_grad: null argument (y is needed with act)");
+  if (!gg_domain(N, C, groups, S))
+    return refuse(LCR_EARG, "lcr_groupnorm_apply_grad: C must be a multiple of 4 and of groups, at most %d, and 1 <= S <= %d", GG_MAX_C, GN_MAX_SEG);
   const GgLayout L = gg_layout(ws, N, C, groups, S);
-  if (ws_bytes < L.bytes) {
-    set_error("lcr_groupnorm_apply_grad: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_EARG;
-  }
+  if (ws_bytes < L.bytes) return refuse_ws(LCR_EARG, "lcr_groupnorm_apply_grad", ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   const int Cl = C < 256 ? C : 256;
   const size_t red_lds = (3 * static_cast<size_t>(groups) + static_cast<size_t>(256 / Cl) * Cl * 2) * sizeof(float);

@@ -438,13 +438,11 @@ size_t icp_layout(void* ws, int S, int64_t ns, int64_t nt, size_t grid_bytes, in
 }
 
 int icp_ws_bytes(const char* name, int S, int64_t ns, int64_t nt, int mom, size_t* bytes) {
-  if (!bytes || S < 1 || S > GRID_MAX_B || ns < 0 || nt < 0 || ns > INT32_MAX || nt > INT32_MAX) {
-    set_error("%s: outside the domain (1 <= S <= %d, 0 <= ns, nt <= 2^31-1): S=%d ns=%lld nt=%lld", name, GRID_MAX_B, S,
-              static_cast<long long>(ns), static_cast<long long>(nt));
-    return LCR_EARG;
-  }
+  if (!bytes || S < 1 || S > GRID_MAX_B || ns < 0 || nt < 0 || ns > INT32_MAX || nt > INT32_MAX)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= S <= %d, 0 <= ns, nt <= 2^31-1): S=%d ns=%lld nt=%lld", name, GRID_MAX_B, S,
+                  static_cast<long long>(ns), static_cast<long long>(nt));
   size_t g = 0;
-  if (lcr_support_grid_ws_bytes(nt, S, &g) != LCR_OK) return LCR_EARG;
+  if (int rc = support_grid_ws_bytes(name, nt, S, &g)) return rc;
   *bytes = icp_layout(nullptr, S, ns, nt, g, mom, nullptr, nullptr, nullptr, nullptr);
   return LCR_OK;
 }
@@ -457,20 +455,14 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
             int check_every, void* ws, size_t ws_bytes, void* stream) {
   const float r = max_correspondence_distance;
   if (max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
-      !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0)) {
-    set_error("%s: outside the domain (0 <= max_iteration <= %d, r > 0 with r*r finite, relative criteria >= 0, check_every >= 0): "
-              "max_iteration=%d r=%g check_every=%d", name, ICP_MAX_ITER, max_iteration, static_cast<double>(r), check_every);
-    return LCR_EARG;
-  }
-  if (!init || !T || !fitness || !inlier_rmse || !iterations || !ws) {
-    set_error("%s: null pointer", name);
-    return LCR_EARG;
-  }
+      !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0))
+    return refuse(LCR_EARG, "%s: outside the domain (0 <= max_iteration <= %d, r > 0 with r*r finite, relative criteria >= 0, check_every >= 0): "
+                  "max_iteration=%d r=%g check_every=%d", name, ICP_MAX_ITER, max_iteration, static_cast<double>(r), check_every);
+  if (!init || !T || !fitness || !inlier_rmse || !iterations || !ws) return refuse(LCR_EARG, "%s: null pointer", name);
   Stack sources, targets;
   const std::string who(name);                                   // the error text says which of the two tables is at fault
-  if (stack_from_lengths((who + ": source lengths").c_str(), src_len, S, &sources) ||
-      stack_from_lengths((who + ": target lengths").c_str(), tgt_len, S, &targets))
-    return LCR_EARG;
+  if (int rc = stack_from_lengths((who + ": source lengths").c_str(), src_len, S, &sources)) return rc;
+  if (int rc = stack_from_lengths((who + ": target lengths").c_str(), tgt_len, S, &targets)) return rc;
   IcpPairs P;
   P.S = S;
   std::copy(sources.off, sources.off + S + 1, P.src_off);
@@ -478,18 +470,13 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
   P.blk_off[0] = 0;
   for (int s = 0; s < S; ++s) P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
   const int64_t ns = P.src_off[S], nt = P.tgt_off[S];
-  if ((ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals)))) {
-    set_error("%s: null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
-    return LCR_EARG;
-  }
+  if ((ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals))))
+    return refuse(LCR_EARG, "%s: null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
   constexpr int mom = PLANE ? ICP_PLANE_MOM : ICP_MOM;
   size_t need = 0, grid_bytes = 0;
   icp_ws_bytes(name, S, ns, nt, mom, &need);
-  lcr_support_grid_ws_bytes(nt, S, &grid_bytes);
-  if (need > ws_bytes) {
-    set_error("%s: workspace of %zu bytes, %zu needed", name, ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  support_grid_ws_bytes(name, nt, S, &grid_bytes);
+  if (need > ws_bytes) return refuse_ws(LCR_ESPACE, name, ws_bytes, need);
   double* slab;
   int32_t *done, *running;
   int64_t* tgt_len_dev;
@@ -499,12 +486,11 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
   hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, P, init, max_iteration + 1, T, fitness, inlier_rmse, iterations, done, running, tgt_len_dev,
                      T_hist, fitness_hist, rmse_hist);
   if (corr && ns > 0 && hipMemsetAsync(corr, 0xff, static_cast<size_t>(ns) * sizeof(int32_t), st) != hipSuccess) {   // -1 for pairs that never run
-    set_error("%s: clearing corr failed", name);
-    return LCR_EHIP;
+    return refuse(LCR_EHIP, "%s: clearing corr failed", name);
   }
   int rc = check_launch(name);
   if (rc) return rc;
-  rc = lcr_support_grid_build(tgt, tgt_len_dev, S, nt, r, nullptr, ws, grid_bytes, stream);
+  rc = support_grid_build(name, tgt, tgt_len_dev, S, nt, r, nullptr, ws, grid_bytes, nullptr, stream);
   if (rc) return rc;
   const int nblk = P.blk_off[S];
   const float r2 = r * r;                                        // fp32 product, as lcr_radius_query
@@ -525,10 +511,8 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
     if (check_every > 0 && k < max_iteration && (k + 1) % check_every == 0) {
       int32_t still = 0;
       if (hipMemcpyAsync(&still, running + (k & 1), sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        set_error("%s: read-back of the running count failed", name);
-        return LCR_EHIP;
-      }
+          hipStreamSynchronize(st) != hipSuccess)
+        return refuse(LCR_EHIP, "%s: read-back of the running count failed", name);
       if (still == 0) break;
     }
   }

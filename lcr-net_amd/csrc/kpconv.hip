@@ -634,7 +634,7 @@ static int grid_for(int64_t rows, int per_block) { return static_cast<int>(std::
 static int g_agg_force_off64 = 0;          // tests: run the 64-bit-offset form of the aggregation (tensors of 2^30 elements and more)
 
 template <typename IdxT>
-static int launch_aggregate(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const IdxT* idx, int64_t M,
+static int launch_aggregate(const char* who, const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const IdxT* idx, int64_t M,
                             int64_t Ns, int H, int C, const KPoints& kp, float sigma, float* A, float* nn, const int32_t* order, int vf,
                             uint16_t* mask, hipStream_t st) {
   dim3 grid(grid_for_xcd(M, KP_WAVES)), block(KP_WAVES * 64);
@@ -653,11 +653,27 @@ static int launch_aggregate(const float* s_feats, const uint8_t* s_pos, const fl
     case 64: LCR_AGG(64);
     case 128: LCR_AGG(128);
     case 256: LCR_AGG(256);
-    default: set_error("lcr_kpconv_aggregate: C must be 32, 64, 128 or 256 (got %d)", C); return LCR_EARG;
+    default: return refuse(LCR_EARG, "%s: C must be 32, 64, 128 or 256 (got %d)", who, C);
   }
 #undef LCR_AGG
 #undef LCR_AGG_M
-  return check_launch("lcr_kpconv_aggregate");
+  return check_launch(who);
+}
+
+// the body of lcr_kpconv_aggregate{,_ex,_mask}; `who` = the one that was called
+static int kpconv_aggregate(const char* who, const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
+                            int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma, float* A, float* nn,
+                            uint16_t* mask, const int32_t* order, int flags, void* stream) {
+  if (!s_feats || !s_pos || !q_pts || !s_pts || !idx || !kernel_points_host || !A || !nn || M < 0 || Ns < 0 || H < 1 || H > KP_HMAX ||
+      !(sigma > 0.f))
+    return refuse(LCR_EARG, "%s: bad argument (H must be in [1,%d])", who, KP_HMAX);
+  if (M == 0) return LCR_OK;
+  const KPoints kp = load_kp(kernel_points_host);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KernelTimerScope timed(KT_AGGREGATE, st, M, Ns, H, C, idx_is_64 ? 8 : 4);
+  const int vf = (flags & LCR_KP_VALID_FIRST) ? 1 : 0;
+  return idx_is_64 ? launch_aggregate(who, s_feats, s_pos, q_pts, s_pts, static_cast<const int64_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st)
+                   : launch_aggregate(who, s_feats, s_pos, q_pts, s_pts, static_cast<const int32_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st);
 }
 
 }  // namespace lcr
@@ -669,31 +685,22 @@ extern "C" void lcr_kpconv_debug_off64(int on) { g_agg_force_off64 = on; }
 extern "C" int lcr_kpconv_aggregate(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
                                     int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma,
                                     float* A, float* nn, const int32_t* order, void* stream) {
-  return lcr_kpconv_aggregate_ex(s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn, order, 0, stream);
+  return kpconv_aggregate("lcr_kpconv_aggregate", s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn, nullptr,
+                          order, 0, stream);
 }
 
 extern "C" int lcr_kpconv_aggregate_ex(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
                                        int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma,
                                        float* A, float* nn, const int32_t* order, int flags, void* stream) {
-  return lcr_kpconv_aggregate_mask(s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn, nullptr, order, flags,
-                                   stream);
+  return kpconv_aggregate("lcr_kpconv_aggregate_ex", s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn,
+                          nullptr, order, flags, stream);
 }
 
 extern "C" int lcr_kpconv_aggregate_mask(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
                                          int idx_is_64, int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma,
                                          float* A, float* nn, uint16_t* mask, const int32_t* order, int flags, void* stream) {
-  if (!s_feats || !s_pos || !q_pts || !s_pts || !idx || !kernel_points_host || !A || !nn || M < 0 || Ns < 0 || H < 1 || H > KP_HMAX ||
-      !(sigma > 0.f)) {
-    set_error("lcr_kpconv_aggregate: bad argument (H must be in [1,%d])", KP_HMAX);
-    return LCR_EARG;
-  }
-  if (M == 0) return LCR_OK;
-  const KPoints kp = load_kp(kernel_points_host);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  KernelTimerScope timed(KT_AGGREGATE, st, M, Ns, H, C, idx_is_64 ? 8 : 4);
-  const int vf = (flags & LCR_KP_VALID_FIRST) ? 1 : 0;
-  return idx_is_64 ? launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int64_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st)
-                   : launch_aggregate(s_feats, s_pos, q_pts, s_pts, static_cast<const int32_t*>(idx), M, Ns, H, C, kp, sigma, A, nn, order, vf, mask, st);
+  return kpconv_aggregate("lcr_kpconv_aggregate_mask", s_feats, s_pos, q_pts, s_pts, idx, idx_is_64, M, Ns, H, C, kernel_points_host, sigma, A, nn,
+                          mask, order, flags, stream);
 }
 
 extern "C" int lcr_kpconv_fused(const float* s_feats, const uint8_t* s_pos, const float* q_pts, const float* s_pts, const void* idx,
@@ -701,14 +708,10 @@ extern "C" int lcr_kpconv_fused(const float* s_feats, const uint8_t* s_pos, cons
                                 const float* W, const float* bias, float* out, const int64_t* seg_len, int S, int groups, double* stats,
                                 const int32_t* order, void* stream) {
   if (!s_feats || !s_pos || !q_pts || !s_pts || !idx || !kernel_points_host || !W || !out || M < 0 || Ns < 0 || H < 1 || H > KP_HMAX ||
-      !(sigma > 0.f) || C != KF_C) {
-    set_error("lcr_kpconv_fused: bad argument (C must be %d, H in [1,%d])", KF_C, KP_HMAX);
-    return LCR_EARG;
-  }
-  if (stats && (!seg_len || S < 1 || S > KF_MAX_SEG || groups < 1 || C % groups != 0)) {
-    set_error("lcr_kpconv_fused: statistics need seg_len, 1 <= S <= %d and groups dividing C", KF_MAX_SEG);
-    return LCR_EARG;
-  }
+      !(sigma > 0.f) || C != KF_C)
+    return refuse(LCR_EARG, "lcr_kpconv_fused: bad argument (C must be %d, H in [1,%d])", KF_C, KP_HMAX);
+  if (stats && (!seg_len || S < 1 || S > KF_MAX_SEG || groups < 1 || C % groups != 0))
+    return refuse(LCR_EARG, "lcr_kpconv_fused: statistics need seg_len, 1 <= S <= %d and groups dividing C", KF_MAX_SEG);
   if (M == 0) return LCR_OK;
   const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -735,10 +738,8 @@ extern "C" int lcr_kpconv_fused(const float* s_feats, const uint8_t* s_pos, cons
 extern "C" int lcr_kpconv_cin1(const float* s_feats, const float* q_pts, const float* s_pts, const void* idx, int idx_is_64, int64_t M,
                                int64_t Ns, int H, const float* kernel_points_host, float sigma, const float* W, const float* bias, int Cout,
                                float* out, const int32_t* order, void* stream) {
-  if (!s_feats || !q_pts || !s_pts || !idx || !kernel_points_host || !W || !out || M < 0 || H < 1 || Cout < 1 || Cout > 256 || !(sigma > 0.f)) {
-    set_error("lcr_kpconv_cin1: bad argument");
-    return LCR_EARG;
-  }
+  if (!s_feats || !q_pts || !s_pts || !idx || !kernel_points_host || !W || !out || M < 0 || H < 1 || Cout < 1 || Cout > 256 || !(sigma > 0.f))
+    return refuse(LCR_EARG, "lcr_kpconv_cin1: bad argument");
   if (M == 0) return LCR_OK;
   const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -758,10 +759,7 @@ extern "C" int lcr_kpconv_cin1(const float* s_feats, const float* q_pts, const f
 
 extern "C" int lcr_maxpool(const float* x, const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int C, float* out,
                            const int32_t* order, void* stream) {
-  if (!x || !idx || !out || M < 0 || H < 1 || H > KP_HMAX || C < 1) {
-    set_error("lcr_maxpool: bad argument");
-    return LCR_EARG;
-  }
+  if (!x || !idx || !out || M < 0 || H < 1 || H > KP_HMAX || C < 1) return refuse(LCR_EARG, "lcr_maxpool: bad argument");
   if (M == 0) return LCR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   dim3 grid(grid_for_xcd(M, 4)), block(256);
@@ -771,10 +769,7 @@ extern "C" int lcr_maxpool(const float* x, const void* idx, int idx_is_64, int64
 }
 
 extern "C" int lcr_row_positive(const float* x, int64_t N, int C, uint8_t* pos, void* stream) {
-  if (!x || !pos || N < 0 || C < 1) {
-    set_error("lcr_row_positive: bad argument");
-    return LCR_EARG;
-  }
+  if (!x || !pos || N < 0 || C < 1) return refuse(LCR_EARG, "lcr_row_positive: bad argument");
   if (N == 0) return LCR_OK;
   hipLaunchKernelGGL(k_row_pos, dim3(grid_for(N, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, N, C, pos);
   return check_launch("lcr_row_positive");

@@ -474,26 +474,19 @@ static bool list_args_ok(int64_t M, int64_t Ns, int H) {
 using namespace lcr;
 
 extern "C" int lcr_neighbor_transpose_ws_bytes(int64_t M, int H, size_t* bytes) {
-  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30)) {
-    set_error("lcr_neighbor_transpose_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
-    return LCR_EARG;
-  }
+  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30))
+    return refuse(LCR_EARG, "lcr_neighbor_transpose_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
   *bytes = nt_layout(nullptr, M * H).bytes;
   return LCR_OK;
 }
 
 extern "C" int lcr_neighbor_transpose(const void* idx, int idx_is_64, int64_t M, int64_t Ns, int H, int32_t* row_start, uint32_t* edges,
                                       void* ws, size_t ws_bytes, void* stream) {
-  if (!idx || !row_start || !edges || !ws || !list_args_ok(M, Ns, H)) {
-    set_error("lcr_neighbor_transpose: bad argument (H in [1,%d], M * H < 2^30, Ns < 2^31 - 1)", KP_HMAX);
-    return LCR_EARG;
-  }
+  if (!idx || !row_start || !edges || !ws || !list_args_ok(M, Ns, H))
+    return refuse(LCR_EARG, "lcr_neighbor_transpose: bad argument (H in [1,%d], M * H < 2^30, Ns < 2^31 - 1)", KP_HMAX);
   const int64_t E = M * H;
   const NtLayout L = nt_layout(ws, E);
-  if (ws_bytes < L.bytes) {
-    set_error("lcr_neighbor_transpose: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_EARG;
-  }
+  if (ws_bytes < L.bytes) return refuse_ws(LCR_EARG, "lcr_neighbor_transpose", ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   int bits = 0;
   while ((Ns >> bits) != 0) ++bits;                        // the largest key is Ns (padding)
@@ -501,7 +494,7 @@ extern "C" int lcr_neighbor_transpose(const void* idx, int idx_is_64, int64_t M,
   if (idx_is_64) hipLaunchKernelGGL((k_nt_keys<int64_t>), dim3(blocks_for(E)), dim3(256), 0, st, static_cast<const int64_t*>(idx), E, Ns, passes, L.ctl, L.kA, L.vA);
   else hipLaunchKernelGGL((k_nt_keys<int32_t>), dim3(blocks_for(E)), dim3(256), 0, st, static_cast<const int32_t*>(idx), E, Ns, passes, L.ctl, L.kA, L.vA);
   if (E > 0) {
-    const int rc = radix_sort_pairs(L.ctl, L.kA, L.kB, L.vA, L.vB, E, passes, L.hist, L.scan, st);
+    const int rc = radix_sort_pairs("lcr_neighbor_transpose", L.ctl, L.kA, L.kB, L.vA, L.vB, E, passes, L.hist, L.scan, st);
     if (rc) return rc;
   }
   const bool in_b = (passes & 1) != 0;
@@ -512,14 +505,9 @@ extern "C" int lcr_neighbor_transpose(const void* idx, int idx_is_64, int64_t M,
 extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, const float* s_pts, const int32_t* row_start, const uint32_t* edges,
                                          int64_t M, int64_t Ns, int H, int C, const float* kernel_points_host, float sigma, float* d_s_feats,
                                          void* stream) {
-  if (!dA || !q_pts || !s_pts || !row_start || !edges || !kernel_points_host || !d_s_feats || !list_args_ok(M, Ns, H) || !(sigma > 0.f)) {
-    set_error("lcr_kpconv_aggregate_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
-    return LCR_EARG;
-  }
-  if (C != 32 && C != 64 && C != 128 && C != 256) {
-    set_error("lcr_kpconv_aggregate_grad: C must be 32, 64, 128 or 256 (got %d)", C);
-    return LCR_EARG;
-  }
+  if (!dA || !q_pts || !s_pts || !row_start || !edges || !kernel_points_host || !d_s_feats || !list_args_ok(M, Ns, H) || !(sigma > 0.f))
+    return refuse(LCR_EARG, "lcr_kpconv_aggregate_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
+  if (C != 32 && C != 64 && C != 128 && C != 256) return refuse(LCR_EARG, "lcr_kpconv_aggregate_grad: C must be 32, 64, 128 or 256 (got %d)", C);
   if (Ns == 0) return LCR_OK;
   const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
@@ -539,10 +527,8 @@ extern "C" int lcr_kpconv_aggregate_grad(const float* dA, const float* q_pts, co
 static size_t points_grad_bytes(int64_t M, int H) { return align_up(static_cast<size_t>(std::max<int64_t>(M * H, 1)) * 3 * sizeof(float)); }
 
 extern "C" int lcr_kpconv_points_grad_ws_bytes(int64_t M, int H, size_t* bytes) {
-  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30)) {
-    set_error("lcr_kpconv_points_grad_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
-    return LCR_EARG;
-  }
+  if (!bytes || M < 0 || H < 1 || H > KP_HMAX || M * H >= (int64_t(1) << 30))
+    return refuse(LCR_EARG, "lcr_kpconv_points_grad_ws_bytes: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
   *bytes = points_grad_bytes(M, H);
   return LCR_OK;
 }
@@ -551,18 +537,10 @@ extern "C" int lcr_kpconv_points_grad(const float* dA, const float* s_feats, con
                                       const int32_t* row_start, const uint32_t* edges, int64_t M, int64_t Ns, int H, int C,
                                       const float* kernel_points_host, float sigma, float* d_q, float* d_s, void* ws, size_t ws_bytes, void* stream) {
   if (!list_args_ok(M, Ns, H) || !kernel_points_host || !(sigma > 0.f) || (M > 0 && (!dA || !q_pts || !idx)) || (Ns > 0 && (!s_feats || !s_pts)) ||
-      (d_s && (!row_start || !edges || !ws))) {
-    set_error("lcr_kpconv_points_grad: bad argument (H in [1,%d], M * H < 2^30; d_s needs the inverted list and the workspace)", KP_HMAX);
-    return LCR_EARG;
-  }
-  if (C != 32 && C != 64 && C != 128 && C != 256) {
-    set_error("lcr_kpconv_points_grad: C must be 32, 64, 128 or 256 (got %d)", C);
-    return LCR_EARG;
-  }
-  if (d_s && ws_bytes < points_grad_bytes(M, H)) {
-    set_error("lcr_kpconv_points_grad: workspace of %zu bytes, %zu needed", ws_bytes, points_grad_bytes(M, H));
-    return LCR_EARG;
-  }
+      (d_s && (!row_start || !edges || !ws)))
+    return refuse(LCR_EARG, "lcr_kpconv_points_grad: bad argument (H in [1,%d], M * H < 2^30; d_s needs the inverted list and the workspace)", KP_HMAX);
+  if (C != 32 && C != 64 && C != 128 && C != 256) return refuse(LCR_EARG, "lcr_kpconv_points_grad: C must be 32, 64, 128 or 256 (got %d)", C);
+  if (d_s && ws_bytes < points_grad_bytes(M, H)) return refuse_ws(LCR_EARG, "lcr_kpconv_points_grad", ws_bytes, points_grad_bytes(M, H));
   if ((!d_q && !d_s) || (M == 0 && (Ns == 0 || !d_s))) return LCR_OK;
   const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
@@ -595,10 +573,7 @@ static size_t cin1_grad_bytes(int64_t M, int Cout, bool feats) {
 }
 
 extern "C" int lcr_kpconv_cin1_grad_ws_bytes(int64_t M, int Cout, int want_feats, size_t* bytes) {
-  if (!bytes || M < 0 || Cout < 1 || Cout > 256) {
-    set_error("lcr_kpconv_cin1_grad_ws_bytes: bad argument");
-    return LCR_EARG;
-  }
+  if (!bytes || M < 0 || Cout < 1 || Cout > 256) return refuse(LCR_EARG, "lcr_kpconv_cin1_grad_ws_bytes: bad argument");
   *bytes = cin1_grad_bytes(M, Cout, want_feats != 0);
   return LCR_OK;
 }
@@ -608,14 +583,10 @@ extern "C" int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, co
                                     const float* kernel_points_host, float sigma, const float* W, int Cout, float* dW, float* dbias,
                                     float* d_s_feats, void* ws, size_t ws_bytes, void* stream) {
   if (!d_out || !s_feats || !q_pts || !s_pts || !idx || !kernel_points_host || !W || !dW || !ws || !list_args_ok(M, Ns, H) || Cout < 1 ||
-      Cout > 256 || !(sigma > 0.f) || (d_s_feats && (!row_start || !edges))) {
-    set_error("lcr_kpconv_cin1_grad: bad argument (Cout in [1,256], H in [1,%d]; d_s_feats needs the inverted list)", KP_HMAX);
-    return LCR_EARG;
-  }
-  if (ws_bytes < cin1_grad_bytes(M, Cout, d_s_feats != nullptr)) {
-    set_error("lcr_kpconv_cin1_grad: workspace of %zu bytes, %zu needed", ws_bytes, cin1_grad_bytes(M, Cout, d_s_feats != nullptr));
-    return LCR_EARG;
-  }
+      Cout > 256 || !(sigma > 0.f) || (d_s_feats && (!row_start || !edges)))
+    return refuse(LCR_EARG, "lcr_kpconv_cin1_grad: bad argument (Cout in [1,256], H in [1,%d]; d_s_feats needs the inverted list)", KP_HMAX);
+  if (ws_bytes < cin1_grad_bytes(M, Cout, d_s_feats != nullptr))
+    return refuse_ws(LCR_EARG, "lcr_kpconv_cin1_grad", ws_bytes, cin1_grad_bytes(M, Cout, d_s_feats != nullptr));
   const KPoints kp = load_kp(kernel_points_host);
   hipStream_t st = ST(stream);
   const int nblk = static_cast<int>(std::max<int64_t>(1, (M + CG_ROWS - 1) / CG_ROWS));
@@ -641,10 +612,8 @@ extern "C" int lcr_kpconv_cin1_grad(const float* d_out, const float* s_feats, co
 
 extern "C" int lcr_maxpool_grad(const float* d_out, const float* x, const float* pooled, const void* idx, int idx_is_64, const int32_t* row_start,
                                 const uint32_t* edges, int64_t M, int64_t Ns, int H, int C, uint8_t* winners, float* d_x, void* stream) {
-  if (!d_out || !x || !pooled || !idx || !row_start || !edges || !winners || !d_x || !list_args_ok(M, Ns, H) || C < 1) {
-    set_error("lcr_maxpool_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
-    return LCR_EARG;
-  }
+  if (!d_out || !x || !pooled || !idx || !row_start || !edges || !winners || !d_x || !list_args_ok(M, Ns, H) || C < 1)
+    return refuse(LCR_EARG, "lcr_maxpool_grad: bad argument (H in [1,%d], M * H < 2^30)", KP_HMAX);
   hipStream_t st = ST(stream);
   if (M > 0) {
     const int grid = blocks_for(M, 4);

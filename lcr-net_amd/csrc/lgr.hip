@@ -249,14 +249,15 @@ __global__ __launch_bounds__(256) void k_inlier_weights_seg(const float* __restr
 using namespace lcr;
 
 extern "C" int lcr_procrustes_batched(const float* src, const float* ref, const float* w, const int32_t* start, int P, float eps, float* T, void* stream) {
-  if (!src || !ref || !w || !start || !T || P < 1) return LCR_EARG;
+  if (!src || !ref || !w || !start || !T || P < 1) return refuse(LCR_EARG, "lcr_procrustes_batched: null pointer or P < 1: P=%d", P);
   hipLaunchKernelGGL(k_procrustes, dim3(P), dim3(64), 0, ST(stream), src, ref, w, start, eps, T);
   return check_launch("lcr_procrustes_batched");
 }
 
 extern "C" int lcr_inlier_count(const float* T, int P, const float* src, const float* ref, int n, float radius, const int32_t* start, int min_count,
                                 int32_t* counts, int32_t* best, void* stream) {
-  if (!T || !counts || P < 1 || n < 0 || (n > 0 && (!src || !ref))) return LCR_EARG;       // no rows: nothing to read, null src / ref allowed
+  if (!T || !counts || P < 1 || n < 0 || (n > 0 && (!src || !ref)))                        // no rows: nothing to read, null src / ref allowed
+    return refuse(LCR_EARG, "lcr_inlier_count: null pointer, P < 1 or n < 0: P=%d n=%d", P, n);
   hipLaunchKernelGGL(k_inlier_count, dim3(P), dim3(256), 0, ST(stream), T, src, ref, n, radius, start, min_count, counts);
   if (best) hipLaunchKernelGGL(k_argmax_i32, dim3(1), dim3(64), 0, ST(stream), counts, P, best);
   return check_launch("lcr_inlier_count");
@@ -265,7 +266,7 @@ extern "C" int lcr_inlier_count(const float* T, int P, const float* src, const f
 extern "C" int lcr_inlier_weights(const float* T_all, const int32_t* sel, const float* src, const float* ref, const float* score, int n, float radius,
                                   float* w_out, void* stream) {
   if (n == 0) return LCR_OK;                               // no rows: nothing to read or write, null pointers allowed
-  if (!T_all || !src || !ref || !score || !w_out || n < 0) return LCR_EARG;
+  if (!T_all || !src || !ref || !score || !w_out || n < 0) return refuse(LCR_EARG, "lcr_inlier_weights: null pointer or a negative count: n=%d", n);
   hipLaunchKernelGGL(k_inlier_weights, dim3(blocks_for(n)), dim3(256), 0, ST(stream), T_all, sel, src, ref, score, n, radius, w_out);
   return check_launch("lcr_inlier_weights");
 }
@@ -296,29 +297,21 @@ static LgrLayout lgr_layout(void* ws, int64_t n, int H, int S) {
   return L;
 }
 extern "C" int lcr_lgr_ws_bytes(int64_t n, int H, int S, size_t* bytes) {
-  if (!bytes || n < 0 || H < 1 || S < 1) return LCR_EARG;
+  if (!bytes || n < 0 || H < 1 || S < 1)
+    return refuse(LCR_EARG, "lcr_lgr_ws_bytes: null pointer or outside the domain (n >= 0, H >= 1, S >= 1): n=%lld H=%d S=%d", static_cast<long long>(n), H, S);
   *bytes = lgr_layout(nullptr, n, H, S).bytes;
   return LCR_OK;
 }
-extern "C" int lcr_local_global_registration(const float* src, const float* ref, const float* score, int64_t n, const int32_t* hyp_start, int H,
-                                             const int32_t* seg_hyp_start, int S, float radius, int min_count, int steps, float* T_out /*[S,4,4]*/,
-                                             float* hyp_out /*[H,4,4] or NULL*/, int32_t* counts_out /*[H] or NULL*/, int32_t* best_out /*[S] or NULL*/,
-                                             void* ws, size_t ws_bytes, void* stream) {
-  return lcr_local_global_registration_ex(src, ref, score, n, hyp_start, H, seg_hyp_start, S, radius, min_count, steps, 0, T_out, hyp_out, counts_out,
-                                          best_out, ws, ws_bytes, stream);
-}
+// the body of lcr_local_global_registration and lcr_local_global_registration_ex; `who` = the one that was called
 // correspondence_limit > 0: the per-pair verification set of local_global_registration.py:152-160 (k_lgr_topl); 0 = every correspondence
-extern "C" int lcr_local_global_registration_ex(const float* src, const float* ref, const float* score, int64_t n, const int32_t* hyp_start, int H,
-                                                const int32_t* seg_hyp_start, int S, float radius, int min_count, int steps, int correspondence_limit,
-                                                float* T_out, float* hyp_out, int32_t* counts_out, int32_t* best_out, void* ws, size_t ws_bytes,
-                                                void* stream) {
-  if (correspondence_limit < 0) return LCR_EARG;
-  if (!src || !ref || !score || !hyp_start || !seg_hyp_start || !T_out || !ws || n < 1 || H < 1 || S < 1 || steps < 1 || n > 2147483647) {
-    set_error("lcr_local_global_registration: bad argument");
-    return LCR_EARG;
-  }
+static int local_global_registration(const char* who, const float* src, const float* ref, const float* score, int64_t n, const int32_t* hyp_start,
+                                     int H, const int32_t* seg_hyp_start, int S, float radius, int min_count, int steps, int correspondence_limit,
+                                     float* T_out, float* hyp_out, int32_t* counts_out, int32_t* best_out, void* ws, size_t ws_bytes, void* stream) {
+  if (correspondence_limit < 0) return refuse(LCR_EARG, "%s: correspondence_limit must not be negative (%d)", who, correspondence_limit);
+  if (!src || !ref || !score || !hyp_start || !seg_hyp_start || !T_out || !ws || n < 1 || H < 1 || S < 1 || steps < 1 || n > 2147483647)
+    return refuse(LCR_EARG, "%s: bad argument", who);
   const LgrLayout L = lgr_layout(ws, n, H, S);
-  if (L.bytes > ws_bytes) return LCR_ESPACE;
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, who, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   const int ni = static_cast<int>(n);
   hipLaunchKernelGGL(k_lgr_seg_rows, dim3(1), dim3(64), 0, st, hyp_start, seg_hyp_start, S, L.seg_rows);
@@ -339,5 +332,19 @@ extern "C" int lcr_local_global_registration_ex(const float* src, const float* r
   }
   if (hyp_out) hipMemcpyAsync(hyp_out, L.hyp, sizeof(float) * 16 * H, hipMemcpyDeviceToDevice, st);
   if (counts_out) hipMemcpyAsync(counts_out, L.counts, sizeof(int32_t) * H, hipMemcpyDeviceToDevice, st);
-  return check_launch("lcr_local_global_registration");
+  return check_launch(who);
+}
+extern "C" int lcr_local_global_registration(const float* src, const float* ref, const float* score, int64_t n, const int32_t* hyp_start, int H,
+                                             const int32_t* seg_hyp_start, int S, float radius, int min_count, int steps, float* T_out /*[S,4,4]*/,
+                                             float* hyp_out /*[H,4,4] or NULL*/, int32_t* counts_out /*[H] or NULL*/, int32_t* best_out /*[S] or NULL*/,
+                                             void* ws, size_t ws_bytes, void* stream) {
+  return local_global_registration("lcr_local_global_registration", src, ref, score, n, hyp_start, H, seg_hyp_start, S, radius, min_count, steps, 0,
+                                   T_out, hyp_out, counts_out, best_out, ws, ws_bytes, stream);
+}
+extern "C" int lcr_local_global_registration_ex(const float* src, const float* ref, const float* score, int64_t n, const int32_t* hyp_start, int H,
+                                                const int32_t* seg_hyp_start, int S, float radius, int min_count, int steps, int correspondence_limit,
+                                                float* T_out, float* hyp_out, int32_t* counts_out, int32_t* best_out, void* ws, size_t ws_bytes,
+                                                void* stream) {
+  return local_global_registration("lcr_local_global_registration_ex", src, ref, score, n, hyp_start, H, seg_hyp_start, S, radius, min_count, steps,
+                                   correspondence_limit, T_out, hyp_out, counts_out, best_out, ws, ws_bytes, stream);
 }

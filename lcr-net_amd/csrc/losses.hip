@@ -424,20 +424,15 @@ static GapLayout gap_layout(void* ws, int64_t rows, int64_t cols) {
 static int gap_domain(const char* entry, int64_t B, int P, int n_max, int m_max, int64_t elems, int64_t rows, int64_t cols) {
   if (B < 1 || B > 65535 || P < 1 || P > 65535 || P > B || n_max < 0 || m_max < 0 || n_max > 32767 || m_max > 32767 || elems < B ||
       rows < 0 || cols < 0 || rows > B * static_cast<int64_t>(n_max) || cols > B * static_cast<int64_t>(m_max) ||
-      elems > B * static_cast<int64_t>(n_max + 1) * (m_max + 1)) {
-    set_error("%s: outside the domain (1 <= P <= B <= 65535, 0 <= n_max, m_max <= 32767, totals within B slices of that size): B=%lld P=%d "
-              "n_max=%d m_max=%d elems=%lld rows=%lld cols=%lld", entry, static_cast<long long>(B), P, n_max, m_max,
-              static_cast<long long>(elems), static_cast<long long>(rows), static_cast<long long>(cols));
-    return LCR_EARG;
-  }
+      elems > B * static_cast<int64_t>(n_max + 1) * (m_max + 1))
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= P <= B <= 65535, 0 <= n_max, m_max <= 32767, totals within B slices of that size): B=%lld P=%d "
+                  "n_max=%d m_max=%d elems=%lld rows=%lld cols=%lld", entry, static_cast<long long>(B), P, n_max, m_max,
+                  static_cast<long long>(elems), static_cast<long long>(rows), static_cast<long long>(cols));
   return LCR_OK;
 }
 
 extern "C" int lcr_gap_loss_ws_bytes(int64_t rows, int64_t cols, size_t* bytes) {
-  if (!bytes || rows < 0 || cols < 0) {
-    set_error("lcr_gap_loss_ws_bytes: null pointer or negative count");
-    return LCR_EARG;
-  }
+  if (!bytes || rows < 0 || cols < 0) return refuse(LCR_EARG, "lcr_gap_loss_ws_bytes: null pointer or negative count");
   *bytes = gap_layout(nullptr, rows, cols).bytes;
   return LCR_OK;
 }
@@ -454,31 +449,21 @@ extern "C" int lcr_gap_loss(const float* S, const int64_t* soff, const int64_t* 
   const bool lines = rows + cols > 0;
   if (!S || !soff || !roff || !coff || !seg_start || !terms || !kept || !labels || !status || !ws ||
       (lines && (!line_pos || !line_hinge || !line_count || !line_active)) || (rows > 0 && !pmask) || (cols > 0 && !qmask) ||
-      !(gamma == gamma)) {
-    set_error("lcr_gap_loss: null pointer or NaN gamma");
-    return LCR_EARG;
-  }
+      !(gamma == gamma))
+    return refuse(LCR_EARG, "lcr_gap_loss: null pointer or NaN gamma");
   const float r2 = static_cast<float>(positive_radius * positive_radius);
   const float r2neg = static_cast<float>((positive_radius * 2) * (positive_radius * 2));
   if (source == LCR_GAP_LABELS_POINTS) {
-    if (!transforms || (rows > 0 && !p_pts) || (cols > 0 && !q_pts) || !(positive_radius >= 0) || !(r2neg < INFINITY)) {
-      set_error("lcr_gap_loss: the point labels need points, transforms and a radius >= 0 with a finite fp32 square");
-      return LCR_EARG;
-    }
+    if (!transforms || (rows > 0 && !p_pts) || (cols > 0 && !q_pts) || !(positive_radius >= 0) || !(r2neg < INFINITY))
+      return refuse(LCR_EARG, "lcr_gap_loss: the point labels need points, transforms and a radius >= 0 with a finite fp32 square");
   } else if (source == LCR_GAP_LABELS_OVERLAPS) {
-    if (C < 0 || c_max < 0 || c_max > C || !corr_start || (C > 0 && (!corr || !overlaps)) || !(positive_overlap >= 0)) {
-      set_error("lcr_gap_loss: the overlap labels need the correspondence list, its offsets and positive_overlap >= 0");
-      return LCR_EARG;
-    }
+    if (C < 0 || c_max < 0 || c_max > C || !corr_start || (C > 0 && (!corr || !overlaps)) || !(positive_overlap >= 0))
+      return refuse(LCR_EARG, "lcr_gap_loss: the overlap labels need the correspondence list, its offsets and positive_overlap >= 0");
   } else {
-    set_error("lcr_gap_loss: unknown label source %d", source);
-    return LCR_EARG;
+    return refuse(LCR_EARG, "lcr_gap_loss: unknown label source %d", source);
   }
   const GapLayout L = gap_layout(ws, rows, cols);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_gap_loss: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_gap_loss", ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   const GapGeom g{soff, roff, coff, elems, rows, cols, n_max, m_max};
   const int Bi = static_cast<int>(B);
@@ -509,10 +494,8 @@ extern "C" int lcr_gap_loss_grad(const float* S, const int64_t* soff, const int6
   const int rc = gap_domain("lcr_gap_loss_grad", B, P, n_max, m_max, elems, rows, cols);
   if (rc != LCR_OK) return rc;
   if (!S || !soff || !roff || !coff || !seg_start || !upstream || !kept || !labels || !dS ||
-      (rows + cols > 0 && (!line_pos || !line_hinge || !line_count || !line_active))) {
-    set_error("lcr_gap_loss_grad: null pointer");
-    return LCR_EARG;
-  }
+      (rows + cols > 0 && (!line_pos || !line_hinge || !line_count || !line_active)))
+    return refuse(LCR_EARG, "lcr_gap_loss_grad: null pointer");
   const GapGeom g{soff, roff, coff, elems, rows, cols, n_max, m_max};
   hipLaunchKernelGGL(k_gap_grad, dim3(div_up(static_cast<int64_t>(n_max + 1) * (m_max + 1), 256), static_cast<int>(B)), dim3(256), 0, ST(stream),
                      g, seg_start, P, S, labels, line_pos, line_hinge, line_count, line_active, kept, upstream, gamma, dS);
@@ -520,11 +503,9 @@ extern "C" int lcr_gap_loss_grad(const float* S, const int64_t* soff, const int6
 }
 
 static int md_domain(const char* entry, int P, int64_t na, int64_t nd, int64_t q_max) {
-  if (P < 1 || P > 65535 || na < 0 || nd < 0 || na > INT32_MAX / 3 || nd > INT32_MAX / 3 || q_max < 0 || q_max > na) {
-    set_error("%s: outside the domain (1 <= P <= 65535, 0 <= q_max <= na, na and nd at most (2^31-1)/3): P=%d na=%lld nd=%lld q_max=%lld", entry,
-              P, static_cast<long long>(na), static_cast<long long>(nd), static_cast<long long>(q_max));
-    return LCR_EARG;
-  }
+  if (P < 1 || P > 65535 || na < 0 || nd < 0 || na > INT32_MAX / 3 || nd > INT32_MAX / 3 || q_max < 0 || q_max > na)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= P <= 65535, 0 <= q_max <= na, na and nd at most (2^31-1)/3): P=%d na=%lld nd=%lld q_max=%lld", entry,
+                  P, static_cast<long long>(na), static_cast<long long>(nd), static_cast<long long>(q_max));
   return LCR_OK;
 }
 
@@ -532,10 +513,7 @@ extern "C" int lcr_min_dist(const float* A, const int32_t* a_start, int64_t na, 
                             const uint8_t* valid, int P, int64_t q_max, float* dist, int32_t* arg, float* mean, int32_t* count, void* stream) {
   const int rc = md_domain("lcr_min_dist", P, na, nd, q_max);
   if (rc != LCR_OK) return rc;
-  if (!a_start || !d_start || !mean || !count || (na > 0 && (!A || !dist || !arg)) || (nd > 0 && !D)) {
-    set_error("lcr_min_dist: null pointer");
-    return LCR_EARG;
-  }
+  if (!a_start || !d_start || !mean || !count || (na > 0 && (!A || !dist || !arg)) || (nd > 0 && !D)) return refuse(LCR_EARG, "lcr_min_dist: null pointer");
   hipStream_t st = ST(stream);
   if (q_max > 0)
     hipLaunchKernelGGL(k_min_dist, dim3(div_up(q_max, MD_Q), P), dim3(256), 0, st, A, a_start, na, D, d_start, nd, dist, arg);
@@ -548,10 +526,8 @@ extern "C" int lcr_min_dist_grad(const float* A, const int32_t* a_start, int64_t
                                  const float* upstream, float* dA, void* stream) {
   const int rc = md_domain("lcr_min_dist_grad", P, na, nd, q_max);
   if (rc != LCR_OK) return rc;
-  if (!a_start || !d_start || !count || !upstream || (na > 0 && (!A || !dist || !arg || !dA)) || (nd > 0 && !D)) {
-    set_error("lcr_min_dist_grad: null pointer");
-    return LCR_EARG;
-  }
+  if (!a_start || !d_start || !count || !upstream || (na > 0 && (!A || !dist || !arg || !dA)) || (nd > 0 && !D))
+    return refuse(LCR_EARG, "lcr_min_dist_grad: null pointer");
   if (q_max > 0)
     hipLaunchKernelGGL(k_md_grad, dim3(div_up(q_max, 256), P), dim3(256), 0, ST(stream), A, a_start, na, D, d_start, nd, valid, arg, dist,
                        count, upstream, dA);

@@ -372,25 +372,24 @@ static auto top1_layout(void* ws, int64_t B, int M, int N) { return match_layout
 static auto topk_layout(void* ws, int64_t B, int M, int N) { return match_layout<float, int32_t>(ws, B, M, N); }     // rowv, rowj, colv, coli
 
 extern "C" int lcr_top1_matching_ws_bytes(int64_t B, int M, int N, size_t* bytes) {
-  if (!bytes || B < 1 || M < 1 || N < 1) return LCR_EARG;
+  if (!bytes || B < 1 || M < 1 || N < 1)
+    return refuse(LCR_EARG, "lcr_top1_matching_ws_bytes: null pointer or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   *bytes = top1_layout(nullptr, B, M, N).bytes;
   return LCR_OK;
 }
 
+// The body of lcr_top1_matching and lcr_top1_matching_ex; `who` = the one that was called.
 // Two-phase: out_bij == NULL -> only *total (device i64) is produced (and the per-row offsets kept in ws);
 // then call again with buffers of `total` entries.  (b,i,j) triplets in row-major order; scores in the exp domain.
-extern "C" int lcr_top1_matching(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int64_t* total,
-                                 int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
-  return lcr_top1_matching_ex(logS, B, M, N, row_mask, col_mask, 0, total, out_bij, out_score, ws, ws_bytes, stream);
-}
-
 // mutual != 0: a pair is kept only if it is BOTH its row's and its column's dustbin-beating maximum (LocalGlobalRegistration(mutual=True),
 // local_global_registration.py:84-85); 0: either (the shipped configuration)
-extern "C" int lcr_top1_matching_ex(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int mutual,
-                                    int64_t* total, int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
-  if (!logS || !ws || B < 1 || M < 1 || N < 1 || (!out_bij && !total)) return LCR_EARG;
+static int top1_matching(const char* who, const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int mutual,
+                         int64_t* total, int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  if (!logS || !ws || B < 1 || M < 1 || N < 1 || (!out_bij && !total))
+    return refuse(LCR_EARG, "%s: null pointer (out_bij or total is needed) or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", who,
+                  static_cast<long long>(B), M, N);
   const auto L = top1_layout(ws, B, M, N);
-  if (L.bytes > ws_bytes) return LCR_ESPACE;
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, who, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   if (!out_bij) {
     const int slices = B >= 64 ? 1 : std::max(1, std::min(32, (M + 1 + 15) / 16));
@@ -401,36 +400,45 @@ extern "C" int lcr_top1_matching_ex(const float* logS, int64_t B, int M, int N, 
     hipLaunchKernelGGL((k_top1_emit<0>), dim3(blocks_for(B * M)), dim3(256), 0, st, logS, B, M, N, L.rowa, L.rowb, L.cola, L.colb, row_mask, col_mask,
                        L.counts, L.offsets, out_bij, out_score, mutual);
     hipMemsetAsync(L.counts + B * M, 0, sizeof(int32_t), st);
-    int rc = exclusive_scan_i32(L.counts, L.offsets, B * M + 1, total, L.scan_ws, st);
+    int rc = exclusive_scan_i32(who, L.counts, L.offsets, B * M + 1, total, L.scan_ws, st);
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL((k_top1_emit<1>), dim3(blocks_for(B * M)), dim3(256), 0, st, logS, B, M, N, L.rowa, L.rowb, L.cola, L.colb, row_mask, col_mask,
                        L.counts, L.offsets, out_bij, out_score, mutual);
   }
-  return check_launch("lcr_top1_matching");
+  return check_launch(who);
+}
+
+extern "C" int lcr_top1_matching(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int64_t* total,
+                                 int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  return top1_matching("lcr_top1_matching", logS, B, M, N, row_mask, col_mask, 0, total, out_bij, out_score, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_top1_matching_ex(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int mutual,
+                                    int64_t* total, int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  return top1_matching("lcr_top1_matching_ex", logS, B, M, N, row_mask, col_mask, mutual, total, out_bij, out_score, ws, ws_bytes, stream);
 }
 
 extern "C" int lcr_topk_matching_ws_bytes(int64_t B, int M, int N, size_t* bytes) {
-  if (!bytes || B < 1 || M < 1 || N < 1) return LCR_EARG;
+  if (!bytes || B < 1 || M < 1 || N < 1)
+    return refuse(LCR_EARG, "lcr_topk_matching_ws_bytes: null pointer or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   *bytes = topk_layout(nullptr, B, M, N).bytes;
   return LCR_OK;
 }
 
-// dustbin top-K matching (K >= 1), two-phase like lcr_top1_matching; for K = 1 the rows equal lcr_top1_matching_ex's
-extern "C" int lcr_topk_matching(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int K, int mutual,
-                                 int64_t* total, int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
-  return lcr_topk_matching_ex(logS, B, M, N, row_mask, col_mask, K, mutual, 1, 0.f, nullptr, total, out_bij, out_score, ws, ws_bytes, stream);
-}
-
+// The body of lcr_topk_matching and lcr_topk_matching_ex; `who` = the one that was called.
+// dustbin top-K matching (K >= 1), two-phase like lcr_top1_matching; for K = 1 the rows equal lcr_top1_matching_ex's;
 // every switch of LocalGlobalRegistration.compute_correspondence_matrix (local_global_registration.py:48-93) + use_global_score (:236-237):
 // use_dustbin = 0 takes the K largest over the M x N interior and keeps what exceeds confidence_threshold; global_scores [B] (or NULL)
 // multiplies the emitted scores of patch pair b
-extern "C" int lcr_topk_matching_ex(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int K, int mutual,
-                                    int use_dustbin, float confidence_threshold, const float* global_scores, int64_t* total, int32_t* out_bij,
-                                    float* out_score, void* ws, size_t ws_bytes, void* stream) {
-  if (!logS || !ws || B < 1 || M < 1 || N < 1 || K < 1 || (!out_bij && !total)) return LCR_EARG;
+static int topk_matching(const char* who, const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int K,
+                         int mutual, int use_dustbin, float confidence_threshold, const float* global_scores, int64_t* total, int32_t* out_bij,
+                         float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  if (!logS || !ws || B < 1 || M < 1 || N < 1 || K < 1 || (!out_bij && !total))
+    return refuse(LCR_EARG, "%s: null pointer (out_bij or total is needed) or outside the domain (B, M, N, K >= 1): B=%lld M=%d N=%d K=%d", who,
+                  static_cast<long long>(B), M, N, K);
   const auto L = topk_layout(ws, B, M, N);
-  if (L.bytes > ws_bytes) return LCR_ESPACE;
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, who, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   const int dust = use_dustbin ? 1 : 0;
   if (!out_bij) {
@@ -439,12 +447,24 @@ extern "C" int lcr_topk_matching_ex(const float* logS, int64_t B, int M, int N, 
     hipLaunchKernelGGL((k_topk_emit<0>), dim3(blocks_for(B * M)), dim3(256), 0, st, logS, B, M, N, L.rowa, L.rowb, L.cola, L.colb, row_mask, col_mask, L.counts,
                        L.offsets, out_bij, out_score, mutual, dust, confidence_threshold, global_scores);
     hipMemsetAsync(L.counts + B * M, 0, sizeof(int32_t), st);
-    int rc = exclusive_scan_i32(L.counts, L.offsets, B * M + 1, total, L.scan_ws, st);
+    int rc = exclusive_scan_i32(who, L.counts, L.offsets, B * M + 1, total, L.scan_ws, st);
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL((k_topk_emit<1>), dim3(blocks_for(B * M)), dim3(256), 0, st, logS, B, M, N, L.rowa, L.rowb, L.cola, L.colb, row_mask, col_mask, L.counts,
                        L.offsets, out_bij, out_score, mutual, dust, confidence_threshold, global_scores);
   }
-  return check_launch("lcr_topk_matching");
+  return check_launch(who);
+}
+
+extern "C" int lcr_topk_matching(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int K, int mutual,
+                                 int64_t* total, int32_t* out_bij, float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  return topk_matching("lcr_topk_matching", logS, B, M, N, row_mask, col_mask, K, mutual, 1, 0.f, nullptr, total, out_bij, out_score, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_topk_matching_ex(const float* logS, int64_t B, int M, int N, const uint8_t* row_mask, const uint8_t* col_mask, int K, int mutual,
+                                    int use_dustbin, float confidence_threshold, const float* global_scores, int64_t* total, int32_t* out_bij,
+                                    float* out_score, void* ws, size_t ws_bytes, void* stream) {
+  return topk_matching("lcr_topk_matching_ex", logS, B, M, N, row_mask, col_mask, K, mutual, use_dustbin, confidence_threshold, global_scores, total,
+                       out_bij, out_score, ws, ws_bytes, stream);
 }
 

@@ -370,19 +370,15 @@ __global__ __launch_bounds__(D) void k_gate_out(const float* __restrict__ hp, co
 namespace nv {
 
 int seg_offsets(const char* who, const int64_t* seg_len_host, int S, int s_min, int s_max, std::vector<int64_t>* off, int* Lmax) {
-  if (!seg_len_host || S < s_min || (s_max && S > s_max)) {
-    if (s_max) set_error("%s: S = %d outside %d .. %d, or no segment lengths", who, S, s_min, s_max);
-    else set_error("%s: S = %d below %d, or no segment lengths", who, S, s_min);
-    return LCR_EARG;
-  }
+  if (!seg_len_host || S < s_min || (s_max && S > s_max))
+    return s_max ? refuse(LCR_EARG, "%s: S = %d outside %d .. %d, or no segment lengths", who, S, s_min, s_max)
+                 : refuse(LCR_EARG, "%s: S = %d below %d, or no segment lengths", who, S, s_min);
   off->resize(static_cast<size_t>(S) + 1);
   int64_t N = 0, longest = 0;
   for (int s = 0; s < S; ++s) {
-    if (seg_len_host[s] < 1 || seg_len_host[s] > 2147483647LL - N) {
-      set_error("%s: segment %d has length %lld (each at least 1, %lld rows before it, 2^31-1 in all)", who, s,
-                static_cast<long long>(seg_len_host[s]), static_cast<long long>(N));
-      return LCR_EARG;
-    }
+    if (seg_len_host[s] < 1 || seg_len_host[s] > 2147483647LL - N)
+      return refuse(LCR_EARG, "%s: segment %d has length %lld (each at least 1, %lld rows before it, 2^31-1 in all)", who, s,
+                    static_cast<long long>(seg_len_host[s]), static_cast<long long>(N));
     (*off)[s] = N;
     N += seg_len_host[s];
     longest = std::max(longest, seg_len_host[s]);
@@ -420,7 +416,7 @@ static NetvladLayout netvlad_layout(void* ws, int64_t n_rows, int S) {
 }
 
 extern "C" int lcr_netvlad_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
+  if (!bytes || n_rows < 0 || S < 1) return refuse(LCR_EARG, "lcr_netvlad_ws_bytes: null pointer or outside the domain (n_rows >= 0, S >= 1): n_rows=%lld S=%d", static_cast<long long>(n_rows), S);
   *bytes = netvlad_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
 }
@@ -429,20 +425,14 @@ extern "C" int lcr_netvlad_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
 extern "C" int lcr_netvlad_forward(const float* feats, const int64_t* seg_len_host, int S, const LcrNetvladWeights* wt, float* out,
                                    void* ws, size_t ws_bytes, void* stream) {
   const char* who = "lcr_netvlad_forward";
-  if (!feats || !wt || !out || !ws) {
-    set_error("%s: bad argument", who);
-    return LCR_EARG;
-  }
+  if (!feats || !wt || !out || !ws) return refuse(LCR_EARG, "%s: bad argument", who);
   std::vector<int64_t> off;
   int Lmax = 0;
   int rc = seg_offsets(who, seg_len_host, S, 1, 0, &off, &Lmax);
   if (rc) return rc;
   const int64_t N = off[S];
   const NetvladLayout L = netvlad_layout(ws, N, S);
-  if (L.bytes > ws_bytes) {
-    set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse(LCR_ESPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   launch_row_l2norm(feats, N, L.xn, st);
   rc = lcr_gemm_f32(L.xn, wt->cluster_weights, L.act, N, K, F, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
@@ -480,13 +470,13 @@ static FwdWs fwd_layout(void* p, int64_t n_rows, int S) {
 }
 
 extern "C" int lcr_netvlad_train_saved_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
+  if (!bytes || n_rows < 0 || S < 1) return refuse(LCR_EARG, "lcr_netvlad_train_saved_bytes: null pointer or outside the domain (n_rows >= 0, S >= 1): n_rows=%lld S=%d", static_cast<long long>(n_rows), S);
   *bytes = saved_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
 }
 
 extern "C" int lcr_netvlad_train_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
+  if (!bytes || n_rows < 0 || S < 1) return refuse(LCR_EARG, "lcr_netvlad_train_ws_bytes: null pointer or outside the domain (n_rows >= 0, S >= 1): n_rows=%lld S=%d", static_cast<long long>(n_rows), S);
   *bytes = fwd_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
 }
@@ -496,10 +486,7 @@ extern "C" int lcr_netvlad_train_ws_bytes(int64_t n_rows, int S, size_t* bytes) 
 extern "C" int lcr_netvlad_train_forward(const float* feats, const int64_t* seg_len_host, int S, const LcrNetvladWeights* wt, float* out,
                                          float* batch_stats, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream) {
   const char* who = "lcr_netvlad_train_forward";
-  if (!feats || !wt || !out || !batch_stats || !saved || !ws) {
-    set_error("%s: bad argument", who);
-    return LCR_EARG;
-  }
+  if (!feats || !wt || !out || !batch_stats || !saved || !ws) return refuse(LCR_EARG, "%s: bad argument", who);
   std::vector<int64_t> off;
   int Lmax = 0;
   int rc = seg_offsets(who, seg_len_host, S, 2, S_MAX, &off, &Lmax);
@@ -507,10 +494,8 @@ extern "C" int lcr_netvlad_train_forward(const float* feats, const int64_t* seg_
   const int64_t N = off[S];
   const Saved sv = saved_layout(saved, N, S);
   const FwdWs L = fwd_layout(ws, N, S);
-  if (sv.bytes > saved_bytes || L.bytes > ws_bytes) {
-    set_error("%s: buffer too small (saved %zu < %zu or workspace %zu < %zu)", who, saved_bytes, sv.bytes, ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (sv.bytes > saved_bytes || L.bytes > ws_bytes)
+    return refuse(LCR_ESPACE, "%s: buffer too small (saved %zu < %zu or workspace %zu < %zu)", who, saved_bytes, sv.bytes, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   float* st_mean1 = batch_stats;
   float* st_var1 = batch_stats + K;

@@ -415,7 +415,7 @@ BwdWs bwd_layout(void* p, int64_t n_rows, int S) {
 }  // namespace
 
 extern "C" int lcr_netvlad_backward_ws_bytes(int64_t n_rows, int S, size_t* bytes) {
-  if (!bytes || n_rows < 0 || S < 1) return LCR_EARG;
+  if (!bytes || n_rows < 0 || S < 1) return refuse(LCR_EARG, "lcr_netvlad_backward_ws_bytes: null pointer or outside the domain (n_rows >= 0, S >= 1): n_rows=%lld S=%d", static_cast<long long>(n_rows), S);
   *bytes = bwd_layout(nullptr, n_rows, S).bytes;
   return LCR_OK;
 }
@@ -424,10 +424,7 @@ extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, cons
                                     const void* saved, size_t saved_bytes, float* d_feats, const LcrNetvladGrads* grads, void* ws, size_t ws_bytes,
                                     void* stream) {
   const char* who = "lcr_netvlad_backward";
-  if (!d_out || !feats || !wt || !saved || !grads || !ws) {
-    set_error("%s: bad argument", who);
-    return LCR_EARG;
-  }
+  if (!d_out || !feats || !wt || !saved || !grads || !ws) return refuse(LCR_EARG, "%s: bad argument", who);
   std::vector<int64_t> off;
   int Lmax = 0;
   int rc = seg_offsets(who, seg_len_host, S, 2, S_MAX, &off, &Lmax);   // the training forward's domain
@@ -436,10 +433,8 @@ extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, cons
   const int64_t N = off[S];
   const Saved sv = saved_layout(const_cast<void*>(saved), N, S);
   const BwdWs L = bwd_layout(ws, N, S);
-  if (sv.bytes > saved_bytes || L.bytes > ws_bytes) {
-    set_error("%s: buffer too small (saved %zu < %zu or workspace %zu < %zu)", who, saved_bytes, sv.bytes, ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (sv.bytes > saved_bytes || L.bytes > ws_bytes)
+    return refuse(LCR_ESPACE, "%s: buffer too small (saved %zu < %zu or workspace %zu < %zu)", who, saved_bytes, sv.bytes, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   const LcrNetvladGrads& g = *grads;
   // the tail: last normalise, gate, context_gating.bn1, gating product, bn2
@@ -458,10 +453,8 @@ extern "C" int lcr_netvlad_backward(const float* d_out, const float* feats, cons
     const size_t lds = static_cast<size_t>(S) * D * sizeof(float);
     static DynLds opt_in_dh, opt_in_dv;
     const void* fn = g.hidden1_weights ? reinterpret_cast<const void*>(&k_hidden_sweep<true>) : reinterpret_cast<const void*>(&k_hidden_sweep<false>);
-    if ((g.hidden1_weights ? opt_in_dh : opt_in_dv).need(fn, lds) != hipSuccess) {
-      set_error("%s: cannot reserve %zu B of dynamic LDS for the sweep over hidden1_weights", who, lds);
-      return LCR_EHIP;
-    }
+    if ((g.hidden1_weights ? opt_in_dh : opt_in_dv).need(fn, lds) != hipSuccess)
+      return refuse(LCR_EHIP, "%s: cannot reserve %zu B of dynamic LDS for the sweep over hidden1_weights", who, lds);
     if (g.hidden1_weights)
       hipLaunchKernelGGL((k_hidden_sweep<true>), dim3(FK / SW_ROWS), dim3(SW_THREADS), lds, st, wt->hidden1_weights, sv.v, L.dh, S, L.dv, g.hidden1_weights);
     else

@@ -242,23 +242,15 @@ struct NcLayout {
 // the plan from the host offsets; LCR_EARG (with a message) outside the domain
 static int nc_plan(const char* entry, const int64_t* point_off, const int64_t* node_off, int P, int K, NcPlan* pl, int64_t* n_pts, int64_t* n_nodes,
                    int64_t* n_max, int* m_max_cloud, int* m_max_ref, int* n_max_src) {
-  if (!point_off || !node_off || P < 1 || P > NC_MAX_PAIRS || K < 1 || K > NC_MAX_K) {
-    set_error("%s: null offsets or outside the domain (1 <= P <= %d, 1 <= K <= %d): P=%d K=%d", entry, NC_MAX_PAIRS, NC_MAX_K, P, K);
-    return LCR_EARG;
-  }
+  if (!point_off || !node_off || P < 1 || P > NC_MAX_PAIRS || K < 1 || K > NC_MAX_K)
+    return refuse(LCR_EARG, "%s: null offsets or outside the domain (1 <= P <= %d, 1 <= K <= %d): P=%d K=%d", entry, NC_MAX_PAIRS, NC_MAX_K, P, K);
   *n_max = 0;
   *m_max_cloud = *m_max_ref = *n_max_src = 0;
   for (int c = 0; c <= 2 * P; ++c) {
-    if (c && (point_off[c] < point_off[c - 1] || node_off[c] < node_off[c - 1])) {
-      set_error("%s: offsets must not decrease", entry);
-      return LCR_EARG;
-    }
+    if (c && (point_off[c] < point_off[c - 1] || node_off[c] < node_off[c - 1])) return refuse(LCR_EARG, "%s: offsets must not decrease", entry);
     pl->po[c] = point_off[c] - point_off[0];
     const int64_t mo = node_off[c] - node_off[0];
-    if (pl->po[c] > INT32_MAX || mo > INT32_MAX) {
-      set_error("%s: more than 2^31-1 points or nodes", entry);
-      return LCR_EARG;
-    }
+    if (pl->po[c] > INT32_MAX || mo > INT32_MAX) return refuse(LCR_EARG, "%s: more than 2^31-1 points or nodes", entry);
     pl->mo[c] = static_cast<int32_t>(mo);
     if (c) {
       *n_max = std::max(*n_max, pl->po[c] - pl->po[c - 1]);
@@ -274,10 +266,7 @@ static int nc_plan(const char* entry, const int64_t* point_off, const int64_t* n
     const int64_t M = pl->mo[2 * p + 1] - pl->mo[2 * p], N = pl->mo[2 * p + 2] - pl->mo[2 * p + 1];
     pl->to[p + 1] = pl->to[p] + M * N;
     pl->ro[p + 1] = pl->ro[p] + static_cast<int32_t>(M);
-    if (pl->to[p + 1] > INT32_MAX) {
-      set_error("%s: more than 2^31-1 node pairs", entry);
-      return LCR_EARG;
-    }
+    if (pl->to[p + 1] > INT32_MAX) return refuse(LCR_EARG, "%s: more than 2^31-1 node pairs", entry);
   }
   *n_pts = pl->po[2 * P];
   *n_nodes = pl->mo[2 * P];
@@ -302,10 +291,7 @@ extern "C" int lcr_node_correspondences_ws_bytes(const int64_t* point_off, const
   NcPlan pl;
   int64_t n_pts, n_nodes, n_max;
   int mc, mr, nsrc;
-  if (!bytes) {
-    set_error("lcr_node_correspondences_ws_bytes: null pointer");
-    return LCR_EARG;
-  }
+  if (!bytes) return refuse(LCR_EARG, "lcr_node_correspondences_ws_bytes: null pointer");
   const int rc = nc_plan("lcr_node_correspondences_ws_bytes", point_off, node_off, P, K, &pl, &n_pts, &n_nodes, &n_max, &mc, &mr, &nsrc);
   if (rc != LCR_OK) return rc;
   *bytes = nc_layout(nullptr, pl, n_pts, n_nodes).bytes;
@@ -324,15 +310,10 @@ extern "C" int lcr_node_correspondences(const float* points, const int64_t* poin
   if (rc != LCR_OK) return rc;
   const float r2 = static_cast<float>(pos_radius * pos_radius);
   if (!transforms || !start || !status || !ws || cap < 0 || (cap > 0 && (!corr || !overlap)) || (n_pts > 0 && !points) ||
-      (n_nodes > 0 && (!knn || !knn_mask || !node_mask)) || !(pos_radius >= 0) || !(r2 < INFINITY)) {
-    set_error("lcr_node_correspondences: null pointer, negative cap, or pos_radius negative / not finite when squared");
-    return LCR_EARG;
-  }
+      (n_nodes > 0 && (!knn || !knn_mask || !node_mask)) || !(pos_radius >= 0) || !(r2 < INFINITY))
+    return refuse(LCR_EARG, "lcr_node_correspondences: null pointer, negative cap, or pos_radius negative / not finite when squared");
   const NcLayout L = nc_layout(ws, pl, n_pts, n_nodes);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_node_correspondences: workspace of %zu bytes, %zu needed", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_node_correspondences", ws_bytes, L.bytes);
   // the box screen's radius: the smallest float at or above pos_radius whose rounded square reaches r2
   float rbox = static_cast<float>(pos_radius);
   while (rbox * rbox < r2) rbox = nextafterf(rbox, INFINITY);
@@ -348,7 +329,7 @@ extern "C" int lcr_node_correspondences(const float* points, const int64_t* poin
                        L.table);
   }
   hipLaunchKernelGGL(k_nc_rowcount, dim3(div_up(R + 1, 4)), dim3(256), 0, st, L.table, pl, R, L.count);
-  const int src = exclusive_scan_i32(L.count, L.scan, R + 1, nullptr, L.scan_ws, st);
+  const int src = exclusive_scan_i32("lcr_node_correspondences", L.count, L.scan, R + 1, nullptr, L.scan_ws, st);
   if (src != LCR_OK) return src;
   if (R > 0) hipLaunchKernelGGL(k_nc_write, dim3(div_up(R, 4)), dim3(256), 0, st, L.table, pl, R, L.scan, cap, corr, overlap);
   hipLaunchKernelGGL(k_nc_start, dim3(1), dim3(64), 0, st, pl, R, L.scan, cap, start, status);

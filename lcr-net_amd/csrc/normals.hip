@@ -264,37 +264,28 @@ size_t normals_layout(void* ws, int B, int64_t n, size_t grid_bytes, double** co
 }  // namespace
 
 extern "C" int lcr_normals_ws_bytes(int B, int64_t n, size_t* bytes) {
-  if (!bytes || B < 1 || B > GRID_MAX_B || n < 0 || n > INT32_MAX) {
-    set_error("lcr_normals_ws_bytes: outside the domain (1 <= B <= %d, 0 <= n <= 2^31-1): B=%d n=%lld", GRID_MAX_B, B, static_cast<long long>(n));
-    return LCR_EARG;
-  }
+  if (!bytes || B < 1 || B > GRID_MAX_B || n < 0 || n > INT32_MAX)
+    return refuse(LCR_EARG, "lcr_normals_ws_bytes: outside the domain (1 <= B <= %d, 0 <= n <= 2^31-1): B=%d n=%lld", GRID_MAX_B, B, static_cast<long long>(n));
   size_t g = 0;
-  if (lcr_support_grid_ws_bytes(n, B, &g) != LCR_OK) return LCR_EARG;
+  if (int rc = support_grid_ws_bytes("lcr_normals_ws_bytes", n, B, &g)) return rc;
   *bytes = normals_layout(nullptr, B, n, g, nullptr, nullptr, nullptr);
   return LCR_OK;
 }
 
 extern "C" int lcr_estimate_normals(const float* points, const int64_t* lengths, int B, float radius, int max_nn, const float* viewpoint,
                                     float* normals, float* curvature, int32_t* count, void* ws, size_t ws_bytes, void* stream) {
-  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 1 || max_nn > NRM_MAX_NN) {
-    set_error("lcr_estimate_normals: outside the domain (radius > 0 with radius*radius finite, 1 <= max_nn <= %d): radius=%g max_nn=%d",
-              NRM_MAX_NN, static_cast<double>(radius), max_nn);
-    return LCR_EARG;
-  }
+  if (!(radius > 0.f) || !std::isfinite(radius * radius) || max_nn < 1 || max_nn > NRM_MAX_NN)
+    return refuse(LCR_EARG, "lcr_estimate_normals: outside the domain (radius > 0 with radius*radius finite, 1 <= max_nn <= %d): radius=%g max_nn=%d",
+                  NRM_MAX_NN, static_cast<double>(radius), max_nn);
   Stack C;
-  if (stack_from_lengths("lcr_estimate_normals", lengths, B, &C)) return LCR_EARG;
+  if (int rc = stack_from_lengths("lcr_estimate_normals", lengths, B, &C)) return rc;
   const int64_t n = C.off[B];
-  if (!ws || (n > 0 && (!points || !normals))) {
-    set_error("lcr_estimate_normals: null workspace, or a null point / normal array (n=%lld)", static_cast<long long>(n));
-    return LCR_EARG;
-  }
+  if (!ws || (n > 0 && (!points || !normals)))
+    return refuse(LCR_EARG, "lcr_estimate_normals: null workspace, or a null point / normal array (n=%lld)", static_cast<long long>(n));
   size_t need = 0, grid_bytes = 0;
   lcr_normals_ws_bytes(B, n, &need);
-  lcr_support_grid_ws_bytes(n, B, &grid_bytes);
-  if (need > ws_bytes) {
-    set_error("lcr_estimate_normals: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  support_grid_ws_bytes("lcr_estimate_normals", n, B, &grid_bytes);
+  if (need > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_estimate_normals", ws_bytes, need);
   if (n == 0) return LCR_OK;
   double* cov;
   int32_t* cnt;
@@ -302,9 +293,9 @@ extern "C" int lcr_estimate_normals(const float* points, const int64_t* lengths,
   normals_layout(ws, B, n, grid_bytes, &cov, &cnt, &len_dev);
   const GridLayout L = grid_layout(ws, n, B);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = stack_to_device("lcr_estimate_normals (init)", C, len_dev, nullptr, nullptr, st);
+  int rc = stack_to_device("lcr_estimate_normals", C, len_dev, nullptr, nullptr, st);
   if (rc) return rc;
-  rc = lcr_support_grid_build(points, len_dev, B, n, radius, nullptr, ws, grid_bytes, stream);
+  rc = support_grid_build("lcr_estimate_normals", points, len_dev, B, n, radius, nullptr, ws, grid_bytes, nullptr, stream);
   if (rc) return rc;
   const float r2 = radius * radius;                              // fp32 product, as lcr_radius_query
   hipLaunchKernelGGL(k_normals_cov, dim3(div_up(n, NRM_WAVES)), dim3(NRM_WAVES * 64), 0, st, C, points, L.hdr, L.cell_start, L.sorted, r2, max_nn,

@@ -244,17 +244,13 @@ extern "C" int lcr_patch_scores(const float* feats_a, int64_t Na, const float* f
                                 const uint8_t* mask_a, const uint8_t* mask_b, int64_t P, int K, float scale, const float* alpha, float inf_val,
                                 float* S, void* stream) {
   if (!feats_a || !feats_b || !idx_a || !idx_b || !mask_a || !mask_b || !alpha || !S || P < 0 || Na < 0 || Nb < 0 || K != PS_K || C < PS_BK ||
-      C % PS_BK != 0 || (reinterpret_cast<uintptr_t>(feats_a) | reinterpret_cast<uintptr_t>(feats_b)) % 16 != 0 || P > 2147483647) {
-    set_error("lcr_patch_scores: bad argument (patches of %d points, C a multiple of %d, 16-byte aligned features)", PS_K, PS_BK);
-    return LCR_EARG;
-  }
+      C % PS_BK != 0 || (reinterpret_cast<uintptr_t>(feats_a) | reinterpret_cast<uintptr_t>(feats_b)) % 16 != 0 || P > 2147483647)
+    return refuse(LCR_EARG, "lcr_patch_scores: bad argument (patches of %d points, C a multiple of %d, 16-byte aligned features)", PS_K, PS_BK);
   if (P == 0) return LCR_OK;
   constexpr size_t lds = sizeof(float) * 4 * PS_BK * PS_LD;
   static DynLds opt_in;
-  if (opt_in.need(reinterpret_cast<const void*>(&k_patch_scores), lds) != hipSuccess) {
-    set_error("lcr_patch_scores: cannot reserve %zu B of dynamic LDS", lds);
-    return LCR_EHIP;
-  }
+  if (opt_in.need(reinterpret_cast<const void*>(&k_patch_scores), lds) != hipSuccess)
+    return refuse(LCR_EHIP, "lcr_patch_scores: cannot reserve %zu B of dynamic LDS", lds);
   hipLaunchKernelGGL(k_patch_scores, dim3(static_cast<unsigned>(P)), dim3(PS_T), lds, static_cast<hipStream_t>(stream), feats_a, Na, feats_b, Nb, C, idx_a,
                      idx_b, mask_a, mask_b, scale, alpha, inf_val, S);
   return check_launch("lcr_patch_scores");
@@ -263,10 +259,8 @@ extern "C" int lcr_patch_scores(const float* feats_a, int64_t Na, const float* f
 static bool psg_domain(int64_t P, int K, int C) { return P >= 0 && K == PS_K && C >= PS_BK && C % PS_BK == 0 && P * PS_K < (int64_t(1) << 30); }
 
 extern "C" int lcr_patch_scores_grad_ws_bytes(int64_t P, int K, int C, size_t* bytes) {
-  if (!bytes || !psg_domain(P, K, C)) {
-    set_error("lcr_patch_scores_grad_ws_bytes: bad argument (patches of %d points, C a multiple of %d, P * K < 2^30)", PS_K, PS_BK);
-    return LCR_EARG;
-  }
+  if (!bytes || !psg_domain(P, K, C))
+    return refuse(LCR_EARG, "lcr_patch_scores_grad_ws_bytes: bad argument (patches of %d points, C a multiple of %d, P * K < 2^30)", PS_K, PS_BK);
   *bytes = sizeof(float) * 2 * static_cast<size_t>(P) * PS_K * C;
   return LCR_OK;
 }
@@ -277,17 +271,13 @@ extern "C" int lcr_patch_scores_grad(const float* dS, const float* feats_a, int6
                                      float* d_feats_a, float* d_feats_b, void* ws, size_t ws_bytes, void* stream) {
   const int64_t n_lim = (int64_t(1) << 31) - 1;
   if (!psg_domain(P, K, C) || Na < 0 || Nb < 0 || Na >= n_lim || Nb >= n_lim ||
-      (reinterpret_cast<uintptr_t>(d_feats_a) | reinterpret_cast<uintptr_t>(d_feats_b)) % 16 != 0) {
-    set_error("lcr_patch_scores_grad: bad argument (patches of %d points, C a multiple of %d, P * K < 2^30, 16-byte aligned gradients)", PS_K, PS_BK);
-    return LCR_EARG;
-  }
+      (reinterpret_cast<uintptr_t>(d_feats_a) | reinterpret_cast<uintptr_t>(d_feats_b)) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_patch_scores_grad: bad argument (patches of %d points, C a multiple of %d, P * K < 2^30, 16-byte aligned gradients)", PS_K, PS_BK);
   hipStream_t st = ST(stream);
   if (P == 0) {                                                        // no patch lists any row: zeros
     if ((d_feats_a && Na > 0 && hipMemsetAsync(d_feats_a, 0, sizeof(float) * Na * C, st) != hipSuccess) ||
-        (d_feats_b && Nb > 0 && hipMemsetAsync(d_feats_b, 0, sizeof(float) * Nb * C, st) != hipSuccess)) {
-      set_error("lcr_patch_scores_grad: cannot zero the gradients");
-      return LCR_EHIP;
-    }
+        (d_feats_b && Nb > 0 && hipMemsetAsync(d_feats_b, 0, sizeof(float) * Nb * C, st) != hipSuccess))
+      return refuse(LCR_EHIP, "lcr_patch_scores_grad: cannot zero the gradients");
     return LCR_OK;
   }
   const bool want_a = d_feats_a != nullptr, want_b = d_feats_b != nullptr;
@@ -295,21 +285,14 @@ extern "C" int lcr_patch_scores_grad(const float* dS, const float* feats_a, int6
   const size_t side_bytes = sizeof(float) * static_cast<size_t>(P) * PS_K * C;
   if (!dS || (Na > 0 && !feats_a) || (Nb > 0 && !feats_b) || !idx_a || !idx_b || !mask_a || !mask_b || !ws || (want_a && Na > 0 && (!row_start_a || !edges_a)) ||
       (want_b && Nb > 0 && (!row_start_b || !edges_b)) ||
-      (reinterpret_cast<uintptr_t>(feats_a) | reinterpret_cast<uintptr_t>(feats_b) | reinterpret_cast<uintptr_t>(ws)) % 16 != 0) {
-    set_error("lcr_patch_scores_grad: null pointer, or features / workspace not 16-byte aligned (each gradient needs the inverted list of its idx)");
-    return LCR_EARG;
-  }
-  if (ws_bytes < 2 * side_bytes) {
-    set_error("lcr_patch_scores_grad: workspace of %zu bytes, %zu needed", ws_bytes, 2 * side_bytes);
-    return LCR_EARG;
-  }
+      (reinterpret_cast<uintptr_t>(feats_a) | reinterpret_cast<uintptr_t>(feats_b) | reinterpret_cast<uintptr_t>(ws)) % 16 != 0)
+    return refuse(LCR_EARG, "lcr_patch_scores_grad: null pointer, or features / workspace not 16-byte aligned (each gradient needs the inverted list of its idx)");
+  if (ws_bytes < 2 * side_bytes) return refuse_ws(LCR_EARG, "lcr_patch_scores_grad", ws_bytes, 2 * side_bytes);
   constexpr size_t lds = sizeof(float) * PS_K * PSG_LD;
   static_assert(2 * PS_K * PS_BK <= PS_K * PSG_LD, "the row tiles live in the LDS of the G image");
   static DynLds opt_in;
-  if (opt_in.need(reinterpret_cast<const void*>(&k_patch_scores_grad), lds) != hipSuccess) {
-    set_error("lcr_patch_scores_grad: cannot reserve %zu B of dynamic LDS", lds);
-    return LCR_EHIP;
-  }
+  if (opt_in.need(reinterpret_cast<const void*>(&k_patch_scores_grad), lds) != hipSuccess)
+    return refuse(LCR_EHIP, "lcr_patch_scores_grad: cannot reserve %zu B of dynamic LDS", lds);
   float* prod = static_cast<float*>(ws);
   hipLaunchKernelGGL(k_patch_scores_grad, dim3(static_cast<unsigned>(P), want_a && want_b ? 2 : 1), dim3(PS_T), lds, st, dS, feats_a, Na, feats_b, Nb, C,
                      idx_a, idx_b, mask_a, mask_b, scale, P, want_a ? 0 : 1, prod);

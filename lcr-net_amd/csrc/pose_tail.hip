@@ -402,10 +402,7 @@ using namespace lcr;
 
 extern "C" int lcr_vote_shift_grad(const float* offsets, const float* d_out, int64_t N, float max_range, float* d_off, void* stream) {
   if (N == 0) return LCR_OK;
-  if (!offsets || !d_out || !d_off || N < 0) {
-    set_error("lcr_vote_shift_grad: bad argument (null pointer or N < 0)");
-    return LCR_EARG;
-  }
+  if (!offsets || !d_out || !d_off || N < 0) return refuse(LCR_EARG, "lcr_vote_shift_grad: bad argument (null pointer or N < 0)");
   hipLaunchKernelGGL(k_vote_shift_grad, dim3(blocks_for(N)), dim3(256), 0, ST(stream), offsets, d_out, N, max_range, d_off);
   return check_launch("lcr_vote_shift_grad");
 }
@@ -413,10 +410,8 @@ extern "C" int lcr_vote_shift_grad(const float* offsets, const float* d_out, int
 extern "C" int lcr_neighbor_mean_grad(const float* d_out, const void* idx, int idx_is_64, const int32_t* row_start, const uint32_t* edges, int64_t M,
                                       int H, int64_t pad, float* d_pts, void* stream) {
   if (M < 0 || pad < 0 || pad >= (int64_t(1) << 31) - 1 || H < 1 || H > 128 || M * H >= (int64_t(1) << 30) || (pad > 0 && (!row_start || !edges || !d_pts)) ||
-      (M > 0 && (!d_out || !idx))) {
-    set_error("lcr_neighbor_mean_grad: bad argument (H in [1,128], M * H < 2^30, pad < 2^31 - 1, no null pointer)");
-    return LCR_EARG;
-  }
+      (M > 0 && (!d_out || !idx)))
+    return refuse(LCR_EARG, "lcr_neighbor_mean_grad: bad argument (H in [1,128], M * H < 2^30, pad < 2^31 - 1, no null pointer)");
   if (pad == 0) return LCR_OK;                               // no points: nothing to write
   const int nb = blocks_for(pad, 4, 8192);                   // one wavefront per point
   if (idx_is_64) hipLaunchKernelGGL((k_neighbor_mean_grad<int64_t>), dim3(nb), dim3(256), 0, ST(stream), d_out, static_cast<const int64_t*>(idx), row_start, edges, M, H, pad, d_pts);
@@ -427,10 +422,8 @@ extern "C" int lcr_neighbor_mean_grad(const float* d_out, const void* idx, int i
 extern "C" int lcr_upsample_concat_grad(const float* d_out, const int32_t* row_start, const uint32_t* edges, int64_t N, int64_t Nx, int C1, int C2,
                                         float* d_x, float* d_skip, void* stream) {
   if (N < 0 || N >= (int64_t(1) << 30) || Nx < 0 || Nx >= (int64_t(1) << 31) - 1 || C1 < 1 || C2 < 1 || (N > 0 && !d_out) ||
-      (d_x && Nx > 0 && (!row_start || !edges))) {
-    set_error("lcr_upsample_concat_grad: bad argument (N < 2^30, C1, C2 >= 1; d_x needs the inverted list of column 0)");
-    return LCR_EARG;
-  }
+      (d_x && Nx > 0 && (!row_start || !edges)))
+    return refuse(LCR_EARG, "lcr_upsample_concat_grad: bad argument (N < 2^30, C1, C2 >= 1; d_x needs the inverted list of column 0)");
   hipStream_t st = ST(stream);
   const bool vec = C1 % 4 == 0 && C2 % 4 == 0 &&
                    ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_skip)) & 15) == 0;
@@ -449,20 +442,20 @@ extern "C" int lcr_upsample_concat_grad(const float* d_out, const int32_t* row_s
 
 extern "C" int lcr_vote_shift(const float* xyz, const float* offsets, int64_t N, float max_range, float* out, void* stream) {
   if (N == 0) return LCR_OK;                               // no points: nothing to read or write, null pointers allowed
-  if (!xyz || !offsets || !out || N < 0) return LCR_EARG;
+  if (!xyz || !offsets || !out || N < 0) return refuse(LCR_EARG, "lcr_vote_shift: null pointer or a negative count: N=%lld", static_cast<long long>(N));
   hipLaunchKernelGGL(k_vote_shift, dim3(blocks_for(N)), dim3(256), 0, ST(stream), xyz, offsets, N, max_range, out);
   return check_launch("lcr_vote_shift");
 }
 
 extern "C" int lcr_greedy_nms_ws_bytes(int64_t n_total, size_t* bytes) {
-  if (!bytes || n_total < 0) return LCR_EARG;
+  if (!bytes || n_total < 0) return refuse(LCR_EARG, "lcr_greedy_nms_ws_bytes: null pointer or a negative count: n_total=%lld", static_cast<long long>(n_total));
   *bytes = align_up(static_cast<size_t>(n_total) + 16) + sizeof(int32_t) * static_cast<size_t>(n_total + 1) * (NMS_NB + 1);
   return LCR_OK;
 }
 
 extern "C" int lcr_greedy_nms(const float* pts, const int64_t* len, int B, int64_t n_total, float radius, uint8_t* keep, int64_t* out_len,
                               void* ws, void* stream) {
-  if (!pts || !len || !keep || !out_len || !ws || B < 1) return LCR_EARG;
+  if (!pts || !len || !keep || !out_len || !ws || B < 1) return refuse(LCR_EARG, "lcr_greedy_nms: null pointer or B < 1: B=%d", B);
   int8_t* st = static_cast<int8_t*>(ws);
   int32_t* nbr = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + align_up(static_cast<size_t>(n_total) + 16));
   hipLaunchKernelGGL(k_greedy_nms, dim3(B), dim3(NMS_T), 0, ST(stream), pts, len, B, radius, keep, out_len, st, nbr);
@@ -471,7 +464,7 @@ extern "C" int lcr_greedy_nms(const float* pts, const int64_t* len, int B, int64
 
 extern "C" int lcr_neighbor_mean(const float* pts, const void* idx, int idx_is_64, int64_t M, int H, int64_t pad, float* out, void* stream) {
   if (M == 0) return LCR_OK;                               // no rows: nothing to read or write, null pointers allowed
-  if (!pts || !idx || !out || M < 0 || H < 1) return LCR_EARG;
+  if (!pts || !idx || !out || M < 0 || H < 1) return refuse(LCR_EARG, "lcr_neighbor_mean: null pointer, M < 0 or H < 1: M=%lld H=%d", static_cast<long long>(M), H);
   if (idx_is_64) hipLaunchKernelGGL((k_neighbor_mean<int64_t>), dim3(blocks_for(M)), dim3(256), 0, ST(stream), pts, static_cast<const int64_t*>(idx), M, H, pad, out);
   else hipLaunchKernelGGL((k_neighbor_mean<int32_t>), dim3(blocks_for(M)), dim3(256), 0, ST(stream), pts, static_cast<const int32_t*>(idx), M, H, pad, out);
   return check_launch("lcr_neighbor_mean");
@@ -498,24 +491,24 @@ static P2nLayout p2n_layout(void* ws, int64_t N, int M) {
 }
 
 extern "C" int lcr_point_to_node_ws_bytes(int64_t N, int M, size_t* bytes) {
-  if (!bytes || N < 0 || M < 1) return LCR_EARG;
+  if (!bytes || N < 0 || M < 1) return refuse(LCR_EARG, "lcr_point_to_node_ws_bytes: null pointer, N < 0 or M < 1: N=%lld M=%d", static_cast<long long>(N), M);
   *bytes = p2n_layout(nullptr, N, M).bytes;
   return LCR_OK;
 }
 
-// the launch sequence of both partition entries (arguments already validated; `entry` names the caller in a launch error)
+// the launch sequence of both partition entries (arguments already validated but the workspace size; `entry` names the caller in a refusal)
 static int p2n_run(const char* entry, const float* points, const float* nodes, const P2nStack& sk, int64_t n_max, int m_max, int K, int32_t* p2n_out,
                    int64_t* knn, uint8_t* knn_mask, uint8_t* node_mask, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
   const int C = sk.C;
   const int64_t N = sk.po[C];
   const int M = sk.mo[C];
   const P2nLayout L = p2n_layout(ws, N, M);
-  if (L.bytes > ws_bytes) return LCR_ESPACE;
+  if (L.bytes > ws_bytes) return refuse_ws(LCR_ESPACE, entry, ws_bytes, L.bytes);
   hipStream_t st = ST(stream);
   hipMemsetAsync(L.cnt, 0, static_cast<size_t>(reinterpret_cast<char*>(L.cursor + M + 2) - reinterpret_cast<char*>(L.cnt)), st);   // counts .. cursor: one fill
   const int bx = blocks_for(n_max, 256, 2048);
   hipLaunchKernelGGL(k_point_to_node_stack, dim3(bx, C), dim3(256), sizeof(float) * 4 * m_max, st, points, nodes, sk, L.p2n, L.cnt);
-  int rc = exclusive_scan_i32(L.cnt, L.start, M + 1, nullptr, L.scan_ws, st);
+  int rc = exclusive_scan_i32(entry, L.cnt, L.start, M + 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_p2n_scatter_stack, dim3(blocks_for(n_max), C), dim3(256), 0, st, L.p2n, sk, L.start, L.cursor, L.members);
   hipLaunchKernelGGL(k_node_topk_stack, dim3(M), dim3(256), 0, st, points, nodes, sk, L.start, L.members, K, knn, knn_mask, node_mask, status);
@@ -526,10 +519,8 @@ static int p2n_run(const char* entry, const float* points, const float* nodes, c
 // point_to_node_partition (pointcloud_partition.py:60-107), a stack of one cloud: knn i64[M,K] (pad = N), knn_mask u8[M,K], node_mask u8[M], p2n i32[N]
 extern "C" int lcr_point_to_node_partition(const float* points, int64_t N, const float* nodes, int M, int K, int32_t* p2n_out, int64_t* knn,
                                            uint8_t* knn_mask, uint8_t* node_mask, uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !nodes || !knn || !knn_mask || !node_mask || !status || !ws || N < 1 || M < 1 || K < 1 || M > 4000) {
-    set_error("lcr_point_to_node_partition: bad argument (1 <= M <= 4000)");
-    return LCR_EARG;
-  }
+  if (!points || !nodes || !knn || !knn_mask || !node_mask || !status || !ws || N < 1 || M < 1 || K < 1 || M > 4000)
+    return refuse(LCR_EARG, "lcr_point_to_node_partition: bad argument (1 <= M <= 4000)");
   const P2nStack sk = {{0, N}, {0, M}, 1};
   return p2n_run("lcr_point_to_node_partition", points, nodes, sk, N, M, K, p2n_out, knn, knn_mask, node_mask, status, ws, ws_bytes, stream);
 }
@@ -540,16 +531,15 @@ extern "C" int lcr_point_to_node_partition(const float* points, int64_t N, const
 extern "C" int lcr_point_to_node_partition_stack(const float* points, const int64_t* point_off, const float* nodes, const int64_t* node_off, int C,
                                                  int K, int32_t* p2n_out, int64_t* knn, uint8_t* knn_mask, uint8_t* node_mask, uint32_t* status,
                                                  void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !point_off || !nodes || !node_off || !knn || !knn_mask || !node_mask || !status || !ws || C < 1 || C > P2N_MAX_CLOUDS || K < 1) {
-    set_error("lcr_point_to_node_partition_stack: bad argument (1 <= clouds <= %d)", P2N_MAX_CLOUDS);
-    return LCR_EARG;
-  }
+  if (!points || !point_off || !nodes || !node_off || !knn || !knn_mask || !node_mask || !status || !ws || C < 1 || C > P2N_MAX_CLOUDS || K < 1)
+    return refuse(LCR_EARG, "lcr_point_to_node_partition_stack: bad argument (1 <= clouds <= %d)", P2N_MAX_CLOUDS);
   P2nStack sk;
   sk.C = C;
   int64_t n_max = 0;
   int m_max = 0;
   for (int c = 0; c <= C; ++c) {
-    if (c && (point_off[c] < point_off[c - 1] || node_off[c] < node_off[c - 1])) return LCR_EARG;
+    if (c && (point_off[c] < point_off[c - 1] || node_off[c] < node_off[c - 1]))
+      return refuse(LCR_EARG, "lcr_point_to_node_partition_stack: offsets must not decrease (cloud %d)", c - 1);
     sk.po[c] = point_off[c] - point_off[0];
     sk.mo[c] = static_cast<int32_t>(node_off[c] - node_off[0]);
     if (c) {
@@ -557,10 +547,7 @@ extern "C" int lcr_point_to_node_partition_stack(const float* points, const int6
       m_max = std::max(m_max, sk.mo[c] - sk.mo[c - 1]);
     }
   }
-  if (sk.po[C] < 1 || sk.mo[C] < 1 || m_max > 4000) {
-    set_error("lcr_point_to_node_partition_stack: empty stack or more than 4000 nodes in a cloud");
-    return LCR_EARG;
-  }
+  if (sk.po[C] < 1 || sk.mo[C] < 1 || m_max > 4000) return refuse(LCR_EARG, "lcr_point_to_node_partition_stack: empty stack or more than 4000 nodes in a cloud");
   return p2n_run("lcr_point_to_node_partition_stack", points + 3 * point_off[0], nodes + 3 * node_off[0], sk, n_max, m_max, K, p2n_out, knn, knn_mask,
                  node_mask, status, ws, ws_bytes, stream);
 }
@@ -568,7 +555,8 @@ extern "C" int lcr_point_to_node_partition_stack(const float* points, const int6
 extern "C" int lcr_upsample_concat(const float* x, int64_t Nx, int C1, const void* idx, int idx_is_64, int H, const float* skip, int C2, int64_t N,
                                    float* out, void* stream) {
   if (N == 0) return LCR_OK;
-  if (!x || !idx || !skip || !out || N < 0 || C1 < 1 || C2 < 1 || H < 1) return LCR_EARG;
+  if (!x || !idx || !skip || !out || N < 0 || C1 < 1 || C2 < 1 || H < 1)
+    return refuse(LCR_EARG, "lcr_upsample_concat: null pointer, N < 0, or C1, C2 or H below 1: N=%lld C1=%d C2=%d H=%d", static_cast<long long>(N), C1, C2, H);
   const bool vec = C1 % 4 == 0 && C2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
   if (vec) {
     const int nbr = blocks_for(N * 64, 256, 8192);         // one wavefront per row
@@ -584,7 +572,7 @@ extern "C" int lcr_upsample_concat(const float* x, int64_t Nx, int C1, const voi
 
 extern "C" int lcr_gather_rows(const float* src, int64_t pad, int C, const int64_t* idx, int64_t R, float* out, void* stream) {
   if (R == 0) return LCR_OK;                               // an empty selection: nothing to read, null pointers allowed
-  if (!src || !idx || !out || R < 0 || C < 1) return LCR_EARG;
+  if (!src || !idx || !out || R < 0 || C < 1) return refuse(LCR_EARG, "lcr_gather_rows: null pointer, R < 0 or C < 1: R=%lld C=%d", static_cast<long long>(R), C);
   if (C % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
     hipLaunchKernelGGL(k_gather_rows_vec, dim3(blocks_for(R * 64, 256, 8192)), dim3(256), 0, ST(stream), src, pad, C, idx, R, out);
     return check_launch("lcr_gather_rows");

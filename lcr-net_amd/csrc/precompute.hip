@@ -130,10 +130,8 @@ using namespace lcr;
 
 extern "C" int lcr_precompute_layout(int64_t n0, int B, int num_stages, const int* limits, int upsampling, int64_t n_raw,
                                      LcrPrecomputeLayout* L) {
-  if (!L || !limits || n0 < 0 || n_raw < 0 || B < 1 || B > 64 || num_stages < 1 || num_stages > LCR_MAX_STAGES) {
-    set_error("lcr_precompute_layout: bad argument (B <= 64, stages <= %d)", LCR_MAX_STAGES);
-    return LCR_EARG;
-  }
+  if (!L || !limits || n0 < 0 || n_raw < 0 || B < 1 || B > 64 || num_stages < 1 || num_stages > LCR_MAX_STAGES)
+    return refuse(LCR_EARG, "lcr_precompute_layout: bad argument (B <= 64, stages <= %d)", LCR_MAX_STAGES);
   std::memset(L, 0, sizeof(*L));
   L->num_stages = num_stages;
   L->B = B;
@@ -142,10 +140,7 @@ extern "C" int lcr_precompute_layout(int64_t n0, int B, int num_stages, const in
   const int64_t cap = n0 > 0 ? n0 : 1;
   Carver c(nullptr, ~size_t(0));
   for (int i = 0; i < num_stages; ++i) {
-    if (limits[i] < 1) {
-      set_error("lcr_precompute_layout: neighbor limits must be >= 1");
-      return LCR_EARG;
-    }
+    if (limits[i] < 1) return refuse(LCR_EARG, "lcr_precompute_layout: neighbor limits must be >= 1");
     L->limits[i] = limits[i];
     L->cap[i] = cap;
   }
@@ -176,25 +171,8 @@ extern "C" int lcr_precompute_layout(int64_t n0, int B, int num_stages, const in
   return LCR_OK;
 }
 
-extern "C" int lcr_precompute_batch(const float* points0, const int64_t* lengths0, const LcrPrecomputeLayout* L, float voxel_size,
-                                    float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws, size_t ws_bytes,
-                                    int64_t* lengths_host, uint32_t* status_host, void* stream) {
-  return lcr_precompute_batch_rows(points0, 3, lengths0, L, voxel_size, radius, raw_voxel, key_bits_hint, out, out_bytes, ws, ws_bytes, lengths_host,
-                                   status_host, stream);
-}
-
-extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
-                                         float voxel_size, float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws,
-                                         size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
-  return lcr_precompute_batch_rows_ex(points0, raw_row_floats, lengths0, L, voxel_size, radius, static_cast<double>(raw_voxel), 0, key_bits_hint, out,
-                                      out_bytes, ws, ws_bytes, lengths_host, status_host, stream);
-}
-
 extern "C" int lcr_precompute_ws_bytes_ex(const LcrPrecomputeLayout* L, int raw_method, size_t* bytes) {
-  if (!L || !bytes || raw_method < 0 || raw_method > 1) {
-    set_error("lcr_precompute_ws_bytes_ex: bad argument");
-    return LCR_EARG;
-  }
+  if (!L || !bytes || raw_method < 0 || raw_method > 1) return refuse(LCR_EARG, "lcr_precompute_ws_bytes_ex: bad argument");
   PreWs W;
   int rc = carve_ws(nullptr, *L, &W, raw_method);
   if (rc) return rc;
@@ -202,30 +180,24 @@ extern "C" int lcr_precompute_ws_bytes_ex(const LcrPrecomputeLayout* L, int raw_
   return LCR_OK;
 }
 
-extern "C" int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
-                                            float voxel_size, float radius, double raw_voxel, int raw_method, int key_bits_hint, void* out,
-                                            size_t out_bytes, void* ws, size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
-  if (raw_method < 0 || raw_method > 1) {
-    set_error("lcr_precompute_batch: raw_method %d (0 = grid subsampling, 1 = Open3D VoxelDownSample)", raw_method);
-    return LCR_EARG;
-  }
-  if (L && raw_row_floats != 3 && !(L->n_raw > 0)) {
-    set_error("lcr_precompute_batch: rows of %d floats need raw mode (stage-0 points are then produced as [n,3] inside the call)", raw_row_floats);
-    return LCR_EARG;
-  }
-  if (!points0 || !lengths0 || !L || !out || !ws || !lengths_host || !status_host || !(voxel_size > 0.f) || !(radius > 0.f)) {
-    set_error("lcr_precompute_batch: bad argument");
-    return LCR_EARG;
-  }
+// the body of lcr_precompute_batch{,_rows,_rows_ex}; `who` = the one that was called
+static int precompute_batch(const char* who, const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
+                            float voxel_size, float radius, double raw_voxel, int raw_method, int key_bits_hint, void* out, size_t out_bytes,
+                            void* ws, size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  if (raw_method < 0 || raw_method > 1) return refuse(LCR_EARG, "%s: raw_method %d (0 = grid subsampling, 1 = Open3D VoxelDownSample)", who, raw_method);
+  if (L && raw_row_floats != 3 && !(L->n_raw > 0))
+    return refuse(LCR_EARG, "%s: rows of %d floats need raw mode (stage-0 points are then produced as [n,3] inside the call)", who, raw_row_floats);
+  if (!points0 || !lengths0 || !L || !out || !ws || !lengths_host || !status_host || !(voxel_size > 0.f) || !(radius > 0.f))
+    return refuse(LCR_EARG, "%s: bad argument", who);
+  if (raw_row_floats < 3 || raw_row_floats > 64)     // the voxelisation's own domain, refused here in the caller's name
+    return refuse(LCR_EARG, "%s: rows of %d floats (3 .. 64: x, y, z first)", who, raw_row_floats);
   size_t ws_need = L->ws_bytes;
   if (raw_method != 0 && L->n_raw > 0) {
     int rc = lcr_precompute_ws_bytes_ex(L, raw_method, &ws_need);
     if (rc) return rc;
   }
-  if (out_bytes < L->out_bytes || ws_bytes < ws_need) {
-    set_error("lcr_precompute_batch: arena too small (out %zu < %zu or ws %zu < %zu)", out_bytes, L->out_bytes, ws_bytes, ws_need);
-    return LCR_ESPACE;
-  }
+  if (out_bytes < L->out_bytes || ws_bytes < ws_need)
+    return refuse(LCR_ESPACE, "%s: arena too small (out %zu < %zu or ws %zu < %zu)", who, out_bytes, L->out_bytes, ws_bytes, ws_need);
   const int S = L->num_stages, B = L->B;
   // LCR_PRE_HOST_STATS=1: where this call's host time goes (issuing the launches vs waiting for the stream), printed at exit
   struct HostStats {
@@ -248,10 +220,7 @@ extern "C" int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_fl
   const float* pts[LCR_MAX_STAGES];
   const int64_t* lens[LCR_MAX_STAGES];
   const bool raw = L->n_raw > 0;
-  if (raw && !(raw_voxel > 0.0)) {
-    set_error("lcr_precompute_batch: raw mode needs raw_voxel > 0");
-    return LCR_EARG;
-  }
+  if (raw && !(raw_voxel > 0.0)) return refuse(LCR_EARG, "%s: raw mode needs raw_voxel > 0", who);
   pts[0] = points0;
   lens[0] = lengths0;
   for (int i = raw ? 0 : 1; i < S; ++i) {
@@ -345,11 +314,29 @@ extern "C" int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_fl
     hs.wait_s += std::chrono::duration<double>(t_done - t_issued).count();
     ++hs.calls;
   }
-  if (e != hipSuccess) {
-    set_error("lcr_precompute_batch: %s", hipGetErrorString(e));
-    return LCR_EHIP;
-  }
+  if (e != hipSuccess) return refuse(LCR_EHIP, "%s: %s", who, hipGetErrorString(e));
   for (int i = 0; i < S; ++i) std::memcpy(lengths_host + static_cast<size_t>(i) * B, C.pinned + i * 64, sizeof(int64_t) * B);
   *status_host = static_cast<uint32_t>(C.pinned[LCR_MAX_STAGES * 64]);
-  return check_launch("lcr_precompute_batch");
+  return check_launch(who);
+}
+
+extern "C" int lcr_precompute_batch(const float* points0, const int64_t* lengths0, const LcrPrecomputeLayout* L, float voxel_size,
+                                    float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws, size_t ws_bytes,
+                                    int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  return precompute_batch("lcr_precompute_batch", points0, 3, lengths0, L, voxel_size, radius, static_cast<double>(raw_voxel), 0, key_bits_hint, out,
+                          out_bytes, ws, ws_bytes, lengths_host, status_host, stream);
+}
+
+extern "C" int lcr_precompute_batch_rows(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
+                                         float voxel_size, float radius, float raw_voxel, int key_bits_hint, void* out, size_t out_bytes, void* ws,
+                                         size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  return precompute_batch("lcr_precompute_batch_rows", points0, raw_row_floats, lengths0, L, voxel_size, radius, static_cast<double>(raw_voxel), 0,
+                          key_bits_hint, out, out_bytes, ws, ws_bytes, lengths_host, status_host, stream);
+}
+
+extern "C" int lcr_precompute_batch_rows_ex(const float* points0, int raw_row_floats, const int64_t* lengths0, const LcrPrecomputeLayout* L,
+                                            float voxel_size, float radius, double raw_voxel, int raw_method, int key_bits_hint, void* out,
+                                            size_t out_bytes, void* ws, size_t ws_bytes, int64_t* lengths_host, uint32_t* status_host, void* stream) {
+  return precompute_batch("lcr_precompute_batch_rows_ex", points0, raw_row_floats, lengths0, L, voxel_size, radius, raw_voxel, raw_method, key_bits_hint,
+                          out, out_bytes, ws, ws_bytes, lengths_host, status_host, stream);
 }

@@ -524,36 +524,21 @@ __global__ __launch_bounds__(RS_WAVES * 64) void k_radius_query_multi(RqMulti m)
   for (int i = 0; i < m.n; ++i) rq_search<false, true>(m.s[i], m.B, s_qoff[i], s_keys[w], s_perm[w], s_cnt[w], s_fill[w], s_base[w]);
 }
 
-}  // namespace lcr
-
-using namespace lcr;
-
-extern "C" int lcr_support_grid_ws_bytes(int64_t ns_cap, int B, size_t* bytes) {
-  if (!bytes || ns_cap < 0 || B < 1 || B > GRID_MAX_B) return LCR_EARG;
+// what grid.h declares: the bodies of the lcr_support_grid_* entry points, in the name of the entry point `who` that was called
+int support_grid_ws_bytes(const char* who, int64_t ns_cap, int B, size_t* bytes) {
+  if (!bytes || ns_cap < 0 || B < 1 || B > GRID_MAX_B)
+    return refuse(LCR_EARG, "%s: null pointer or outside the domain (ns_cap >= 0, 1 <= B <= %d): ns_cap=%lld B=%d", who, GRID_MAX_B,
+                  static_cast<long long>(ns_cap), B);
   *bytes = grid_layout(nullptr, ns_cap, B).bytes;
   return LCR_OK;
 }
 
-extern "C" int lcr_support_grid_build(const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status,
-                                      void* grid_ws, size_t grid_ws_bytes, void* stream) {
-  return lcr_support_grid_build_ex(s, slen, B, ns_cap, radius, status, grid_ws, grid_ws_bytes, nullptr, stream);
-}
-
-extern "C" int lcr_support_grid_build_ex(const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status,
-                                         void* grid_ws, size_t grid_ws_bytes, int32_t* order, void* stream) {
-  if (!slen || !grid_ws || B < 1 || B > GRID_MAX_B || ns_cap < 0 || !(radius > 0.f)) {
-    set_error("lcr_support_grid_build: bad argument");
-    return LCR_EARG;
-  }
-  if (ns_cap > (int64_t(1) << 31) - 1) {
-    set_error("lcr_support_grid_build: more than 2^31-1 support points");
-    return LCR_EARG;
-  }
+int support_grid_build(const char* who, const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status, void* grid_ws,
+                       size_t grid_ws_bytes, int32_t* order, void* stream) {
+  if (!slen || !grid_ws || B < 1 || B > GRID_MAX_B || ns_cap < 0 || !(radius > 0.f)) return refuse(LCR_EARG, "%s: bad argument", who);
+  if (ns_cap > (int64_t(1) << 31) - 1) return refuse(LCR_EARG, "%s: more than 2^31-1 support points", who);
   GridLayout L = grid_layout(grid_ws, ns_cap, B);
-  if (L.bytes > grid_ws_bytes) {
-    set_error("lcr_support_grid_build: workspace too small (%zu < %zu)", grid_ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > grid_ws_bytes) return refuse(LCR_ESPACE, "%s: workspace too small (%zu < %zu)", who, grid_ws_bytes, L.bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t cell_cap = CELL_PER_PT * ns_cap + static_cast<int64_t>(CELL_MIN) * B;
   hipLaunchKernelGGL(k_grid_init, dim3(1), dim3(64), 0, st, L.hdr, slen, B, ns_cap, cell_cap, status);
@@ -564,15 +549,10 @@ extern "C" int lcr_support_grid_build_ex(const float* s, const int64_t* slen, in
   // coarse stages fill a small part of it
   hipLaunchKernelGGL(k_grid_zero, dim3(min(div_up(cell_cap + 1, 1024), 2048)), dim3(256), 0, st, L.hdr, L.cell_cnt);
   hipLaunchKernelGGL(k_grid_count, dim3(nblk), dim3(256), 0, st, L.hdr, s, L.cell_cnt, L.pt_cell);
-  int rc = exclusive_scan_i32_dev(L.cell_cnt, L.cell_start, cell_cap + 1, &L.hdr->n_cells, 1, nullptr, L.scan_ws, st);
+  int rc = exclusive_scan_i32_dev(who, L.cell_cnt, L.cell_start, cell_cap + 1, &L.hdr->n_cells, 1, nullptr, L.scan_ws, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_grid_scatter, dim3(nblk), dim3(256), 0, st, L.hdr, s, L.cell_cnt, L.cell_start, L.pt_cell, L.sorted, order);
-  return check_launch("lcr_support_grid_build");
-}
-
-extern "C" int lcr_radius_query(const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap,
-                                float radius, int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt, void* stream) {
-  return lcr_radius_query_ordered(q, qlen, B, nq_cap, grid_ws, ns_cap, radius, limit, out_idx64, out_idx32, out_cnt, nullptr, stream);
+  return check_launch(who);
 }
 
 // residency of the query kernels (workgroups per CU the grids are sized for) and the CU count, once per process
@@ -608,25 +588,12 @@ static int rq_qb(int64_t nq_cap) {
   return qb_env ? qb_env : (nq_cap >= 65536 ? 4 : (nq_cap >= 16384 ? 2 : 1));
 }
 
-extern "C" int lcr_radius_query_ordered(const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap,
-                                        float radius, int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt,
-                                        const int32_t* q_order, void* stream) {
-  if (!qlen || !grid_ws || B < 1 || B > GRID_MAX_B || nq_cap < 0 || ns_cap < 0 || limit < 0 || !(radius > 0.f)) {
-    set_error("lcr_radius_query: bad argument");
-    return LCR_EARG;
-  }
-  if (limit == 0 && !out_cnt) {
-    set_error("lcr_radius_query: limit == 0 needs out_cnt");
-    return LCR_EARG;
-  }
-  if (limit > 0 && !out_idx64 && !out_idx32) {
-    set_error("lcr_radius_query: limit > 0 needs an index output");
-    return LCR_EARG;
-  }
-  if (nq_cap > (int64_t(1) << 31) - 1) {
-    set_error("lcr_radius_query: more than 2^31-1 query points");
-    return LCR_EARG;
-  }
+int radius_query(const char* who, const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap, float radius,
+                 int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt, const int32_t* q_order, void* stream) {
+  if (!qlen || !grid_ws || B < 1 || B > GRID_MAX_B || nq_cap < 0 || ns_cap < 0 || limit < 0 || !(radius > 0.f)) return refuse(LCR_EARG, "%s: bad argument", who);
+  if (limit == 0 && !out_cnt) return refuse(LCR_EARG, "%s: limit == 0 needs out_cnt", who);
+  if (limit > 0 && !out_idx64 && !out_idx32) return refuse(LCR_EARG, "%s: limit > 0 needs an index output", who);
+  if (nq_cap > (int64_t(1) << 31) - 1) return refuse(LCR_EARG, "%s: more than 2^31-1 query points", who);
   if (nq_cap == 0) return LCR_OK;
   static const bool no_order = getenv("LCR_RS_NO_ORDER") != nullptr;      // A/B switch
   if (no_order) q_order = nullptr;
@@ -643,14 +610,39 @@ extern "C" int lcr_radius_query_ordered(const float* q, const int64_t* qlen, int
   if (out_idx64 && out_idx32) LCR_LAUNCH_TIMED((k_radius_query<true, true>), grid, block, 0, st, A, B);
   else if (out_idx64) LCR_LAUNCH_TIMED((k_radius_query<true, false>), grid, block, 0, st, A, B);
   else LCR_LAUNCH_TIMED((k_radius_query<false, true>), grid, block, 0, st, A, B);
-  return check_launch("lcr_radius_query");
+  return check_launch(who);
+}
+
+}  // namespace lcr
+
+using namespace lcr;
+
+extern "C" int lcr_support_grid_ws_bytes(int64_t ns_cap, int B, size_t* bytes) { return support_grid_ws_bytes("lcr_support_grid_ws_bytes", ns_cap, B, bytes); }
+
+extern "C" int lcr_support_grid_build(const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status,
+                                      void* grid_ws, size_t grid_ws_bytes, void* stream) {
+  return support_grid_build("lcr_support_grid_build", s, slen, B, ns_cap, radius, status, grid_ws, grid_ws_bytes, nullptr, stream);
+}
+
+extern "C" int lcr_support_grid_build_ex(const float* s, const int64_t* slen, int B, int64_t ns_cap, float radius, uint32_t* status,
+                                         void* grid_ws, size_t grid_ws_bytes, int32_t* order, void* stream) {
+  return support_grid_build("lcr_support_grid_build_ex", s, slen, B, ns_cap, radius, status, grid_ws, grid_ws_bytes, order, stream);
+}
+
+extern "C" int lcr_radius_query(const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap,
+                                float radius, int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt, void* stream) {
+  return radius_query("lcr_radius_query", q, qlen, B, nq_cap, grid_ws, ns_cap, radius, limit, out_idx64, out_idx32, out_cnt, nullptr, stream);
+}
+
+extern "C" int lcr_radius_query_ordered(const float* q, const int64_t* qlen, int B, int64_t nq_cap, const void* grid_ws, int64_t ns_cap,
+                                        float radius, int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt,
+                                        const int32_t* q_order, void* stream) {
+  return radius_query("lcr_radius_query_ordered", q, qlen, B, nq_cap, grid_ws, ns_cap, radius, limit, out_idx64, out_idx32, out_cnt, q_order, stream);
 }
 
 extern "C" int lcr_radius_query_multi(const LcrRadiusQuery* list, int n, int B, void* stream) {
-  if (!list || n < 1 || n > RQ_MAX_SEARCHES || B < 1 || B > GRID_MAX_B) {
-    set_error("lcr_radius_query_multi: bad argument (1 <= n <= %d searches)", RQ_MAX_SEARCHES);
-    return LCR_EARG;
-  }
+  if (!list || n < 1 || n > RQ_MAX_SEARCHES || B < 1 || B > GRID_MAX_B)
+    return refuse(LCR_EARG, "lcr_radius_query_multi: bad argument (1 <= n <= %d searches)", RQ_MAX_SEARCHES);
   static const bool no_order = getenv("LCR_RS_NO_ORDER") != nullptr;
   RqMulti m;
   m.n = 0, m.B = B;
@@ -658,10 +650,8 @@ extern "C" int lcr_radius_query_multi(const LcrRadiusQuery* list, int n, int B, 
   for (int i = 0; i < n; ++i) {
     const LcrRadiusQuery& e = list[i];
     if (!e.qlen || !e.grid_ws || !e.out_idx32 || e.nq_cap < 0 || e.ns_cap < 0 || e.limit < 1 || !(e.radius > 0.f) ||
-        e.nq_cap > (int64_t(1) << 31) - 1) {
-      set_error("lcr_radius_query_multi: bad search %d", i);
-      return LCR_EARG;
-    }
+        e.nq_cap > (int64_t(1) << 31) - 1)
+      return refuse(LCR_EARG, "lcr_radius_query_multi: bad search %d", i);
     if (e.nq_cap == 0) continue;
     GridLayout L = grid_layout(const_cast<void*>(e.grid_ws), e.ns_cap, B);
     RqSearch& A = m.s[m.n++];
@@ -690,7 +680,9 @@ __global__ __launch_bounds__(256) void k_grid_order(const GridHeader* __restrict
 }
 
 extern "C" int lcr_support_grid_order(const void* grid_ws, int64_t ns_cap, int B, int32_t* order, void* stream) {
-  if (!grid_ws || !order || ns_cap < 0 || B < 1 || B > GRID_MAX_B) return LCR_EARG;
+  if (!grid_ws || !order || ns_cap < 0 || B < 1 || B > GRID_MAX_B)
+    return refuse(LCR_EARG, "lcr_support_grid_order: null pointer or outside the domain (ns_cap >= 0, 1 <= B <= %d): ns_cap=%lld B=%d", GRID_MAX_B,
+                  static_cast<long long>(ns_cap), B);
   if (ns_cap == 0) return LCR_OK;
   GridLayout L = grid_layout(const_cast<void*>(grid_ws), ns_cap, B);
   hipLaunchKernelGGL(k_grid_order, dim3(min(div_up(ns_cap, 256), 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), L.hdr, L.sorted, order);
@@ -699,13 +691,13 @@ extern "C" int lcr_support_grid_order(const void* grid_ws, int64_t ns_cap, int B
 
 extern "C" int lcr_radius_search_ws_bytes(int64_t nq_cap, int64_t ns_cap, int B, size_t* bytes) {
   (void)nq_cap;
-  return lcr_support_grid_ws_bytes(ns_cap, B, bytes);
+  return support_grid_ws_bytes("lcr_radius_search_ws_bytes", ns_cap, B, bytes);
 }
 
 extern "C" int lcr_radius_search(const float* q, const float* s, const int64_t* qlen, const int64_t* slen, int B, int64_t nq_cap,
                                  int64_t ns_cap, float radius, int limit, int64_t* out_idx64, int32_t* out_idx32, int32_t* out_cnt,
                                  uint32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  int rc = lcr_support_grid_build(s, slen, B, ns_cap, radius, status, ws, ws_bytes, stream);
+  int rc = support_grid_build("lcr_radius_search", s, slen, B, ns_cap, radius, status, ws, ws_bytes, nullptr, stream);
   if (rc) return rc;
-  return lcr_radius_query(q, qlen, B, nq_cap, ws, ns_cap, radius, limit, out_idx64, out_idx32, out_cnt, stream);
+  return radius_query("lcr_radius_search", q, qlen, B, nq_cap, ws, ns_cap, radius, limit, out_idx64, out_idx32, out_cnt, nullptr, stream);
 }

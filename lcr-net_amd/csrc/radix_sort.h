@@ -27,7 +27,7 @@ struct RadixCtl {
 inline size_t radix_hist_elems(int64_t n_cap) { return static_cast<size_t>((n_cap + RX_TILE - 1) / RX_TILE) * RX_D + 1; }
 __host__ __device__ inline int radix_passes(int key_bits) { return (key_bits + RX_BITS - 1) / RX_BITS; }
 
-int radix_sort_pairs(const RadixCtl* ctl, uint64_t* keysA, uint64_t* keysB, uint32_t* valsA, uint32_t* valsB, int64_t n_cap,
+int radix_sort_pairs(const char* who, const RadixCtl* ctl, uint64_t* keysA, uint64_t* keysB, uint32_t* valsA, uint32_t* valsB, int64_t n_cap,
                      int max_passes, int32_t* hist /*radix_hist_elems*/, void* scan_ws, hipStream_t st);
 
 }  // namespace lcr

@@ -86,18 +86,18 @@ __global__ __launch_bounds__(RX_T) void k_rx_scatter(const RadixCtl* __restrict_
   }
 }
 
-int radix_sort_pairs(const RadixCtl* ctl, uint64_t* keysA, uint64_t* keysB, uint32_t* valsA, uint32_t* valsB, int64_t n_cap,
+int radix_sort_pairs(const char* who, const RadixCtl* ctl, uint64_t* keysA, uint64_t* keysB, uint32_t* valsA, uint32_t* valsB, int64_t n_cap,
                      int max_passes, int32_t* hist, void* scan_ws, hipStream_t st) {
   if (n_cap <= 0) return LCR_OK;
   const int ntiles = static_cast<int>((n_cap + RX_TILE - 1) / RX_TILE);
   for (int p = 0; p < max_passes; ++p) {
     hipLaunchKernelGGL(k_rx_hist, dim3(ntiles), dim3(RX_T), 0, st, ctl, keysA, keysB, p, hist, ntiles);
     // scanning stale histograms on skipped passes is harmless (the scatter exits first)
-    int rc = exclusive_scan_i32(hist, hist, static_cast<int64_t>(ntiles) * RX_D, nullptr, scan_ws, st);
+    int rc = exclusive_scan_i32(who, hist, hist, static_cast<int64_t>(ntiles) * RX_D, nullptr, scan_ws, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_rx_scatter, dim3(ntiles), dim3(RX_T), 0, st, ctl, keysA, keysB, valsA, valsB, p, hist, ntiles);
   }
-  return check_launch("radix_sort_pairs");
+  return check_launch(who);
 }
 
 }  // namespace lcr

@@ -340,20 +340,16 @@ __global__ __launch_bounds__(256) void k_ransac_select(const float* __restrict__
 using namespace lcr;
 
 static int ransac_domain(int S, int ransac_n, int iterations, const char* what) {
-  if (S < 1 || S > 65535 || ransac_n < 3 || ransac_n > RS_MAX_N || iterations < 1 || iterations > 1000000) {
-    set_error("%s: outside the domain (1 <= S <= 65535, 3 <= ransac_n <= 8, 1 <= iterations <= 1e6): S=%d ransac_n=%d iterations=%d", what, S,
-              ransac_n, iterations);
-    return LCR_EARG;
-  }
+  if (S < 1 || S > 65535 || ransac_n < 3 || ransac_n > RS_MAX_N || iterations < 1 || iterations > 1000000)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= S <= 65535, 3 <= ransac_n <= 8, 1 <= iterations <= 1e6): S=%d ransac_n=%d iterations=%d", what, S,
+                  ransac_n, iterations);
   return LCR_OK;
 }
 
 extern "C" int lcr_ransac_sample_host(uint64_t seed, int64_t h0, int64_t count, int ransac_n, int64_t n, int32_t* idx_host) {
-  if (!idx_host || h0 < 0 || count < 0 || h0 + count > 1000000 || ransac_n < 1 || ransac_n > RS_MAX_N || n < 1 || n > INT32_MAX) {
-    set_error("lcr_ransac_sample_host: bad argument (h0=%lld count=%lld ransac_n=%d n=%lld)", static_cast<long long>(h0),
-              static_cast<long long>(count), ransac_n, static_cast<long long>(n));
-    return LCR_EARG;
-  }
+  if (!idx_host || h0 < 0 || count < 0 || h0 + count > 1000000 || ransac_n < 1 || ransac_n > RS_MAX_N || n < 1 || n > INT32_MAX)
+    return refuse(LCR_EARG, "lcr_ransac_sample_host: bad argument (h0=%lld count=%lld ransac_n=%d n=%lld)", static_cast<long long>(h0),
+                  static_cast<long long>(count), ransac_n, static_cast<long long>(n));
   for (int64_t k = 0; k < count; ++k)
     for (int j = 0; j < ransac_n; ++j) idx_host[k * ransac_n + j] = static_cast<int32_t>(ransac_draw(seed, h0 + k, j, static_cast<uint32_t>(n)));
   return LCR_OK;
@@ -376,20 +372,17 @@ static size_t ransac_carve(Carver& c, int S, int iterations, bool checked, int64
 }
 
 extern "C" int lcr_ransac_ws_bytes(int S, int iterations, size_t* bytes) {
-  if (!bytes) return LCR_EARG;
-  if (ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ws_bytes") != LCR_OK) return LCR_EARG;
+  if (!bytes) return refuse(LCR_EARG, "lcr_ransac_ws_bytes: null pointer");
+  if (int rc = ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ws_bytes")) return rc;
   Carver c(nullptr, ~size_t(0));
   *bytes = ransac_carve(c, S, iterations, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   return LCR_OK;
 }
 
 extern "C" int lcr_ransac_ex_ws_bytes(int S, int iterations, int64_t n_corr, size_t* bytes) {
-  if (!bytes) return LCR_EARG;
-  if (ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ex_ws_bytes") != LCR_OK) return LCR_EARG;
-  if (n_corr < 0 || n_corr > INT32_MAX) {
-    set_error("lcr_ransac_ex_ws_bytes: n_corr outside 0..2^31-1 (%lld)", static_cast<long long>(n_corr));
-    return LCR_EARG;
-  }
+  if (!bytes) return refuse(LCR_EARG, "lcr_ransac_ex_ws_bytes: null pointer");
+  if (int rc = ransac_domain(S, RS_MAX_N, iterations, "lcr_ransac_ex_ws_bytes")) return rc;
+  if (n_corr < 0 || n_corr > INT32_MAX) return refuse(LCR_EARG, "lcr_ransac_ex_ws_bytes: n_corr outside 0..2^31-1 (%lld)", static_cast<long long>(n_corr));
   Carver c(nullptr, ~size_t(0));
   *bytes = ransac_carve(c, S, iterations, true, n_corr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   return LCR_OK;
@@ -399,30 +392,23 @@ static int ransac_run(const char* what, const float* src, const float* ref, cons
                       const int32_t* src_start, const int32_t* ref_start, int64_t n_corr, float thr, int ransac_n, int iterations, uint64_t seed,
                       float edge_similarity, float checker_distance, float* T, int32_t* inliers, float* rmse, int32_t* best_h, float* T_all,
                       int32_t* counts_all, float* sse_all, uint8_t* reject_all, void* ws, size_t ws_bytes, void* stream) {
-  if (ransac_domain(S, ransac_n, iterations, what) != LCR_OK) return LCR_EARG;
-  if (!src || !ref || !start || !T || !inliers || !rmse || !ws || !(thr > 0.f) || !std::isfinite(thr) || !std::isfinite(thr * thr)) {
-    set_error("%s: null pointer or distance threshold not finite and > 0 (thr=%g)", what, static_cast<double>(thr));
-    return LCR_EARG;
-  }
+  if (int rc = ransac_domain(S, ransac_n, iterations, what)) return rc;
+  if (!src || !ref || !start || !T || !inliers || !rmse || !ws || !(thr > 0.f) || !std::isfinite(thr) || !std::isfinite(thr * thr))
+    return refuse(LCR_EARG, "%s: null pointer or distance threshold not finite and > 0 (thr=%g)", what, static_cast<double>(thr));
   const float edge_k2 = edge_similarity > 0.f ? edge_similarity * edge_similarity : 0.f;
   const float check_d2 = checker_distance > 0.f ? checker_distance * checker_distance : 0.f;
   if (std::isnan(edge_similarity) || std::isnan(checker_distance) || !std::isfinite(edge_k2) || !std::isfinite(check_d2) ||
-      (corr && (!src_start || !ref_start || n_corr < 0 || n_corr > INT32_MAX))) {
-    set_error("%s: checker parameter not finite when squared (edge_similarity=%g checker_distance=%g), or the index form without "
-              "src_start / ref_start or with n_corr outside 0..2^31-1", what, static_cast<double>(edge_similarity),
-              static_cast<double>(checker_distance));
-    return LCR_EARG;
-  }
+      (corr && (!src_start || !ref_start || n_corr < 0 || n_corr > INT32_MAX)))
+    return refuse(LCR_EARG, "%s: checker parameter not finite when squared (edge_similarity=%g checker_distance=%g), or the index form without "
+                  "src_start / ref_start or with n_corr outside 0..2^31-1", what, static_cast<double>(edge_similarity),
+                  static_cast<double>(checker_distance));
   const bool checked = edge_k2 > 0.f || check_d2 > 0.f;
   const int64_t n_gather = corr ? n_corr : 0;
   float *hyp, *cs, *gs, *gr;
   int32_t *cc, *ch, *surv, *nsurv;
   Carver c(ws, ws_bytes);
   const size_t need = ransac_carve(c, S, iterations, checked, n_gather, &hyp, &cc, &cs, &ch, &surv, &nsurv, &gs, &gr);
-  if (need > ws_bytes) {
-    set_error("%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  if (need > ws_bytes) return refuse_ws(LCR_ESPACE, what, ws_bytes, need);
   const int tiles = div_up(iterations, RS_TILE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n_gather > 0) {

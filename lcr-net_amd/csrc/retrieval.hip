@@ -178,7 +178,8 @@ static RetrievalLayout retrieval_layout(void* ws, int64_t Q, int64_t C) {
 }
 
 extern "C" int lcr_retrieval_ws_bytes(int64_t Q, int64_t C, size_t* bytes) {
-  if (!bytes || Q < 0 || C < 0) return LCR_EARG;
+  if (!bytes || Q < 0 || C < 0)
+    return refuse(LCR_EARG, "lcr_retrieval_ws_bytes: null pointer or a negative count: Q=%lld C=%lld", static_cast<long long>(Q), static_cast<long long>(C));
   *bytes = retrieval_layout(nullptr, Q, C).bytes;
   return LCR_OK;
 }
@@ -186,19 +187,11 @@ extern "C" int lcr_retrieval_ws_bytes(int64_t Q, int64_t C, size_t* bytes) {
 // queries [Q, D] (global frames q0 .. q0+Q-1), database [C, D] (frames 0 .. C-1) -> out_idx i32[Q,k], out_d2 f32[Q,k]
 extern "C" int lcr_retrieval_topk(const float* queries, int64_t Q, int64_t q0, const float* database, int64_t C, int D, int k, int exclude,
                                   int32_t* out_idx, float* out_d2, void* ws, size_t ws_bytes, void* stream) {
-  if (!queries || !database || !out_idx || !out_d2 || !ws || Q < 0 || C < 1 || D < 1 || k < 1 || k > TK_KMAX || exclude < 0) {
-    set_error("lcr_retrieval_topk: bad argument (k <= %d)", TK_KMAX);
-    return LCR_EARG;
-  }
-  if (C > (int64_t(1) << 31) - 1) {
-    set_error("lcr_retrieval_topk: more than 2^31-1 database rows");
-    return LCR_EARG;
-  }
+  if (!queries || !database || !out_idx || !out_d2 || !ws || Q < 0 || C < 1 || D < 1 || k < 1 || k > TK_KMAX || exclude < 0)
+    return refuse(LCR_EARG, "lcr_retrieval_topk: bad argument (k <= %d)", TK_KMAX);
+  if (C > (int64_t(1) << 31) - 1) return refuse(LCR_EARG, "lcr_retrieval_topk: more than 2^31-1 database rows");
   const RetrievalLayout L = retrieval_layout(ws, Q, C);
-  if (L.bytes > ws_bytes) {
-    set_error("lcr_retrieval_topk: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
-    return LCR_ESPACE;
-  }
+  if (L.bytes > ws_bytes) return refuse(LCR_ESPACE, "lcr_retrieval_topk: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
   if (Q == 0) return LCR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_row_sqnorm, dim3(static_cast<int>(std::min<int64_t>((Q + 3) / 4, 4096))), dim3(256), 0, st, queries, Q, D, L.qn);

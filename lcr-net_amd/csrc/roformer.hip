@@ -48,7 +48,7 @@ static int rf_layer(const LcrRoformerLayerW& L, int d, int heads, const float* x
   float* y1 = a.take(static_cast<size_t>(nx) * d);
   float* e = a.take(static_cast<size_t>(nx) * 2 * d);
   float* sq = a.take(static_cast<size_t>(nx) * d);
-  if (!q || !k || !v || !h || !h2 || !y1 || !e || !sq) return LCR_ESPACE;
+  if (!q || !k || !v || !h || !h2 || !y1 || !e || !sq) return refuse(LCR_ESPACE, "lcr_roformer_forward: a layer ran out of workspace");
   int rc;
   if ((rc = rf_linear(L.q, x, nx, d, d, q, false, s))) return rc;
   if ((rc = rf_linear(L.k, mem, nm, d, d, k, false, s))) return rc;
@@ -72,7 +72,8 @@ static size_t rf_layer_floats(int64_t n, int d) { return static_cast<size_t>(n) 
 using namespace lcr;
 
 extern "C" int lcr_roformer_ws_bytes(const LcrRoformerW* W, int64_t n_rows, size_t* bytes) {
-  if (!W || !bytes || n_rows < 0 || W->d_model < 1) return LCR_EARG;
+  if (!W || !bytes || n_rows < 0 || W->d_model < 1)
+    return refuse(LCR_EARG, "lcr_roformer_ws_bytes: null pointer, n_rows < 0 or d_model < 1: n_rows=%lld", static_cast<long long>(n_rows));
   const size_t n = static_cast<size_t>(std::max<int64_t>(n_rows, 1));
   // embedding hidden [n, d] + ping + pong [n, d] + the layer scratch
   *bytes = align_up(sizeof(float) * n * W->d_model) * 3 + align_up(sizeof(float) * rf_layer_floats(n_rows, W->d_model)) + 4096;
@@ -82,17 +83,12 @@ extern "C" int lcr_roformer_ws_bytes(const LcrRoformerW* W, int64_t n_rows, size
 extern "C" int lcr_roformer_forward(const LcrRoformerW* W, const float* points, const float* feats, const int64_t* lens0_host, const int64_t* lens1_host,
                                     int P, float* out, float* theta_out, void* ws, size_t ws_bytes, void* stream) {
   if (!W || !points || !feats || !lens0_host || !lens1_host || !out || !theta_out || !ws || P < 1 || 2 * P > 64 || W->num_blocks < 0 ||
-      W->num_blocks > LCR_ROFORMER_MAX_BLOCKS || W->heads < 1 || W->d_model % W->heads != 0 || W->d_model / W->heads != 32) {
-    set_error("lcr_roformer_forward: bad argument (1 <= pairs <= 32, head dim 32, <= %d blocks)", LCR_ROFORMER_MAX_BLOCKS);
-    return LCR_EARG;
-  }
+      W->num_blocks > LCR_ROFORMER_MAX_BLOCKS || W->heads < 1 || W->d_model % W->heads != 0 || W->d_model / W->heads != 32)
+    return refuse(LCR_EARG, "lcr_roformer_forward: bad argument (1 <= pairs <= 32, head dim 32, <= %d blocks)", LCR_ROFORMER_MAX_BLOCKS);
   int64_t n0 = 0, n1 = 0;
   int64_t cat[64];
   for (int p = 0; p < P; ++p) {
-    if (lens0_host[p] < 1 || lens1_host[p] < 1) {
-      set_error("lcr_roformer_forward: pair %d has an empty cloud", p);
-      return LCR_EARG;
-    }
+    if (lens0_host[p] < 1 || lens1_host[p] < 1) return refuse(LCR_EARG, "lcr_roformer_forward: pair %d has an empty cloud", p);
     cat[p] = lens0_host[p];
     cat[P + p] = lens1_host[p];
     n0 += lens0_host[p];
@@ -101,17 +97,14 @@ extern "C" int lcr_roformer_forward(const LcrRoformerW* W, const float* points, 
   const int64_t n = n0 + n1;
   size_t need = 0;
   lcr_roformer_ws_bytes(W, n, &need);
-  if (ws_bytes < need) {
-    set_error("lcr_roformer_forward: workspace too small (%zu < %zu)", ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  if (ws_bytes < need) return refuse(LCR_ESPACE, "lcr_roformer_forward: workspace too small (%zu < %zu)", ws_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int d = W->d_model;
   RfArena top{static_cast<char*>(ws), 0, ws_bytes};
   float* emb_h = top.take(static_cast<size_t>(n) * d);
   float* ping = top.take(static_cast<size_t>(n) * d);
   float* pong = top.take(static_cast<size_t>(n) * d);
-  if (!emb_h || !ping || !pong) return LCR_ESPACE;
+  if (!emb_h || !ping || !pong) return refuse(LCR_ESPACE, "lcr_roformer_forward: ran out of workspace");
   int rc;
   // LinearLearnablePosEmbedding: two Linears, no activation (Rotary3DPosEmb.py:34-38) -> theta [n, d/2]; in_proj
   if ((rc = rf_linear(W->emb1, points, n, 3, d, emb_h, false, s))) return rc;

@@ -154,11 +154,9 @@ int so_params(const char* who, int H, int W, double fov_up, double fov_down, dou
   const double fu = fov_up * SO_PI / 180.0, fd = fov_down * SO_PI / 180.0;
   const double fov = std::fabs(fu) + std::fabs(fd);
   if (H < 1 || H > SO_MAX_H || W < 1 || W > SO_MAX_W || !(max_range > 0.0) || !(eps > 0.0) || !(fov > 0.0) ||
-      !std::isfinite(fov)) {
-    set_error("%s: outside the domain (1 <= H <= %d, 1 <= W <= %d, max_range > 0, eps > 0, |fov_up| + |fov_down| > 0 and finite): H=%d W=%d "
-              "fov_up=%g fov_down=%g max_range=%g eps=%g", who, SO_MAX_H, SO_MAX_W, H, W, fov_up, fov_down, max_range, eps);
-    return LCR_EARG;
-  }
+      !std::isfinite(fov))
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= H <= %d, 1 <= W <= %d, max_range > 0, eps > 0, |fov_up| + |fov_down| > 0 and finite): H=%d W=%d "
+                  "fov_up=%g fov_down=%g max_range=%g eps=%g", who, SO_MAX_H, SO_MAX_W, H, W, fov_up, fov_down, max_range, eps);
   pr->H = H;
   pr->W = W;
   pr->afd = std::fabs(fd);
@@ -178,10 +176,8 @@ int so_launch(const char* who, int64_t blocks, const float* points, const int64_
               int32_t* status, hipStream_t st) {
   const size_t lds = sizeof(uint32_t) * static_cast<size_t>(band_rows) * pr.W;
   static DynLds opt_in;                                          // > 64 KB of dynamic LDS needs an explicit opt-in
-  if (lds > 48 * 1024 && opt_in.need(reinterpret_cast<const void*>(&k_so_image<PAIR>), SO_LDS_BYTES) != hipSuccess) {
-    set_error("%s: cannot opt in to %zu bytes of LDS", who, SO_LDS_BYTES);
-    return LCR_EHIP;
-  }
+  if (lds > 48 * 1024 && opt_in.need(reinterpret_cast<const void*>(&k_so_image<PAIR>), SO_LDS_BYTES) != hipSuccess)
+    return refuse(LCR_EHIP, "%s: cannot opt in to %zu bytes of LDS", who, SO_LDS_BYTES);
   hipLaunchKernelGGL(k_so_image<PAIR>, dim3(static_cast<unsigned>(blocks)), dim3(SO_THREADS), lds, st, points, off, B, pr, band_rows, images_out,
                      valid_out, images, valid, pairs, rel, counts, status);
   return check_launch(who);
@@ -190,10 +186,7 @@ int so_launch(const char* who, int64_t blocks, const float* points, const int64_
 }  // namespace
 
 extern "C" int lcr_range_images_ws_bytes(int B, size_t* bytes) {
-  if (!bytes || B < 1 || B > GRID_MAX_B) {
-    set_error("lcr_range_images_ws_bytes: outside the domain (1 <= B <= %d, bytes non-null): B=%d", GRID_MAX_B, B);
-    return LCR_EARG;
-  }
+  if (!bytes || B < 1 || B > GRID_MAX_B) return refuse(LCR_EARG, "lcr_range_images_ws_bytes: outside the domain (1 <= B <= %d, bytes non-null): B=%d", GRID_MAX_B, B);
   *bytes = so_ws_bytes(B);
   return LCR_OK;
 }
@@ -204,36 +197,25 @@ extern "C" int lcr_range_images(const float* points, const int64_t* lengths, int
   int band_rows = 0;
   int rc = so_params("lcr_range_images", H, W, fov_up, fov_down, max_range, 1.0, &pr, &band_rows);
   if (rc) return rc;
-  if (!images || !valid || !ws) {
-    set_error("lcr_range_images: null pointer");
-    return LCR_EARG;
-  }
+  if (!images || !valid || !ws) return refuse(LCR_EARG, "lcr_range_images: null pointer");
   Stack C;
   rc = stack_from_lengths("lcr_range_images", lengths, B, &C);
   if (rc) return rc;
   const int64_t n = C.off[B];
-  if (n > 0 && !points) {
-    set_error("lcr_range_images: null point array (n=%lld)", static_cast<long long>(n));
-    return LCR_EARG;
-  }
-  if (so_ws_bytes(B) > ws_bytes) {
-    set_error("lcr_range_images: workspace of %zu bytes, %zu needed", ws_bytes, so_ws_bytes(B));
-    return LCR_ESPACE;
-  }
+  if (n > 0 && !points) return refuse(LCR_EARG, "lcr_range_images: null point array (n=%lld)", static_cast<long long>(n));
+  if (so_ws_bytes(B) > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_range_images", ws_bytes, so_ws_bytes(B));
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t* off = static_cast<int64_t*>(ws);
-  rc = stack_to_device("lcr_range_images (init)", C, nullptr, off, nullptr, st);
+  rc = stack_to_device("lcr_range_images", C, nullptr, off, nullptr, st);
   if (rc) return rc;
   return so_launch<false>("lcr_range_images", B, points, off, B, pr, band_rows, images, valid, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                           st);
 }
 
 extern "C" int lcr_scan_overlap_ws_bytes(int B, int64_t P, size_t* bytes) {
-  if (!bytes || B < 1 || B > GRID_MAX_B || P < 0 || P > INT32_MAX) {
-    set_error("lcr_scan_overlap_ws_bytes: outside the domain (1 <= B <= %d, 0 <= P <= 2^31-1, bytes non-null): B=%d P=%lld", GRID_MAX_B, B,
-              static_cast<long long>(P));
-    return LCR_EARG;
-  }
+  if (!bytes || B < 1 || B > GRID_MAX_B || P < 0 || P > INT32_MAX)
+    return refuse(LCR_EARG, "lcr_scan_overlap_ws_bytes: outside the domain (1 <= B <= %d, 0 <= P <= 2^31-1, bytes non-null): B=%d P=%lld", GRID_MAX_B, B,
+                  static_cast<long long>(P));
   *bytes = so_ws_bytes(B);
   return LCR_OK;
 }
@@ -241,34 +223,22 @@ extern "C" int lcr_scan_overlap_ws_bytes(int B, int64_t P, size_t* bytes) {
 extern "C" int lcr_scan_overlap(const float* points, const int64_t* lengths, int B, const float* images, const int32_t* valid, const int32_t* pairs,
                                 const double* rel, int64_t P, int H, int W, double fov_up, double fov_down, double max_range, double eps,
                                 int32_t* counts, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (P < 0 || P > INT32_MAX) {
-    set_error("lcr_scan_overlap: outside the domain (0 <= P <= 2^31-1): P=%lld", static_cast<long long>(P));
-    return LCR_EARG;
-  }
+  if (P < 0 || P > INT32_MAX) return refuse(LCR_EARG, "lcr_scan_overlap: outside the domain (0 <= P <= 2^31-1): P=%lld", static_cast<long long>(P));
   if (P == 0) return LCR_OK;
   SoProj pr;
   int band_rows = 0;
   int rc = so_params("lcr_scan_overlap", H, W, fov_up, fov_down, max_range, eps, &pr, &band_rows);
   if (rc) return rc;
-  if (!images || !valid || !pairs || !rel || !counts || !status || !ws) {
-    set_error("lcr_scan_overlap: null pointer");
-    return LCR_EARG;
-  }
+  if (!images || !valid || !pairs || !rel || !counts || !status || !ws) return refuse(LCR_EARG, "lcr_scan_overlap: null pointer");
   Stack C;
   rc = stack_from_lengths("lcr_scan_overlap", lengths, B, &C);
   if (rc) return rc;
   const int64_t n = C.off[B];
-  if (n > 0 && !points) {
-    set_error("lcr_scan_overlap: null point array (n=%lld)", static_cast<long long>(n));
-    return LCR_EARG;
-  }
-  if (so_ws_bytes(B) > ws_bytes) {
-    set_error("lcr_scan_overlap: workspace of %zu bytes, %zu needed", ws_bytes, so_ws_bytes(B));
-    return LCR_ESPACE;
-  }
+  if (n > 0 && !points) return refuse(LCR_EARG, "lcr_scan_overlap: null point array (n=%lld)", static_cast<long long>(n));
+  if (so_ws_bytes(B) > ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_scan_overlap", ws_bytes, so_ws_bytes(B));
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t* off = static_cast<int64_t*>(ws);
-  rc = stack_to_device("lcr_scan_overlap (init)", C, nullptr, off, status, st);
+  rc = stack_to_device("lcr_scan_overlap", C, nullptr, off, status, st);
   if (rc) return rc;
   return so_launch<true>("lcr_scan_overlap", P, points, off, B, pr, band_rows, nullptr, nullptr, images, valid, pairs, rel, counts, status, st);
 }

@@ -685,7 +685,7 @@ using namespace lcr;
 
 extern "C" int lcr_build_padded_scores(const float* raw, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, float scale,
                                        const float* alpha, float inf_val, float* S, void* stream) {
-  if (!raw || !row_mask || !col_mask || !alpha || !S || B < 1 || M < 1 || N < 1) return LCR_EARG;
+  if (!raw || !row_mask || !col_mask || !alpha || !S || B < 1 || M < 1 || N < 1) return refuse(LCR_EARG, "lcr_build_padded_scores: null pointer or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   hipLaunchKernelGGL(k_build_padded_scores_rows, dim3(blocks_for(B * (M + 1) * 64, 256, 8192)), dim3(256), 0, ST(stream), raw, row_mask, col_mask, B, M,
                      N, scale, alpha, inf_val, S);
   return check_launch("lcr_build_padded_scores");
@@ -747,44 +747,36 @@ static SkPlan sk_plan(int64_t B, int M, int N, size_t uv_floats) {
 }
 
 extern "C" int lcr_log_sinkhorn_ws_floats(int64_t B, int M, int N, size_t* floats) {
-  if (!floats || B < 1 || M < 1 || N < 1) return LCR_EARG;
+  if (!floats || B < 1 || M < 1 || N < 1) return refuse(LCR_EARG, "lcr_log_sinkhorn_ws_floats: null pointer or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   *floats = sk_plan(B, M, N, SK_WS_FULL).ws_floats;
   return LCR_OK;
 }
 // the form lcr_log_sinkhorn_ex takes with a workspace of lcr_log_sinkhorn_ws_floats floats
 extern "C" int lcr_log_sinkhorn_form(int64_t B, int M, int N, int* form) {
-  if (!form || B < 1 || M < 1 || N < 1) return LCR_EARG;
+  if (!form || B < 1 || M < 1 || N < 1) return refuse(LCR_EARG, "lcr_log_sinkhorn_form: null pointer or outside the domain (B, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   *form = sk_plan(B, M, N, SK_WS_FULL).form;
   return LCR_OK;
 }
-// the legacy entry: a workspace of B * (2 * (M + N + 2) + 1) floats, too short for the persistent form's buffers wherever they are larger
-extern "C" int lcr_log_sinkhorn(float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters, float inf_val,
-                                float* uv_ws, void* stream) {
-  return lcr_log_sinkhorn_ex(S, row_mask, col_mask, B, M, N, iters, inf_val, uv_ws, static_cast<size_t>(B) * (2 * (static_cast<size_t>(M) + N + 2) + 1), stream);
-}
-// in place on S [B, M+1, N+1]; uv_ws: uv_floats floats, lcr_log_sinkhorn_ws_floats(B, M, N) of them for the form lcr_log_sinkhorn_form reports
-extern "C" int lcr_log_sinkhorn_ex(float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters, float inf_val,
-                                   float* uv_ws, size_t uv_floats, void* stream) {
-  if (!S || !row_mask || !col_mask || !uv_ws || B < 1 || M < 1 || N < 1 || iters < 0) return LCR_EARG;
+// the body of lcr_log_sinkhorn and lcr_log_sinkhorn_ex; `who` = the one that was called
+static int log_sinkhorn(const char* who, float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters, float inf_val,
+                        float* uv_ws, size_t uv_floats, void* stream) {
+  if (!S || !row_mask || !col_mask || !uv_ws || B < 1 || M < 1 || N < 1 || iters < 0)
+    return refuse(LCR_EARG, "%s: null pointer or outside the domain (B, M, N >= 1, iters >= 0): B=%lld M=%d N=%d iters=%d", who, static_cast<long long>(B), M, N, iters);
   const SkPlan p = sk_plan(B, M, N, uv_floats);
   KernelTimerScope timed(KT_SINKHORN, ST(stream), B, M, N, iters, p.form);      // brackets every launch of the call (bench.py's pair block)
   if (p.form == 0) {
     unsigned* redo = p.scaled ? reinterpret_cast<unsigned*>(uv_ws) : nullptr;    // B words of the workspace: problems handed back
     if (p.scaled) {
       static DynLds opt_in;                              // up to 132 x 132 floats of dynamic LDS beside the static vectors
-      if (opt_in.need(reinterpret_cast<const void*>(&k_sinkhorn_scaled), sizeof(float) * SKR_LINES * SKR_LINES) != hipSuccess) {
-        set_error("lcr_log_sinkhorn: cannot reserve dynamic LDS for the scaled-domain kernel");
-        return LCR_EHIP;
-      }
+      if (opt_in.need(reinterpret_cast<const void*>(&k_sinkhorn_scaled), sizeof(float) * SKR_LINES * SKR_LINES) != hipSuccess)
+        return refuse(LCR_EHIP, "%s: cannot reserve dynamic LDS for the scaled-domain kernel", who);
       hipLaunchKernelGGL(k_sinkhorn_scaled, dim3(static_cast<int>(B)), dim3(SKR_T), p.lds, ST(stream), S, row_mask, col_mask, M, N, iters, inf_val, redo);
     }
     hipLaunchKernelGGL(k_log_sinkhorn_reg, dim3(static_cast<int>(B)), dim3(SKR_T), 0, ST(stream), S, row_mask, col_mask, M, N, iters, inf_val, redo);
   } else if (p.form == 1) {
     static DynLds opt_in;                                // > 64 KB of dynamic LDS needs an explicit opt-in
-    if (opt_in.need(reinterpret_cast<const void*>(&k_log_sinkhorn_lds), SK_LDS_ROOM) != hipSuccess) {
-      set_error("lcr_log_sinkhorn: cannot reserve dynamic LDS for the LDS-resident kernel");
-      return LCR_EHIP;
-    }
+    if (opt_in.need(reinterpret_cast<const void*>(&k_log_sinkhorn_lds), SK_LDS_ROOM) != hipSuccess)
+      return refuse(LCR_EHIP, "%s: cannot reserve dynamic LDS for the LDS-resident kernel", who);
     hipLaunchKernelGGL(k_log_sinkhorn_lds, dim3(static_cast<int>(B)), dim3(SK_T), p.lds, ST(stream), S, row_mask, col_mask, M, N, iters, inf_val,
                        uv_ws);
   } else if (p.form == 2) {
@@ -796,14 +788,12 @@ extern "C" int lcr_log_sinkhorn_ex(float* S, const uint8_t* row_mask, const uint
     c.slab = p.slab;
     c.nsub = p.nsub;
     static DynLds opt_in;
-    if (opt_in.need(reinterpret_cast<const void*>(&k_log_sinkhorn_coop), p.lds) != hipSuccess) {
-      set_error("lcr_log_sinkhorn: cannot reserve %zu B of dynamic LDS for the persistent kernel", p.lds);
-      return LCR_EHIP;
-    }
+    if (opt_in.need(reinterpret_cast<const void*>(&k_log_sinkhorn_coop), p.lds) != hipSuccess)
+      return refuse(LCR_EHIP, "%s: cannot reserve %zu B of dynamic LDS for the persistent kernel", who, p.lds);
     hipLaunchKernelGGL(k_sk_coop_init, dim3(1), dim3(64), 0, ST(stream), c.counter, c.status, static_cast<int>(B));
     hipLaunchKernelGGL(k_log_sinkhorn_coop, dim3(static_cast<int>(B) * p.G), dim3(SKC_T), p.lds, ST(stream), S, row_mask, col_mask, M, N, iters, inf_val, c);
   } else {
-    if (B > 65535) return LCR_EARG;
+    if (B > 65535) return refuse(LCR_EARG, "%s: more than 65535 problems in the launch-per-half-iteration form (B=%lld)", who, static_cast<long long>(B));
     // the last B floats of uv_ws's per-problem blocks are not spare, so norms live after all of them (caller sizes uv_ws with +B)
     float* norm_ws = uv_ws + B * 2 * (static_cast<int64_t>(M) + N + 2);
     hipLaunchKernelGGL(k_sk_init, dim3(static_cast<int>(B)), dim3(SK_T), 0, ST(stream), row_mask, col_mask, M, N, inf_val, uv_ws, norm_ws);
@@ -814,5 +804,16 @@ extern "C" int lcr_log_sinkhorn_ex(float* S, const uint8_t* row_mask, const uint
     }
     hipLaunchKernelGGL(k_sk_final, dim3(64, static_cast<int>(B)), dim3(256), 0, ST(stream), S, M, N, uv_ws, norm_ws);
   }
-  return check_launch("lcr_log_sinkhorn");
+  return check_launch(who);
+}
+// the legacy entry: a workspace of B * (2 * (M + N + 2) + 1) floats, too short for the persistent form's buffers wherever they are larger
+extern "C" int lcr_log_sinkhorn(float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters, float inf_val,
+                                float* uv_ws, void* stream) {
+  return log_sinkhorn("lcr_log_sinkhorn", S, row_mask, col_mask, B, M, N, iters, inf_val, uv_ws,
+                      static_cast<size_t>(B) * (2 * (static_cast<size_t>(M) + N + 2) + 1), stream);
+}
+// in place on S [B, M+1, N+1]; uv_ws: uv_floats floats, lcr_log_sinkhorn_ws_floats(B, M, N) of them for the form lcr_log_sinkhorn_form reports
+extern "C" int lcr_log_sinkhorn_ex(float* S, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N, int iters, float inf_val,
+                                   float* uv_ws, size_t uv_floats, void* stream) {
+  return log_sinkhorn("lcr_log_sinkhorn_ex", S, row_mask, col_mask, B, M, N, iters, inf_val, uv_ws, uv_floats, stream);
 }

@@ -457,13 +457,16 @@ static Plan skg_plan(int64_t B, int M, int N, int iters) {
 using namespace lcr;
 
 extern "C" int lcr_log_sinkhorn_grad_ws_bytes(int64_t B, int M, int N, int iters, size_t* bytes) {
-  if (!bytes || B < 0 || M < 1 || N < 1 || iters < 1) return LCR_EARG;
+  if (!bytes || B < 0 || M < 1 || N < 1 || iters < 1)
+    return refuse(LCR_EARG, "lcr_log_sinkhorn_grad_ws_bytes: null pointer or outside the domain (B >= 0, M, N, iters >= 1): B=%lld M=%d N=%d iters=%d",
+                  static_cast<long long>(B), M, N, iters);
   *bytes = skg::skg_plan(B, M, N, iters).ws_bytes;
   return LCR_OK;
 }
 
 extern "C" int lcr_log_sinkhorn_grad_form(int64_t B, int M, int N, int* form) {
-  if (!form || B < 0 || M < 1 || N < 1) return LCR_EARG;
+  if (!form || B < 0 || M < 1 || N < 1)
+    return refuse(LCR_EARG, "lcr_log_sinkhorn_grad_form: null pointer or outside the domain (B >= 0, M, N >= 1): B=%lld M=%d N=%d", static_cast<long long>(B), M, N);
   *form = skg::skg_plan(B, M, N, 1).form;
   return LCR_OK;
 }
@@ -471,24 +474,20 @@ extern "C" int lcr_log_sinkhorn_grad_form(int64_t B, int M, int N, int* form) {
 extern "C" int lcr_log_sinkhorn_grad(const float* S0, const float* G, const uint8_t* row_mask, const uint8_t* col_mask, int64_t B, int M, int N,
                                      int iters, float inf_val, float* dS, float* d_alpha_part, void* ws, size_t ws_bytes, void* stream) {
   (void)inf_val;      // masked lines are taken from the masks, whatever S0 holds there
-  if (B < 0 || M < 1 || N < 1 || iters < 1) return LCR_EARG;
+  if (B < 0 || M < 1 || N < 1 || iters < 1)
+    return refuse(LCR_EARG, "lcr_log_sinkhorn_grad: outside the domain (B >= 0, M, N, iters >= 1): B=%lld M=%d N=%d iters=%d", static_cast<long long>(B), M, N, iters);
   if (B == 0) return LCR_OK;
-  if (!S0 || !G || !row_mask || !col_mask || !dS || !d_alpha_part || !ws) return LCR_EARG;
+  if (!S0 || !G || !row_mask || !col_mask || !dS || !d_alpha_part || !ws) return refuse(LCR_EARG, "lcr_log_sinkhorn_grad: null pointer");
   const skg::Plan p = skg::skg_plan(B, M, N, iters);
-  if (ws_bytes < p.ws_bytes) {
-    set_error("lcr_log_sinkhorn_grad: workspace of %zu bytes, %zu needed", ws_bytes, p.ws_bytes);
-    return LCR_ESPACE;
-  }
+  if (ws_bytes < p.ws_bytes) return refuse_ws(LCR_ESPACE, "lcr_log_sinkhorn_grad", ws_bytes, p.ws_bytes);
   hipStream_t st = ST(stream);
   if (p.form == 0) {
-    if (B > 0x7fffffff) return LCR_EARG;
+    if (B > 0x7fffffff) return refuse(LCR_EARG, "lcr_log_sinkhorn_grad: more than 2^31-1 problems (B=%lld)", static_cast<long long>(B));
     const dim3 grid(static_cast<unsigned>(B));
     if (p.hist_lds) {
       static DynLds opt_in;                                // > 64 KB of dynamic LDS needs an explicit opt-in
-      if (opt_in.need(reinterpret_cast<const void*>(&skg::k_sinkhorn_grad_res<true>), skg::GR_LDS_ROOM) != hipSuccess) {
-        set_error("lcr_log_sinkhorn_grad: cannot reserve dynamic LDS for the recorded duals");
-        return LCR_EHIP;
-      }
+      if (opt_in.need(reinterpret_cast<const void*>(&skg::k_sinkhorn_grad_res<true>), skg::GR_LDS_ROOM) != hipSuccess)
+        return refuse(LCR_EHIP, "lcr_log_sinkhorn_grad: cannot reserve dynamic LDS for the recorded duals");
       hipLaunchKernelGGL(skg::k_sinkhorn_grad_res<true>, grid, dim3(SKR_T), p.hist_floats * sizeof(float), st, S0, G, row_mask, col_mask, M, N,
                          iters, dS, d_alpha_part, static_cast<float*>(nullptr));
     } else {
@@ -497,7 +496,7 @@ extern "C" int lcr_log_sinkhorn_grad(const float* S0, const float* G, const uint
     }
     return check_launch("lcr_log_sinkhorn_grad");
   }
-  if (B > 65535) return LCR_EARG;
+  if (B > 65535) return refuse(LCR_EARG, "lcr_log_sinkhorn_grad: more than 65535 problems in the launch-per-half-iteration form (B=%lld)", static_cast<long long>(B));
   size_t used = 0;
   const skg::GenWs w = skg::gen_carve(ws, ws_bytes, B, M, N, iters, &used);
   const int nb = static_cast<int>(B);

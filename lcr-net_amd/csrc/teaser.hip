@@ -526,11 +526,9 @@ __global__ __launch_bounds__(TZ_SEL_T) void k_tz_vote_scan(const TzState* __rest
 using namespace lcr;
 
 static int teaser_shape(const char* what, int S, int64_t n, int max_rows, int mode) {
-  if (S < 1 || S > 65535 || n < 0 || max_rows < 0 || max_rows > TZ_MAX_ROWS || n > static_cast<int64_t>(S) * max_rows || mode < 0 || mode > 1) {
-    set_error("%s: outside the domain (1 <= S <= 65535, 0 <= max_rows <= %d rows per problem, 0 <= n <= S * max_rows, mode 0 = kcore or "
-              "1 = none): S=%d n=%lld max_rows=%d mode=%d", what, TZ_MAX_ROWS, S, static_cast<long long>(n), max_rows, mode);
-    return LCR_EARG;
-  }
+  if (S < 1 || S > 65535 || n < 0 || max_rows < 0 || max_rows > TZ_MAX_ROWS || n > static_cast<int64_t>(S) * max_rows || mode < 0 || mode > 1)
+    return refuse(LCR_EARG, "%s: outside the domain (1 <= S <= 65535, 0 <= max_rows <= %d rows per problem, 0 <= n <= S * max_rows, mode 0 = kcore or "
+                  "1 = none): S=%d n=%lld max_rows=%d mode=%d", what, TZ_MAX_ROWS, S, static_cast<long long>(n), max_rows, mode);
   return LCR_OK;
 }
 
@@ -561,11 +559,8 @@ static size_t teaser_carve(Carver& c, int S, int max_rows, int mode, TzCarve* o)
 }
 
 extern "C" int lcr_teaser_ws_bytes(int S, int64_t n, int max_rows, int mode, size_t* bytes) {
-  if (!bytes) {
-    set_error("lcr_teaser_ws_bytes: null pointer");
-    return LCR_EARG;
-  }
-  if (teaser_shape("lcr_teaser_ws_bytes", S, n, max_rows, mode) != LCR_OK) return LCR_EARG;
+  if (!bytes) return refuse(LCR_EARG, "lcr_teaser_ws_bytes: null pointer");
+  if (int rc = teaser_shape("lcr_teaser_ws_bytes", S, n, max_rows, mode)) return rc;
   Carver c(nullptr, ~size_t(0));
   *bytes = teaser_carve(c, S, max_rows, mode, nullptr);
   return LCR_OK;
@@ -577,25 +572,17 @@ extern "C" int lcr_teaser_registration(const float* src, const float* ref, const
                                        int32_t* iterations, double* cost, uint8_t* selected_mask, int32_t* core, void* ws, size_t ws_bytes,
                                        void* stream) {
   const char* what = "lcr_teaser_registration";
-  if (teaser_shape(what, S, n, max_rows, mode) != LCR_OK) return LCR_EARG;
+  if (int rc = teaser_shape(what, S, n, max_rows, mode)) return rc;
   if (!(noise_bound > 0.0) || !(cbar2 > 0.0) || !(gnc_factor > 1.0) || !std::isfinite(noise_bound) || !std::isfinite(cbar2) ||
-      !std::isfinite(gnc_factor) || max_iterations < 1 || max_iterations > 1000 || !(cost_threshold >= 0.0) || !std::isfinite(cost_threshold)) {
-    set_error("%s: outside the domain (noise_bound > 0, cbar2 > 0, gnc_factor > 1, all finite, 1 <= max_iterations <= 1000, "
-              "cost_threshold >= 0): noise_bound=%g cbar2=%g gnc_factor=%g max_iterations=%d cost_threshold=%g", what, noise_bound, cbar2,
-              gnc_factor, max_iterations, cost_threshold);
-    return LCR_EARG;
-  }
-  if (!start || !T || !valid || !n_selected || !rot_inliers || !t_count || !ws || (n > 0 && (!src || !ref))) {
-    set_error("%s: null pointer", what);
-    return LCR_EARG;
-  }
+      !std::isfinite(gnc_factor) || max_iterations < 1 || max_iterations > 1000 || !(cost_threshold >= 0.0) || !std::isfinite(cost_threshold))
+    return refuse(LCR_EARG, "%s: outside the domain (noise_bound > 0, cbar2 > 0, gnc_factor > 1, all finite, 1 <= max_iterations <= 1000, "
+                  "cost_threshold >= 0): noise_bound=%g cbar2=%g gnc_factor=%g max_iterations=%d cost_threshold=%g", what, noise_bound, cbar2,
+                  gnc_factor, max_iterations, cost_threshold);
+  if (!start || !T || !valid || !n_selected || !rot_inliers || !t_count || !ws || (n > 0 && (!src || !ref))) return refuse(LCR_EARG, "%s: null pointer", what);
   TzCarve w;
   Carver c(ws, ws_bytes);
   const size_t need = teaser_carve(c, S, max_rows, mode, &w);
-  if (need > ws_bytes) {
-    set_error("%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
-    return LCR_ESPACE;
-  }
+  if (need > ws_bytes) return refuse_ws(LCR_ESPACE, what, ws_bytes, need);
   TzParams P;
   P.beta = 2.0 * noise_bound * std::sqrt(cbar2);
   P.rho = noise_bound * std::sqrt(cbar2);

@@ -197,7 +197,7 @@ def test_aggregate_grad_refuses_outside_its_domain():
     for M, Ns, H, C in [(4, 4, 129, 32), (4, 4, 4, 48), (4, 4, 0, 32)]:
         rc = L.lib().lcr_kpconv_aggregate_grad(L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), M, Ns, H, C, ctypes.c_void_p(kp.ctypes.data), 0.6, L.ptr(x),
                                                L.stream_ptr(torch.device(DEV, 0)))
-        assert rc != 0 and L.lib().lcr_last_error()
+        assert rc == -1 and L.lib().lcr_last_error().startswith(b"lcr_kpconv_aggregate_grad:")
 
 
 # ------------------------------------------------------------------------------------------------ lcr_groupnorm_apply_grad

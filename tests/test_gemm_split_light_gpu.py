@@ -102,7 +102,7 @@ def test_split_anorm_refuses_shapes_outside_its_domain(N, K):
     rc = _lib.lib().lcr_gemm_f32_bsplit_anorm(_lib.ptr(a), _lib.ptr(planes), _lib.ptr(c), M, N, K, None, _lib.ptr(a_stats), _lib.ptr(gamma),
                                               _lib.ptr(beta), a_groups, GN_EPS, SLOPE, _lib.ptr(seg_len), 1, 0, None, _lib.stream_ptr(dev))
     torch.cuda.synchronize()
-    assert rc != 0 and b"lcr_gemm_f32_bsplit_anorm" in _lib.lib().lcr_last_error()
+    assert rc == -1 and _lib.lib().lcr_last_error().startswith(b"lcr_gemm_f32_bsplit_anorm:")
     assert (c == 7.0).all()
 
 

@@ -202,7 +202,7 @@ def test_refusals_leave_the_output_alone():
                                    ("segment of 2^31 rows", {}, huge, EARG), ("workspace one byte short", {"ws_short": 1}, seg_lens, ESPACE)):
         run = Owned("seeded", x, lens, **kwargs)
         assert run.rc == rc, (what, run.rc)
-        assert _lib.lib().lcr_last_error(), what
+        assert _lib.lib().lcr_last_error().startswith(b"lcr_netvlad_forward:"), what
         assert run.output_untouched() and run.canaries_intact(), what
         assert bool(torch.isnan(run.buf[:run.nbytes].view(torch.float32)).all()), what      # refused before anything was launched
     nb = ctypes.c_size_t(0)

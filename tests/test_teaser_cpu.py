@@ -158,7 +158,7 @@ def test_ws_bytes_answers_on_the_host_and_refuses_outside_the_domain():
     for bad in [(0, 10, 10, 0), (65536, 10, 10, 0), (1, 10, 4097, 0), (1, 10, -1, 0), (1, -1, 10, 0), (2, 21, 10, 0), (1, 10, 10, 2),
                 (1, 10, 10, -1)]:
         rc, _, text = ws_bytes(*bad)
-        assert rc != 0 and "lcr_teaser_ws_bytes" in text and "domain" in text, bad
+        assert rc == -1 and text.startswith("lcr_teaser_ws_bytes:") and "domain" in text, bad
     import lcrnet_amd._lib as L
     assert L.lib().lcr_teaser_ws_bytes(1, 10, 10, 0, None) != 0
 
@@ -174,7 +174,7 @@ def test_the_entry_refuses_bad_parameters_before_any_launch():
             p = dict(good, **{key: v})
             rc = lib.lcr_teaser_registration(None, None, None, 1, 10, 10, p["noise_bound"], p["cbar2"], p["gnc_factor"], p["max_iterations"],
                                              p["cost_threshold"], 0, None, None, None, None, None, None, None, None, None, None, 0, None)
-            assert rc != 0 and "lcr_teaser_registration" in lib.lcr_last_error().decode(), (key, v)
+            assert rc == -1 and lib.lcr_last_error().startswith(b"lcr_teaser_registration:"), (key, v)
     # shape outside the domain, then null pointers: refused too
     assert lib.lcr_teaser_registration(None, None, None, 1, 10, 5000, 0.01, 1.0, 1.4, 100, 1e-12, 0, None, None, None, None, None, None, None,
                                        None, None, None, 0, None) != 0

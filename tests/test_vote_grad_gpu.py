@@ -181,7 +181,7 @@ def test_points_grad_domain_and_empty_calls():
     for M, Ns, H, C in [(4, 4, 129, 32), (4, 4, 4, 48), (4, 4, 0, 32), (1 << 24, 4, 64, 32)]:
         rc = L.lib().lcr_kpconv_points_grad(L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), 0, L.ptr(x), L.ptr(x), M, Ns, H, C,
                                             ctypes.c_void_p(kp.ctypes.data), 0.6, L.ptr(x), L.ptr(x), L.ptr(x), 1 << 40, stream())
-        assert rc != 0 and L.lib().lcr_last_error()
+        assert rc == -1 and L.lib().lcr_last_error().startswith(b"lcr_kpconv_points_grad:")
     assert L.lib().lcr_kpconv_points_grad_ws_bytes(4, 129, ctypes.byref(n)) != 0
     # d_s without the list or with a short workspace, sigma <= 0
     args = lambda rs, ws, nws, sigma: (L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(x), 0, rs, rs, 2, 2, 2, 32, ctypes.c_void_p(kp.ctypes.data), sigma,
@@ -236,7 +236,8 @@ def test_vote_shift_grad_matches_fp64():
     torch.cuda.synchronize()
     assert intact(t_1) and same_bytes(d1.cpu(), got[5:6])
     assert L.lib().lcr_vote_shift_grad(None, None, 0, V.SHIFT_RANGE, None, stream()) == 0
-    assert L.lib().lcr_vote_shift_grad(None, L.ptr(d1), 1, V.SHIFT_RANGE, L.ptr(d1), stream()) != 0 and L.lib().lcr_last_error()
+    assert L.lib().lcr_vote_shift_grad(None, L.ptr(d1), 1, V.SHIFT_RANGE, L.ptr(d1), stream()) == -1
+    assert L.lib().lcr_last_error().startswith(b"lcr_vote_shift_grad:")
     assert F.vote_shift_grad(torch.zeros(0, 3, device=DEV), torch.zeros(0, 3, device=DEV), 4.2).shape == (0, 3)
 
 
@@ -301,7 +302,8 @@ def test_upsample_concat_grad_matches_fp64(C1, C2):
     assert same_bytes(xa.grad.cpu(), got_x) and same_bytes(sa.grad.cpu(), got_s)
     only_x, none_s = F.upsample_concat_grad(g.to(DEV), idx.to(DEV), Nx, C1, want_skip=False)
     assert none_s is None and same_bytes(only_x.cpu(), got_x)
-    assert L.lib().lcr_upsample_concat_grad(L.ptr(g_d), None, None, N, Nx, C1, C2, L.ptr(dx), None, stream()) != 0 and L.lib().lcr_last_error()
+    assert L.lib().lcr_upsample_concat_grad(L.ptr(g_d), None, None, N, Nx, C1, C2, L.ptr(dx), None, stream()) == -1
+    assert L.lib().lcr_last_error().startswith(b"lcr_upsample_concat_grad:")
     assert L.lib().lcr_upsample_concat_grad(None, None, None, 0, 0, C1, C2, None, None, stream()) == 0
 
 
