@@ -1200,6 +1200,60 @@ int lcr_teaser_registration(const float* src, const float* ref, const int32_t* s
                             int32_t* n_selected, int64_t* rot_inliers, int32_t* t_count, int32_t* iterations, double* cost,
                             uint8_t* selected_mask, int32_t* core, void* ws, size_t ws_bytes, void* stream);
 
+/* Scan Context (Kim & Kim, IROS 2018): a polar max-height image per scan, compared under all column shifts; the learning-free loop
+ * detector.  Restated in tests/scan_context_restatement.py; parity with the authors' code is not pinned.
+ *   Parameters (defaults): R = 20 rings, W = 60 sectors, max_length = 80.0, lidar_height = 2.0.
+ *   Descriptor of one cloud.  (x, y, z) is fp32; x and y are promoted to fp64 for the bin decision.
+ *     - r = sqrt(x*x + y*y), every operation rounded, no FMA.  theta = atan2(y, x), and theta += 2 pi if theta < 0.
+ *     - A point is kept iff r < max_length and z is finite.  Points with a NaN or infinite coordinate therefore drop out.
+ *     - ring = min(floor(r / max_length * R), R-1); sector = min(floor(theta / (2 pi) * W), W-1); x = y = 0 goes to bin (0, 0).
+ *     - Bin value = the maximum over its points of fl32(z + fl32(lidar_height)); an empty bin holds 0.0f.  A bin whose points are all
+ *       below -lidar_height keeps its negative maximum.  desc is f32[R, W].
+ *   Derived outputs of the same call.
+ *     - ring_key[R] = the fp32 sum of a row, j ascending, divided by fl32(W).
+ *     - n_j = sqrtf(sum_i d_ij^2), i ascending in fp32, every operation rounded.  unit_ij = d_ij / n_j where n_j > 0; the whole column is
+ *       zero otherwise.  mask is u64: bit j is set iff n_j > 0.
+ *   Distance of descriptors a, b at shift s in [0, W).
+ *     - V(s) = { j : mask_a[j] and mask_b[(j+s) mod W] }, c(s) = |V(s)|.
+ *     - d(s) = 1 - (sum over j in V(s), ascending, of unit_a[:, j] . unit_b[:, (j+s) mod W]) / c(s), or 1 when c(s) = 0.
+ *     - dist(a, b) = min_s d(s); shift(a, b) is the smallest minimising s.  This is the paper's exhaustive minimum over all shifts (the
+ *       authors' code aligns first with a sector key and searches a few columns around it; that shortcut is not built).
+ *     - The column products are fp32 on v_mfma_f32_32x32x2_f32, rings ascending in pairs; the sum over j, the division and the
+ *       subtraction are fp32, every operation rounded.
+ *   Sign convention: if b is a rotated about +z by phi, then shift ~ phi / (2 pi / W), and Rz(-shift * 2 pi / W) brings b into a's heading.
+ *
+ * lcr_scan_context: points f32[N,3] stacked cloud-major, lengths HOST int64[B] -> desc f32[B,R,W], ring_key f32[B,R], unit f32[B,R,W],
+ *   mask u64[B].  The bin maximum is an integer atomic maximum on an order-preserving map of the fp32 bits, in LDS per workgroup and then
+ *   across the workgroups of a cloud: order-free, so a cloud gives the same bytes alone, at any position of a stack, and run to run.
+ *   ws: lcr_scan_context_ws_bytes(B, R, W) = 4 B R W bytes rounded up to 256 (the bins being built).
+ *   Domain: 1 <= B <= 64, 1 <= R <= 32, 1 <= W <= 64, 0 < max_length finite, lidar_height finite, lengths >= 0, N <= 2^31-1.
+ * lcr_scan_context_distance: P pairs (i, j) = pairs[p] (device i32[P,2]) over unit f32[B,R,W] and mask u64[B] -> dist f32[P],
+ *   shift i32[P].  A pair with an index outside 0..B-1 reads nothing, gets (NaN, -1) and raises status i32[1] (device) to the largest such
+ *   p + 1; status is 0 after a call without one.  P == 0 is legal once B, R, W are in the domain: nothing is launched and status is not
+ *   written.  ws: lcr_scan_context_distance_ws_bytes answers 0 (a pair's Gram tile lives in LDS); ws may be NULL.
+ *   Domain: 1 <= B <= 2^31-1, 0 <= P <= 2^31-1, R and W as above.
+ * lcr_scan_context_topk: the exhaustive causal search, with the semantics of lcr_retrieval_topk.  Query row r is frame q0 + r of
+ *   db_unit f32[C,R,W] / db_mask u64[C]; its database is frames [0, q0 + r - exclude).  idx i32[Q,k], dist f32[Q,k], shift i32[Q,k]; a
+ *   row is ascending in (dist, index); a row with fewer than k candidates is padded with (-1, +inf, -1).  Q == 0 is legal once the other
+ *   arguments are in the domain.  ws: lcr_scan_context_topk_ws_bytes(Q, q0, C, exclude) = 8 Q Cw bytes plus rounding, Cw =
+ *   clamp(q0 + Q - 1 - exclude, 0, C) the columns the last row sees: every admissible pair's distance and shift are written once, then
+ *   one workgroup per row selects.
+ *   Domain: 1 <= C <= 2^31-1, 0 <= Q, 0 <= q0, q0 + Q <= C, exclude >= 0, 1 <= k <= 128, R and W as above.
+ * A pair's (dist, shift) has the same bytes in both distance entries, at any position in any call, and run to run: one wavefront computes
+ * it by one routine, whatever surrounds it.  No floating-point atomics; every sum has one order.
+ * All entries are asynchronous and stream-ordered, allocate nothing and never synchronise with the host; the argument checks and the
+ * _ws_bytes helpers are host-only.  LCR_EARG with text and no launch outside a domain (the all-zero call included), LCR_ESPACE for a
+ * workspace below the helper's answer. */
+int lcr_scan_context_ws_bytes(int B, int R, int W, size_t* bytes);
+int lcr_scan_context(const float* points, const int64_t* lengths, int B, int R, int W, double max_length, double lidar_height, float* desc,
+                     float* ring_key, float* unit, uint64_t* mask, void* ws, size_t ws_bytes, void* stream);
+int lcr_scan_context_distance_ws_bytes(int64_t B, int R, int W, int64_t P, size_t* bytes);
+int lcr_scan_context_distance(const float* unit, const uint64_t* mask, int64_t B, int R, int W, const int32_t* pairs, int64_t P, float* dist,
+                              int32_t* shift, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int lcr_scan_context_topk_ws_bytes(int64_t Q, int64_t q0, int64_t C, int exclude, size_t* bytes);
+int lcr_scan_context_topk(const float* db_unit, const uint64_t* db_mask, int64_t C, int R, int W, int64_t Q, int64_t q0, int k, int exclude,
+                          int32_t* idx, float* dist, int32_t* shift, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2097,6 +2097,67 @@ def scan_overlap(points, lengths, images, valid, pairs, rel, H=64, W=900, fov_up
     return counts, status
 
 
+SCAN_CONTEXT_MAX_CLOUDS = 64   # clouds per lcr_scan_context call
+SCAN_CONTEXT_PARAMS = dict(R=20, W=60, max_length=80.0, lidar_height=2.0)    # the defaults of include/lcr_hip.h
+SCAN_CONTEXT_MAX_K = 128
+
+
+def scan_context(points, lengths, R=20, W=60, max_length=80.0, lidar_height=2.0):
+    """Scan Context descriptors (include/lcr_hip.h, lcr_scan_context) of B <= 64 clouds in one native call: points f32 [N,3] on the device
+    stacked cloud-major, lengths host ints [B] -> (desc f32 [B,R,W], ring_key f32 [B,R], unit f32 [B,R,W], mask int64 [B] holding the
+    u64 column bits).  Asynchronous on the current stream."""
+    points, ln = _scan_clouds("scan_context", points, lengths)
+    dev, B, R, W = points.device, len(ln), int(R), int(W)
+    ws = _lib.ws("lcr_scan_context_ws_bytes", B, R, W, device=dev)
+    desc = torch.empty((B, R, W), dtype=torch.float32, device=dev)
+    ring_key = torch.empty((B, R), dtype=torch.float32, device=dev)
+    unit = torch.empty((B, R, W), dtype=torch.float32, device=dev)
+    mask = torch.empty((B,), dtype=torch.int64, device=dev)
+    _lib.call.lcr_scan_context(_lib.ptr(points), ln.ctypes.data, B, R, W, float(max_length), float(lidar_height), _lib.ptr(desc),
+                               _lib.ptr(ring_key), _lib.ptr(unit), _lib.ptr(mask), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return desc, ring_key, unit, mask
+
+
+def _scan_context_db(who, unit, mask):
+    _lib.require_cuda(unit, mask)
+    if unit.dim() != 3 or unit.dtype != torch.float32 or mask.dtype != torch.int64 or tuple(mask.shape) != (unit.shape[0],):
+        raise ValueError("%s: unit must be float32 [B,R,W] and mask int64 [B]" % who)
+    return unit.contiguous(), mask.contiguous()
+
+
+def scan_context_distance(unit, mask, pairs):
+    """Scan Context distances (include/lcr_hip.h, lcr_scan_context_distance) of P pairs of the B descriptors: unit / mask as scan_context
+    returned them, pairs int32 [P,2] (i, j) on the device -> (dist f32 [P], shift int32 [P], status int32 [1]: 0, or p + 1 of a pair with
+    an index outside 0..B-1, whose result is (NaN, -1)).  Raw form: asynchronous on the current stream, the status is not read here."""
+    unit, mask = _scan_context_db("scan_context_distance", unit, mask)
+    _lib.require_cuda(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+        raise ValueError("scan_context_distance: pairs must be int32 [P,2]")
+    pairs = pairs.contiguous()
+    dev, (B, R, W), P = unit.device, unit.shape, pairs.shape[0]
+    dist = torch.empty((P,), dtype=torch.float32, device=dev)
+    shift = torch.empty((P,), dtype=torch.int32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.call.lcr_scan_context_distance(_lib.ptr(unit), _lib.ptr(mask), B, R, W, _lib.ptr(pairs), P, _lib.ptr(dist), _lib.ptr(shift),
+                                        _lib.ptr(status), None, 0, _lib.stream_ptr(dev))
+    return dist, shift, status
+
+
+def scan_context_topk(unit, mask, q0, Q, k, exclude):
+    """The exhaustive causal Scan Context search (include/lcr_hip.h, lcr_scan_context_topk): query row r is frame q0 + r of unit f32
+    [C,R,W] / mask int64 [C] and sees frames [0, q0 + r - exclude) -> (idx int32 [Q,k], dist f32 [Q,k], shift int32 [Q,k]), rows ascending
+    in (dist, index), padded with (-1, +inf, -1).  Asynchronous on the current stream."""
+    unit, mask = _scan_context_db("scan_context_topk", unit, mask)
+    dev, (C, R, W), Q, k = unit.device, unit.shape, int(Q), int(k)
+    ws = _lib.ws("lcr_scan_context_topk_ws_bytes", Q, int(q0), C, int(exclude), device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    shift = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    _lib.call.lcr_scan_context_topk(_lib.ptr(unit), _lib.ptr(mask), C, R, W, Q, int(q0), k, int(exclude), _lib.ptr(idx), _lib.ptr(dist),
+                                    _lib.ptr(shift), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return idx, dist, shift
+
+
 # ------------------------------------------------------------------------------------------------ registration loss terms
 class GapGeometry:
     """The slice tables of lcr_gap_loss (include/lcr_hip.h) for B score slices of (n_b + 1) x (m_b + 1) grouped into pairs: n, m = host

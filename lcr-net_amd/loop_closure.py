@@ -69,19 +69,32 @@ def register_pairs(pair_model, clouds, pairs, limits, pairs_per_call=16, workers
 
 
 def run(desc_model, pair_model, raw_frames, thres, out_dir, seq=0, desc_limits=(64, 65, 74, 80), pair_limits=(74, 68, 70, 67), pairs_per_call=16,
-        max_pairs=None, write_descriptors=True, voxelizer="grid"):
+        max_pairs=None, write_descriptors=True, voxelizer="grid", detector="descriptor", sc_params=None):
     """The whole chain; writes `{out_dir}/features/{seq}_{idx}.npz`, `{out_dir}/features/predicted_des_L2_dis.npz`,
     `{out_dir}/result/top1_with_thres_%.2f/%02d.txt` and `{out_dir}/registration/{seq}_pose`.  -> dict with the in-memory results.
-    voxelizer: the raw-scan voxeliser of voxelise_frames ("grid" or "open3d")."""
+    voxelizer: the raw-scan voxeliser of voxelise_frames ("grid" or "open3d").
+    detector: "descriptor" (the learned 256-D descriptor of desc_model) or "scan_context" (scan_context.detect_loops on the raw scans:
+    learning-free, desc_model is not used and may be None, no per-frame descriptor files; `thres` is then a Scan Context distance and the
+    result also holds "scan_contexts" and "yaw"; sc_params: the keywords of functional.scan_context)."""
+    if detector not in ("descriptor", "scan_context"):
+        raise ValueError("loop_closure.run: detector must be 'descriptor' or 'scan_context', got %r" % (detector,))
     clouds = voxelise_frames(raw_frames, method=voxelizer)
-    desc = sequence_descriptors(desc_model, clouds, list(desc_limits))
     feat_dir = os.path.join(out_dir, "features")
     os.makedirs(feat_dir, exist_ok=True)
-    if write_descriptors:
-        dh = desc.cpu().numpy()
-        for i in range(len(dh)):
-            io.save_descriptor(feat_dir, seq, i, dh[i])
-    rows, kept = detect_loops(desc, thres)
+    extra = {}
+    if detector == "scan_context":
+        from . import scan_context
+        desc = None
+        sc = scan_context.sequence_scan_contexts(raw_frames, **(sc_params or {}))
+        rows, kept, yaw = scan_context.detect_loops(sc, thres)
+        extra = {"scan_contexts": sc, "yaw": yaw}
+    else:
+        desc = sequence_descriptors(desc_model, clouds, list(desc_limits))
+        if write_descriptors:
+            dh = desc.cpu().numpy()
+            for i in range(len(dh)):
+                io.save_descriptor(feat_dir, seq, i, dh[i])
+        rows, kept = detect_loops(desc, thres)
     io.save_pair_dist(feat_dir, rows)
     name = io.save_top1_with_threshold(out_dir, seq, kept, thres)
     pairs = io.load_loop_pairs(name)                       # through the file, like the reference's loader
@@ -94,4 +107,5 @@ def run(desc_model, pair_model, raw_frames, thres, out_dir, seq=0, desc_limits=(
     with open(pose_file, "a") as f:
         for (pos, anc), o in zip(pairs, outs):
             f.write(io.pose_line(pos, anc, o["estimated_transform"].cpu().numpy()))
-    return {"clouds": clouds, "descriptors": desc, "rows": rows, "kept": kept, "top1_file": name, "pairs": pairs, "outputs": outs, "pose_file": pose_file}
+    return {"clouds": clouds, "descriptors": desc, "rows": rows, "kept": kept, "top1_file": name, "pairs": pairs, "outputs": outs, "pose_file": pose_file,
+            **extra}

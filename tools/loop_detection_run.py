@@ -2,7 +2,7 @@
 """End-to-end loop detection over a whole sequence (BASELINE configs[2] on one GPU, configs[3] sharded over N GPUs), on synthetic
 stand-in data, writing and reading the reference's own file formats; one JSON line.
 
-    python tools/loop_detection_run.py [--frames 4541] [--gpus N] [--out DIR] [--unique 16]
+    python tools/loop_detection_run.py [--frames 4541] [--gpus N] [--out DIR] [--unique 16] [--detector descriptor|scan_context]
 
 What runs, per rank (frames are split into contiguous ranges, one process per GPU like bench.py):
   raw scans --DescriptorPipeline--> 256-D descriptors                      (the hot path bench.py measures)
@@ -17,7 +17,13 @@ The KITTI dataset is not available offline: frames are `--unique` synthetic 64-b
 rigid motion per frame (yaw i * 2.39996 rad, +-2 m shifts) so that every frame is a different cloud.  Revisits (frame i == frame
 i - K) make the metrics non-trivial: with --revisit-every K (default 1500) frame i >= K repeats the pose of frame i - K with 1 cm
 noise, and the ground truth marks it.  With random weights the numbers mean nothing for place recognition; the point is the path,
-its formats and its timing (scans/s over a whole sequence, retrieval ms, file I/O excluded from the scan rate like bench.py)."""
+its formats and its timing (scans/s over a whole sequence, retrieval ms, file I/O excluded from the scan rate like bench.py).
+
+--detector scan_context replaces the learned descriptor by Scan Context (lcrnet_amd.scan_context: polar max-height images, the exhaustive
+search over all column shifts; one GPU): no weights, so its numbers DO say something about place recognition, and it writes the same
+`predicted_des_L2_dis.npz` (no per-frame descriptor files).  Mind the data: with --unique below --frames the frames that share a base scan
+are rotated, slightly shifted twins of each other, which a geometric detector rightly flags although the synthetic ground truth marks only
+the planted revisits; a claim about it therefore needs --unique == --frames, or the overlap labels of tools/loop_gt_run.py (--gt-labels)."""
 import argparse
 import json
 import os
@@ -46,6 +52,8 @@ def parse():
     ap.add_argument("--voxelizer", choices=["grid", "open3d"], default="grid",
                     help="raw-scan voxeliser of the ingest leg: the collate's grid subsampling, or Open3D's VoxelDownSample")
     ap.add_argument("--gt-labels", default=None, help="overlap labels .npz (tools/loop_gt_run.py writes them; one entry per frame) instead of the KITTI 00 asset / the synthetic revisits")
+    ap.add_argument("--detector", choices=["descriptor", "scan_context"], default="descriptor",
+                    help="the learned 256-D descriptor, or the learning-free Scan Context detector (one GPU)")
     ap.add_argument("--dump", default=None, help="rank 0 writes the gathered descriptors and the rows to this .npz (strong-scaling identity check of tools/scale_run.sh; small corpora only)")
     return ap.parse_args()
 
@@ -71,6 +79,66 @@ def frame_cloud(base, i, revisit):
     if src != i:
         pts = pts + np.random.default_rng(i).standard_normal(pts.shape).astype(np.float32) * 0.01
     return pts.astype(np.float32), src != i
+
+
+def evaluate(args, base, rows, out_dir, C):
+    """rows -> `predicted_des_L2_dis.npz`, read back, and the reference's metrics against the ground truth the arguments select"""
+    from lcrnet_amd import evaluation as ev
+    from lcrnet_amd import io_formats as io
+    io.save_pair_dist(out_dir, rows)
+    back = np.load(os.path.join(out_dir, "predicted_des_L2_dis.npz"))["arr_0"]
+    assert back.shape == ((C - 102) * 50, 1, 3)
+    gt_file = os.path.join(ROOT, "tests", "golden", "loop_gt_seq00_0.3overlap_inactive.npz")
+    if args.gt_labels:
+        from lcrnet_amd.loop_gt import load_loop_labels
+        gt, gt_name = load_loop_labels(args.gt_labels), "labels of %s" % os.path.basename(args.gt_labels)
+        if len(gt) != C:
+            raise SystemExit("--gt-labels holds %d frames, --frames is %d" % (len(gt), C))
+    elif C == 4541 and os.path.exists(gt_file):
+        gt, gt_name = np.load(gt_file, allow_pickle=True)["arr_0"], "reference asset loop_gt_seq00_0.3overlap_inactive.npz (KITTI 00)"
+    else:
+        gt = np.empty(C, dtype=object)
+        for i in range(C):
+            rev = frame_cloud(base[:1], i, args.revisit_every)[1]
+            gt[i] = np.array([float(i - args.revisit_every)]) if rev else np.array([])
+        gt_name = "synthetic revisits (frame i repeats frame i - %d)" % args.revisit_every
+    pair = back.reshape(-1, 3)
+    top1, top45 = ev.compute_topN(pair, gt, 1), ev.compute_topN(pair, gt, 45)
+    P, R = ev.compute_PR_overlap(pair, gt)
+    f1, _ = ev.compute_F1(P, R)
+    return dict(rows=int(pair.shape[0]), ground_truth=gt_name, recall_at_1=round(float(top1), 4), recall_at_45=round(float(top45), 4),
+                f1_max=round(float(f1), 4), ap=round(float(ev.compute_AP(P, R)), 4), auc=round(ev.auc(P, R), 3))
+
+
+def scan_context_main(args, dev, base, C):
+    """--detector scan_context: descriptors of every frame, the exhaustive causal search, the same file and metrics"""
+    from lcrnet_amd import io_formats as io
+    from lcrnet_amd import scan_context as sc_mod
+    clouds = [torch.from_numpy(frame_cloud(base, i, args.revisit_every)[0]).to(dev) for i in range(C)]
+    sc_mod.sequence_scan_contexts(clouds[:4])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    sc = sc_mod.sequence_scan_contexts(clouds)
+    torch.cuda.synchronize()
+    t_desc = time.perf_counter() - t0
+    sc_mod.scan_context_topk(sc, 101, min(C - 1, 105), 50, 100)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    idx, dist, shift = sc_mod.scan_context_topk(sc, 101, C - 1, 50, 100)
+    torch.cuda.synchronize()
+    t_ret = time.perf_counter() - t0
+    rows = io.pair_dist_rows(np.arange(101, C - 1), idx.cpu().numpy(), np.where(idx.cpu().numpy() >= 0, dist.cpu().numpy(), np.inf))
+    out_dir = args.out or tempfile.mkdtemp(prefix="lcr_ld_")
+    os.makedirs(out_dir, exist_ok=True)
+    m = evaluate(args, base, rows, out_dir, C)
+    print(json.dumps({"metric": "loop detection over a sequence, end to end", "detector": "scan_context", "frames": C, "n_gpus": 1,
+                      "descriptor_scans_per_s": round(C / t_desc, 1), "descriptor_s": round(t_desc, 3), "inputs": "resident in HBM",
+                      "search_ms": round(t_ret * 1e3, 2), "pairs_searched": int(sum(max(0, i - 100) for i in range(101, C - 1))), **m,
+                      "files": "predicted_des_L2_dis.npz in %s" % ("a temporary directory" if not args.out else out_dir),
+                      "data": "synthetic (%d unique scans, a rigid motion per frame); no weights" % args.unique}), flush=True)
+    if not args.out:
+        import shutil
+        shutil.rmtree(out_dir, ignore_errors=True)
 
 
 def main():
@@ -100,6 +168,10 @@ def main():
     C = args.frames
     lo, hi = shard_range(C, world, rank)
     base = [synthetic.synthetic_scan(1000 + u) for u in range(args.unique)]
+    if args.detector == "scan_context":
+        if world > 1:
+            raise SystemExit("--detector scan_context runs on one GPU")
+        return scan_context_main(args, dev, base, C)
     model = create_model().eval()
     model.load_state_dict(seeded_state_dict(model.state_dict(), 7351))
     model = model.to(dev)
@@ -166,35 +238,13 @@ def main():
         desc_sha1, rows_sha1 = hashlib.sha1(full_host.tobytes()).hexdigest(), hashlib.sha1(np.ascontiguousarray(rows).tobytes()).hexdigest()
         if args.dump:
             np.savez(args.dump, desc=full_host, rows=rows)
-        io.save_pair_dist(out_dir, rows)
-        back = np.load(os.path.join(out_dir, "predicted_des_L2_dis.npz"))["arr_0"]
-        assert back.shape == ((C - 102) * 50, 1, 3)
-        gt_file = os.path.join(ROOT, "tests", "golden", "loop_gt_seq00_0.3overlap_inactive.npz")
-        if args.gt_labels:
-            from lcrnet_amd.loop_gt import load_loop_labels
-            gt, gt_name = load_loop_labels(args.gt_labels), "labels of %s" % os.path.basename(args.gt_labels)
-            if len(gt) != C:
-                raise SystemExit("--gt-labels holds %d frames, --frames is %d" % (len(gt), C))
-        elif C == 4541 and os.path.exists(gt_file):
-            gt, gt_name = np.load(gt_file, allow_pickle=True)["arr_0"], "reference asset loop_gt_seq00_0.3overlap_inactive.npz (KITTI 00)"
-        else:
-            gt = np.empty(C, dtype=object)
-            for i in range(C):
-                rev = frame_cloud(base[:1], i, args.revisit_every)[1]
-                gt[i] = np.array([float(i - args.revisit_every)]) if rev else np.array([])
-            gt_name = "synthetic revisits (frame i repeats frame i - %d)" % args.revisit_every
-        pair = back.reshape(-1, 3)
-        top1, top45 = ev.compute_topN(pair, gt, 1), ev.compute_topN(pair, gt, 45)
-        P, R = ev.compute_PR_overlap(pair, gt)
-        f1, _ = ev.compute_F1(P, R)
+        m = evaluate(args, base, rows, out_dir, C)
         print(json.dumps({"metric": "loop detection over a sequence, end to end", "voxelizer": args.voxelizer, "frames": C, "n_gpus": world,
                           "descriptor_scans_per_s": round(C / t_desc, 1), "descriptor_s": round(t_desc, 3), "inputs": "host [N,4] rows through the ingest leg" if args.host_rows else "resident in HBM",
                           "retrieval_ms_slowest_rank": round(t_ret * 1e3, 2), "retrieval_ms_per_rank": t_ret_all, "query_rows_per_rank": q_rows_all,
                           "wall_s_descriptors_plus_retrieval": round(t_desc + t_ret, 3), "gathered_descriptors_sha1": desc_sha1, "rows_sha1": rows_sha1,
                           "npz_write_s_rank0": round(t_write, 2),
-                          "rows": int(pair.shape[0]), "ground_truth": gt_name, "recall_at_1": round(float(top1), 4),
-                          "recall_at_45": round(float(top45), 4), "f1_max": round(float(f1), 4), "ap": round(float(ev.compute_AP(P, R)), 4),
-                          "auc": round(ev.auc(P, R), 3), "files": "%d x {seq}_{idx}.npz + predicted_des_L2_dis.npz in %s" % (hi - lo, "a temporary directory" if not args.out else out_dir),
+                          **m, "files": "%d x {seq}_{idx}.npz + predicted_des_L2_dis.npz in %s" % (hi - lo, "a temporary directory" if not args.out else out_dir),
                           "data": "synthetic (%d unique scans, a rigid motion per frame); seeded random weights" % args.unique}), flush=True)
     if world > 1:
         dist.barrier()
