@@ -952,6 +952,35 @@ int lcr_icp_point_to_plane(const float* src, const int64_t* src_len, const float
                            double relative_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr,
                            double* T_hist, double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream);
 
+/* Generalized ICP (plane-to-plane; Open3D's registration_generalized_icp with TransformationEstimationForGeneralizedICP(epsilon), no
+ * robust kernel): the arguments, outputs, loop, stopping rule, check_every, history, determinism and domain of lcr_icp_point_to_plane,
+ * plus src_normals f32[ns,3] (stacked like src; lcr_estimate_normals writes them) and epsilon.
+ *   - Correspondence step: unchanged (the same q, partner, count, fitness, inlier_rmse (Euclidean, as Open3D's RegistrationICP loop uses
+ *     for every estimator) and corr rows as point-to-point at any pose).
+ *   - Covariance of a row with normal n (fp32 promoted to fp64, not renormalised): C(n) = I - (1 - epsilon) n n^T, the surface model
+ *     "epsilon along the normal, 1 across it" (R diag(epsilon, 1, 1) R^T for a unit n).  A zero normal (a degenerate row of
+ *     lcr_estimate_normals) gives C = I.
+ *   - Update at pose T (rows 0..2, Rm = its 3x3) over every partnered source row i with partner j: s = T p_i in fp64 (((T00*x + T01*y) +
+ *     T02*z) + T03, not the rounded q), t = tgt_j, d = s - t, a = Rm n_i with the same association ((Tr0*nx + Tr1*ny) + Tr2*nz),
+ *     b = n_j, M = 2I - (1 - epsilon)(a a^T + b b^T) (= C_t + Rm C_s Rm^T), W = M^-1 in fp64 (symmetric 3x3, adjugate / determinant),
+ *     J = [-[s]x | I] (3x6).  A = sum J^T W J (21 unique entries) and g = sum J^T W d in fp64, over the same fixed tree of the pair's
+ *     rows as the other two estimators.  A x = -g is solved by the LDL^T of point-to-plane with its pivot rule, and T <- dT(x) T with the
+ *     same dT (Open3D's TransformVector6dToMatrix4d).  T is left unchanged when count < 3 or a pivot fails.
+ *   - Relation to Open3D: its GICP builds per-point covariances R diag(epsilon, 1, 1) R^T from a normal, or from the estimated
+ *     covariance with its eigenvalues replaced by (epsilon, 1, 1), the normal being the smallest eigenvector; C(n) above is that matrix.
+ *     Parity with Open3D's binary is not pinned (as for lcr_estimate_normals and lcr_fpfh); tests/gicp_restatement.py is the definition.
+ *   - ws: lcr_icp_generalized_ws_bytes(S, ns, nt).  The call uses 29 doubles per block row (count, sum d2, A[21], g[6]); the query never
+ *     answers less than lcr_icp_plane_ws_bytes, so a workspace of this size serves all three estimators on the same shapes.
+ * Domain: that of lcr_icp_point_to_plane, plus 1e-6 <= epsilon <= 1 and non-null src_normals / tgt_normals where the side has rows.  The
+ * lower bound keeps M positive definite when two fp32-rounded unit normals are parallel (its smallest eigenvalue is then
+ * 2 epsilon - O(1e-7)); normals are expected to be unit or zero.  LCR_EARG outside. */
+int lcr_icp_generalized_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes);
+int lcr_icp_generalized(const float* src, const int64_t* src_len, const float* src_normals, const float* tgt, const int64_t* tgt_len,
+                        const float* tgt_normals, int S, const double* init, float max_correspondence_distance, double epsilon,
+                        int max_iteration, double relative_fitness, double relative_rmse, double* T, double* fitness, double* inlier_rmse,
+                        int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist, double* rmse_hist, int check_every,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* Surface normals (Open3D's EstimateNormals with KDTreeSearchParamHybrid(radius, max_nn), as utils/utils/open3d.py:53-58 calls it) for B
  * stacked clouds in one call, made exact and batch-invariant.
  *   - Input: points f32[N,3] stacked cloud-major, lengths HOST int64[B]; radius > 0; 1 <= max_nn <= 128; viewpoint f32[B,3] on the

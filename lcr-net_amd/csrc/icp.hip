@@ -22,6 +22,9 @@
 // Point-to-plane (lcr_icp_point_to_plane) runs the same loop with k_icp_match_plane / k_icp_update_plane: the same nearest-partner search
 // (icp_nearest), a row block of ICP_PLANE_MOM doubles (count, sum d², usable rows, the 21 entries of A = sum J J^T, g = sum J r), and an
 // fp64 LDL^T solve of A x = -g in the update.
+// Generalized ICP (lcr_icp_generalized) is the third estimator of the same loop, k_icp_match_gicp / k_icp_update_gicp: per partnered row the
+// 3x3 weight W = (C_t + R C_s R^T)^-1 from both normals, a row block of ICP_GICP_MOM doubles (count, sum d², the 21 entries of
+// A = sum J^T W J, g = sum J^T W d) and the same solve and composition as point-to-plane (icp_solve_commit).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -37,6 +40,7 @@ constexpr int ICP_BLOCK = 256;   // source rows (= threads) per k_icp_match work
 constexpr int ICP_UNROLL = 4;    // candidate loads in flight per lane
 constexpr int ICP_MOM = 17;      // count, sum d², sum dp[3], sum dr[3], sum dp dr^T [9]  (dp = p - anchor_src, dr = r - anchor_tgt)
 constexpr int ICP_PLANE_MOM = 30;  // count, sum d², usable rows, A = sum J J^T [21, upper triangle row by row], g = sum J r [6]
+constexpr int ICP_GICP_MOM = 29;   // count, sum d², A = sum J^T W J [21, upper triangle row by row], g = sum J^T W d [6]
 
 // pair table, by value in the kernel arguments (S <= GRID_MAX_B): the first k_icp_match block of every pair and the off[] of the two Stacks
 struct IcpPairs {
@@ -376,6 +380,29 @@ __device__ inline bool icp_solve6(const double* au, const double* g, double x[6]
   return true;
 }
 
+// thread 0 of a pair's k_icp_update_plane / k_icp_update_gicp: update k from the summed normal equations (au = A's upper triangle row by
+// row, g), T <- dT(x) T with dT = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)], then icp_commit.  T is kept when `enough` is false or a pivot of
+// icp_solve6 fails.
+__device__ __forceinline__ void icp_solve_commit(int s, int k, int max_iter, bool enough, const double* au, const double* g, double* __restrict__ T,
+                                                 int32_t* __restrict__ iters, int32_t* __restrict__ running, double* __restrict__ T_hist) {
+  double Tn[12];
+  for (int q = 0; q < 12; ++q) Tn[q] = T[16 * s + q];
+  double x[6];
+  if (enough && icp_solve6(au, g, x)) {
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cc = cos(x[2]), sc = sin(x[2]);
+    const double R[3][3] = {{cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa},     // Rz(x2) Ry(x1) Rx(x0)
+                            {sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa},
+                            {-sb, cb * sa, cb * ca}};
+    double To[12];
+    for (int q = 0; q < 12; ++q) To[q] = Tn[q];
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 4; ++c) Tn[4 * r + c] = (R[r][0] * To[c] + R[r][1] * To[4 + c]) + R[r][2] * To[8 + c];
+      Tn[4 * r + 3] += x[3 + r];
+    }
+  }
+  icp_commit(s, k, max_iter, Tn, T, iters, running, T_hist);
+}
+
 // one workgroup per pair: result_k as k_icp_update, then the point-to-plane update T <- dT(x) T
 __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update_plane(IcpPairs P, const double* __restrict__ slab, int k, int max_iter, double rel_fit,
                                                                 double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
@@ -392,22 +419,116 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_update_plane(IcpPairs P, cons
   if (tid != 0) return;
   if (!icp_result(P, s, m[0], m[1], k, max_iter, rel_fit, rel_rmse, fitness, rmse, done, fit_hist, rmse_hist)) return;
   // update k: T unchanged when fewer than 6 rows are usable or A is (numerically) singular
-  double Tn[12];
-  for (int q = 0; q < 12; ++q) Tn[q] = T[16 * s + q];
-  double x[6];
-  if (m[2] >= 6.0 && icp_solve6(m + 3, m + 24, x)) {
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cc = cos(x[2]), sc = sin(x[2]);
-    const double R[3][3] = {{cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa},     // Rz(x2) Ry(x1) Rx(x0)
-                            {sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa},
-                            {-sb, cb * sa, cb * ca}};
-    double To[12];
-    for (int q = 0; q < 12; ++q) To[q] = Tn[q];
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 4; ++c) Tn[4 * r + c] = (R[r][0] * To[c] + R[r][1] * To[4 + c]) + R[r][2] * To[8 + c];
-      Tn[4 * r + 3] += x[3 + r];
+  icp_solve_commit(s, k, max_iter, m[2] >= 6.0, m + 3, m + 24, T, iters, running, T_hist);
+}
+
+// generalized ICP: one thread per source row, the partner of k_icp_match; a partnered row weights its residual d = s - t (s = T p in
+// fp64) by W = M^-1, M = 2I - (1 - eps)(a a^T + b b^T) with a = Rm n_src and b = n_tgt (zero normals: C = I on that side), and adds
+// J^T W J and J^T W d, J = [-[s]x | I], to its row block, reduced into slab[blockIdx.x][ICP_GICP_MOM].  As in k_icp_match_plane the row
+// keeps only s, d and the six entries of W (zero without a partner); each of the 29 block sums is formed from them and reduced on its own,
+// so that the moments are never live at once and the candidate loop keeps its occupancy.
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_match_gicp(IcpPairs P, const float* __restrict__ src, const float* __restrict__ src_nrm,
+                                                              const float* __restrict__ tgt, const float* __restrict__ tgt_nrm,
+                                                              const GridHeader* __restrict__ h, const int32_t* __restrict__ cell_start,
+                                                              const float4* __restrict__ sorted, float r2, double one_minus_eps,
+                                                              const double* __restrict__ T, const int32_t* __restrict__ done,
+                                                              double* __restrict__ slab, int32_t* __restrict__ corr) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_GICP_MOM];
+  const int blk = blockIdx.x;
+  const int s = cloud_of(P.blk_off, P.S, blk);
+  if (done[s]) return;                                         // workgroup-uniform
+  const int64_t a = P.src_off[s], n = P.src_off[s + 1] - a, tb = P.tgt_off[s];
+  const int64_t row = static_cast<int64_t>(blk - P.blk_off[s]) * ICP_BLOCK + threadIdx.x;     // pair-local
+  double found = 0.0, d2 = 0.0, sp[3] = {0.0, 0.0, 0.0}, dv[3] = {0.0, 0.0, 0.0};
+  double W[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                // xx, xy, xz, yy, yz, zz
+  if (row < n) {
+    const int64_t i = a + row;
+    double Tm[12], p[3];
+    int64_t j;
+    if (icp_match_row(T, s, src, i, tb, h, cell_start, sorted, r2, corr, Tm, p, j, d2)) {
+      const double x = p[0], y = p[1], z = p[2];
+      const double nx = src_nrm[3 * i], ny = src_nrm[3 * i + 1], nz = src_nrm[3 * i + 2];
+      found = 1.0;
+      double av[3], bv[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        sp[r] = dadd(dadd(dadd(dmul(Tm[4 * r], x), dmul(Tm[4 * r + 1], y)), dmul(Tm[4 * r + 2], z)), Tm[4 * r + 3]);
+        dv[r] = sp[r] - static_cast<double>(tgt[3 * j + r]);
+        av[r] = dadd(dadd(dmul(Tm[4 * r], nx), dmul(Tm[4 * r + 1], ny)), dmul(Tm[4 * r + 2], nz));
+        bv[r] = tgt_nrm[3 * j + r];
+      }
+      auto Mrc = [&](int r, int c) {
+        return (r == c ? 2.0 : 0.0) - dmul(one_minus_eps, dadd(dmul(av[r], av[c]), dmul(bv[r], bv[c])));
+      };
+      const double m00 = Mrc(0, 0), m01 = Mrc(0, 1), m02 = Mrc(0, 2), m11 = Mrc(1, 1), m12 = Mrc(1, 2), m22 = Mrc(2, 2);
+      // W = adj(M) / det(M); det > 0 on the domain (eps >= 1e-6, normals unit or zero)
+      const double c00 = dmul(m11, m22) - dmul(m12, m12), c01 = dmul(m02, m12) - dmul(m01, m22), c02 = dmul(m01, m12) - dmul(m02, m11);
+      const double c11 = dmul(m00, m22) - dmul(m02, m02), c12 = dmul(m01, m02) - dmul(m00, m12), c22 = dmul(m00, m11) - dmul(m01, m01);
+      const double det = dadd(dadd(dmul(m00, c00), dmul(m01, c01)), dmul(m02, c02));
+      W[0] = c00 / det;
+      W[1] = c01 / det;
+      W[2] = c02 / det;
+      W[3] = c11 / det;
+      W[4] = c12 / det;
+      W[5] = c22 / det;
     }
   }
-  icp_commit(s, k, max_iter, Tn, T, iters, running, T_hist);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  auto wave_sum = [&](double v, int q) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = dadd(v, __shfl_xor(v, d));
+    if (lane == 0) s_red[w][q] = v;
+  };
+  auto Wrc = [&](int r, int c) { return W[r <= c ? (r == 0 ? c : r + c + 1) : (c == 0 ? r : r + c + 1)]; };      // the symmetric W
+  // B = [s]x W = A_rt: column c is s x (column c of W)
+  auto Brc = [&](int r, int c) { return dmul(sp[(r + 1) % 3], Wrc((r + 2) % 3, c)) - dmul(sp[(r + 2) % 3], Wrc((r + 1) % 3, c)); };
+  // A_rr = -[s]x W [s]x = B [s]x^T: entry (r, c) is row r of B against row c of [s]x
+  auto Arr = [&](int r, int c) { return dmul(Brc(r, (c + 2) % 3), sp[(c + 1) % 3]) - dmul(Brc(r, (c + 1) % 3), sp[(c + 2) % 3]); };
+  wave_sum(found, 0);
+  wave_sum(d2, 1);
+  int q = 2;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {                                  // rows 0..2 of A: A_rr from the diagonal on, then A_rt
+#pragma unroll
+    for (int c = r; c < 3; ++c) wave_sum(Arr(r, c), q++);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) wave_sum(Brc(r, c), q++);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)                                    // rows 3..5: A_tt = W
+#pragma unroll
+    for (int c = r; c < 3; ++c) wave_sum(Wrc(r, c), q++);
+  double u[3];                                                   // u = W d;  g = [s x u ; u]
+#pragma unroll
+  for (int r = 0; r < 3; ++r) u[r] = dadd(dadd(dmul(Wrc(r, 0), dv[0]), dmul(Wrc(r, 1), dv[1])), dmul(Wrc(r, 2), dv[2]));
+#pragma unroll
+  for (int r = 0; r < 3; ++r) wave_sum(dmul(sp[(r + 1) % 3], u[(r + 2) % 3]) - dmul(sp[(r + 2) % 3], u[(r + 1) % 3]), 23 + r);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) wave_sum(u[r], 26 + r);
+  __syncthreads();
+  if (threadIdx.x < ICP_GICP_MOM) {                                // the cross-wave step of icp_block_sum, one moment per thread
+    double v = s_red[0][threadIdx.x];
+    for (int u2 = 1; u2 < ICP_BLOCK / 64; ++u2) v = dadd(v, s_red[u2][threadIdx.x]);
+    slab[static_cast<int64_t>(blk) * ICP_GICP_MOM + threadIdx.x] = v;
+  }
+}
+
+// one workgroup per pair: result_k as k_icp_update, then the generalized update T <- dT(x) T (T unchanged when count < 3 or a pivot fails)
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_update_gicp(IcpPairs P, const double* __restrict__ slab, int k, int max_iter, double rel_fit,
+                                                               double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
+                                                               double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ done,
+                                                               int32_t* __restrict__ running, double* __restrict__ T_hist,
+                                                               double* __restrict__ fit_hist, double* __restrict__ rmse_hist) {
+  __shared__ double s_red[ICP_BLOCK / 64][ICP_GICP_MOM];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (s == 0 && tid == 0) running[(k + 1) & 1] = 0;          // the other slot: read by the host after the previous launch, if at all
+  if (done[s]) return;
+  const int b0 = P.blk_off[s], nb = P.blk_off[s + 1] - b0;
+  double m[ICP_GICP_MOM];
+  icp_slab_sum<ICP_GICP_MOM>(slab, b0, nb, m, s_red);
+  if (tid != 0) return;
+  if (!icp_result(P, s, m[0], m[1], k, max_iter, rel_fit, rel_rmse, fitness, rmse, done, fit_hist, rmse_hist)) return;
+  icp_solve_commit(s, k, max_iter, m[0] >= 3.0, m + 2, m + 23, T, iters, running, T_hist);
 }
 
 }  // namespace lcr
@@ -447,17 +568,23 @@ int icp_ws_bytes(const char* name, int S, int64_t ns, int64_t nt, int mom, size_
   return LCR_OK;
 }
 
-// the host loop of both estimators (tgt_normals == nullptr: point-to-point)
-template <bool PLANE>
-int icp_run(const char* name, const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, const float* tgt_normals, int S,
-            const double* init, float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse, double* T,
-            double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist, double* rmse_hist,
-            int check_every, void* ws, size_t ws_bytes, void* stream) {
+enum class IcpEst { POINT, PLANE, GICP };
+constexpr double ICP_GICP_MIN_EPS = 1e-6;
+
+// the host loop of the three estimators (POINT reads no normals, PLANE tgt_normals, GICP both sides' and epsilon)
+template <IcpEst EST>
+int icp_run(const char* name, const float* src, const int64_t* src_len, const float* src_normals, const float* tgt, const int64_t* tgt_len,
+            const float* tgt_normals, int S, const double* init, float max_correspondence_distance, double epsilon, int max_iteration,
+            double relative_fitness, double relative_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr,
+            double* T_hist, double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
+  constexpr bool PLANE = EST == IcpEst::PLANE, GICP = EST == IcpEst::GICP;
   const float r = max_correspondence_distance;
   if (max_iteration < 0 || max_iteration > ICP_MAX_ITER || !(r > 0.f) || !std::isfinite(r * r) || check_every < 0 ||
       !(relative_fitness >= 0.0) || !(relative_rmse >= 0.0))
     return refuse(LCR_EARG, "%s: outside the domain (0 <= max_iteration <= %d, r > 0 with r*r finite, relative criteria >= 0, check_every >= 0): "
                   "max_iteration=%d r=%g check_every=%d", name, ICP_MAX_ITER, max_iteration, static_cast<double>(r), check_every);
+  if (GICP && !(epsilon >= ICP_GICP_MIN_EPS && epsilon <= 1.0))
+    return refuse(LCR_EARG, "%s: outside the domain (%g <= epsilon <= 1): epsilon=%g", name, ICP_GICP_MIN_EPS, epsilon);
   if (!init || !T || !fitness || !inlier_rmse || !iterations || !ws) return refuse(LCR_EARG, "%s: null pointer", name);
   Stack sources, targets;
   const std::string who(name);                                   // the error text says which of the two tables is at fault
@@ -470,9 +597,9 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
   P.blk_off[0] = 0;
   for (int s = 0; s < S; ++s) P.blk_off[s + 1] = P.blk_off[s] + div_up(src_len[s], ICP_BLOCK);
   const int64_t ns = P.src_off[S], nt = P.tgt_off[S];
-  if ((ns > 0 && !src) || (nt > 0 && (!tgt || (PLANE && !tgt_normals))))
-    return refuse(LCR_EARG, "%s: null point array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
-  constexpr int mom = PLANE ? ICP_PLANE_MOM : ICP_MOM;
+  if ((ns > 0 && (!src || (GICP && !src_normals))) || (nt > 0 && (!tgt || ((PLANE || GICP) && !tgt_normals))))
+    return refuse(LCR_EARG, "%s: null point or normal array (ns=%lld nt=%lld)", name, static_cast<long long>(ns), static_cast<long long>(nt));
+  constexpr int mom = GICP ? ICP_GICP_MOM : PLANE ? ICP_PLANE_MOM : ICP_MOM;
   size_t need = 0, grid_bytes = 0;
   icp_ws_bytes(name, S, ns, nt, mom, &need);
   support_grid_ws_bytes(name, nt, S, &grid_bytes);
@@ -495,7 +622,13 @@ int icp_run(const char* name, const float* src, const int64_t* src_len, const fl
   const int nblk = P.blk_off[S];
   const float r2 = r * r;                                        // fp32 product, as lcr_radius_query
   for (int k = 0; k <= max_iteration; ++k) {
-    if constexpr (PLANE) {
+    if constexpr (GICP) {
+      if (nblk > 0)
+        hipLaunchKernelGGL(k_icp_match_gicp, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, src_normals, tgt, tgt_normals, L.hdr, L.cell_start,
+                           L.sorted, r2, 1.0 - epsilon, T, done, slab, corr);
+      hipLaunchKernelGGL(k_icp_update_gicp, dim3(S), dim3(ICP_BLOCK), 0, st, P, slab, k, max_iteration, relative_fitness, relative_rmse, T,
+                         fitness, inlier_rmse, iterations, done, running, T_hist, fitness_hist, rmse_hist);
+    } else if constexpr (PLANE) {
       if (nblk > 0)
         hipLaunchKernelGGL(k_icp_match_plane, dim3(nblk), dim3(ICP_BLOCK), 0, st, P, src, tgt, tgt_normals, L.hdr, L.cell_start, L.sorted, r2, T,
                            done, slab, corr);
@@ -532,9 +665,9 @@ extern "C" int lcr_icp_point_to_point(const float* src, const int64_t* src_len, 
                                       float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
                                       double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist,
                                       double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
-  return icp_run<false>("lcr_icp_point_to_point", src, src_len, tgt, tgt_len, nullptr, S, init, max_correspondence_distance, max_iteration,
-                        relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist, fitness_hist, rmse_hist, check_every,
-                        ws, ws_bytes, stream);
+  return icp_run<IcpEst::POINT>("lcr_icp_point_to_point", src, src_len, nullptr, tgt, tgt_len, nullptr, S, init, max_correspondence_distance, 0.0,
+                                max_iteration, relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist, fitness_hist,
+                                rmse_hist, check_every, ws, ws_bytes, stream);
 }
 
 extern "C" int lcr_icp_point_to_plane(const float* src, const int64_t* src_len, const float* tgt, const int64_t* tgt_len, const float* tgt_normals,
@@ -542,7 +675,22 @@ extern "C" int lcr_icp_point_to_plane(const float* src, const int64_t* src_len, 
                                       double relative_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* corr,
                                       double* T_hist, double* fitness_hist, double* rmse_hist, int check_every, void* ws, size_t ws_bytes,
                                       void* stream) {
-  return icp_run<true>("lcr_icp_point_to_plane", src, src_len, tgt, tgt_len, tgt_normals, S, init, max_correspondence_distance, max_iteration,
-                       relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist, fitness_hist, rmse_hist, check_every,
-                       ws, ws_bytes, stream);
+  return icp_run<IcpEst::PLANE>("lcr_icp_point_to_plane", src, src_len, nullptr, tgt, tgt_len, tgt_normals, S, init, max_correspondence_distance,
+                                0.0, max_iteration, relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist,
+                                fitness_hist, rmse_hist, check_every, ws, ws_bytes, stream);
+}
+
+extern "C" int lcr_icp_generalized_ws_bytes(int S, int64_t ns, int64_t nt, size_t* bytes) {
+  // never less than point-to-plane's answer: a workspace sized here serves all three estimators on the same shapes
+  return icp_ws_bytes("lcr_icp_generalized_ws_bytes", S, ns, nt, std::max(ICP_GICP_MOM, ICP_PLANE_MOM), bytes);
+}
+
+extern "C" int lcr_icp_generalized(const float* src, const int64_t* src_len, const float* src_normals, const float* tgt, const int64_t* tgt_len,
+                                   const float* tgt_normals, int S, const double* init, float max_correspondence_distance, double epsilon,
+                                   int max_iteration, double relative_fitness, double relative_rmse, double* T, double* fitness,
+                                   double* inlier_rmse, int32_t* iterations, int32_t* corr, double* T_hist, double* fitness_hist,
+                                   double* rmse_hist, int check_every, void* ws, size_t ws_bytes, void* stream) {
+  return icp_run<IcpEst::GICP>("lcr_icp_generalized", src, src_len, src_normals, tgt, tgt_len, tgt_normals, S, init, max_correspondence_distance,
+                               epsilon, max_iteration, relative_fitness, relative_rmse, T, fitness, inlier_rmse, iterations, corr, T_hist,
+                               fitness_hist, rmse_hist, check_every, ws, ws_bytes, stream);
 }

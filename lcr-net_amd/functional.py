@@ -1940,10 +1940,21 @@ def icp_point_to_plane(src, src_len, tgt, tgt_len, tgt_normals, init, max_corres
                 relative_rmse, check_every, want_corr, want_history)
 
 
+def icp_generalized(src, src_len, src_normals, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, epsilon=1e-3, max_iteration=30,
+                    relative_fitness=1e-6, relative_rmse=1e-6, check_every=16, want_corr=False, want_history=False):
+    """Generalized (plane-to-plane) ICP (include/lcr_hip.h, lcr_icp_generalized): icp_point_to_plane's arguments and outputs, plus the source
+    normals src_normals f32 [ns,3] on the device and epsilon in [1e-6, 1], the covariance along a normal against 1 across it (zero normal
+    rows count as isotropic)."""
+    if src_normals is None or tgt_normals is None:
+        raise ValueError("icp_generalized: both clouds need normals")
+    return _icp("icp_generalized", src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, max_iteration, relative_fitness,
+                relative_rmse, check_every, want_corr, want_history, src_normals=src_normals, epsilon=epsilon)
+
+
 def _icp(name, src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
-         check_every, want_corr, want_history):
-    plane = tgt_normals is not None
-    _lib.require_cuda(src, tgt, init, *([tgt_normals] if plane else []))
+         check_every, want_corr, want_history, src_normals=None, epsilon=None):
+    plane, gicp = tgt_normals is not None, src_normals is not None
+    _lib.require_cuda(src, tgt, init, *([tgt_normals] if plane else []), *([src_normals] if gicp else []))
     dev = src.device
     S, iters = len(src_len), int(max_iteration)
     sl = np.ascontiguousarray(np.asarray(src_len, dtype=np.int64).reshape(-1))
@@ -1954,18 +1965,26 @@ def _icp(name, src, src_len, tgt, tgt_len, tgt_normals, init, max_correspondence
         raise ValueError("%s: the point arrays do not hold sum(src_len) / sum(tgt_len) rows" % name)
     if plane and (tuple(tgt_normals.shape) != tuple(tgt.shape) or tgt_normals.dtype != torch.float32):
         raise ValueError("%s: tgt_normals must be float32 with the shape of tgt" % name)
+    if gicp and (tuple(src_normals.shape) != tuple(src.shape) or src_normals.dtype != torch.float32):
+        raise ValueError("%s: src_normals must be float32 with the shape of src" % name)
     src, tgt, init = src.contiguous(), tgt.contiguous(), init.contiguous()
-    ws = _lib.ws("lcr_icp_plane_ws_bytes" if plane else "lcr_icp_ws_bytes", S, src.shape[0], tgt.shape[0], device=dev)
+    ws = _lib.ws("lcr_icp_generalized_ws_bytes" if gicp else "lcr_icp_plane_ws_bytes" if plane else "lcr_icp_ws_bytes", S, src.shape[0],
+                 tgt.shape[0], device=dev)
     f64 = dict(dtype=torch.float64, device=dev)
     out = {"T": torch.empty((S, 4, 4), **f64), "fitness": torch.empty((S,), **f64), "inlier_rmse": torch.empty((S,), **f64),
            "iterations": torch.empty((S,), dtype=torch.int32, device=dev)}
     corr = torch.empty((src.shape[0],), dtype=torch.int32, device=dev) if want_corr else None
     hist = [torch.full((S, iters + 1, 4, 4), float("nan"), **f64), torch.full((S, iters + 1), float("nan"), **f64),
             torch.full((S, iters + 1), float("nan"), **f64)] if want_history else [None, None, None]
-    tail = (float(max_correspondence_distance), iters, float(relative_fitness), float(relative_rmse), _lib.ptr(out["T"]), _lib.ptr(out["fitness"]),
+    tail = (iters, float(relative_fitness), float(relative_rmse), _lib.ptr(out["T"]), _lib.ptr(out["fitness"]),
             _lib.ptr(out["inlier_rmse"]), _lib.ptr(out["iterations"]), _lib.ptr(corr), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
             int(check_every), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(src.device))
-    if plane:
+    tail = (float(max_correspondence_distance),) + ((float(epsilon),) if gicp else ()) + tail
+    if gicp:
+        sn, nrm = src_normals.contiguous(), tgt_normals.contiguous()
+        _lib.call.lcr_icp_generalized(_lib.ptr(src), sl.ctypes.data, _lib.ptr(sn), _lib.ptr(tgt), tl.ctypes.data, _lib.ptr(nrm), S, _lib.ptr(init),
+                                      *tail)
+    elif plane:
         nrm = tgt_normals.contiguous()
         _lib.call.lcr_icp_point_to_plane(_lib.ptr(src), sl.ctypes.data, _lib.ptr(tgt), tl.ctypes.data, _lib.ptr(nrm), S, _lib.ptr(init), *tail)
     else:

@@ -17,7 +17,8 @@ generators run for their ground truth, data/Kitti/generate_kitti_pairs.py:145-14
 `icp_batched` (S pairs per native call, csrc/icp.hip), exact and batch-invariant as include/lcr_hip.h (lcr_icp_point_to_point) states.
 Both also run point-to-plane ICP (estimation_method="point_to_plane", Open3D's TransformationEstimationPointToPlane), which needs target
 normals: `estimate_normals` / `estimate_normals_batched` compute them on the GPU (csrc/normals.hip; utils/utils/open3d.py:53-58 with a
-radius, KDTreeSearchParamHybrid).
+radius, KDTreeSearchParamHybrid).  Generalized ICP (plane-to-plane, Open3D's registration_generalized_icp) has its own pair of functions,
+`registration_generalized_icp` / `gicp_batched`, with the normals of both clouds (lcr_icp_generalized).
 
 TEASER-style robust registration (experiments/registration/eval.py:197-218, `--method teaser`): `teaser_batched` /
 `registration_with_teaser_from_correspondences` (csrc/teaser.hip; consistency graph, k-core selection, GNC-TLS rotation, voted
@@ -154,24 +155,27 @@ def icp_batched(src, src_len, tgt, tgt_len, init, max_correspondence_distance, m
     functional.icp_point_to_point).  estimation_method "point_to_plane" needs tgt_normals f32 [nt,3] on the device (stacked like tgt).
     Batches of more than 64 pairs are split into chunks; every pair's result is the same in any chunk."""
     plane = _estimation(estimation_method, tgt_normals)
+    tail = (max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, check_every)
+    kw = dict(want_corr=want_corr, want_history=want_history)
+    if plane:
+        return _icp_chunks(src_len, tgt_len, init, src.device,
+                           lambda s, t, sl, tl, T0: F.icp_point_to_plane(src[s], sl, tgt[t], tl, tgt_normals[t], T0, *tail, **kw))
+    return _icp_chunks(src_len, tgt_len, init, src.device, lambda s, t, sl, tl, T0: F.icp_point_to_point(src[s], sl, tgt[t], tl, T0, *tail, **kw))
+
+
+def _icp_chunks(src_len, tgt_len, init, device, one):
+    """The chunk loop of icp_batched / gicp_batched: one(source rows, target rows (slices of the stacked arrays), src_len, tgt_len, init
+    f64 [s,4,4] on the device) per chunk of at most 64 pairs, the dicts concatenated pair-major."""
     src_len = [int(x) for x in np.asarray(src_len).reshape(-1)]
     tgt_len = [int(x) for x in np.asarray(tgt_len).reshape(-1)]
     S = len(src_len)
-    dev = src.device
-    init = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init))).to(device=dev, dtype=torch.float64).reshape(S, 4, 4)
+    init = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init))).to(device=device, dtype=torch.float64).reshape(S, 4, 4)
     so = np.concatenate([[0], np.cumsum(src_len)]).astype(np.int64)
     to = np.concatenate([[0], np.cumsum(tgt_len)]).astype(np.int64)
     parts = []
     for c0 in range(0, S, ICP_MAX_PAIRS_PER_CALL):
         c1 = min(S, c0 + ICP_MAX_PAIRS_PER_CALL)
-        if plane:
-            parts.append(F.icp_point_to_plane(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1],
-                                              tgt_normals[to[c0]:to[c1]], init[c0:c1], max_correspondence_distance, max_iteration,
-                                              relative_fitness, relative_rmse, check_every, want_corr=want_corr, want_history=want_history))
-        else:
-            parts.append(F.icp_point_to_point(src[so[c0]:so[c1]], src_len[c0:c1], tgt[to[c0]:to[c1]], tgt_len[c0:c1], init[c0:c1],
-                                              max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, check_every,
-                                              want_corr=want_corr, want_history=want_history))
+        parts.append(one(slice(so[c0], so[c1]), slice(to[c0], to[c1]), src_len[c0:c1], tgt_len[c0:c1], init[c0:c1]))
     if len(parts) == 1:
         return parts[0]
     return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
@@ -208,6 +212,51 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
     nrm = _device_points(target_normals, dev) if target_normals is not None else None
     r = icp_batched(src, [src.shape[0]], tgt, [tgt.shape[0]], T0, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
                     want_corr=True, estimation_method=estimation_method, tgt_normals=nrm)
+    corr = r["corr"].cpu().numpy().astype(np.int64)
+    rows = np.nonzero(corr >= 0)[0]
+    return ICPResult(r["T"][0].cpu().numpy(), float(r["fitness"][0].item()), float(r["inlier_rmse"][0].item()),
+                     np.stack([rows, corr[rows]], axis=1).astype(np.int64), int(r["iterations"][0].item()))
+
+
+# ---- generalized ICP (Open3D's registration_generalized_icp; plane-to-plane, normals of both clouds) ----
+def gicp_batched(src, src_len, src_normals, tgt, tgt_len, tgt_normals, init, max_correspondence_distance, epsilon=1e-3, max_iteration=30,
+                 relative_fitness=1e-6, relative_rmse=1e-6, check_every=16, want_history=False, want_corr=False):
+    """Generalized ICP for S pairs on the GPU: icp_batched's arguments and outputs, with src_normals f32 [ns,3] / tgt_normals f32 [nt,3] on
+    the device (stacked like src / tgt) and epsilon, the covariance along a normal (functional.icp_generalized).  Batches of more than 64
+    pairs are split into chunks; every pair's result is the same in any chunk."""
+    if src_normals is None or tgt_normals is None:
+        raise ValueError("generalized ICP needs the normals of both clouds (estimate_normals computes them)")
+    tail = (max_correspondence_distance, epsilon, max_iteration, relative_fitness, relative_rmse, check_every)
+    return _icp_chunks(src_len, tgt_len, init, src.device,
+                       lambda s, t, sl, tl, T0: F.icp_generalized(src[s], sl, src_normals[s], tgt[t], tl, tgt_normals[t], T0, *tail,
+                                                                  want_corr=want_corr, want_history=want_history))
+
+
+def registration_generalized_icp(source, target, max_correspondence_distance, init=np.eye(4), max_iteration=30, relative_fitness=1e-6,
+                                 relative_rmse=1e-6, epsilon=1e-3, source_normals=None, target_normals=None, normal_radius=None,
+                                 normal_max_nn=30):
+    """Open3D's call shape, registration_generalized_icp(source, target, max_correspondence_distance, init,
+    TransformationEstimationForGeneralizedICP(epsilon), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)), on the
+    GPU.  source / target: numpy arrays or torch tensors [N,3] / [M,3].  A side without normals gets them from estimate_normals_batched at
+    normal_radius / normal_max_nn; without a radius that is a ValueError.  Returns an ICPResult."""
+    if (source_normals is None or target_normals is None) and normal_radius is None:
+        raise ValueError("generalized ICP needs the normals of both clouds, or normal_radius to estimate the missing ones")
+    if torch.is_tensor(target) and target.is_cuda:
+        dev = target.device
+    elif torch.is_tensor(source) and source.is_cuda:
+        dev = source.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    src, tgt = _device_points(source, dev), _device_points(target, dev)
+    T0 = (init if torch.is_tensor(init) else torch.from_numpy(np.asarray(init, dtype=np.float64))).to(device=dev, dtype=torch.float64).reshape(1, 4, 4)
+
+    def normals_of(given, cloud):
+        if given is not None:
+            return _device_points(given, dev)
+        return estimate_normals_batched(cloud, [cloud.shape[0]], normal_radius, normal_max_nn)["normals"]
+
+    r = gicp_batched(src, [src.shape[0]], normals_of(source_normals, src), tgt, [tgt.shape[0]], normals_of(target_normals, tgt), T0,
+                     max_correspondence_distance, epsilon, max_iteration, relative_fitness, relative_rmse, want_corr=True)
     corr = r["corr"].cpu().numpy().astype(np.int64)
     rows = np.nonzero(corr >= 0)[0]
     return ICPResult(r["T"][0].cpu().numpy(), float(r["fitness"][0].item()), float(r["inlier_rmse"][0].item()),

@@ -2,7 +2,7 @@
 """Point-to-point ICP throughput (csrc/icp.hip) on raw scans; one JSON line.
 
     python tools/icp_bench.py [--pairs 16] [--steps 5] [--warmup 2] [--gt-iterations 5000] [--trips 40] [--cpu]
-                              [--estimation point_to_point|point_to_plane|both] [--normals]
+                              [--estimation point_to_point|point_to_plane|both|generalized] [--normals]
 
 Workload: S pairs; each target is a synthetic raw scan (lcrnet_amd.synthetic, ~120 k rays), each source a random 70 % of the target's rows
 moved by a planted motion (3 deg, 0.6 m) with 1 cm noise; ICP starts 1 deg / 0.25 m off the motion, r = 0.5 m.  Timed (device-synchronised
@@ -18,6 +18,11 @@ available) for one pair at the default criteria, labelled as the CPU baseline.
 against the plant, per estimator (both: point-to-point and point-to-plane calls alternated, --steps each), and the per-trip cost of
 point-to-plane.  Target normals come from lcr_estimate_normals on the raw targets (r = 0.5 m, max_nn 30).  Either estimator's kernel-A bound
 uses the VALU count of its own candidate loop (k_icp_match, k_icp_match_plane).
+--estimation generalized runs all three estimators alternated in the same way: the `estimators` block gains a `generalized` entry
+(lcr_icp_generalized at epsilon 1e-3, with the per-trip cost and the VALU bound of k_icp_match_gicp) and every entry carries
+ms_per_iteration (ms per call over the longest pair's iterations + 1).  Source normals (lcr_estimate_normals on the raw sources, the same
+radius) are computed outside the timed calls and reported on their own as source_normals_ms_per_call.  With --cpu the generalized
+restatement (tests/gicp_restatement.py, normals from the GPU) is timed for one pair.
 --normals (implied by --estimation other than point_to_point) adds a `normals` block: lcr_estimate_normals per call on the 16 raw targets
 (r = 0.5 m) and on the same scans voxelised at 0.3 m (r = 0.9 m), max_nn 30, the candidates per query (host count, cell = r) and the
 share of rows whose ball holds max_nn rows or more (those take the radix select); with --cpu also the normals restatement's time for one
@@ -42,6 +47,7 @@ LANE_INSTR_PER_S = 256 * 4 * 32 * 2.4e9
 R = 0.5
 NORMAL_R, NORMAL_MAX_NN = 0.5, 30          # normals of the raw targets (point-to-plane, and the raw half of the normals block)
 VOXEL, VOXEL_NORMAL_R = 0.3, 0.9           # the voxelised half of the normals block
+GICP_EPS = 1e-3                            # Open3D's default epsilon of TransformationEstimationForGeneralizedICP
 
 
 def kernel_asm(src_name, kernel):
@@ -142,7 +148,7 @@ def main():
     p.add_argument("--gt-iterations", type=int, default=5000)
     p.add_argument("--trips", type=int, default=40)
     p.add_argument("--cpu", action="store_true")
-    p.add_argument("--estimation", choices=["point_to_point", "point_to_plane", "both"], default="point_to_point")
+    p.add_argument("--estimation", choices=["point_to_point", "point_to_plane", "both", "generalized"], default="point_to_point")
     p.add_argument("--normals", action="store_true")
     args = p.parse_args()
     import icp_restatement as ir
@@ -210,6 +216,11 @@ def main():
         runs = {"point_to_point": lambda: call(max_iteration=30), "point_to_plane": lambda: plane(max_iteration=30)}
         if args.estimation == "point_to_plane":
             del runs["point_to_point"]
+        if args.estimation == "generalized":
+            t_sn, o_sn = timed(lambda: F.estimate_normals(src, sl, NORMAL_R, NORMAL_MAX_NN), args.steps, args.warmup)
+            src_nrm = o_sn["normals"]
+            gicp = lambda **kw: F.icp_generalized(src, sl, src_nrm, tgt, tl, nrm, init, R, GICP_EPS, **kw)
+            runs["generalized"] = lambda: gicp(max_iteration=30)
         for _ in range(args.warmup):
             for fn in runs.values():
                 fn()
@@ -228,6 +239,7 @@ def main():
             T = res[k]["T"].cpu().numpy()
             e = [ev.compute_registration_error(m, T[i])[:2] for i, m in enumerate(motions)]
             est[k] = {"ms_per_call_mean": float(np.mean(times[k])) * 1e3, "ms_per_call_min": float(np.min(times[k])) * 1e3,
+                      "ms_per_iteration": float(np.mean(times[k])) * 1e3 / (int(it.max()) + 1),
                       "iterations_mean": float(it.mean()), "iterations_max": int(it.max()),
                       "rre_deg_max": float(max(x[0] for x in e)), "rte_m_max": float(max(x[1] for x in e)),
                       "rre_deg_mean": float(np.mean([x[0] for x in e])), "rte_m_mean": float(np.mean([x[1] for x in e]))}
@@ -241,6 +253,21 @@ def main():
             vpp = None
         est["point_to_plane"]["valu_per_candidate_isa"] = vpp
         est["point_to_plane"]["kernel_a_valu_bound_ms_per_trip"] = cand * vpp / LANE_INSTR_PER_S * nq * 1e3 if vpp else None
+        if args.estimation == "generalized":
+            t_gf, _ = timed(lambda: gicp(max_iteration=args.trips, relative_fitness=0.0, relative_rmse=0.0, check_every=0), args.steps, args.warmup)
+            t_g0, _ = timed(lambda: gicp(max_iteration=0, check_every=0), args.steps, args.warmup)
+            g = est["generalized"]
+            g["epsilon"] = GICP_EPS
+            g["source_normals_ms_per_call"] = t_sn * 1e3
+            g["trip_ms_all_pairs_live"] = (t_gf - t_g0) / args.trips * 1e3
+            g["trip_ratio_to_point_to_plane"] = g["trip_ms_all_pairs_live"] / est["point_to_plane"]["trip_ms_all_pairs_live"]
+            try:
+                vpg, _ = valu_per_candidate("k_icp_match_gicp")
+            except Exception as e:                                  # no compiler where the bench runs
+                print("ISA count unavailable: %s" % e, file=sys.stderr)
+                vpg = None
+            g["valu_per_candidate_isa"] = vpg
+            g["kernel_a_valu_bound_ms_per_trip"] = cand * vpg / LANE_INSTR_PER_S * nq * 1e3 if vpg else None
         est["normals"] = {"radius": NORMAL_R, "max_nn": NORMAL_MAX_NN}
         out["estimators"] = est
     if args.cpu:
@@ -255,6 +282,13 @@ def main():
             r = ipr.icp(srcs[0], tgts[0], n0, R, inits[0], max_iteration=30)
             out["cpu_baseline"]["point_to_plane_ms_per_pair"] = (time.perf_counter() - t0) * 1e3
             out["cpu_baseline"]["point_to_plane_iterations"] = r["iterations"]
+            if args.estimation == "generalized":
+                import gicp_restatement as gr
+                s0 = src_nrm[:sl[0]].cpu().numpy()
+                t0 = time.perf_counter()
+                r = gr.icp(srcs[0], s0, tgts[0], n0, R, inits[0], eps=GICP_EPS, max_iteration=30)
+                out["cpu_baseline"]["generalized_ms_per_pair"] = (time.perf_counter() - t0) * 1e3
+                out["cpu_baseline"]["generalized_iterations"] = r["iterations"]
         if "normals" in out:
             import normals_restatement as nr
             t0 = time.perf_counter()

@@ -4,8 +4,8 @@
     python tools/registration_eval.py FEATURES_DIR [--method lgr|ransac|svd|teaser|ransac_featurematch|fpfh_ransac] [--num_corr K] [--seed S]
                                       [--pairs-per-call P] [--distance-threshold 0.3] [--ransac-n 4] [--num-iterations 50000]
                                       [--write-back] [--mutual-filter] [--edge-similarity 0.9]
-                                      [--refine icp|icp_plane [--icp-distance 0.5] [--icp-iterations 30]
-                                                              [--normal-radius 1.0] [--normal-max-nn 30]]
+                                      [--refine icp|icp_plane|gicp [--icp-distance 0.5] [--icp-iterations 30]
+                                                                   [--normal-radius 1.0] [--normal-max-nn 30] [--gicp-epsilon 1e-3]]
                                       [--fpfh-radius 2.5] [--fpfh-max-nn 100]
                                       [--noise-bound 0.01] [--inlier-selection kcore|none]
 
@@ -37,7 +37,9 @@ registers the anchor onto the positive:
 --refine icp (opt-in) then refines every estimate by point-to-point ICP of the dense anchor cloud (`anc_points_f`) onto the positive's
 (`pos_points_f`), Open3D's criteria with --icp-distance / --icp-iterations, batched on the GPU (lcrnet_amd.registration.icp_batched).
 --refine icp_plane does the same with point-to-plane ICP, on normals of `pos_points_f` computed on the GPU (radius --normal-radius,
-at most --normal-max-nn neighbours; lcrnet_amd.registration.estimate_normals_batched).
+at most --normal-max-nn neighbours; lcrnet_amd.registration.estimate_normals_batched).  --refine gicp runs generalized (plane-to-plane)
+ICP on normals of both `anc_points_f` and `pos_points_f` (the same radius and neighbour limit) with --gicp-epsilon (1e-3, Open3D's
+default; lcrnet_amd.registration.gicp_batched).
 Prints the reference's Fine Matching line (FMR / IR at acceptance_radius 0.6 with inlier_ratio_threshold 0.05, IR@0.3, IR@0.1,
 num_Corr; config_reg.py:64-65) and Registration line (RR, RRE, RTE, Rx, Ry, Rz: evaluation.registration_summary), then one JSON line.
 When at least one pair file carries non-empty `gt_node_corr_indices` (modules.registration.get_node_correspondences_batched stores
@@ -152,9 +154,10 @@ def estimate_fpfh(group, args, device):
 
 def refine_icp(pairs, est, args, device):
     """The estimates (anchor onto positive) refined by ICP of each pair's anc_points_f onto its pos_points_f; float64 (4,4) each.
-    --refine icp_plane: point-to-plane, on normals of pos_points_f estimated on the GPU first."""
+    --refine icp_plane: point-to-plane, on normals of pos_points_f estimated on the GPU first.  --refine gicp: generalized ICP, on normals
+    of both clouds."""
     import torch
-    from lcrnet_amd.registration import estimate_normals_batched, icp_batched
+    from lcrnet_amd.registration import estimate_normals_batched, gicp_batched, icp_batched
     out = []
     for g in range(0, len(pairs), args.pairs_per_call):
         group = pairs[g:g + args.pairs_per_call]
@@ -167,6 +170,11 @@ def refine_icp(pairs, est, args, device):
             nrm = estimate_normals_batched(tgt, tl, args.normal_radius, args.normal_max_nn)["normals"]
             r = icp_batched(cat(srcs), [len(x) for x in srcs], tgt, tl, init, args.icp_distance, args.icp_iterations,
                             estimation_method="point_to_plane", tgt_normals=nrm)
+        elif args.refine == "gicp":
+            src, sl = cat(srcs), [len(x) for x in srcs]
+            nrm = estimate_normals_batched(tgt, tl, args.normal_radius, args.normal_max_nn)["normals"]
+            src_nrm = estimate_normals_batched(src, sl, args.normal_radius, args.normal_max_nn)["normals"]
+            r = gicp_batched(src, sl, src_nrm, tgt, tl, nrm, init, args.icp_distance, args.gicp_epsilon, args.icp_iterations)
         else:
             r = icp_batched(cat(srcs), [len(x) for x in srcs], tgt, tl, init, args.icp_distance, args.icp_iterations)
         out += list(r["T"].cpu().numpy())
@@ -202,12 +210,13 @@ def main(argv=None):
     p.add_argument("--write-back", action="store_true", help="store estimated_transform_ransac in each file (eval.py:184-185)")
     p.add_argument("--mutual-filter", action="store_true", help="ransac_featurematch: keep only mutual nearest neighbours")
     p.add_argument("--edge-similarity", type=float, default=0.9, help="ransac_featurematch: edge-length checker (<= 0: off)")
-    p.add_argument("--refine", choices=["icp", "icp_plane"], default=None,
-                   help="refine each estimate by point-to-point (icp) or point-to-plane (icp_plane) ICP of the dense clouds")
+    p.add_argument("--refine", choices=["icp", "icp_plane", "gicp"], default=None,
+                   help="refine each estimate by point-to-point (icp), point-to-plane (icp_plane) or generalized (gicp) ICP of the dense clouds")
     p.add_argument("--icp-distance", type=float, default=0.5)
     p.add_argument("--icp-iterations", type=int, default=30)
-    p.add_argument("--normal-radius", type=float, default=1.0, help="--refine icp_plane / fpfh_ransac: normal search radius")
-    p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane / fpfh_ransac: neighbours per normal at most")
+    p.add_argument("--gicp-epsilon", type=float, default=1e-3, help="--refine gicp: covariance along a normal (1 across it)")
+    p.add_argument("--normal-radius", type=float, default=1.0, help="--refine icp_plane / gicp / fpfh_ransac: normal search radius")
+    p.add_argument("--normal-max-nn", type=int, default=30, help="--refine icp_plane / gicp / fpfh_ransac: neighbours per normal at most")
     p.add_argument("--fpfh-radius", type=float, default=2.5, help="fpfh_ransac: FPFH search radius")
     p.add_argument("--fpfh-max-nn", type=int, default=100, help="fpfh_ransac: neighbours per FPFH row at most")
     p.add_argument("--noise-bound", type=float, default=0.01, help="teaser: noise bound in metres (eval.py:201)")
@@ -315,8 +324,10 @@ def main(argv=None):
                               "edge_similarity": args.edge_similarity, "num_corr": float(np.mean(fm_corr)) if fm_corr else float("nan")}
     if args.refine:
         out["refine"] = {"method": args.refine, "max_correspondence_distance": args.icp_distance, "max_iteration": args.icp_iterations}
-        if args.refine == "icp_plane":
+        if args.refine in ("icp_plane", "gicp"):
             out["refine"].update(normal_radius=args.normal_radius, normal_max_nn=args.normal_max_nn)
+        if args.refine == "gicp":
+            out["refine"]["epsilon"] = args.gicp_epsilon
     print(json.dumps(out))
     return out
 
